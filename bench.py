@@ -2,7 +2,12 @@
 (sample -> BC/IC forward -> PDE residual -> backward -> clip -> Adam -> scheduler; reference
 trainer/diffusion_train.py:30-49,81-90) on the 4-qubit cascade model (1 layer, H=50), synthetic uniform batches.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+
+K is the number of timed steps; ``ms_per_step`` is their wall time over K.  The clock pre-roll before them runs on
+a second trainer, so the timed steps start from the state W warm-up steps leave: with the same arguments every run
+computes the same steps, and ``--dump-outputs DIR`` writes what the last of them computed (parameters, Adam moments,
+[gradient | loss sums], losses, the K steps' loss history) as DIR/<name>.npy for output-for-output comparisons.
 
 N = 1 is BASELINE.json config 2 (65 536 residual + 2 x 21 845 value points).  N > 1 is config 4's shard size,
 131 072 residual points per GPU (1 048 576 over 8 GPUs), weak scaling; the N = 1 line also reports the step at
@@ -220,26 +225,49 @@ PREROLL_MS = 60.0              # untimed GPU time before the timed region (stead
 PREROLL_MAX_STEPS = 4096
 
 
-def timed_steps(model_args, global_batch, steps, warmup, dev, dist=None, preroll_ms=0.0, windows=0):
-    """`steps` full training steps of one configuration on this rank; returns (seconds, trainer, model, host_s)."""
+def make_trainer(model_args, global_batch, dev, capacity):
+    """Model (initial weights from torch seed 1) and its fused trainer (sampler seed drawn from the same stream)."""
     Solver = importlib.import_module(PKG + ".nn.DVPDESolver").DVPDESolver
     trainer = importlib.import_module(PKG + ".trainer.diffusion_train")
     torch.manual_seed(1)
     model = Solver(model_args, Log(), device=dev)
-    tr = trainer.FusedTrainer(model, global_batch, capacity=steps * (1 + windows) + warmup + PREROLL_MAX_STEPS)
+    return trainer.FusedTrainer(model, global_batch, capacity=capacity), model
+
+
+def step_outputs(tr, steps):
+    """What a caller of the training step receives after its last step, as host arrays: the updated parameters, the
+    Adam moments, the step's [gradient | 3 loss sums] vector, its loss record and the losses of the last `steps` steps."""
+    rec = tr.opt.read()
+    return {
+        "params": tr.eng.flat.detach().cpu().numpy().astype("float32"),
+        "adam_m": tr.opt.m.cpu().numpy().astype("float32"),
+        "adam_v": tr.opt.v.cpu().numpy().astype("float32"),
+        "grad_and_loss_sums": tr.fs.flat_grad.cpu().numpy().astype("float32"),
+        "losses": torch.tensor([rec[k] for k in ("loss", "loss_res", "loss_bc", "loss_ic", "grad_norm", "lr")],
+                               dtype=torch.float64).numpy(),
+        "loss_history": torch.tensor(tr.opt.loss_history()[-steps:], dtype=torch.float32).numpy(),
+    }
+
+
+def timed_steps(model_args, global_batch, steps, warmup, dev, dist=None, preroll_ms=0.0, windows=0, capture=False):
+    """`steps` full training steps of one configuration on this rank; returns (seconds, trainer, model, host_s).
+    With `capture`, ``tr.outputs`` holds ``step_outputs`` right after the last of the `steps` timed steps."""
+    tr, model = make_trainer(model_args, global_batch, dev, capacity=steps * (1 + windows) + warmup)
     for _ in range(warmup):
         tr.sample()
         tr.step()
     # clock pre-roll (untimed, beyond the W warm-up steps): a short timed region right after an idle GPU measures the
     # clock ramp, not the kernels.  A 16-step probe gives the pace; the count derived from it is made the same on
-    # every rank (the steps contain a collective).
-    preroll = 0
+    # every rank (the steps contain a collective).  The pre-roll steps run on a second trainer of the same
+    # configuration, so the state the timed steps start from does not depend on the pace.
+    preroll, warm = 0, None
     if preroll_ms > 0:
+        warm, _ = make_trainer(model_args, global_batch, dev, capacity=PREROLL_MAX_STEPS)
         torch.cuda.synchronize()
         w0 = time.perf_counter()
         for _ in range(16):
-            tr.sample()
-            tr.step()
+            warm.sample()
+            warm.step()
         torch.cuda.synchronize()
         per = (time.perf_counter() - w0) / 16 * 1e3
         if dist is not None:
@@ -248,8 +276,8 @@ def timed_steps(model_args, global_batch, steps, warmup, dev, dist=None, preroll
             per = float(t.item())
         more = int(min(PREROLL_MAX_STEPS - 16, max(0, round(preroll_ms / max(per, 1e-3)) - 16)))
         for _ in range(more):
-            tr.sample()
-            tr.step()
+            warm.sample()
+            warm.step()
         preroll = 16 + more
     if dist is not None:
         dist.barrier()
@@ -263,6 +291,8 @@ def timed_steps(model_args, global_batch, steps, warmup, dev, dist=None, preroll
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    del warm
+    tr.outputs = step_outputs(tr, steps) if capture else None
     # further windows of K steps each (extra keys of the line: spread of the same measurement)
     win = []
     for _ in range(windows):
@@ -333,6 +363,8 @@ def launch_ranks(a):
     if a.no_cpu_baseline:
         cmd += ["--no-cpu-baseline"]
     cmd += ["--collective", a.collective, "--windows", str(a.windows)]
+    if a.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     env.setdefault("OMP_NUM_THREADS", "4")
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
@@ -356,11 +388,17 @@ def main():
                     help="residual points per GPU (default: 65536 = config 2 at N = 1, 131072 = config 4's shard at N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--windows", type=int, default=4, help="extra timed windows of K steps (min / median reported beside the line)")
+    ap.add_argument("--windows", type=int, default=0,
+                    help="extra timed windows of K steps after the measured one (min / median reported beside the line); "
+                         "default 0, so that --steps is the number of timed steps")
     ap.add_argument("--collective", choices=("torch", "rccl"), default=os.environ.get("QC_DP_COLLECTIVE", "torch"),
                     help="N > 1: the step's all-reduce through torch.distributed (default) or inside the library call "
                          "(qc_step_desc.comm: RCCL on the step's own stream, one host call per step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (parameters, Adam moments, gradient, losses) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or a.windows < 0:
+        ap.error("--steps must be >= 1, --warmup and --windows >= 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a))             # before any GPU call in this process
@@ -389,7 +427,13 @@ def main():
     per_gpu = a.batch_per_gpu or (65536 if world == 1 else 131072)
     args = base_args()
     global_batch = per_gpu * world
-    dt, tr, model, t_enqueue = timed_steps(args, global_batch, a.steps, a.warmup, dev, dist, preroll_ms=PREROLL_MS, windows=a.windows)
+    dt, tr, model, t_enqueue = timed_steps(args, global_batch, a.steps, a.warmup, dev, dist, preroll_ms=PREROLL_MS,
+                                           windows=a.windows, capture=bool(a.dump_outputs))
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in tr.outputs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

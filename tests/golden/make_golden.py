@@ -1,7 +1,7 @@
 """Generates the golden fixtures in this directory.  Run ONCE in the build container
-(``python tests/golden/make_golden.py``); needs /root/reference (read-only) on disk.
+(``QC_REFERENCE_DIR=<checkout of the reference project> python tests/golden/make_golden.py``).
 
-What is pinned by the *reference's own code* (imported from /root/reference, never copied):
+What is pinned by the *reference's own code* (imported from QC_REFERENCE_DIR, never copied):
   * ``analytic.npz``  — data/diffusion_dataset.py ``u`` and ``r`` on a fixed batch;
   * ``operator_*.npz`` — nn/pde.py ``diffusion_operator`` driving the oracle-backed solver;
   * ``train_*.npz``   — trainer/diffusion_train.py ``train`` driving the oracle-backed solver
@@ -22,7 +22,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-sys.path.insert(1, "/root/reference")
+if not os.environ.get("QC_REFERENCE_DIR"):
+    sys.exit("make_golden.py imports the reference project: set QC_REFERENCE_DIR to its checkout")
+sys.path.insert(1, os.environ["QC_REFERENCE_DIR"])
 
 from oracle import statevector as sv                      # noqa: E402
 from oracle import solver as osol                          # noqa: E402

@@ -1,6 +1,6 @@
 """The CPU oracle against closed forms, its independent dense twin, the committed golden vectors
-and the reference's own analytic functions (analytic.npz was produced by importing
-/root/reference/data/diffusion_dataset.py)."""
+and the reference's own analytic functions (analytic.npz was produced by importing the reference's
+data/diffusion_dataset.py, tests/golden/make_golden.py)."""
 import glob
 import math
 import os
