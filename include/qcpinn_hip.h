@@ -230,7 +230,7 @@ size_t qc_step_workspace_bytes(const qc_program* prog, int64_t B_res, int64_t B_
  * per-kernel timing; QC_ERR_UNSUPPORTED when the step would take the two-stream form instead. */
 #define QC_STAGE_PRE_FWD 0
 #define QC_STAGE_CIRCUIT_FWD 1
-#define QC_STAGE_POST 2          /* point kernel + weight-gradient kernel */
+#define QC_STAGE_POST 2          /* one kernel: point values, cotangents and weight gradients */
 #define QC_STAGE_CIRCUIT_BWD 3
 #define QC_STAGE_PRE_BWD 4
 #define QC_STAGE_COUNT 5

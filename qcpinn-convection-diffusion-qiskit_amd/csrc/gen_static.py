@@ -1,8 +1,10 @@
-"""Generates gen/qc_static_<id>.hip, gen/qc_static_wave_<id>.hip + gen/qc_static_table.hip: compile-time
-specialised register-family (n <= 5) and lanes-as-amplitudes-family (n = 6..8) kernels for the gate programs named below (lowered by ../circuits.py, so the static kernels
-and the run-time interpreter see the same gate lists).  Run by the Makefile before compiling."""
+"""Generates gen/qc_static_[wave_|h2_]<id>.hip + one gen/qc_static_[wave_|h2_]table.hip per family: compile-time
+specialised register-family (n <= 5), lanes-as-amplitudes-family (n = 6..8) and HBM-family (n >= 9) kernels for the gate
+programs named below (lowered by ../circuits.py, so the static kernels and the run-time interpreters see the same gate
+lists).  Run by the Makefile before compiling."""
 import importlib.util
 import os
+import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,109 +55,101 @@ def device_rows(prog):
     return out
 
 
-def main():
-    gen = os.path.join(HERE, "gen")
-    os.makedirs(gen, exist_ok=True)
-    table = ['// generated by gen_static.py - do not edit', '#include "../qc_circuit_reg_kernels.h"', '',
-             'struct QcStaticEntry { int n_qubits, n_gates; const int* gates; const QcRegLaunchers* launch; };']
-    entries = []
-    for i, (ans, n, L, haar) in enumerate(PROGRAMS):
-        prog = circuits.build_program(ans, n, L, haar)
-        rows = device_rows(prog)
-        body = ", ".join("{%d, %d, %d, %d}" % r for r in rows)
-        src = [f'// generated by gen_static.py - do not edit: {ans} n={n} L={L} haar={haar}',
-               '#include "../qc_circuit_reg_kernels.h"', '',
-               'namespace {', f'struct SP{i} {{', f'  static constexpr int N = {n};',
-               f'  static constexpr int G = {len(rows)};', f'  static constexpr int P = {prog.n_params};', f'  static constexpr SGate g[{len(rows)}] = {{{body}}};',
-               '};', '}  // namespace', '',
-               f'extern QcRegLaunchers qc_static_launch_{i};',
-               f'QcRegLaunchers qc_static_launch_{i} = RegLaunch<StatProg<SP{i}>>::table();', '']
-        path = os.path.join(gen, f"qc_static_{i}.hip")
-        text = "\n".join(src)
-        if not os.path.exists(path) or open(path).read() != text:
-            open(path, "w").write(text)
-        flat = ", ".join(str(v) for r in rows for v in r)
-        table.append(f'extern QcRegLaunchers qc_static_launch_{i};')
-        table.append(f'static const int qc_static_gates_{i}[] = {{{flat}}};')
-        entries.append(f'  {{{n}, {len(rows)}, qc_static_gates_{i}, &qc_static_launch_{i}}},')
-    table += ['extern const QcStaticEntry qc_static_table[];', 'extern const int qc_static_count;',
-              'const QcStaticEntry qc_static_table[] = {'] + entries + ['};',
-              f'const int qc_static_count = {len(PROGRAMS)};', '']
-    path = os.path.join(gen, "qc_static_table.hip")
-    text = "\n".join(table)
-    if not os.path.exists(path) or open(path).read() != text:
-        open(path, "w").write(text)
-    # ---- wave family (own table file: the two kernel headers are not meant to share a translation unit)
-    table = ['// generated by gen_static.py - do not edit', '#include "../qc_circuit_wave_kernels.h"', '',
-              'struct QcStaticWaveEntry { int n_qubits, n_gates; const int* gates; const QcWaveLaunchers* launch; };']
-    wentries, wfiles = [], []
-    for i, (ans, n, L, haar) in enumerate(WAVE_PROGRAMS):
-        prog = circuits.build_program(ans, n, L, haar)
-        rows = device_rows(prog)
-        body = ", ".join("{%d, %d, %d, %d}" % r for r in rows)
-        src = [f'// generated by gen_static.py - do not edit: wave family, {ans} n={n} L={L} haar={haar}',
-               '#include "../qc_circuit_wave_kernels.h"', '',
-               'namespace {', f'struct WP{i} {{', f'  static constexpr int N = {n};',
-               f'  static constexpr int G = {len(rows)};', f'  static constexpr WGate g[{len(rows)}] = {{{body}}};',
-               '};', '}  // namespace', '',
-               f'extern QcWaveLaunchers qc_static_wave_launch_{i};',
-               f'QcWaveLaunchers qc_static_wave_launch_{i} = WaveLaunch<{n - 4}, StatWave<WP{i}>>::table();', '']
-        path = os.path.join(gen, f"qc_static_wave_{i}.hip")
-        text = "\n".join(src)
-        if not os.path.exists(path) or open(path).read() != text:
-            open(path, "w").write(text)
-        wfiles.append(f"gen/qc_static_wave_{i}.hip")
-        flat = ", ".join(str(v) for r in rows for v in r)
-        table.append(f'extern QcWaveLaunchers qc_static_wave_launch_{i};')
-        table.append(f'static const int qc_static_wave_gates_{i}[] = {{{flat}}};')
-        wentries.append(f'  {{{n}, {len(rows)}, qc_static_wave_gates_{i}, &qc_static_wave_launch_{i}}},')
-    table += ['extern const QcStaticWaveEntry qc_static_wave_table[];', 'extern const int qc_static_wave_count;',
-              'const QcStaticWaveEntry qc_static_wave_table[] = {'] + wentries + ['};',
-              f'const int qc_static_wave_count = {len(WAVE_PROGRAMS)};', '']
-    path = os.path.join(gen, "qc_static_wave_table.hip")
-    text = "\n".join(table)
-    if not os.path.exists(path) or open(path).read() != text:
-        open(path, "w").write(text)
-    # ---- HBM family: the planner itself (qc_hbm2_plan.h, host C++) produces the constexpr plan records
-    import subprocess
-    tool = os.path.join(gen, "h2_plan_tool")
+def gate_struct(name, n, rows, gate_type, extra=()):
+    """the compile-time program of the register and wave families: qubits, gates, (parameters,) gate rows"""
+    body = ", ".join("{%d, %d, %d, %d}" % r for r in rows)
+    return "\n".join(["namespace {", f"struct {name} {{", f"  static constexpr int N = {n};",
+                      f"  static constexpr int G = {len(rows)};", *extra,
+                      f"  static constexpr {gate_type} g[{len(rows)}] = {{{body}}};", "};", "}  // namespace"])
+
+
+def reg_program(i, spec, prog, rows, gates):
+    ans, n, L, haar = spec
+    return dict(title=f"{ans} n={n} L={L} haar={haar}",
+                body=gate_struct(f"SP{i}", n, rows, "SGate", [f"  static constexpr int P = {prog.n_params};"]),
+                launch=f"RegLaunch<StatProg<SP{i}>>::table()", table_lines=[], entry=[n, len(rows), gates])
+
+
+def wave_program(i, spec, prog, rows, gates):
+    ans, n, L, haar = spec
+    return dict(title=f"wave family, {ans} n={n} L={L} haar={haar}", body=gate_struct(f"WP{i}", n, rows, "WGate"),
+                launch=f"WaveLaunch<{n - 4}, StatWave<WP{i}>>::table()", table_lines=[], entry=[n, len(rows), gates])
+
+
+def h2_plan_tool():
+    """the planner itself (qc_hbm2_plan.h, host C++) produces the constexpr plan records of the HBM family"""
+    tool = os.path.join(HERE, "gen", "h2_plan_tool")
     deps = [os.path.join(HERE, f) for f in ("h2_plan_tool.cpp", "qc_hbm2_plan.h", "qc_types.h")]
     if not os.path.exists(tool) or any(os.path.getmtime(d) > os.path.getmtime(tool) for d in deps):
         subprocess.run([os.environ.get("HOSTCXX", "g++"), "-O1", "-std=c++17", "-I", HERE, deps[0], "-o", tool], check=True)
-    table = ['// generated by gen_static.py - do not edit', '#include "../qc_circuit_h2s_kernels.h"', '',
-             'struct QcStaticH2Entry { int n_qubits, n_gates, absorb, rb; const int* gates; const int* describe; int n_describe; const H2sLaunchers* launch; };']
-    hentries, hfiles = [], []
-    for i, (ans, n, L, haar, rb) in enumerate(H2_PROGRAMS):
-        prog = circuits.build_program(ans, n, L, haar)
-        rows = device_rows(prog)
-        absorb = lead_rx(rows, n)
-        stdin = "\n".join("%d %d %d %d" % r for r in rows) + "\n"
-        out = subprocess.run([tool, f"HP{i}", str(n), str(absorb), str(rb)], input=stdin, capture_output=True, text=True, check=True).stdout
-        body, describe = out[:out.index("static const int HP")], out[out.index("static const int HP"):]
-        src = [f'// generated by gen_static.py - do not edit: HBM family, {ans} n={n} L={L} haar={haar} rb={rb}',
-               '#include "../qc_circuit_h2s_kernels.h"', '', 'namespace {', body.rstrip(), '}  // namespace', '',
-               f'extern H2sLaunchers qc_static_h2_launch_{i};',
-               f'H2sLaunchers qc_static_h2_launch_{i} = H2sLaunch<HP{i}>::table();', '']
-        path = os.path.join(gen, f"qc_static_h2_{i}.hip")
-        text = "\n".join(src)
-        if not os.path.exists(path) or open(path).read() != text:
-            open(path, "w").write(text)
-        hfiles.append(f"gen/qc_static_h2_{i}.hip")
-        flat = ", ".join(str(v) for r in rows for v in r)
-        ndesc = describe.count(",") + 1
-        table.append(f'extern H2sLaunchers qc_static_h2_launch_{i};')
-        table.append(f'static const int qc_static_h2_gates_{i}[] = {{{flat}}};')
-        table.append(describe.rstrip())
-        hentries.append(f'  {{{n}, {len(rows)}, {absorb}, {rb}, qc_static_h2_gates_{i}, HP{i}_describe, {ndesc}, &qc_static_h2_launch_{i}}},')
-    table += ['extern const QcStaticH2Entry qc_static_h2_table[];', 'extern const int qc_static_h2_count;',
-              'const QcStaticH2Entry qc_static_h2_table[] = {'] + hentries + ['};',
-              f'const int qc_static_h2_count = {len(H2_PROGRAMS)};', '']
-    path = os.path.join(gen, "qc_static_h2_table.hip")
-    text = "\n".join(table)
+    return tool
+
+
+def h2_program(i, spec, prog, rows, gates):
+    ans, n, L, haar, rb = spec
+    absorb = lead_rx(rows, n)
+    stdin = "\n".join("%d %d %d %d" % r for r in rows) + "\n"
+    out = subprocess.run([h2_plan_tool(), f"HP{i}", str(n), str(absorb), str(rb)], input=stdin, capture_output=True,
+                         text=True, check=True).stdout
+    body, describe = out[:out.index("static const int HP")], out[out.index("static const int HP"):]
+    return dict(title=f"HBM family, {ans} n={n} L={L} haar={haar} rb={rb}",
+                body="\n".join(["namespace {", body.rstrip(), "}  // namespace"]),
+                launch=f"H2sLaunch<HP{i}>::table()", table_lines=[describe.rstrip()],
+                entry=[n, len(rows), absorb, rb, gates, f"HP{i}_describe", describe.count(",") + 1])
+
+
+# per family: file tag, kernel header, launcher record, table entry type and its fields, programs, and the emitter that
+# returns one program's title, namespace body, launcher expression, extra table lines and table entry fields
+FAMILIES = [
+    dict(tag="", header="qc_circuit_reg_kernels.h", launchers="QcRegLaunchers", entry="QcStaticEntry",
+         struct="int n_qubits, n_gates; const int* gates; const QcRegLaunchers* launch;", programs=PROGRAMS,
+         emit=reg_program),
+    dict(tag="wave_", header="qc_circuit_wave_kernels.h", launchers="QcWaveLaunchers", entry="QcStaticWaveEntry",
+         struct="int n_qubits, n_gates; const int* gates; const QcWaveLaunchers* launch;", programs=WAVE_PROGRAMS,
+         emit=wave_program),
+    dict(tag="h2_", header="qc_circuit_h2s_kernels.h", launchers="H2sLaunchers", entry="QcStaticH2Entry",
+         struct="int n_qubits, n_gates, absorb, rb; const int* gates; const int* describe; int n_describe; "
+                "const H2sLaunchers* launch;", programs=H2_PROGRAMS, emit=h2_program),
+]
+
+
+def write(path, text):
     if not os.path.exists(path) or open(path).read() != text:
         open(path, "w").write(text)
-    print(" ".join([f"gen/qc_static_{i}.hip" for i in range(len(PROGRAMS))] + wfiles + hfiles +
-                   ["gen/qc_static_table.hip", "gen/qc_static_wave_table.hip", "gen/qc_static_h2_table.hip"]))
+
+
+def main():
+    gen = os.path.join(HERE, "gen")
+    os.makedirs(gen, exist_ok=True)
+    files, tables = [], []
+    # one table file per family: the kernel headers are not meant to share a translation unit
+    for fam in FAMILIES:
+        tag, launchers = fam["tag"], fam["launchers"]
+        table = ["// generated by gen_static.py - do not edit", f'#include "../{fam["header"]}"', "",
+                 f'struct {fam["entry"]} {{ {fam["struct"]} }};']
+        entries = []
+        for i, spec in enumerate(fam["programs"]):
+            prog = circuits.build_program(*spec[:4])
+            rows = device_rows(prog)
+            launch, gates = f"qc_static_{tag}launch_{i}", f"qc_static_{tag}gates_{i}"
+            p = fam["emit"](i, spec, prog, rows, gates)
+            write(os.path.join(gen, f"qc_static_{tag}{i}.hip"),
+                  "\n".join([f'// generated by gen_static.py - do not edit: {p["title"]}', f'#include "../{fam["header"]}"',
+                             "", p["body"], "", f"extern {launchers} {launch};",
+                             f'{launchers} {launch} = {p["launch"]};', ""]))
+            files.append(f"gen/qc_static_{tag}{i}.hip")
+            flat = ", ".join(str(v) for r in rows for v in r)
+            table.append(f"extern {launchers} {launch};")
+            table.append(f"static const int {gates}[] = {{{flat}}};")
+            table += p["table_lines"]
+            entries.append("  {" + ", ".join(str(v) for v in p["entry"] + ["&" + launch]) + "},")
+        name = f"qc_static_{tag}table"
+        table += [f'extern const {fam["entry"]} {name}[];', f"extern const int qc_static_{tag}count;",
+                  f'const {fam["entry"]} {name}[] = {{'] + entries + ["};",
+                  f'const int qc_static_{tag}count = {len(fam["programs"])};', ""]
+        write(os.path.join(gen, f"{name}.hip"), "\n".join(table))
+        tables.append(f"gen/{name}.hip")
+    print(" ".join(files + tables))
 
 
 if __name__ == "__main__":

@@ -32,19 +32,17 @@ static QcPde to_pde(const qc_pde* p) {
   return q;
 }
 
-// Which kernel family serves n qubits: registers (one lane per statevector) up to 5,
-// lanes-as-amplitudes above.
-static inline bool force_wave() {
-  static const bool f = [] { const char* e = getenv("QC_FORCE_WAVE"); return e && e[0] == '1'; }();
-  return f;   // test hook: route n <= 5 through the wave family too (cross-checks the two families)
+// Which kernel family serves n qubits: registers (one lane per statevector) up to 5, lanes-as-amplitudes up to 8,
+// statevector tiles in HBM up to 20 (the round-structured plan of qc_circuit_hbm2.hip; compile-time stage programs
+// where one is registered, the plan interpreter with QC_NO_STATIC=1).  QC_FORCE_WAVE=1 is a test hook: it routes
+// n <= 5 through the wave family too (cross-checks the two families).
+static const QcFamily* pick_family(int n) {
+  static const bool force_wave = [] { const char* e = getenv("QC_FORCE_WAVE"); return e && e[0] == '1'; }();
+  if (n >= 2 && n <= 5 && !force_wave) return &qc_family_reg;
+  if (n >= 1 && n <= 8) return &qc_family_wave;
+  if (n >= 9 && n <= 20) return &qc_family_hbm;
+  return nullptr;
 }
-static inline bool use_reg(int n) { return n >= 2 && n <= 5 && !force_wave(); }
-static inline bool use_wave(int n) { return n >= 1 && n <= 8; }
-static inline bool use_hbm(int n) { return n >= 9 && n <= 20; }
-// n >= 9: the round-structured plan (qc_circuit_hbm2.hip; compile-time stage programs where one is registered).  The
-// round-1 kernels (one LDS round trip or one pass per gate) are gone since round 3; the plan interpreter
-// (QC_NO_STATIC=1) is the cross-check of the generated programs.
-static inline bool use_h2(const qc_program* p) { return p->h2 != nullptr; }
 // Budget of the resident per-tile stores: QC_HBM_KEEP_GB (default 96), never more than 85 % of the memory that is free
 // on the current device when a workspace is sized (a smaller or partly occupied GPU gets fewer resident tiles, not an
 // allocation failure).
@@ -82,6 +80,17 @@ static QcSide* side_stream() {
            hipEventCreateWithFlags(&q.join, hipEventDisableTiming) == hipSuccess;
   }
   return q.ok ? &q : nullptr;
+}
+
+bool qc_static_match(const qc_program* pg, int n_qubits, int n_gates, const int* rows) {
+  static const bool off = [] { const char* e = getenv("QC_NO_STATIC"); return e && e[0] == '1'; }();
+  if (off || n_qubits != pg->n_qubits || n_gates != pg->n_gates) return false;
+  for (int g = 0; g < n_gates; ++g) {
+    const QcGate& a = pg->h_gates[g];
+    const int* b = rows + 4 * g;
+    if (a.op != b[0] || a.ba != b[1] || a.bb != b[2] || a.slot != b[3]) return false;
+  }
+  return true;
 }
 
 extern "C" {
@@ -139,26 +148,29 @@ static bool absorb_enabled() {
   return !no_absorb;
 }
 
+// the staged plan folds the leading RX layer only for angle encoding (the generated programs embed angles)
+static void* h2_plan(const qc_program* p, int amplitude) {
+  return qc_h2_create(p, (p->lead_rx && !amplitude && absorb_enabled()) ? 1 : 0, amplitude);
+}
+
 int qc_program_create(const int32_t* rows, int n_gates, int n_qubits, int n_params, qc_program** out) {
   if (!rows || !out || n_gates <= 0 || n_qubits < 1 || n_qubits > 24 || n_params < 0) return QC_ERR_ARG;
+  qc_program* p = (qc_program*)calloc(1, sizeof(qc_program));
   QcGate* h = (QcGate*)malloc(sizeof(QcGate) * n_gates);
-  if (!h) return QC_ERR_ALLOC;
-  int n_u4 = 0;
-  if (!parse_rows(rows, n_gates, n_qubits, n_params, h, &n_u4)) {
+  if (!p || !h) {
     free(h);
-    return QC_ERR_ARG;
-  }
-  qc_program* p = (qc_program*)malloc(sizeof(qc_program));
-  if (!p) {
-    free(h);
+    free(p);
     return QC_ERR_ALLOC;
   }
-  p->n_qubits = n_qubits; p->n_gates = n_gates; p->n_params = n_params; p->n_u4 = n_u4;
-  p->h_gates = h; p->d_gates = nullptr;
+  p->n_qubits = n_qubits; p->n_gates = n_gates; p->n_params = n_params;
+  p->h_gates = h;
+  if (!parse_rows(rows, n_gates, n_qubits, n_params, h, &p->n_u4)) {
+    qc_program_destroy(p);
+    return QC_ERR_ARG;
+  }
+  p->fam = pick_family(n_qubits);
   p->static_id = (n_qubits >= 2 && n_qubits <= 5) ? qc_reg_match_static(p)
                  : ((n_qubits >= 6 && n_qubits <= 8) ? qc_wave_match_static(p) : -1);
-  p->h2 = nullptr;
-  p->amplitude = 0;
   qc_find_diag_runs(p);
   p->lead_rx = detect_lead_rx(h, n_gates, n_qubits);
   hipError_t e = hipMalloc((void**)&p->d_gates, sizeof(QcGate) * n_gates);
@@ -180,22 +192,11 @@ int qc_program_create(const int32_t* rows, int n_gates, int n_qubits, int n_para
     }
   }
 #endif
-  if (e != hipSuccess) {
-    if (p->d_gates) (void)hipFree(p->d_gates);
-    if (p->d_diag_list) (void)hipFree(p->d_diag_list);
-    free(h);
-    free(p);
-    return hip_fail(e);
-  }
-  if (n_qubits >= 9 && n_qubits <= 20) {
-    p->h2 = qc_h2_create(p, (p->lead_rx && absorb_enabled()) ? 1 : 0);
-    if (!p->h2) {
-      (void)hipFree(p->d_gates);
-      if (p->d_diag_list) (void)hipFree(p->d_diag_list);
-      free(h);
-      free(p);
-      return QC_ERR_ALLOC;
-    }
+  int rc = e == hipSuccess ? QC_OK : hip_fail(e);
+  if (rc == QC_OK && p->fam == &qc_family_hbm && !(p->h2 = h2_plan(p, 0))) rc = QC_ERR_ALLOC;
+  if (rc != QC_OK) {
+    qc_program_destroy(p);
+    return rc;
   }
   *out = p;
   return QC_OK;
@@ -214,9 +215,8 @@ int qc_program_destroy(qc_program* p) {
 int qc_program_set_encoding(qc_program* p, int amplitude) {
   if (!p || (amplitude != 0 && amplitude != 1)) return QC_ERR_ARG;
   if (amplitude && ((int64_t)1 << p->n_qubits) < p->n_qubits) return QC_ERR_ARG;
-  if (p->amplitude != amplitude && p->h2) {   // the staged plan folds the leading RX layer only for angle encoding, and
-    p->amplitude = amplitude;                 // the generated programs embed angles
-    void* h2 = qc_h2_create(p, (p->lead_rx && !amplitude && absorb_enabled()) ? 1 : 0);
+  if (p->amplitude != amplitude && p->h2) {   // a plan for the new encoding first; the program changes only with it
+    void* h2 = h2_plan(p, amplitude);
     if (!h2) return QC_ERR_ALLOC;
     qc_h2_destroy(p->h2);
     p->h2 = h2;
@@ -250,17 +250,17 @@ int qc_prepare_gates(const qc_program* p, const float* theta, void* trig, void* 
 static int check_circuit(const qc_program* p, const void* trig, const float* umat, int64_t B) {
   if (!p || !trig || B <= 0) return QC_ERR_ARG;
   if (p->n_u4 > 0 && !umat) return QC_ERR_ARG;
-  if (!use_reg(p->n_qubits) && !use_wave(p->n_qubits) && !use_hbm(p->n_qubits)) return QC_ERR_UNSUPPORTED;
+  if (!p->fam) return QC_ERR_UNSUPPORTED;
   return QC_OK;
 }
 
 size_t qc_circuit_workspace_bytes(const qc_program* p, int nch, int backward) {
-  if (!p || !use_hbm(p->n_qubits) || (nch != 1 && nch != 6)) return 0;
+  if (!p || p->fam != &qc_family_hbm || (nch != 1 && nch != 6)) return 0;
   return qc_h2_bytes(p, p->h2, nch, backward != 0, 1);
 }
 
 size_t qc_circuit_workspace_bytes_batch(const qc_program* p, int nch, int backward, int64_t B) {
-  if (!p || B <= 0 || !use_hbm(p->n_qubits) || (nch != 1 && nch != 6)) return 0;
+  if (!p || B <= 0 || p->fam != &qc_family_hbm || (nch != 1 && nch != 6)) return 0;
   const int64_t tiles = qc_ceil_div(B, 64);
   const size_t all = qc_h2_bytes(p, p->h2, nch, backward != 0, tiles);
   if ((double)all <= hbm_budget_bytes()) return all;
@@ -269,31 +269,62 @@ size_t qc_circuit_workspace_bytes_batch(const qc_program* p, int nch, int backwa
 }
 
 static size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-// h2, fused step: residual tiles (6 channels) and value tiles (1 channel) each keep their own resident slots
-static size_t h2_res_bytes(const qc_program* p, int64_t B_res) {
-  return B_res > 0 ? ((qc_h2_bytes(p, p->h2, 6, true, qc_ceil_div(B_res, 64)) + 255) & ~(size_t)255) : 0;
-}
-static size_t h2_val_bytes(const qc_program* p, int64_t B_val) {
-  return B_val > 0 ? ((qc_h2_bytes(p, p->h2, 1, true, qc_ceil_div(B_val, 64)) + 255) & ~(size_t)255) : 0;
-}
-static size_t h2_min_bytes(const qc_program* p) { return (qc_h2_bytes(p, p->h2, 6, true, 1) + 255) & ~(size_t)255; }
-static size_t step_circuit_bytes(const qc_program* p, int64_t B_res, int64_t B_val = 0) {
-  if (use_hbm(p->n_qubits) && use_h2(p)) {
-    const size_t all = h2_res_bytes(p, B_res) + h2_val_bytes(p, B_val);
+
+// The workspace of one fused step, every piece 256-byte aligned:
+//   [ circuit region | amplitude encoding: u_res | ub_res | u_val | ub_val ]
+// The circuit region holds the residual pipeline's store, then the value pipeline's.  Register / wave family: the kept
+// final states (optional: without them the adjoint pass recomputes; the value store only behind a residual store).
+// HBM family: the resident tiles of both pipelines when the budget holds them all; otherwise as many six-channel tiles
+// as it holds, shared by both pipelines (one launch sequence per group of resident tiles, the adjoint pass recomputes
+// its group's forward pass); never less than one tile.  Called without a workspace it also sizes one.
+struct QcStepLayout {
+  size_t bytes;                             // (called without a workspace) what the whole workspace should hold
+  bool fits;                                // the workspace holds what the family cannot do without (HBM: one tile)
+  QcCircStore res, val;                     // circuit stores of the residual (six-channel) and value pipelines
+  float *u_res, *ub_res, *u_val, *ub_val;   // amplitude encoding: initial-amplitude jets and their cotangents
+};
+static QcStepLayout step_layout(const qc_program* p, int64_t B_res, int64_t B_val, void* ws, size_t ws_bytes) {
+  const QcFamily* f = p->fam;
+  const bool hbm = f == &qc_family_hbm;
+  const size_t rs = f ? round256(f->store_bytes(p, 6, B_res)) : 0, vs = f ? round256(f->store_bytes(p, 1, B_val)) : 0;
+  const size_t one_tile = hbm ? round256(qc_h2_bytes(p, p->h2, 6, true, 1)) : 0;
+  auto region = [&](size_t r, size_t v) -> size_t {
+    if (!hbm) return r > 0 ? r + v : 0;
     const double budget = hbm_budget_bytes();
-    if ((double)all <= budget) return all > h2_min_bytes(p) ? all : h2_min_bytes(p);
-    // not everything fits: as many six-channel tiles as the budget holds, shared by both pipelines (one launch
-    // sequence per group of resident tiles, the adjoint pass recomputes its group's forward pass)
+    if ((double)(r + v) <= budget) return r + v > one_tile ? r + v : one_tile;
     const int64_t fit = qc_h2_tiles_that_fit(p, p->h2, 6, true, (size_t)budget);
-    const size_t some = (qc_h2_bytes(p, p->h2, 6, true, fit < 1 ? 1 : fit) + 255) & ~(size_t)255;
-    return some > h2_min_bytes(p) ? some : h2_min_bytes(p);
+    const size_t some = round256(qc_h2_bytes(p, p->h2, 6, true, fit < 1 ? 1 : fit));
+    return some > one_tile ? some : one_tile;
+  };
+  const size_t ar = round256(sizeof(float) * 6 * p->n_qubits * (size_t)B_res);
+  const size_t av = round256(sizeof(float) * p->n_qubits * (size_t)B_val);
+  QcStepLayout s = {};
+  if (!ws) s.bytes = round256(region(rs, vs)) + (p->amplitude ? 2 * ar + 2 * av : 0);
+  char* cws = (char*)ws;
+  size_t cws_bytes = ws_bytes;
+  if (p->amplitude && ws) {
+    // the circuit region is carved for the residual tiles alone: the value tiles of the HBM family never get the
+    // resident slots that `bytes` pays for (follow-up: round256(region(rs, vs)))
+    cws_bytes = round256(region(rs, 0));
+    char* a = (char*)ws + cws_bytes;
+    s.u_res = (float*)a;
+    s.ub_res = (float*)(a + ar);
+    s.u_val = (float*)(a + 2 * ar);
+    s.ub_val = (float*)(a + 2 * ar + av);
+    if (cws_bytes == 0) cws = nullptr;
   }
-  if (use_reg(p->n_qubits)) return qc_reg_chi_store_bytes(p, B_res);   // optional: enables the no-recompute adjoint
-  if (use_wave(p->n_qubits)) {   // same, compile-time programs at n = 6..8: residual store, then the value pipeline's
-    const size_t rb = round256(qc_wave_chi_store_bytes(p, B_res));
-    return rb > 0 ? rb + qc_wave_val_store_bytes(p, B_val) : 0;
+  if (hbm) {
+    s.fits = cws && cws_bytes >= one_tile;
+    const bool resident = cws_bytes >= rs + vs;
+    s.res = {cws, resident ? rs : cws_bytes, resident};
+    s.val = {resident ? cws + rs : cws, resident ? vs : cws_bytes, resident};
+  } else {
+    s.fits = true;
+    s.res = {cws, cws_bytes, cws && rs > 0 && cws_bytes >= rs};
+    const bool keep_val = cws && rs > 0 && vs > 0 && cws_bytes >= rs + vs;   // one byte short: the residual store only
+    s.val = keep_val ? QcCircStore{cws + rs, vs, true} : QcCircStore{cws, cws_bytes, false};
   }
-  return 0;
+  return s;
 }
 
 int qc_hbm_plan_describe(const int32_t* rows, int n_gates, int n_qubits, int n_params, int32_t* out, int cap) {
@@ -332,10 +363,7 @@ int qc_wave_sched_describe(const int32_t* rows, int n_gates, int n_qubits, int n
 
 size_t qc_step_workspace_bytes(const qc_program* p, int64_t B_res, int64_t B_val) {
   if (!p || B_res < 0 || B_val < 0) return 0;
-  size_t b = round256(step_circuit_bytes(p, B_res, B_val));
-  if (p->amplitude)   // initial-amplitude jets and their cotangents, both pipelines
-    b += 2 * round256(sizeof(float) * 6 * p->n_qubits * (size_t)B_res) + 2 * round256(sizeof(float) * p->n_qubits * (size_t)B_val);
-  return b;
+  return step_layout(p, B_res, B_val, nullptr, 0).bytes;
 }
 
 int qc_forward_expval(const qc_program* p, const void* trig, const float* umat, const float* angles,
@@ -343,13 +371,7 @@ int qc_forward_expval(const qc_program* p, const void* trig, const float* umat, 
   int rc = check_circuit(p, trig, umat, B);
   if (rc) return rc;
   if (!angles || !expval) return QC_ERR_ARG;
-  if (use_hbm(p->n_qubits)) {
-    rc = qc_h2_forward(p, p->h2, (const QcTrig*)trig, umat, angles, expval, B, 1, ws, ws_bytes, false, (hipStream_t)stream);
-    return rc ? rc : after_launch();
-  }
-  rc = use_reg(p->n_qubits)
-           ? qc_reg_value_fwd(p, (const QcTrig*)trig, umat, angles, expval, B, (hipStream_t)stream)
-           : qc_wave_value_fwd(p, (const QcTrig*)trig, umat, angles, expval, B, nullptr, (hipStream_t)stream);
+  rc = p->fam->fwd(p, (const QcTrig*)trig, umat, angles, expval, B, 1, {ws, ws_bytes, false}, (hipStream_t)stream);
   return rc ? rc : after_launch();
 }
 
@@ -359,16 +381,8 @@ int qc_backward_expval(const qc_program* p, const void* trig, const float* umat,
   int rc = check_circuit(p, trig, umat, B);
   if (rc) return rc;
   if (!angles || !cot || !d_angles || !part || part_stride < p->n_params || row0 < 0) return QC_ERR_ARG;
-  if (use_hbm(p->n_qubits)) {
-    rc = qc_h2_backward(p, p->h2, (const QcTrig*)trig, umat, angles, cot, d_angles, part, part_stride, row0, B, 1, ws,
-                                    ws_bytes, false, (hipStream_t)stream);
-    return rc ? rc : after_launch();
-  }
-  rc = use_reg(p->n_qubits)
-           ? qc_reg_value_bwd(p, (const QcTrig*)trig, umat, angles, cot, d_angles, part, part_stride, row0, B,
-                              (hipStream_t)stream)
-           : qc_wave_value_bwd(p, (const QcTrig*)trig, umat, angles, cot, d_angles, part, part_stride, row0, B, nullptr,
-                               (hipStream_t)stream);
+  rc = p->fam->bwd(p, (const QcTrig*)trig, umat, angles, cot, d_angles, part, part_stride, row0, B, 1, {ws, ws_bytes, false},
+                   (hipStream_t)stream);
   return rc ? rc : after_launch();
 }
 
@@ -377,13 +391,7 @@ int qc_forward_jets(const qc_program* p, const void* trig, const float* umat, co
   int rc = check_circuit(p, trig, umat, B);
   if (rc) return rc;
   if (!ajets || !qjets) return QC_ERR_ARG;
-  if (use_hbm(p->n_qubits)) {
-    rc = qc_h2_forward(p, p->h2, (const QcTrig*)trig, umat, ajets, qjets, B, 6, ws, ws_bytes, false, (hipStream_t)stream);
-    return rc ? rc : after_launch();
-  }
-  rc = use_reg(p->n_qubits)
-           ? qc_reg_jets_fwd(p, (const QcTrig*)trig, umat, ajets, qjets, B, nullptr, (hipStream_t)stream)
-           : qc_wave_jets_fwd(p, (const QcTrig*)trig, umat, ajets, qjets, B, nullptr, (hipStream_t)stream);
+  rc = p->fam->fwd(p, (const QcTrig*)trig, umat, ajets, qjets, B, 6, {ws, ws_bytes, false}, (hipStream_t)stream);
   return rc ? rc : after_launch();
 }
 
@@ -393,16 +401,8 @@ int qc_backward_jets(const qc_program* p, const void* trig, const float* umat, c
   int rc = check_circuit(p, trig, umat, B);
   if (rc) return rc;
   if (!ajets || !qbar || !abar || !part || part_stride < p->n_params || row0 < 0) return QC_ERR_ARG;
-  if (use_hbm(p->n_qubits)) {
-    rc = qc_h2_backward(p, p->h2, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, 6, ws,
-                                    ws_bytes, false, (hipStream_t)stream);
-    return rc ? rc : after_launch();
-  }
-  rc = use_reg(p->n_qubits)
-           ? qc_reg_jets_bwd(p, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, nullptr,
-                             (hipStream_t)stream)
-           : qc_wave_jets_bwd(p, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, nullptr,
-                              (hipStream_t)stream);
+  rc = p->fam->bwd(p, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, 6, {ws, ws_bytes, false},
+                   (hipStream_t)stream);
   return rc ? rc : after_launch();
 }
 
@@ -413,8 +413,8 @@ int qc_forward_jets_keep(const qc_program* p, const void* trig, const float* uma
   int rc = check_circuit(p, trig, umat, B);
   if (rc) return rc;
   if (!ajets || !qjets || !chi) return QC_ERR_ARG;
-  if (!use_reg(p->n_qubits)) return QC_ERR_UNSUPPORTED;
-  rc = qc_reg_jets_fwd(p, (const QcTrig*)trig, umat, ajets, qjets, B, chi, (hipStream_t)stream);
+  if (p->fam != &qc_family_reg) return QC_ERR_UNSUPPORTED;
+  rc = p->fam->fwd(p, (const QcTrig*)trig, umat, ajets, qjets, B, 6, {chi, 0, true}, (hipStream_t)stream);
   return rc ? rc : after_launch();
 }
 
@@ -424,9 +424,9 @@ int qc_backward_jets_kept(const qc_program* p, const void* trig, const float* um
   int rc = check_circuit(p, trig, umat, B);
   if (rc) return rc;
   if (!ajets || !qbar || !abar || !part || !chi || part_stride < p->n_params || row0 < 0) return QC_ERR_ARG;
-  if (!use_reg(p->n_qubits)) return QC_ERR_UNSUPPORTED;
-  rc = qc_reg_jets_bwd(p, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, chi,
-                       (hipStream_t)stream);
+  if (p->fam != &qc_family_reg) return QC_ERR_UNSUPPORTED;
+  rc = p->fam->bwd(p, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, 6,
+                   {(void*)chi, 0, true}, (hipStream_t)stream);
   return rc ? rc : after_launch();
 }
 
@@ -519,8 +519,8 @@ int qc_sample_collocation(float* X_res, int64_t n_res, int64_t off_res, float* X
 // ---- merged residual + value stages of the fused step (register family, angle encoding)
 static bool merged_ok(const qc_step_desc* d) {
   static const bool no_merge = [] { const char* e = getenv("QC_NO_MERGE"); return e && e[0] == '1'; }();
-  return !no_merge && use_reg(d->n) && !d->prog->amplitude && d->B_res > 0 && d->B_val > 0 && d->circ_ws_dev &&
-         d->circ_ws_bytes >= qc_reg_chi_store_bytes(d->prog, d->B_res) && d->X_res_dev && d->ajets_res_dev &&
+  return !no_merge && d->prog->fam == &qc_family_reg && !d->prog->amplitude && d->B_res > 0 && d->B_val > 0 &&
+         d->circ_ws_dev && d->circ_ws_bytes >= qc_family_reg.store_bytes(d->prog, 6, d->B_res) && d->X_res_dev && d->ajets_res_dev &&
          d->qjets_res_dev && d->qbar_res_dev && d->abar_res_dev && d->X_val_dev && d->ajets_val_dev && d->qjets_val_dev &&
          d->qbar_val_dev && d->abar_val_dev;
 }
@@ -569,6 +569,38 @@ int qc_fused_step_stage(const qc_step_desc* d, int stage, void* stream) {
   return after_launch();
 }
 
+// One pipeline of the two-stream step: the value pipeline (nch = 1) or the residual pipeline (nch = 6)
+struct QcPipe {
+  const float* X;
+  float *ajets, *qjets, *qbar, *abar;
+  float *u, *ub;   // amplitude encoding: initial-amplitude jets and their cotangents, else null
+  int64_t B, row0;
+  int nch;
+  QcCircStore store;
+};
+
+// pre -> [amplitudes] -> circuit -> post -> circuit adjoint -> [amplitude adjoint] -> pre adjoint, on one stream
+static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st) {
+  const qc_program* p = d->prog;
+  const int n = d->n, H = d->H;
+  const QcTrig* trig = (const QcTrig*)d->trig_dev;
+  float* part_theta = d->part_dev + make_layout(H, n, d->n_theta).oTh;
+  if (!q.X || !q.ajets || !q.qjets || !q.qbar || !q.abar || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
+  int rc;
+  if ((rc = qc_pre_forward(q.X, d->params_dev, H, n, d->n_theta, q.ajets, q.B, q.nch, st))) return rc;
+  if (q.u && (rc = qc_amp_forward(q.ajets, q.u, n, q.B, q.nch, st))) return rc;
+  const float* cin = q.u ? q.u : q.ajets;
+  float* cout = q.u ? q.ub : q.abar;
+  if ((rc = p->fam->fwd(p, trig, d->umat_dev, cin, q.qjets, q.B, q.nch, q.store, st)) || (rc = after_launch())) return rc;
+  // abar is written only by the adjoint sweep below: its head serves as per-point cotangent scratch here
+  if ((rc = qc_post(2, q.X, d->params_dev, H, n, d->n_theta, &d->pde, q.qjets, q.abar, q.nch == 6 ? q.abar + q.B : nullptr,
+                    nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st))) return rc;
+  if ((rc = p->fam->bwd(p, trig, d->umat_dev, cin, q.qbar, cout, part_theta, d->part_stride, q.row0, q.B, q.nch, q.store, st)) ||
+      (rc = after_launch())) return rc;
+  if (q.u && (rc = qc_amp_backward(q.ajets, q.ub, q.abar, n, q.B, q.nch, st))) return rc;
+  return qc_pre_backward(q.X, d->params_dev, H, n, d->n_theta, q.abar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st);
+}
+
 int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream) {
   if (!d || !d->prog || !d->trig_dev || !d->params_dev || !d->part_dev || !d->flat_dev) return QC_ERR_ARG;
   const int n = d->n, H = d->H;
@@ -581,22 +613,11 @@ int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream)
   const int64_t rows = rows_res + rows_val;
   if (rows <= 0 || rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const QcTrig* trig = (const QcTrig*)d->trig_dev;
-  // amplitude encoding: the circuit kernels run on the initial-amplitude jets u(a) and return cotangents
-  // w.r.t. them; both live behind the circuit scratch in the step workspace
-  const bool amp = d->prog->amplitude != 0;
-  float *u_res = nullptr, *ub_res = nullptr, *u_val = nullptr, *ub_val = nullptr;
-  void* cws = d->circ_ws_dev;
-  size_t cws_bytes = d->circ_ws_bytes;
-  if (amp) {
-    if (!d->circ_ws_dev || d->circ_ws_bytes < qc_step_workspace_bytes(d->prog, d->B_res, d->B_val)) return QC_ERR_ARG;
-    char* base = (char*)d->circ_ws_dev + round256(step_circuit_bytes(d->prog, d->B_res));
-    const size_t rb = round256(sizeof(float) * 6 * n * (size_t)d->B_res), vb = round256(sizeof(float) * n * (size_t)d->B_val);
-    u_res = (float*)base; ub_res = (float*)(base + rb);
-    u_val = (float*)(base + 2 * rb); ub_val = (float*)(base + 2 * rb + vb);
-    cws_bytes = round256(step_circuit_bytes(d->prog, d->B_res));
-    if (cws_bytes == 0) cws = nullptr;
-  }
+  // amplitude encoding: the circuit kernels run on the initial-amplitude jets u(a) and return cotangents w.r.t. them,
+  // both kept in the step workspace
+  if (d->prog->amplitude && (!d->circ_ws_dev || d->circ_ws_bytes < qc_step_workspace_bytes(d->prog, d->B_res, d->B_val)))
+    return QC_ERR_ARG;
+  const QcStepLayout ws = step_layout(d->prog, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
 
   // (in the merged form below the first stage draws the points itself)
   const bool draw_in_stage = (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);
@@ -615,25 +636,10 @@ int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream)
     if ((rc = after_launch())) return rc;
   }
   if ((phases & QC_PHASE_GRADS) && !merged) {
+    if (!ws.fits) return QC_ERR_ARG;
     // the two pipelines are independent until the row reduction: fork the value pipeline onto a side
-    // stream (not for n >= 9, where both would share the HBM statevector workspace)
-    QcSide* side = (d->B_res > 0 && d->B_val > 0 && !use_hbm(n)) ? side_stream() : nullptr;
-    // n >= 9 (round-structured plan): residual and value tiles keep their own resident slots when the caller's
-    // workspace holds them all; otherwise both pipelines share the workspace and the adjoint pass recomputes
-    const bool h2 = use_hbm(n) && use_h2(d->prog);
-    bool h2_resident = false;
-    void *h2_res_ws = cws, *h2_val_ws = cws;
-    size_t h2_res_b = cws_bytes, h2_val_b = cws_bytes;
-    if (h2) {
-      if (!cws || cws_bytes < h2_min_bytes(d->prog)) return QC_ERR_ARG;
-      const size_t rb = h2_res_bytes(d->prog, d->B_res), vb = h2_val_bytes(d->prog, d->B_val);
-      h2_resident = cws_bytes >= rb + vb;
-      if (h2_resident) {
-        h2_res_b = rb;
-        h2_val_ws = (char*)cws + rb;
-        h2_val_b = vb;
-      }
-    }
+    // stream (not for the HBM family, where both may share the statevector workspace)
+    QcSide* side = (d->B_res > 0 && d->B_val > 0 && d->prog->fam != &qc_family_hbm) ? side_stream() : nullptr;
     hipStream_t sv = st;
     if (side) {
       if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
@@ -641,92 +647,12 @@ int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream)
       else
         sv = side->s;
     }
-    // lanes-as-amplitudes family, compile-time program, angle encoding: the value pipeline's final states are kept as
-    // well when the workspace holds both stores (behind the residual pipeline's)
-    float* wave_val_store = nullptr;
-    if (!use_reg(n) && use_wave(n) && !amp && cws && qc_wave_val_store_bytes(d->prog, d->B_val) > 0) {
-      const size_t rb = round256(qc_wave_chi_store_bytes(d->prog, d->B_res));
-      if (rb > 0 && cws_bytes >= rb + qc_wave_val_store_bytes(d->prog, d->B_val)) wave_val_store = (float*)((char*)cws + rb);
-    }
-    if (d->B_val > 0) {
-      if (!d->X_val_dev || !d->ajets_val_dev || !d->qjets_val_dev || !d->qbar_val_dev || !d->abar_val_dev)
-        return QC_ERR_ARG;
-      if ((rc = qc_pre_forward(d->X_val_dev, d->params_dev, H, n, d->n_theta, d->ajets_val_dev, d->B_val, 1, sv))) return rc;
-      if (amp && (rc = qc_amp_forward(d->ajets_val_dev, u_val, n, d->B_val, 1, sv))) return rc;
-      const float* cin_val = amp ? u_val : d->ajets_val_dev;
-      float* cout_val = amp ? ub_val : d->abar_val_dev;
-      if (h2) {
-        if ((rc = qc_h2_forward(d->prog, d->prog->h2, trig, d->umat_dev, cin_val, d->qjets_val_dev, d->B_val, 1, h2_val_ws, h2_val_b,
-                                h2_resident, sv))) return rc;
-      } else if (wave_val_store) {
-        if ((rc = qc_wave_value_fwd(d->prog, trig, d->umat_dev, cin_val, d->qjets_val_dev, d->B_val, wave_val_store, sv))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if ((rc = qc_forward_expval(d->prog, trig, d->umat_dev, cin_val, d->qjets_val_dev, d->B_val, cws, cws_bytes, sv))) return rc;
-      if ((rc = qc_post(2, d->X_val_dev, d->params_dev, H, n, d->n_theta, &d->pde, d->qjets_val_dev,
-                        d->abar_val_dev, nullptr, nullptr, nullptr, d->qbar_val_dev, d->part_dev, d->part_stride,
-                        rows_res, d->B_val, 1, sv))) return rc;
-      if (h2) {
-        if ((rc = qc_h2_backward(d->prog, d->prog->h2, trig, d->umat_dev, cin_val, d->qbar_val_dev, cout_val, d->part_dev + L.oTh,
-                                 d->part_stride, rows_res, d->B_val, 1, h2_val_ws, h2_val_b, h2_resident, sv))) return rc;
-      } else if (wave_val_store) {
-        if ((rc = qc_wave_value_bwd(d->prog, trig, d->umat_dev, cin_val, d->qbar_val_dev, cout_val, d->part_dev + L.oTh,
-                                    d->part_stride, rows_res, d->B_val, wave_val_store, sv))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if ((rc = qc_backward_expval(d->prog, trig, d->umat_dev, cin_val, d->qbar_val_dev, cout_val,
-                                          d->part_dev + L.oTh, d->part_stride, rows_res, d->B_val, cws, cws_bytes, sv))) return rc;
-      if (amp && (rc = qc_amp_backward(d->ajets_val_dev, ub_val, d->abar_val_dev, n, d->B_val, 1, sv))) return rc;
-      if ((rc = qc_pre_backward(d->X_val_dev, d->params_dev, H, n, d->n_theta, d->abar_val_dev, d->part_dev,
-                                d->part_stride, rows_res, d->B_val, 1, sv))) return rc;
-    }
-    if (d->B_res > 0) {
-      if (!d->X_res_dev || !d->ajets_res_dev || !d->qjets_res_dev || !d->qbar_res_dev || !d->abar_res_dev)
-        return QC_ERR_ARG;
-      if ((rc = qc_pre_forward(d->X_res_dev, d->params_dev, H, n, d->n_theta, d->ajets_res_dev, d->B_res, 6, st))) return rc;
-      // register family: keep the final states of the forward pass for the adjoint kernel of this step
-      float* chi_store = (use_reg(n) && cws && cws_bytes >= qc_reg_chi_store_bytes(d->prog, d->B_res)) ? (float*)cws : nullptr;
-      // lanes-as-amplitudes family, compile-time program: final states of the forward kernel kept for the adjoint kernel
-      float* wave_store = nullptr;
-      if (!use_reg(n) && use_wave(n) && cws && qc_wave_chi_store_bytes(d->prog, d->B_res) > 0 &&
-          cws_bytes >= qc_wave_chi_store_bytes(d->prog, d->B_res))
-        wave_store = (float*)cws;
-      if (amp && (rc = qc_amp_forward(d->ajets_res_dev, u_res, n, d->B_res, 6, st))) return rc;
-      const float* cin_res = amp ? u_res : d->ajets_res_dev;
-      float* cout_res = amp ? ub_res : d->abar_res_dev;
-      if (use_reg(n)) {
-        if ((rc = qc_reg_jets_fwd(d->prog, trig, d->umat_dev, cin_res, d->qjets_res_dev, d->B_res, chi_store, st)))
-          return rc;
-        if ((rc = after_launch())) return rc;
-      } else if (wave_store) {
-        if ((rc = qc_wave_jets_fwd(d->prog, trig, d->umat_dev, cin_res, d->qjets_res_dev, d->B_res, wave_store, st))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if (h2) {
-        if ((rc = qc_h2_forward(d->prog, d->prog->h2, trig, d->umat_dev, cin_res, d->qjets_res_dev, d->B_res, 6, h2_res_ws, h2_res_b,
-                                h2_resident, st))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if ((rc = qc_forward_jets(d->prog, trig, d->umat_dev, cin_res, d->qjets_res_dev, d->B_res, cws, cws_bytes, st)))
-        return rc;
-      // abar_res is written only by the adjoint sweep below: its head serves as cotangent scratch here
-      if ((rc = qc_post(2, d->X_res_dev, d->params_dev, H, n, d->n_theta, &d->pde, d->qjets_res_dev,
-                        d->abar_res_dev, d->abar_res_dev + d->B_res, nullptr, nullptr, d->qbar_res_dev, d->part_dev,
-                        d->part_stride, 0, d->B_res, 6, st))) return rc;
-      if (use_reg(n)) {
-        if ((rc = qc_reg_jets_bwd(d->prog, trig, d->umat_dev, cin_res, d->qbar_res_dev, cout_res,
-                                  d->part_dev + L.oTh, d->part_stride, 0, d->B_res, chi_store, st))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if (wave_store) {
-        if ((rc = qc_wave_jets_bwd(d->prog, trig, d->umat_dev, cin_res, d->qbar_res_dev, cout_res, d->part_dev + L.oTh,
-                                   d->part_stride, 0, d->B_res, wave_store, st))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if (h2) {
-        if ((rc = qc_h2_backward(d->prog, d->prog->h2, trig, d->umat_dev, cin_res, d->qbar_res_dev, cout_res, d->part_dev + L.oTh,
-                                 d->part_stride, 0, d->B_res, 6, h2_res_ws, h2_res_b, h2_resident, st))) return rc;
-        if ((rc = after_launch())) return rc;
-      } else if ((rc = qc_backward_jets(d->prog, trig, d->umat_dev, cin_res, d->qbar_res_dev, cout_res,
-                                        d->part_dev + L.oTh, d->part_stride, 0, d->B_res, cws, cws_bytes, st))) return rc;
-      if (amp && (rc = qc_amp_backward(d->ajets_res_dev, ub_res, d->abar_res_dev, n, d->B_res, 6, st))) return rc;
-      if ((rc = qc_pre_backward(d->X_res_dev, d->params_dev, H, n, d->n_theta, d->abar_res_dev, d->part_dev,
-                                d->part_stride, 0, d->B_res, 6, st))) return rc;
-    }
+    const QcPipe val = {d->X_val_dev, d->ajets_val_dev, d->qjets_val_dev, d->qbar_val_dev, d->abar_val_dev, ws.u_val,
+                        ws.ub_val, d->B_val, rows_res, 1, ws.val};
+    const QcPipe res = {d->X_res_dev, d->ajets_res_dev, d->qjets_res_dev, d->qbar_res_dev, d->abar_res_dev, ws.u_res,
+                        ws.ub_res, d->B_res, 0, 6, ws.res};
+    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv))) return rc;
+    if (d->B_res > 0 && (rc = run_pipeline(d, res, st))) return rc;
     if (side) {
       hipError_t e = hipEventRecord(side->join, sv);
       if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);

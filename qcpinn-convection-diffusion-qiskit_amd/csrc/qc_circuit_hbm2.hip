@@ -1120,20 +1120,11 @@ extern const int qc_static_h2_count;
 
 // the generated entry for this program, or -1.  QC_NO_STATIC=1: none; QC_H2S_RB=3|4: only entries of that geometry
 static int h2s_match(const qc_program* pg, int absorb) {
-  static const bool off = [] { const char* e = getenv("QC_NO_STATIC"); return e && e[0] == '1'; }();
   static const int want_rb = [] { const char* e = getenv("QC_H2S_RB"); return e ? atoi(e) : 0; }();
-  if (off) return -1;
   for (int i = 0; i < qc_static_h2_count; ++i) {
     const QcStaticH2Entry& e = qc_static_h2_table[i];
-    if (e.n_qubits != pg->n_qubits || e.n_gates != pg->n_gates || e.absorb != absorb) continue;
-    if (want_rb && e.rb != want_rb) continue;
-    bool same = true;
-    for (int g = 0; g < pg->n_gates && same; ++g) {
-      const QcGate& a = pg->h_gates[g];
-      const int* b = e.gates + 4 * g;
-      same = a.op == b[0] && a.ba == b[1] && a.bb == b[2] && a.slot == b[3];
-    }
-    if (same) return i;
+    if (e.absorb != absorb || (want_rb && e.rb != want_rb)) continue;
+    if (qc_static_match(pg, e.n_qubits, e.n_gates, e.gates)) return i;
   }
   return -1;
 }
@@ -1163,10 +1154,10 @@ static std::vector<int> h2s_enumerate_rz_runs(const H2Plan& P) {
   return desc;
 }
 
-void* qc_h2_create(const qc_program* pg, int absorb) {
+void* qc_h2_create(const qc_program* pg, int absorb, int amplitude) {
   QcH2* h = new QcH2();
   H2Dev& D = h->dev;
-  const int sid = pg->amplitude ? -1 : h2s_match(pg, absorb);   // (the generated programs embed angles)
+  const int sid = amplitude ? -1 : h2s_match(pg, absorb);   // (the generated programs embed angles)
   if (sid >= 0) {
     // the kernels were generated from the plan of the SAME planner at build time: trust them only if the plan built
     // now is identical, record by record
@@ -1486,15 +1477,23 @@ static int h2_run(const qc_program* pg, void* hp, const QcTrig* trig, const floa
   return QC_OK;
 }
 
-int qc_h2_forward(const qc_program* pg, void* hp, const QcTrig* trig, const float* umat, const float* ajets, float* qjets,
-                  int64_t B, int nch, void* ws, size_t ws_bytes, bool keep, hipStream_t st) {
-  if (nch == 6) return h2_run<6>(pg, hp, trig, umat, ajets, qjets, nullptr, nullptr, nullptr, 0, 0, B, ws, ws_bytes, keep, false, st);
-  return h2_run<1>(pg, hp, trig, umat, ajets, qjets, nullptr, nullptr, nullptr, 0, 0, B, ws, ws_bytes, keep, false, st);
-}
-int qc_h2_backward(const qc_program* pg, void* hp, const QcTrig* trig, const float* umat, const float* ajets, const float* qbar,
-                   float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* ws, size_t ws_bytes,
-                   bool resident, hipStream_t st) {
+// store.p / store.bytes: the scratch; store.keep: the forward pass keeps every tile resident, and the adjoint pass of the
+// same batch starts from them
+static int h2_fwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* in, float* out, int64_t B,
+                  int nch, QcCircStore ws, hipStream_t st) {
   if (nch == 6)
-    return h2_run<6>(pg, hp, trig, umat, ajets, nullptr, qbar, abar, part, part_stride, row0, B, ws, ws_bytes, false, resident, st);
-  return h2_run<1>(pg, hp, trig, umat, ajets, nullptr, qbar, abar, part, part_stride, row0, B, ws, ws_bytes, false, resident, st);
+    return h2_run<6>(pg, pg->h2, trig, umat, in, out, nullptr, nullptr, nullptr, 0, 0, B, ws.p, ws.bytes, ws.keep, false, st);
+  return h2_run<1>(pg, pg->h2, trig, umat, in, out, nullptr, nullptr, nullptr, 0, 0, B, ws.p, ws.bytes, ws.keep, false, st);
 }
+static int h2_bwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* in, const float* cot,
+                  float* d_in, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, QcCircStore ws,
+                  hipStream_t st) {
+  if (nch == 6)
+    return h2_run<6>(pg, pg->h2, trig, umat, in, nullptr, cot, d_in, part, part_stride, row0, B, ws.p, ws.bytes, false, ws.keep, st);
+  return h2_run<1>(pg, pg->h2, trig, umat, in, nullptr, cot, d_in, part, part_stride, row0, B, ws.p, ws.bytes, false, ws.keep, st);
+}
+// every tile of B points resident through forward and adjoint pass
+static size_t h2_store_bytes(const qc_program* pg, int nch, int64_t B) {
+  return B > 0 ? qc_h2_bytes(pg, pg->h2, nch, true, qc_ceil_div(B, 64)) : 0;
+}
+QcFamily qc_family_hbm = {h2_fwd, h2_bwd, h2_store_bytes};

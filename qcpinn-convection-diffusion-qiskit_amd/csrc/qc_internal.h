@@ -58,23 +58,43 @@ struct QcOptHyper {  // == qc_opt_hyper of the public header
   float w_res, w_bc, w_ic;  // loss = w_res*L_r + w_bc*L_bc + w_ic*L_ic   (2, 4, 2)
 };
 
-// ---- launchers, one group per .hip file
+// ---- circuit families: one record per kernel family, chosen once per program (qc_program_create)
+// Scratch and kept final states of one pipeline.  HBM family: `p`/`bytes` is the scratch, `keep` keeps every tile
+// resident from the forward pass to the adjoint pass of the same batch.  Register and wave families: `p` is the store
+// of the forward pass's final states when `keep` is set, else ignored (the adjoint pass recomputes them).
+struct QcCircStore {
+  void* p;
+  size_t bytes;
+  bool keep;
+};
+// `nch` = 1: expectation values of the angles (value pipeline); 6: jets of the angles (residual pipeline).
+struct QcFamily {
+  int (*fwd)(const qc_program*, const QcTrig*, const float* umat, const float* in, float* out, int64_t B, int nch,
+             QcCircStore, hipStream_t);
+  int (*bwd)(const qc_program*, const QcTrig*, const float* umat, const float* in, const float* cot, float* d_in,
+             float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, QcCircStore, hipStream_t);
+  size_t (*store_bytes)(const qc_program*, int nch, int64_t B);   // what `keep` needs; 0 = this family keeps nothing
+};
+// (not `const`: a const global with a constant initializer would be emitted for the device as well, where the host
+// launchers it points to do not exist)
+extern QcFamily qc_family_reg;    // registers, one lane per statevector: 2 <= n <= 5 (qc_circuit_reg.hip)
+extern QcFamily qc_family_wave;   // lanes as amplitudes: n = 1, 6..8 (qc_circuit_wave.hip)
+extern QcFamily qc_family_hbm;    // statevector tiles in HBM: n = 9..20 (qc_circuit_hbm2.hip)
+
+// the generated program whose rows (n_gates x (op, ba, bb, slot), device encoding) are this program's gates;
+// never with QC_NO_STATIC=1 (read once)
+bool qc_static_match(const qc_program* pg, int n_qubits, int n_gates, const int* rows);
 int qc_reg_match_static(const qc_program* pg);
-int qc_reg_value_fwd(const qc_program*, const QcTrig*, const float* umat, const float* angles, float* expval,
-                     int64_t B, hipStream_t);
-int qc_reg_value_bwd(const qc_program*, const QcTrig*, const float* umat, const float* angles, const float* cot,
-                     float* d_angles, float* part, int64_t part_stride, int64_t row0, int64_t B, hipStream_t);
-int qc_reg_jets_fwd(const qc_program*, const QcTrig*, const float* umat, const float* ajets, float* qjets,
-                    int64_t B, float* chi_store, hipStream_t);
-int qc_reg_jets_bwd(const qc_program*, const QcTrig*, const float* umat, const float* ajets, const float* qbar,
-                    float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, const float* chi_store,
-                    hipStream_t);
+int qc_wave_match_static(const qc_program* pg);
+// merged residual + value stages of the fused step (register family only)
 int qc_reg_circ_fwd_both(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, float* qjets,
                          int64_t Br, float* chi_store, const float* angles, float* expval, int64_t Bv, hipStream_t st);
 int qc_reg_circ_bwd_both(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets,
                          const float* qbar, float* abar, int64_t row0_r, int64_t Br, const float* chi_store,
                          const float* angles, const float* cot, float* d_angles, int64_t row0_v, int64_t Bv, float* part,
                          int64_t part_stride, hipStream_t st);
+
+// ---- launchers, one group per .hip file
 int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, float* ajr, float* ajv, int64_t Br, int64_t Bv,
                         int draw, int64_t n_ic, int64_t off_res, int64_t off_ic, int64_t off_bc, int64_t face_pts,
                         uint64_t seed, uint64_t step, hipStream_t st);
@@ -84,20 +104,6 @@ int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLa
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
                      int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st);
-size_t qc_reg_chi_store_bytes(const qc_program* pg, int64_t B);
-int qc_wave_match_static(const qc_program*);
-int qc_wave_value_fwd(const qc_program*, const QcTrig*, const float* umat, const float* angles, float* expval,
-                      int64_t B, float* value_store, hipStream_t);
-int qc_wave_value_bwd(const qc_program*, const QcTrig*, const float* umat, const float* angles, const float* cot,
-                      float* d_angles, float* part, int64_t part_stride, int64_t row0, int64_t B, const float* value_store,
-                      hipStream_t);
-size_t qc_wave_val_store_bytes(const qc_program* pg, int64_t B);
-int qc_wave_jets_fwd(const qc_program*, const QcTrig*, const float* umat, const float* ajets, float* qjets,
-                     int64_t B, float* chi_store, hipStream_t);
-int qc_wave_jets_bwd(const qc_program*, const QcTrig*, const float* umat, const float* ajets, const float* qbar,
-                     float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, const float* chi_store,
-                     hipStream_t);
-size_t qc_wave_chi_store_bytes(const qc_program* pg, int64_t B);
 int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t);
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
                    int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t);
@@ -118,16 +124,11 @@ int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hip
 int qc_sample_launch(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
                      int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step, hipStream_t);
 // HBM family, n >= 9 (qc_circuit_hbm2.hip, qc_circuit_h2s_kernels.h): all tiles of a batch resident when the workspace allows
-void* qc_h2_create(const qc_program* pg, int absorb);
+void* qc_h2_create(const qc_program* pg, int absorb, int amplitude);   // amplitude: the encoding the plan is built for
 void qc_h2_destroy(void* h2);
 int qc_h2_describe_gates(const QcGate* gates, int n_gates, int n_qubits, int absorb, int32_t* out, int cap);   // host only
 size_t qc_h2_bytes(const qc_program* pg, void* h2, int nch, bool backward, int64_t tiles);
 int64_t qc_h2_tiles_that_fit(const qc_program* pg, void* h2, int nch, bool backward, size_t ws_bytes);
-int qc_h2_forward(const qc_program* pg, void* h2, const QcTrig* trig, const float* umat, const float* ajets, float* qjets,
-                  int64_t B, int nch, void* ws, size_t ws_bytes, bool keep, hipStream_t st);
-int qc_h2_backward(const qc_program* pg, void* h2, const QcTrig* trig, const float* umat, const float* ajets, const float* qbar,
-                   float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* ws, size_t ws_bytes,
-                   bool resident, hipStream_t st);
 int qc_comm_allreduce(float* buf, int64_t count, void* comm, hipStream_t st);   // qc_comm.hip: RCCL sum, fp32, in place
 int qc_amp_fwd_launch(const float* a, float* u, int n, int64_t B, int nch, hipStream_t);
 int qc_amp_bwd_launch(const float* a, const float* ub, float* ab, int n, int64_t B, int nch, hipStream_t);

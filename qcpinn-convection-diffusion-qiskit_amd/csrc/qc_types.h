@@ -32,6 +32,7 @@ struct QcTrig {
 
 #define QC_MAX_DIAG_RUNS 8
 
+struct QcFamily;
 struct qc_program {
   int n_qubits;
   int n_gates;
@@ -48,4 +49,5 @@ struct qc_program {
                     // trig buffer (see qc_fill_diag_tables)
   int diag_g0[QC_MAX_DIAG_RUNS], diag_g1[QC_MAX_DIAG_RUNS];   // gate ranges [g0, g1) of those runs, or (d_diag_list set)
   int* d_diag_list;                                           // ranges of this device list of gate indices
+  const QcFamily* fam;  // the kernel family that runs this program (qc_internal.h), or null (n > 20: unsupported)
 };

@@ -127,25 +127,9 @@ class Circuit:
         return out
 
     def backward_expval(self, angles_nB: torch.Tensor, cot_nB: torch.Tensor):
-        a = a_in = _need(angles_nB, self.device, "angles")
-        if self.amplitude:
-            a = self._amp_fwd(a_in, 1)
+        a = _need(angles_nB, self.device, "angles")
         g = _need(cot_nB, self.device, "cotangent")
-        B = a.shape[1]
-        rows = (B + 63) // 64
-        P = max(self.n_params, 1)
-        part = torch.empty(rows, P, dtype=torch.float32, device=self.device)
-        d_angles = torch.empty_like(a)
-        st = _stream(self.device)
-        wp, wb = self.workspace(1, True, B)
-        L.check(self.lib.qc_backward_expval(self.handle, self.trig.data_ptr(), _ptr(self.umat), a.data_ptr(),
-                                            g.data_ptr(), d_angles.data_ptr(), part.data_ptr(), P, 0, B, wp, wb, st),
-                "qc_backward_expval")
-        d_theta = torch.empty(P, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, P, P, d_theta.data_ptr(), st), "qc_reduce_rows")
-        if self.amplitude:
-            d_angles = self._amp_bwd(a_in, d_angles, 1)
-        return d_angles, d_theta[: self.n_params]
+        return self._adjoint_reduced(a, g, 1)
 
     def forward_jets(self, ajets: torch.Tensor) -> torch.Tensor:
         a = _need(ajets, self.device, "angle jets")            # (6, n, B)
@@ -159,25 +143,34 @@ class Circuit:
         return out
 
     def backward_jets(self, ajets: torch.Tensor, qbar: torch.Tensor):
-        a = a_in = _need(ajets, self.device, "angle jets")
-        if self.amplitude:
-            a = self._amp_fwd(a_in, NCH)
+        a = _need(ajets, self.device, "angle jets")
         g = _need(qbar, self.device, "cotangent jets")
-        B = a.shape[2]
+        return self._adjoint_reduced(a, g, NCH)
+
+    def _adjoint_reduced(self, a: torch.Tensor, cot: torch.Tensor, nch: int):
+        B = a.shape[-1]
         rows = (B + 63) // 64
         P = max(self.n_params, 1)
         part = torch.empty(rows, P, dtype=torch.float32, device=self.device)
-        abar = torch.empty_like(a)
-        st = _stream(self.device)
-        wp, wb = self.workspace(NCH, True, B)
-        L.check(self.lib.qc_backward_jets(self.handle, self.trig.data_ptr(), _ptr(self.umat), a.data_ptr(),
-                                          g.data_ptr(), abar.data_ptr(), part.data_ptr(), P, 0, B, wp, wb, st),
-                "qc_backward_jets")
+        abar = self._adjoint(a, cot, part.data_ptr(), P, nch)
         d_theta = torch.empty(P, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, P, P, d_theta.data_ptr(), st), "qc_reduce_rows")
-        if self.amplitude:
-            abar = self._amp_bwd(a_in, abar, NCH)
+        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, P, P, d_theta.data_ptr(), _stream(self.device)),
+                "qc_reduce_rows")
         return abar, d_theta[: self.n_params]
+
+    def _adjoint(self, a: torch.Tensor, cot: torch.Tensor, part_ptr: int, stride: int, nch: int) -> torch.Tensor:
+        """Circuit adjoint over the B points of ``a`` (angles [n, B] for nch = 1, angle jets [6, n, B] for nch = 6): returns
+        the cotangent of ``a`` and writes one row of d/d(theta) per 64-point tile at ``part_ptr`` (row stride ``stride``)."""
+        B = a.shape[-1]
+        st = _stream(self.device)
+        wp, wb = self.workspace(nch, True, B)
+        cin = self._amp_fwd(a, nch) if self.amplitude else a
+        abar = torch.empty_like(a)
+        fn, name = (self.lib.qc_backward_expval, "qc_backward_expval") if nch == 1 else \
+            (self.lib.qc_backward_jets, "qc_backward_jets")
+        L.check(fn(self.handle, self.trig.data_ptr(), _ptr(self.umat), cin.data_ptr(), cot.data_ptr(), abar.data_ptr(),
+                   part_ptr, stride, 0, B, wp, wb, st), name)
+        return self._amp_bwd(a, abar, nch) if self.amplitude else abar
 
 
 class SolverEngine:
@@ -271,21 +264,7 @@ class SolverEngine:
         L.check(self.lib.qc_post(3 if ujets else 1, X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
                                  C.byref(pde), qjets.data_ptr(), None, None, _ptr(ub), _ptr(rb), qbar.data_ptr(),
                                  part.data_ptr(), self.NP, 0, B, nch, st), "qc_post(backward)")
-        abar = torch.empty_like(ajets)
-        th = part.data_ptr() + 4 * self.theta_off
-        c = self.circuit
-        wp, wb = c.workspace(nch, True, B)
-        cin = c._amp_fwd(ajets, nch) if c.amplitude else ajets
-        if nch == 1:
-            L.check(self.lib.qc_backward_expval(c.handle, c.trig.data_ptr(), _ptr(c.umat), cin.data_ptr(),
-                                                qbar.data_ptr(), abar.data_ptr(), th, self.NP, 0, B, wp, wb, st),
-                    "qc_backward_expval")
-        else:
-            L.check(self.lib.qc_backward_jets(c.handle, c.trig.data_ptr(), _ptr(c.umat), cin.data_ptr(),
-                                              qbar.data_ptr(), abar.data_ptr(), th, self.NP, 0, B, wp, wb, st),
-                    "qc_backward_jets")
-        if c.amplitude:
-            abar = c._amp_bwd(ajets, abar, nch)
+        abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, nch)
         L.check(self.lib.qc_pre_backward(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
                                          abar.data_ptr(), part.data_ptr(), self.NP, 0, B, nch, st),
                 "qc_pre_backward")
@@ -332,15 +311,7 @@ class SolverEngine:
         L.check(self.lib.qc_post_multi(3, self.flat.data_ptr(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
                                        qjets.data_ptr(), None, ub.data_ptr(), qbar.data_ptr(), part.data_ptr(), self.NP,
                                        partk.data_ptr(), KW, 0, B, st), "qc_post_multi(backward)")
-        abar = torch.empty_like(ajets)
-        th = part.data_ptr() + 4 * self.theta_off
-        c = self.circuit
-        wp, wb = c.workspace(NCH, True, B)
-        cin = c._amp_fwd(ajets, NCH) if c.amplitude else ajets
-        L.check(self.lib.qc_backward_jets(c.handle, c.trig.data_ptr(), _ptr(c.umat), cin.data_ptr(), qbar.data_ptr(),
-                                          abar.data_ptr(), th, self.NP, 0, B, wp, wb, st), "qc_backward_jets")
-        if c.amplitude:
-            abar = c._amp_bwd(ajets, abar, NCH)
+        abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, NCH)
         L.check(self.lib.qc_pre_backward(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
                                          abar.data_ptr(), part.data_ptr(), self.NP, 0, B, NCH, st), "qc_pre_backward")
         d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
