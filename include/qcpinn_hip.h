@@ -107,7 +107,9 @@ int qc_backward_jets_kept(const qc_program* prog, const void* trig_dev, const fl
                           int64_t B, const float* chi_dev, void* stream);
 
 /* ---- classical pre/post networks of DVPDESolver.forward (nn/DVPDESolver.py:37-51,81-110) with
- * the same channels.  nch = 6 (residual points) or 1 (boundary/initial points). */
+ * the same channels.  nch = 6 (residual points) or 1 (boundary/initial points).
+ * Supported shapes (qc_pre_*, qc_post, qc_post_multi and the fused step): 1 <= H <= 1024 hidden units and
+ * 1 <= n <= 16 qubits; any other H or n returns QC_ERR_ARG before anything is launched. */
 int qc_pre_forward(const float* X_dev /*[B][3]*/, const float* params_dev, int H, int n, int n_theta,
                    float* ajets_dev, int64_t B, int nch, void* stream);
 int qc_pre_backward(const float* X_dev, const float* params_dev, int H, int n, int n_theta,

@@ -45,6 +45,20 @@ def param_layout(H: int, n: int, n_theta: int) -> Dict[str, Tuple[int, Tuple[int
     return out
 
 
+# shapes the network kernels serve (check_mlp in csrc/qc_api.hip); the circuit families alone go to 20 qubits
+MLP_MAX_QUBITS = 16
+MLP_MAX_HIDDEN = 1024
+
+
+def check_network_shape(H: int, n: int) -> None:
+    """Raise ValueError, naming the limit, for a model the pre/post network kernels cannot run."""
+    if not 1 <= int(n) <= MLP_MAX_QUBITS:
+        raise ValueError(f"the network kernels (qc_pre_* / qc_post*) serve 1 .. {MLP_MAX_QUBITS} qubits, got {n}: "
+                         f"a DVPDESolver takes at most {MLP_MAX_QUBITS} qubits")
+    if not 1 <= int(H) <= MLP_MAX_HIDDEN:
+        raise ValueError(f"the network kernels (qc_pre_* / qc_post*) serve 1 .. {MLP_MAX_HIDDEN} hidden units, got {H}")
+
+
 class Circuit:
     """A device-resident gate program + its per-gate trig table and fixed-unitary table."""
 
@@ -184,6 +198,7 @@ class SolverEngine:
         self.device = circuit.device
         self.n = circuit.n
         self.H = int(hidden)
+        check_network_shape(self.H, self.n)
         self.n_theta = circuit.n_params
         self.layout = param_layout(self.H, self.n, self.n_theta)
         self.NP = self.layout["__total__"][0]

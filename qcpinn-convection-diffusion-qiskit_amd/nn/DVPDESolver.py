@@ -189,6 +189,7 @@ class DVPDESolver(nn.Module):
         # evaluation of the kernels per output; the fused TRAINING step and residual() are for K = 1
         self.n_out = self.classic_network[-1]
         hidden = self.classic_network[-2]
+        _engine.check_network_shape(hidden, self.num_qubits)
 
         # same construction order as the reference => same RNG consumption (nn/DVPDESolver.py:28-57)
         self.preprocessor = nn.Sequential(nn.Linear(self.classic_network[0], hidden), nn.Tanh(),
