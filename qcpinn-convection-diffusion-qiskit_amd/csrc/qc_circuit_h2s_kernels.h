@@ -249,6 +249,8 @@ __device__ __forceinline__ void h2s_gate(SV<RB> (&v)[KV], float (&gacc)[NPA], co
 template <class PL, int B0, int RB, int KV, bool BWD, int NPA>
 __device__ __forceinline__ void h2s_rz_run(SV<RB> (&v)[KV], float (&gacc)[NPA], const H2Args& A) {
   constexpr int R = 1 << RB, LEN = H2sRz<PL>::len_of(B0);
+  // the phase record of a run holds at most 8 gates (h2s_enumerate_rz_runs, k_h2s_round_phases)
+  static_assert(LEN <= 8, "fused RZ run longer than its phase record");
   const auto* P = h2_const(A.rph + H2sRz<PL>::ordinal(B0) * R);
   if constexpr (BWD) {
     float t[R];

@@ -17,35 +17,13 @@ import numpy as np
 import pytest
 import torch
 
-import mlp_reference as R
 from conftest import pkg
+from step_reference import reference_loss
 from test_gpu_solver import Log, base_args
 
 pytestmark = pytest.mark.gpu
 
 ADAM_FAST_MAX = 3072      # k_adam_fast serves NP + 3 <= 3 x 1024 (csrc/qc_optim.hip:adam_fast_ok)
-
-
-def _reference_loss(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, drop_unit=False):
-    from oracle import jets as oj
-    from oracle import statevector as sv
-    P = R.unpack(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
-    pde = dict(c_t=1.0, c_x=1.0, c_y=1.0, d_xx=0.01, d_yy=0.01, D=0.01, vx=1.0, vy=1.0, problem=0)
-    a = R.pre_jets(P, X_res, 6, drop_unit)
-    q = oj.qjets_from_ajets(a, theta, ansatz, n, haar)
-    u = R.post_jets(P, q, drop_unit)
-    l_r = (R.point_errors(u, X_res, pde, 6) ** 2).mean()
-    out = []
-    for Xv in (X_bc, X_ic):
-        av = R.pre_jets(P, Xv, 1, drop_unit)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar)[None]
-        uv = R.post_jets(P, qv, drop_unit)
-        out.append(((uv[0] - R.analytic_u(Xv)) ** 2).mean())
-    l_bc, l_ic = out
-    loss = 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic
-    grads = torch.autograd.grad(loss, [P[k] for k in R.NAMES])
-    return R.flatten(dict(zip(R.NAMES, grads)), H, n, n_theta), np.array([l_r.item(), l_bc.item(), l_ic.item()])
 
 
 CASES = [(1, {}, 200), (65, {}, 830), (129, {}, 200), (257, {}, 200), (1024, {}, 130),
@@ -81,12 +59,12 @@ def test_fused_step_at_other_widths_matches_fp64(H, over, batch, gpu_device, tmp
     from oracle import statevector as sv
     ql = model.quantum_layer
     haar = sv.haar_pair(ql.haar_seed1, ql.haar_seed2)     # the fixed two-wire unitaries of the seeded layer
-    want_g, want_parts = _reference_loss(flat0, H, n, n_theta, theta_shape, ansatz, haar, *Xs)
+    want_g, want_parts = reference_loss(flat0, H, n, n_theta, theta_shape, ansatz, haar, *Xs)
     gs = max(1.0, np.abs(want_g).max())
     assert np.abs(got[:NP] - want_g).max() < 2e-4 * gs, np.abs(got[:NP] - want_g).max() / gs
     assert np.abs(got[NP:] - want_parts).max() < 1e-4 * max(1.0, np.abs(want_parts).max()), (got[NP:], want_parts)
     # negative control: the reference without hidden unit H - 1 is told apart at this tolerance
-    mut_g, _ = _reference_loss(flat0, H, n, n_theta, theta_shape, ansatz, haar, *Xs, drop_unit=True)
+    mut_g, _ = reference_loss(flat0, H, n, n_theta, theta_shape, ansatz, haar, *Xs, drop_unit=True)
     assert np.abs(got[:NP] - mut_g).max() > 2e-4 * gs
 
     tr.fs.run(L.QC_PHASE_UPDATE)
