@@ -753,161 +753,101 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
 //            stored straight into the tile's partial row - one row entry has exactly one producing wave.
 // The lane = hidden-unit kernel (k_post_wg) recomputed pre-activations, tanh and cotangents per (hidden unit, point)
 // from LDS copies of the jets: ~130 wave-instructions per (point, 64 hidden lanes) for what costs 24 multiply-adds and
-// a few reductions here.  WPT = waves per tile: 4 (residual tiles: hidden units split four ways, partial sums meet in
-// LDS) or 1 (value tiles: one wave owns the tile, four tiles per block).
-template <int N, int NCH, int WPT>
-__device__ __forceinline__ void k_post_fused_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
-                                                   QcLayout L, QcPde pde, const float* __restrict__ qjets,
-                                                   float* __restrict__ out_u, float* __restrict__ out_res,
-                                                   float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
-                                                   int64_t row0, int64_t B, float* __restrict__ s_z) {
-  __shared__ float s_buf[WPT == 4 ? QC_MS : 1][WPT == 4 ? NCH * N : 1][64];
+// a few reductions here.  Residual tiles: k_post_fused6_body below; value tiles: this body.
+//
+// Value tiles (64 boundary / initial points, value channel only): TPB tiles per block, WPT = 4 / TPB waves per tile.
+// Wave k of a tile owns the hidden-unit quarters [k QPW, (k + 1) QPW) of the same quarter split as the four-wave kernels
+// (QPW = 4 / WPT quarters per wave), so u is still formed as (q0 + q1) + (q2 + q3) from the same quarter sums.  Per tile
+// the LDS holds s_g = [H][64] (the tanh values of phase A, overwritten in place by the pre-activation cotangents of
+// phase B) and the waves' u partials [WPT][64].  After phase B wave k forms qbar[i] for i = k, k + WPT, ... as ONE chain
+// of multiply-adds over m = 0 .. H - 1 from s_g: the same sums in the same order as a single wave walking every hidden
+// unit, so the tile's outputs - u, the loss sums, qbar and every row entry - do not depend on WPT.  A block's tiles past
+// the end of the batch skip the work but still meet the barriers.
+// Measured at BASELINE config 2 (merged stage isolated): 1 tile x 4 waves (683 blocks after the 1 024
+// residual blocks) 24.5 us, 2 tiles x 2 waves 27.4, 4 tiles x 1 wave (round 3) 27.9.
+constexpr int QC_POST_VALUE_TPB = 1;   // value tiles per block of the fused post stage
+
+template <int N, int TPB>
+__device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const float* __restrict__ X,
+                                                        const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                        const float* __restrict__ qjets, float* __restrict__ out_u,
+                                                        float* __restrict__ qbar, float* __restrict__ part,
+                                                        int64_t part_stride, int64_t row0, int64_t B,
+                                                        float* __restrict__ s_v) {
+  constexpr int WPT = QC_MS / TPB, QPW = QC_MS / WPT;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t tile = WPT == 4 ? bid : bid * 4 + wave;
-  if (WPT == 1 && tile * 64 >= B) return;
+  const int slot = wave / WPT, wt = wave % WPT;   // the block's tile, and this wave's place in it
+  const int64_t tile = bid * TPB + slot;
+  const bool tile_ok = tile * 64 < B;
   const int64_t p = tile * 64 + lane;
   const bool live = p < B;
   const int64_t pc = live ? p : B - 1;
-  float q[NCH][N];
+  float* s_g = s_v + (size_t)slot * (L.H + WPT) * 64;   // [H][64]
+  float* s_u = s_g + L.H * 64;                           // [WPT][64]
+  float q[N];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int i = 0; i < N; ++i) q[c][i] = qjets[((int64_t)c * N + i) * B + pc];
+  for (int i = 0; i < N; ++i) q[i] = qjets[(int64_t)i * B + pc];
   const float* W3 = prm + L.oW3;
   const float* b3 = prm + L.ob3;
   const float* W4 = prm + L.oW4;
   const int hq = (L.H + QC_MS - 1) / QC_MS;
-  const int m0 = WPT == 4 ? wave * hq : 0, m1 = WPT == 4 ? ((m0 + hq) < L.H ? (m0 + hq) : L.H) : L.H;
-  // ---------------- phase A
-  float u[NCH];
+  const int m0 = tile_ok ? wt * QPW * hq : 0;
+  const int m1 = !tile_ok ? 0 : ((m0 + QPW * hq) < L.H ? (m0 + QPW * hq) : L.H);
+  // ---------------- phase A: this wave's quarter sums of u; tanh values parked
+  float up[QPW];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) u[c] = 0.f;
-  if constexpr (WPT == 4) {
-    for (int m = m0; m < m1; ++m) {
-      float g[NCH];
+  for (int k = 0; k < QPW; ++k) {
+    up[k] = 0.f;
+    const int k0 = m0 + k * hq, k1 = (k0 + hq) < m1 ? (k0 + hq) : m1;
+    for (int m = k0; m < k1; ++m) {
+      float g = b3[m];
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        float sum = (c == 0) ? b3[m] : 0.f;
-#pragma unroll
-        for (int i = 0; i < N; ++i) sum = fmaf(W3[m * N + i], q[c][i], sum);
-        g[c] = sum;
-      }
-      const float z = qc_tanh(g[0]);
-      s_z[m * 64 + lane] = z;
-      const float w4 = W4[m];
-      u[0] = fmaf(w4, z, u[0]);
-      if constexpr (NCH == 6) {
-        const float d1 = 1.f - z * z, d2 = -2.f * z * d1;
-        u[1] = fmaf(w4, d1 * g[1], u[1]);
-        u[2] = fmaf(w4, d1 * g[2], u[2]);
-        u[3] = fmaf(w4, d1 * g[3], u[3]);
-        u[4] = fmaf(w4, d2 * g[2] * g[2] + d1 * g[4], u[4]);
-        u[5] = fmaf(w4, d2 * g[3] * g[3] + d1 * g[5], u[5]);
-      }
+      for (int i = 0; i < N; ++i) g = fmaf(W3[m * N + i], q[i], g);
+      const float z = qc_tanh(g);
+      s_g[m * 64 + lane] = z;
+      up[k] = fmaf(W4[m], z, up[k]);
     }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) s_buf[wave][c][lane] = u[c];
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      u[c] = (s_buf[0][c][lane] + s_buf[1][c][lane]) + (s_buf[2][c][lane] + s_buf[3][c][lane]);
-    __syncthreads();   // s_buf is reused for the qbar partials below
-  } else {
-    // one wave, all hidden units; the four quarter sums are formed and added as in the four-wave form
-    float up[QC_MS];
-#pragma unroll
-    for (int k = 0; k < QC_MS; ++k) {
-      up[k] = 0.f;
-      const int k0 = k * hq, k1 = (k0 + hq) < L.H ? (k0 + hq) : L.H;
-      for (int m = k0; m < k1; ++m) {
-        float g = b3[m];
-#pragma unroll
-        for (int i = 0; i < N; ++i) g = fmaf(W3[m * N + i], q[0][i], g);
-        up[k] = fmaf(W4[m], qc_tanh(g), up[k]);
-      }
-    }
-    u[0] = (up[0] + up[1]) + (up[2] + up[3]);
   }
-  u[0] += prm[L.ob4];
-  // ---------------- residual / error / loss sums / per-point cotangent
+  float u;
+  if constexpr (QPW == 4) u = (up[0] + up[1]) + (up[2] + up[3]);
+  else s_u[wt * 64 + lane] = QPW == 2 ? up[0] + up[1] : up[0];
+  __syncthreads();
+  if constexpr (WPT == 2) u = s_u[lane] + s_u[64 + lane];
+  if constexpr (WPT == 4) u = (s_u[lane] + s_u[64 + lane]) + (s_u[128 + lane] + s_u[192 + lane]);
+  u += prm[L.ob4];
+  // ---------------- error / loss sums / per-point cotangent (every wave of the tile needs ub0; wave 0 stores)
   const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   float* row = part + (row0 + tile) * part_stride;
-  float ub0 = 0.f, gsc = 0.f;
-  if constexpr (NCH == 6) {
-    const float res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
-    const float target = pde.problem == QC_PB_PURE_DIFFUSION ? 0.f : analytic_r(t, x, y, pde.D, pde.vx, pde.vy);
-    const float e = live ? res - target : 0.f;
-    gsc = pde.w_res * e;
-    if (wave == 0 || WPT == 1) {
-      const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
-      if (lane == 63) {
-        row[L.NP + 0] = ls;
-        row[L.NP + 1] = 0.f;
-        row[L.NP + 2] = 0.f;
-      }
-    }
-  } else {
-    const bool seg_a = p < pde.n_seg_a;
-    const float target = pde.problem == QC_PB_PURE_DIFFUSION ? (seg_a ? analytic_u_diffusion(t, x, y, pde.D) : 0.f)
-                                                             : analytic_u(t, x, y);
-    const float e = live ? u[0] - target : 0.f;
-    ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
-    if (wave == 0 || WPT == 1) {
-      const float la = qc_wave_sum_to_lane63(seg_a ? e * e * pde.inv_n_a : 0.f);
-      const float lb = qc_wave_sum_to_lane63(seg_a ? 0.f : e * e * pde.inv_n_b);
-      if (lane == 63) {
-        row[L.NP + 0] = 0.f;
-        row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
-        row[L.NP + 2] = la;
-      }
-    }
-  }
-  if (live && (wave == 0 || WPT == 1)) {   // the per-point cotangents (MODE 2 contract of qc_post)
-    out_u[p] = ub0;
-    if constexpr (NCH == 6) out_res[p] = gsc;
-  }
-  // d loss / d b4 = sum of the points' cotangents of u (zero for residual tiles: the loss sees u only through the residual)
-  if (wave == 0 || WPT == 1) {
+  const bool seg_a = p < pde.n_seg_a;
+  const float target = pde.problem == QC_PB_PURE_DIFFUSION ? (seg_a ? analytic_u_diffusion(t, x, y, pde.D) : 0.f)
+                                                           : analytic_u(t, x, y);
+  const float e = live ? u - target : 0.f;
+  const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
+  if (wt == 0 && tile_ok) {
+    const float la = qc_wave_sum_to_lane63(seg_a ? e * e * pde.inv_n_a : 0.f);
+    const float lb = qc_wave_sum_to_lane63(seg_a ? 0.f : e * e * pde.inv_n_b);
+    // d loss / d b4 = sum of the points' cotangents of u
     const float sb4 = qc_wave_sum_to_lane63(ub0);
-    if (lane == 63) row[L.ob4] = sb4;
-  }
-  // ---------------- phase B
-  float ub[NCH];
-  expand_ub<NCH>(ub, ub0, gsc, pde);
-  float qb[NCH][N];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int i = 0; i < N; ++i) qb[c][i] = 0.f;
-  for (int m = m0; m < m1; ++m) {
-    float g[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      if (WPT == 4 && c == 0) {   // only tanh(g_0) is needed, and that is parked
-        g[0] = 0.f;
-        continue;
-      }
-      float sum = (c == 0) ? b3[m] : 0.f;
-#pragma unroll
-      for (int i = 0; i < N; ++i) sum = fmaf(W3[m * N + i], q[c][i], sum);
-      g[c] = sum;
+    if (lane == 63) {
+      row[L.NP + 0] = 0.f;
+      row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
+      row[L.NP + 2] = la;
+      row[L.ob4] = sb4;
     }
-    const float z = WPT == 4 ? s_z[m * 64 + lane] : qc_tanh(g[0]);
-    float gb[NCH], gw4;
-    post_cotangents<N, NCH>(gb, gw4, g, ub, z, W4[m]);
+    if (live) out_u[p] = ub0;   // the per-point cotangent (MODE 2 contract of qc_post)
+  }
+  // ---------------- phase B over the same hidden units: weight gradients; gb parked in place of tanh
+  float ub[1];
+  expand_ub<1>(ub, ub0, 0.f, pde);
+  for (int m = m0; m < m1; ++m) {
+    const float g[1] = {0.f};   // post_cotangents reads no pre-activation for one channel
+    float gb[1], gw4;
+    post_cotangents<N, 1>(gb, gw4, g, ub, s_g[m * 64 + lane], W4[m]);
+    s_g[m * 64 + lane] = gb[0];
     float wg[N + 2];
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      const float w3 = W3[m * N + i];
-      float sum = 0.f;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        qb[c][i] = fmaf(w3, gb[c], qb[c][i]);
-        sum = fmaf(gb[c], q[c][i], sum);
-      }
-      wg[i] = sum;
-    }
+    for (int i = 0; i < N; ++i) wg[i] = fmaf(gb[0], q[i], 0.f);
     wg[N] = gb[0];
     wg[N + 1] = gw4;
     qc_wave_sum_multi_to_lane63<N + 2>(wg);
@@ -918,22 +858,14 @@ __device__ __forceinline__ void k_post_fused_body(const int64_t bid, const float
       row[L.oW4 + m] = wg[N + 1];
     }
   }
-  if constexpr (WPT == 4) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int i = 0; i < N; ++i) s_buf[wave][c * N + i][lane] = qb[c][i];
-    __syncthreads();
-    if (live) {
-      for (int f = wave; f < NCH * N; f += QC_MS)
-        qbar[(int64_t)f * B + p] = (s_buf[0][f][lane] + s_buf[1][f][lane]) + (s_buf[2][f][lane] + s_buf[3][f][lane]);
-    }
-  } else {
-    if (live) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int i = 0; i < N; ++i) qbar[((int64_t)c * N + i) * B + p] = qb[c][i];
+  __syncthreads();
+  // ---------------- qbar[i] = sum over m of W3[m][i] gb(m), one chain per i
+  if (live) {
+    const int mh = tile_ok ? L.H : 0;
+    for (int i = wt; i < N; i += WPT) {
+      float qb = 0.f;
+      for (int m = 0; m < mh; ++m) qb = fmaf(W3[m * N + i], s_g[m * 64 + lane], qb);
+      qbar[(int64_t)i * B + p] = qb;
     }
   }
 }
@@ -942,17 +874,23 @@ __device__ __forceinline__ void k_post_fused_body(const int64_t bid, const float
 // register PAIRS: channels (0,1), (2,3), (4,5) of the <Z> jets ride in the two halves of one 64-bit register, so
 //   g_c = sum_i W3[m][i] q_c[i],   qbar_c[i] += W3[m][i] gb_c,   sum_c gb_c q_c[i]
 // are v_pk_fma_f32 with a broadcast scalar weight: two multiply-adds per instruction at the issue cost of one and a
-// bit (csrc/qc_gates.h, tools/ubench/valu_issue.hip).  Same arithmetic as k_post_fused_body<N, 6, 4>, other order of the
-// sums over channel pairs in the weight-gradient products.
+// bit (csrc/qc_gates.h, tools/ubench/valu_issue.hip).  Other order of the sums over channel pairs in the weight-gradient
+// products than the scalar six-channel form.
+// LDS: one dynamic buffer s_dyn of qc_post_fused_lds() floats.  Through phase B it holds the parked tanh values
+// s_z = [H][64] and, behind them, the u-jet exchange [4][6][64]; once every wave is past phase B the qbar exchange
+// [4][6N][64] reuses it from the start (24 KiB at H = 50, n = 4, against 36.5 KiB unaliased: six blocks per CU, not
+// four).
 
 template <int N>
 __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                     QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                                     float* __restrict__ out_u, float* __restrict__ out_res,
                                                     float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
-                                                    int64_t row0, int64_t B, float* __restrict__ s_z) {
+                                                    int64_t row0, int64_t B, float* __restrict__ s_dyn) {
   constexpr int NCH = 6;
-  __shared__ float s_buf[QC_MS][NCH * N][64];
+  float* s_z = s_dyn;                                                        // [H][64]
+  float (*s_u)[NCH][64] = reinterpret_cast<float (*)[NCH][64]>(s_dyn + L.H * 64);   // [QC_MS][NCH][64]
+  float (*s_q)[NCH * N][64] = reinterpret_cast<float (*)[NCH * N][64]>(s_dyn);      // [QC_MS][NCH * N][64], after phase B
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t tile = bid;
@@ -999,12 +937,11 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
     u[5] = fmaf(w4, d2 * g2[1].y * g2[1].y + d1 * g2[2].y, u[5]);
   }
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) s_buf[wave][c][lane] = u[c];
+  for (int c = 0; c < NCH; ++c) s_u[wave][c][lane] = u[c];
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
-    u[c] = (s_buf[0][c][lane] + s_buf[1][c][lane]) + (s_buf[2][c][lane] + s_buf[3][c][lane]);
-  __syncthreads();   // s_buf is reused for the qbar partials below
+    u[c] = (s_u[0][c][lane] + s_u[1][c][lane]) + (s_u[2][c][lane] + s_u[3][c][lane]);
   u[0] += prm[L.ob4];
   // ---------------- residual / error / loss sums / per-point cotangent
   const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
@@ -1064,22 +1001,32 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
       row[L.oW4 + m] = wg[N + 1];
     }
   }
+  __syncthreads();   // every wave is done with s_z and s_u: the qbar partials overwrite them
 #pragma unroll
   for (int cp = 0; cp < 3; ++cp)
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-      s_buf[wave][(2 * cp) * N + i][lane] = qb2[cp][i].x;
-      s_buf[wave][(2 * cp + 1) * N + i][lane] = qb2[cp][i].y;
+      s_q[wave][(2 * cp) * N + i][lane] = qb2[cp][i].x;
+      s_q[wave][(2 * cp + 1) * N + i][lane] = qb2[cp][i].y;
     }
   __syncthreads();
   if (live) {
     for (int f = wave; f < NCH * N; f += QC_MS)
-      qbar[(int64_t)f * B + p] = (s_buf[0][f][lane] + s_buf[1][f][lane]) + (s_buf[2][f][lane] + s_buf[3][f][lane]);
+      qbar[(int64_t)f * B + p] = (s_q[0][f][lane] + s_q[1][f][lane]) + (s_q[2][f][lane] + s_q[3][f][lane]);
   }
 }
 
 // hidden widths the fused post kernel parks tanh values for (LDS: H x 64 floats per residual tile)
 constexpr int QC_POST_FUSED_MAXH = 128;
+
+// dynamic LDS bytes of the fused post kernels: residual tiles (k_post_fused6_body), value tiles (k_post_fused_value_body)
+static inline size_t qc_post_fused_lds_res(const QcLayout& L) {
+  const int a = L.H * 64 + QC_MS * 6 * 64, b = QC_MS * 6 * L.n * 64;
+  return (size_t)(a > b ? a : b) * sizeof(float);
+}
+static inline size_t qc_post_fused_lds_val(const QcLayout& L) {
+  return (size_t)QC_POST_VALUE_TPB * (L.H + QC_MS / QC_POST_VALUE_TPB) * 64 * sizeof(float);
+}
 
 template <int N, int NCH>
 __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
@@ -1088,7 +1035,7 @@ __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X,
                                                     float* __restrict__ part, int64_t part_stride, int64_t row0, int64_t B) {
   extern __shared__ float s_dyn[];
   if constexpr (NCH == 6) k_post_fused6_body<N>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, s_dyn);
-  else k_post_fused_body<N, 1, 1>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, s_dyn);
+  else k_post_fused_value_body<N, QC_POST_VALUE_TPB>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part, part_stride, row0, B, s_dyn);
 }
 
 // ================================================================== K outputs behind one shared network (Navier-Stokes)
@@ -1098,7 +1045,7 @@ __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X,
 // u_k,c = sum_m W4[k][m] f_c(m).  w4k = [K][H + 1] rows (W4[k][0..H-1], b4[k]); the W4 / b4 slots of the flat vector
 // are not read.  MODE 4: forward, out = [K][6][B].  MODE 3: reverse, ubar = [K][6][B] -> qbar [6][n][B], the tile's row
 // of the shared parameters (W3, b3) in `part` and of the last layer in `partk` ([rows][K * (H + 1)]).  lane = point;
-// weight gradients by wave reductions as in k_post_fused_body.
+// weight gradients by wave reductions as in k_post_fused6_body.
 constexpr int QC_KMAX = 4;
 
 template <int N, int MODE>
@@ -1296,15 +1243,17 @@ __global__ void __launch_bounds__(256) k_post_both(const float* __restrict__ prm
     k_post_value4<N>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B);
 }
 
+// fused post stage: here the residual tiles come first and the (shorter) value blocks fill the slots after them
 template <int N>
 __global__ void __launch_bounds__(256) k_post_fused_both(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
                                                          QcPostSeg v, float* __restrict__ part, int64_t part_stride,
-                                                         int n_val) {
+                                                         int n_res) {
   extern __shared__ float s_dyn[];
-  if ((int)blockIdx.x >= n_val)
-    k_post_fused6_body<N>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0, r.B, s_dyn);
+  if ((int)blockIdx.x < n_res)
+    k_post_fused6_body<N>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0, r.B, s_dyn);
   else
-    k_post_fused_body<N, 1, 1>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, nullptr, v.qbar, part, part_stride, v.row0, v.B, s_dyn);
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part,
+                                                  part_stride, v.row0, v.B, s_dyn);
 }
 
 template <int N>
@@ -1401,11 +1350,11 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
 #define LAUNCH_WG(NN, CC)                                                                               \
   hipLaunchKernelGGL((k_post_wg<NN, CC>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets,        \
                      ub_src, (CC == 6 ? rb_src : nullptr), part, part_stride, row0, B, HB, PS, gen)
-  /* the step's form (mode 2): one kernel, lane = point in both phases (k_post_fused_body); QC_POST_SPLIT=1 keeps the pair */ \
-#define LAUNCH_FUSED(NN, CC)                                                                            \
-  hipLaunchKernelGGL((k_post_fused<NN, CC>), dim3(CC == 6 ? tiles : qc_ceil_div(tiles, 4)), dim3(256),   \
-                     CC == 6 ? (size_t)L.H * 64 * sizeof(float) : 0, st, X, prm, L, pde, qjets, out_u,   \
-                     out_res, qbar, part, part_stride, row0, B)
+  /* the step's form (mode 2): one kernel, lane = point in both phases; QC_POST_SPLIT=1 keeps the pair */ \
+#define LAUNCH_FUSED(NN, CC)                                                                                         \
+  hipLaunchKernelGGL((k_post_fused<NN, CC>), dim3(CC == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)),           \
+                     dim3(256), CC == 6 ? qc_post_fused_lds_res(L) : qc_post_fused_lds_val(L), st, X, prm, L, pde,     \
+                     qjets, out_u, out_res, qbar, part, part_stride, row0, B)
 #define CALL(NN)                                                         \
   if (nch == 6) {                                                        \
     if (mode == 0) LAUNCH(NN, 6, 0);                                     \
@@ -1473,10 +1422,13 @@ int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, c
   const int nv4 = qc_ceil_div(nv, 4);   // point kernel: 4 value tiles per block, one per wave
   const QcPostSeg r = {Xr, qjr, ubr, rbr, qbr, row0_r, Br}, v = {Xv, qjv, ubv, nullptr, qbv, row0_v, Bv};
   const bool fused = post_fused_ok(L);
+  // fused: residual blocks, then value blocks of QC_POST_VALUE_TPB tiles; one dynamic LDS size serves both bodies
+  const int nvf = qc_ceil_div(nv, QC_POST_VALUE_TPB);
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L), shf = shr > shv ? shr : shv;
 #define CALL(NN)                                                                                                        \
   if (fused) {                                                                                                          \
-    hipLaunchKernelGGL((k_post_fused_both<NN>), dim3(nr + nv4), dim3(256), (size_t)L.H * 64 * sizeof(float), st, prm, L, \
-                       pde, r, v, part, part_stride, nv4);                                                              \
+    hipLaunchKernelGGL((k_post_fused_both<NN>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,            \
+                       part_stride, nr);                                                                                \
   } else {                                                                                                              \
     hipLaunchKernelGGL((k_post_both<NN>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride, nv4); \
     hipLaunchKernelGGL((k_post_wg_both<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride, \
