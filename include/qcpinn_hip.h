@@ -116,6 +116,22 @@ int qc_pre_backward(const float* X_dev, const float* params_dev, int H, int n, i
                     const float* abar_dev, float* part_dev, int64_t part_stride, int64_t row0, int64_t B,
                     int nch, void* stream);
 
+/* Output map of the pre network.  QC_ANGLE_MAP_TANH_PI: the encoder of trainer/train.py ends in Tanh and its circuit
+ * embeds RX(pi * tanh(v_i)) (:150-155, :206), so the angle jets are those of a = pi tanh(v), v the network's output:
+ * a = pi tau, a_k = pi s v_k, a_kk = pi s (v_kk - 2 tau v_k^2) with tau = tanh v, s = 1 - tau^2.  The reverse pass pulls
+ * the angle cotangents back through the map from the stored angle jets alone.  qc_pre_forward / qc_pre_backward are the
+ * QC_ANGLE_MAP_NONE case; the _map forms take the map explicitly, and the backward form the forward pass's angle jets
+ * (read only when the map is not the identity). */
+#define QC_ANGLE_MAP_NONE 0
+#define QC_ANGLE_MAP_TANH_PI 1
+int qc_pre_forward_map(const float* X_dev, const float* params_dev, int H, int n, int n_theta, int angle_map,
+                       float* ajets_dev, int64_t B, int nch, void* stream);
+int qc_pre_backward_map(const float* X_dev, const float* params_dev, int H, int n, int n_theta, int angle_map,
+                        const float* ajets_dev, const float* abar_dev, float* part_dev, int64_t part_stride, int64_t row0,
+                        int64_t B, int nch, void* stream);
+/* The map the fused step applies between this program's pre network and its embedding (default QC_ANGLE_MAP_NONE). */
+int qc_program_set_angle_map(qc_program* prog, int angle_map);
+
 typedef struct qc_pde {
   float D, vx, vy;        /* nn/pde.py:53-55 defaults 0.01, 1, 1: the constants of the analytic targets (mode 2) */
   /* operator coefficients, residual = c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy): with the sigma scalings of
@@ -125,16 +141,21 @@ typedef struct qc_pde {
   float inv_n_res;        /* 1/N for the logged MSE */
   float w_val_a, w_val_b; /* same for the value segments: a = IC (weight 2), b = BC (weight 4) */
   float inv_n_a, inv_n_b;
-  int problem;            /* analytic targets of mode 2: QC_PROBLEM_CONVECTION_DIFFUSION (0) or QC_PROBLEM_PURE_DIFFUSION (1) */
+  int problem;            /* analytic targets of mode 2: QC_PROBLEM_CONVECTION_DIFFUSION (0), QC_PROBLEM_PURE_DIFFUSION (1)
+                             or QC_PROBLEM_GAUSSIAN_PULSE (2) */
   int64_t n_seg_a;        /* leading value points that are IC points */
 } qc_pde;
 
 /* 0: trainer/diffusion_train.py + data/diffusion_dataset.py:20-38 (Gaussian u on IC and BC1 points, forcing
  *    term r incl. its -400 constant on residual points);
  * 1: the reference's second workload train_hybrid_qpinn.py:116-131,159-203: u = sin(pi x) sin(pi y) exp(-2 pi^2 D t)
- *    on IC points, 0 on the four boundary faces, residual target 0 (pure diffusion: set vx = vy = 0). */
+ *    on IC points, 0 on the four boundary faces, residual target 0 (pure diffusion: set vx = vy = 0);
+ * 2: trainer/train.py:55-93: the Gaussian pulse u = exp(-100((x-1/2)^2 + (y-1/2)^2)) e^{-t} (the u of problem 0) on IC and
+ *    BC points, residual target 0 (no forcing term).
+ * Any other id is refused (QC_ERR_ARG) by qc_post mode 2 and the fused step. */
 #define QC_PROBLEM_CONVECTION_DIFFUSION 0
 #define QC_PROBLEM_PURE_DIFFUSION 1
+#define QC_PROBLEM_GAUSSIAN_PULSE 2
 
 /* mode 0: qjets -> u [B], residual [B] (nn/pde.py:71);
  * mode 1: cotangents (ubar, rbar) [B] -> qbar jets + weight-gradient partial rows;
@@ -186,7 +207,10 @@ int qc_sample_collocation(float* X_res_dev, int64_t n_res, int64_t off_res, floa
                           int64_t off_ic, int64_t n_bc, int64_t off_bc, uint64_t seed, uint64_t step, void* stream);
 /* Same, with the boundary batch spread over the four faces x=0, x=1, y=0, y=1 in that order
  * (train_hybrid_qpinn.py:166-176,689-697): GLOBAL boundary point g lies on face g / bc_face_points.
- * bc_face_points = 0 is the single x=0 face of qc_sample_collocation. */
+ * bc_face_points = 0 is the single x=0 face of qc_sample_collocation.  bc_face_points = QC_BC_RANDOM_FACE: every
+ * boundary point lies on one of the four faces drawn uniformly at random, per point (trainer/train.py:118-135: t and
+ * the free coordinate stay uniform); the face comes from the same Philox draw as the point. */
+#define QC_BC_RANDOM_FACE (-1)
 int qc_sample_collocation_faces(float* X_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev, int64_t n_ic,
                                 int64_t off_ic, int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed,
                                 uint64_t step, void* stream);
@@ -214,7 +238,8 @@ typedef struct qc_step_desc {
   int64_t n_ic;                 /* leading IC points of the value batch (== pde.n_seg_a) */
   int64_t sample_off_res, sample_off_ic, sample_off_bc;
   uint64_t sample_seed, sample_step;
-  int64_t sample_bc_face_points; /* 0: BC batch on the x=0 face; > 0: four faces, see qc_sample_collocation_faces */
+  int64_t sample_bc_face_points; /* 0: BC batch on the x=0 face; > 0 or QC_BC_RANDOM_FACE: four faces, see
+                                    qc_sample_collocation_faces; smaller values are refused (QC_ERR_ARG) */
   void* circ_ws_dev; size_t circ_ws_bytes;   /* qc_step_workspace_bytes(prog, B_res, B_val); NULL/0 allowed for angle encoding at n <= 8 */
   /* data parallelism inside the library: a communicator of qc_comm_create (or NULL).  With it a call with
    * QC_PHASE_GRADS | QC_PHASE_UPDATE all-reduces flat_dev across the ranks between the two phases, on `stream`. */

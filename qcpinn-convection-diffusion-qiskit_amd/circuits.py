@@ -222,6 +222,32 @@ def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool) -
     return GateProgram(n_qubits, n_layers, q_ansatz, n_layers * P, use_haar, gates)
 
 
+ROT_RING = "rot_ring"      # GateProgram.q_ansatz of build_rot_ring_program (not a DVQuantumLayer ansatz)
+
+
+def build_rot_ring_program(n_qubits: int, n_layers: int) -> GateProgram:
+    """The circuit of the reference's ``trainer/train.py`` (``HybridPINN._build_quantum_layer``, :202-222) after its
+    ``RX(pi * tanh v_i)`` embedding: per layer, ``Rot(phi, theta, omega)`` on every wire (RZ(phi), then RY(theta), then
+    RZ(omega) in time order), then a ring of CNOTs ``(i, (i + 1) mod n)``.  No fixed unitaries, no final Hadamard.
+    ``weights[l, i, k]`` of the (L, n, 3) TorchLayer weight sits in slot ``l * 3n + 3i + k``."""
+    n, L = int(n_qubits), int(n_layers)
+    if n < 2:
+        raise ValueError(f"the CNOT ring needs at least 2 wires, got {n}")     # CNOT(0, 0) fails in the reference too
+    if L < 1:
+        raise ValueError(f"need at least one layer, got {L}")
+    gates: List[Gate] = []
+    for layer in range(L):
+        e = _Emitter(n, layer * 3 * n, 3 * n)
+        for q in range(n):
+            e.rot(OP_RZ, q)
+            e.rot(OP_RY, q)
+            e.rot(OP_RZ, q)
+        for q in range(n):
+            e.cnot(q, (q + 1) % n)
+        gates += e.gates
+    return GateProgram(n, L, ROT_RING, 3 * n * L, False, gates)
+
+
 def haar_unitaries(seed1: Optional[int], seed2: Optional[int]) -> Optional[np.ndarray]:
     """The two fixed 4x4 unitaries exactly as the reference draws them on every circuit call
     (``nn/DVQuantumLayer.py:203-207``): ``scipy.stats.unitary_group.rvs(4, RandomState(seed))``.

@@ -18,6 +18,7 @@ PROGRAMS = [
     ("cascade", 4, 1, True), ("cascade", 4, 2, True), ("layered", 4, 1, True), ("layered", 4, 2, True),
     ("cross_mesh", 4, 1, True), ("farhi", 4, 1, True), ("sim_circ_15", 4, 1, True), ("cascade", 4, 1, False),
     ("cascade", 5, 1, True), ("alternate", 5, 1, True), ("cascade", 3, 1, False), ("cascade", 2, 1, False),
+    (circuits.ROT_RING, 4, 2, False),      # trainer/train.py's Config default (circuits.build_rot_ring_program)
 ]
 # lanes-as-amplitudes family (n = 6..8): (ansatz, n_qubits, n_layers, haar)
 WAVE_PROGRAMS = [
@@ -113,6 +114,13 @@ FAMILIES = [
 ]
 
 
+def lower(spec):
+    """the gate program of one (ansatz, n_qubits, n_layers, haar) entry"""
+    if spec[0] == circuits.ROT_RING:
+        return circuits.build_rot_ring_program(spec[1], spec[2])
+    return circuits.build_program(*spec[:4])
+
+
 def write(path, text):
     if not os.path.exists(path) or open(path).read() != text:
         open(path, "w").write(text)
@@ -129,7 +137,7 @@ def main():
                  f'struct {fam["entry"]} {{ {fam["struct"]} }};']
         entries = []
         for i, spec in enumerate(fam["programs"]):
-            prog = circuits.build_program(*spec[:4])
+            prog = lower(spec)
             rows = device_rows(prog)
             launch, gates = f"qc_static_{tag}launch_{i}", f"qc_static_{tag}gates_{i}"
             p = fam["emit"](i, spec, prog, rows, gates)

@@ -10,8 +10,8 @@
 #include <mutex>
 
 static_assert(sizeof(QcPde) == sizeof(qc_pde), "qc_pde layout");
-static_assert(QC_PB_CONVECTION_DIFFUSION == QC_PROBLEM_CONVECTION_DIFFUSION && QC_PB_PURE_DIFFUSION == QC_PROBLEM_PURE_DIFFUSION,
-              "problem ids");
+static_assert(QC_PB_CONVECTION_DIFFUSION == QC_PROBLEM_CONVECTION_DIFFUSION && QC_PB_PURE_DIFFUSION == QC_PROBLEM_PURE_DIFFUSION &&
+              QC_PB_GAUSSIAN_PULSE == QC_PROBLEM_GAUSSIAN_PULSE, "problem ids");
 static_assert(sizeof(QcOptHyper) == sizeof(qc_opt_hyper), "qc_opt_hyper layout");
 
 static thread_local int g_last_hip = 0;
@@ -225,6 +225,20 @@ int qc_program_set_encoding(qc_program* p, int amplitude) {
   return QC_OK;
 }
 
+static bool angle_map_ok(int m) { return m == QC_ANGLE_MAP_NONE || m == QC_ANGLE_MAP_TANH_PI; }
+static bool problem_ok(int pb) { return pb >= QC_PROBLEM_CONVECTION_DIFFUSION && pb <= QC_PROBLEM_GAUSSIAN_PULSE; }
+// what the fused step's analytic targets and boundary draw accept (both step entry points check it, so the merged and
+// the two-stream forms refuse the same descriptors)
+static bool step_desc_ok(const qc_step_desc* d) {
+  return problem_ok(d->pde.problem) && d->sample_bc_face_points >= QC_BC_RANDOM_FACE;
+}
+
+int qc_program_set_angle_map(qc_program* p, int angle_map) {
+  if (!p || !angle_map_ok(angle_map)) return QC_ERR_ARG;
+  p->angle_map = angle_map;
+  return QC_OK;
+}
+
 int qc_amp_forward(const float* ajets, float* ujets, int n, int64_t B, int nch, void* stream) {
   if (!ajets || !ujets || n < 1 || n > 24 || B <= 0 || (nch != 1 && nch != 6)) return QC_ERR_ARG;
   qc_amp_fwd_launch(ajets, ujets, n, B, nch, (hipStream_t)stream);
@@ -435,23 +449,35 @@ static int check_mlp(int H, int n, int n_theta, int64_t B, int nch) {
   return QC_OK;
 }
 
-int qc_pre_forward(const float* X, const float* prm, int H, int n, int n_theta, float* ajets, int64_t B, int nch,
-                   void* stream) {
+int qc_pre_forward_map(const float* X, const float* prm, int H, int n, int n_theta, int angle_map, float* ajets, int64_t B,
+                       int nch, void* stream) {
   int rc = check_mlp(H, n, n_theta, B, nch);
   if (rc) return rc;
-  if (!X || !prm || !ajets) return QC_ERR_ARG;
-  rc = qc_mlp_pre_fwd(X, prm, make_layout(H, n, n_theta), ajets, B, nch, (hipStream_t)stream);
+  if (!X || !prm || !ajets || !angle_map_ok(angle_map)) return QC_ERR_ARG;
+  rc = qc_mlp_pre_fwd(X, prm, make_layout(H, n, n_theta), ajets, B, nch, (hipStream_t)stream, angle_map);
+  return rc ? rc : after_launch();
+}
+
+int qc_pre_forward(const float* X, const float* prm, int H, int n, int n_theta, float* ajets, int64_t B, int nch,
+                   void* stream) {
+  return qc_pre_forward_map(X, prm, H, n, n_theta, QC_ANGLE_MAP_NONE, ajets, B, nch, stream);
+}
+
+int qc_pre_backward_map(const float* X, const float* prm, int H, int n, int n_theta, int angle_map, const float* ajets,
+                        const float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream) {
+  int rc = check_mlp(H, n, n_theta, B, nch);
+  if (rc) return rc;
+  const QcLayout L = make_layout(H, n, n_theta);
+  if (!X || !prm || !abar || !part || part_stride < L.NP || row0 < 0 || !angle_map_ok(angle_map)) return QC_ERR_ARG;
+  if (angle_map != QC_ANGLE_MAP_NONE && !ajets) return QC_ERR_ARG;
+  rc = qc_mlp_pre_bwd(X, prm, L, abar, part, part_stride, row0, B, nch, (hipStream_t)stream, angle_map, ajets);
   return rc ? rc : after_launch();
 }
 
 int qc_pre_backward(const float* X, const float* prm, int H, int n, int n_theta, const float* abar, float* part,
                     int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream) {
-  int rc = check_mlp(H, n, n_theta, B, nch);
-  if (rc) return rc;
-  const QcLayout L = make_layout(H, n, n_theta);
-  if (!X || !prm || !abar || !part || part_stride < L.NP || row0 < 0) return QC_ERR_ARG;
-  rc = qc_mlp_pre_bwd(X, prm, L, abar, part, part_stride, row0, B, nch, (hipStream_t)stream);
-  return rc ? rc : after_launch();
+  return qc_pre_backward_map(X, prm, H, n, n_theta, QC_ANGLE_MAP_NONE, nullptr, abar, part, part_stride, row0, B, nch,
+                             stream);
 }
 
 int qc_post(int mode, const float* X, const float* prm, int H, int n, int n_theta, const qc_pde* pde,
@@ -461,6 +487,7 @@ int qc_post(int mode, const float* X, const float* prm, int H, int n, int n_thet
   if (rc) return rc;
   const QcLayout L = make_layout(H, n, n_theta);
   if (mode < 0 || mode > 4 || !X || !prm || !pde || !qjets) return QC_ERR_ARG;
+  if (mode == 2 && !problem_ok(pde->problem)) return QC_ERR_ARG;   // the analytic targets are defined for 0..2 only
   if (mode >= 3 && nch != 6) return QC_ERR_ARG;          // general jets: six channels only
   if (mode >= 1 && mode <= 3 && (!qbar || !part || row0 < 0 || part_stride < L.NP + (mode == 2 ? 3 : 0))) return QC_ERR_ARG;
   if (mode == 2 && (!out_u || (nch == 6 && !out_res))) return QC_ERR_ARG;  // per-point cotangent scratch
@@ -505,7 +532,8 @@ int qc_adam_step(float* flat, int NP, float* prm, float* m, float* v, void* stat
 int qc_sample_collocation_faces(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
                                 int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step,
                                 void* stream) {
-  if (n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0 || bc_face_points < 0) return QC_ERR_ARG;
+  if (n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0 || bc_face_points < QC_BC_RANDOM_FACE)
+    return QC_ERR_ARG;
   if ((n_res > 0 && !X_res) || (n_ic + n_bc > 0 && !X_val)) return QC_ERR_ARG;
   qc_sample_launch(X_res, n_res, off_res, X_val, n_ic, off_ic, n_bc, off_bc, bc_face_points, seed, step, (hipStream_t)stream);
   return after_launch();
@@ -537,7 +565,8 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
     case QC_STAGE_PRE_FWD:
       return qc_mlp_pre_fwd_both((float*)d->X_res_dev, (float*)d->X_val_dev, prm, L, d->ajets_res_dev, d->ajets_val_dev,
                                  d->B_res, d->B_val, draw ? 1 : 0, d->n_ic, d->sample_off_res, d->sample_off_ic,
-                                 d->sample_off_bc, d->sample_bc_face_points, d->sample_seed, d->sample_step, st);
+                                 d->sample_off_bc, d->sample_bc_face_points, d->sample_seed, d->sample_step, st,
+                                 d->prog->angle_map);
     case QC_STAGE_CIRCUIT_FWD:
       return qc_reg_circ_fwd_both(d->prog, trig, d->umat_dev, d->ajets_res_dev, d->qjets_res_dev, d->B_res, chi_store,
                                   d->ajets_val_dev, d->qjets_val_dev, d->B_val, st);
@@ -553,7 +582,8 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
                                   d->part_dev + L.oTh, d->part_stride, st);
     case QC_STAGE_PRE_BWD:
       return qc_mlp_pre_bwd_both((const float*)d->X_res_dev, (const float*)d->X_val_dev, prm, L, d->abar_res_dev,
-                                 d->abar_val_dev, d->part_dev, d->part_stride, 0, rows_res, d->B_res, d->B_val, st);
+                                 d->abar_val_dev, d->part_dev, d->part_stride, 0, rows_res, d->B_res, d->B_val, st,
+                                 d->prog->angle_map, d->ajets_res_dev, d->ajets_val_dev);
     default: return QC_ERR_ARG;
   }
 }
@@ -561,7 +591,7 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
 int qc_fused_step_stage(const qc_step_desc* d, int stage, void* stream) {
   if (!d || !d->prog || !d->trig_dev || !d->params_dev || !d->part_dev) return QC_ERR_ARG;
   if (d->prog->n_qubits != d->n || d->prog->n_params != d->n_theta) return QC_ERR_ARG;
-  if (stage < 0 || stage >= QC_STAGE_COUNT) return QC_ERR_ARG;
+  if (stage < 0 || stage >= QC_STAGE_COUNT || !step_desc_ok(d)) return QC_ERR_ARG;
   if (!merged_ok(d)) return QC_ERR_UNSUPPORTED;
   int rc = check_mlp(d->H, d->n, d->n_theta, d->B_res, 6);
   if (rc) return rc;
@@ -587,7 +617,7 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st) 
   float* part_theta = d->part_dev + make_layout(H, n, d->n_theta).oTh;
   if (!q.X || !q.ajets || !q.qjets || !q.qbar || !q.abar || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
   int rc;
-  if ((rc = qc_pre_forward(q.X, d->params_dev, H, n, d->n_theta, q.ajets, q.B, q.nch, st))) return rc;
+  if ((rc = qc_pre_forward_map(q.X, d->params_dev, H, n, d->n_theta, p->angle_map, q.ajets, q.B, q.nch, st))) return rc;
   if (q.u && (rc = qc_amp_forward(q.ajets, q.u, n, q.B, q.nch, st))) return rc;
   const float* cin = q.u ? q.u : q.ajets;
   float* cout = q.u ? q.ub : q.abar;
@@ -598,13 +628,14 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st) 
   if ((rc = p->fam->bwd(p, trig, d->umat_dev, cin, q.qbar, cout, part_theta, d->part_stride, q.row0, q.B, q.nch, q.store, st)) ||
       (rc = after_launch())) return rc;
   if (q.u && (rc = qc_amp_backward(q.ajets, q.ub, q.abar, n, q.B, q.nch, st))) return rc;
-  return qc_pre_backward(q.X, d->params_dev, H, n, d->n_theta, q.abar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st);
+  return qc_pre_backward_map(q.X, d->params_dev, H, n, d->n_theta, p->angle_map, q.ajets, q.abar, d->part_dev, d->part_stride,
+                             q.row0, q.B, q.nch, st);
 }
 
 int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream) {
   if (!d || !d->prog || !d->trig_dev || !d->params_dev || !d->part_dev || !d->flat_dev) return QC_ERR_ARG;
   const int n = d->n, H = d->H;
-  if (d->prog->n_qubits != n || d->prog->n_params != d->n_theta) return QC_ERR_ARG;
+  if (d->prog->n_qubits != n || d->prog->n_params != d->n_theta || !step_desc_ok(d)) return QC_ERR_ARG;
   int rc = check_mlp(H, n, d->n_theta, d->B_res > 0 ? d->B_res : 1, 6);
   if (rc) return rc;
   const QcLayout L = make_layout(H, n, d->n_theta);

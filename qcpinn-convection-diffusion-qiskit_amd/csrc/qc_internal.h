@@ -24,7 +24,8 @@ inline QcLayout qc_layout(int H, int n, int n_theta) {
   return L;
 }
 
-constexpr int QC_PB_CONVECTION_DIFFUSION = 0, QC_PB_PURE_DIFFUSION = 1;   // == QC_PROBLEM_* of the public header
+constexpr int QC_PB_CONVECTION_DIFFUSION = 0, QC_PB_PURE_DIFFUSION = 1,
+              QC_PB_GAUSSIAN_PULSE = 2;   // == QC_PROBLEM_* of the public header
 
 struct QcPde {  // == qc_pde of the public header
   float D, vx, vy;                 // physical constants: analytic targets of mode 2
@@ -95,18 +96,21 @@ int qc_reg_circ_bwd_both(const qc_program* pg, const QcTrig* trig, const float* 
                          int64_t part_stride, hipStream_t st);
 
 // ---- launchers, one group per .hip file
+// `map`: output map of the pre network (QC_ANGLE_MAP_*); its reverse pass reads the forward pass's angle jets aj / ajr / ajv
 int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, float* ajr, float* ajv, int64_t Br, int64_t Bv,
                         int draw, int64_t n_ic, int64_t off_res, int64_t off_ic, int64_t off_bc, int64_t face_pts,
-                        uint64_t seed, uint64_t step, hipStream_t st);
+                        uint64_t seed, uint64_t step, hipStream_t st, int map);
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
                         float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
-                        hipStream_t st);
+                        hipStream_t st, int map, const float* ajr, const float* ajv);
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
                      int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st);
-int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t);
+int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t,
+                   int map = 0);
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
-                   int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t);
+                   int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t, int map = 0,
+                   const float* aj = nullptr);
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t);

@@ -59,13 +59,67 @@ __device__ __forceinline__ float analytic_u_diffusion(float t, float x, float y,
   return sinf(pi * x) * sinf(pi * y) * expf(-2.f * pi * pi * D * t);
 }
 
+// targets of mode 2 by qc_pde.problem.  Residual: the forcing term r of problem 0, zero for problem 1 (pure diffusion) and
+// problem 2 (Gaussian pulse, trainer/train.py:62-93).  Value: the Gaussian pulse (analytic_u, the same function as
+// train.py:55-60) on every point of problems 0 and 2; problem 1 takes the diffusion mode on IC points, 0 on the faces.
+__device__ __forceinline__ float residual_target(const QcPde& pde, float t, float x, float y) {
+  return pde.problem != QC_PB_CONVECTION_DIFFUSION ? 0.f : analytic_r(t, x, y, pde.D, pde.vx, pde.vy);
+}
+__device__ __forceinline__ float value_target(const QcPde& pde, bool seg_a, float t, float x, float y) {
+  return pde.problem == QC_PB_PURE_DIFFUSION ? (seg_a ? analytic_u_diffusion(t, x, y, pde.D) : 0.f) : analytic_u(t, x, y);
+}
+
+// ================================================================== output map of the pre network
+// MAP = 1 (QC_ANGLE_MAP_TANH_PI): the third workload's encoder ends in Tanh and its circuit embeds RX(pi tanh v_i)
+// (trainer/train.py:150-155, :206), so the pre stage emits the jets of a = pi tanh(v) and its reverse pass pulls the angle
+// cotangents back through that map first.  MAP = 0 is the identity of the other workloads (same code as before).
+constexpr float QC_PI_F = 3.14159265358979323846f;
+
+// forward epilogue of one wire: network output jets v -> angle jets a, with tau = tanh v0 and s = 1 - tau^2:
+//   a0 = pi tau,  a_k = pi s v_k (k = t, x, y),  a_kk = pi s (v_kk - 2 tau v_k^2) (k = x, y)
+template <int NCH>
+__device__ __forceinline__ void angle_map_fwd(const float (&v)[NCH], float (&a)[NCH]) {
+  const float tau = qc_tanh(v[0]);
+  const float ps = QC_PI_F * (1.f - tau * tau);
+  a[0] = QC_PI_F * tau;
+  if constexpr (NCH == 6) {
+    a[1] = ps * v[1];
+    a[2] = ps * v[2];
+    a[3] = ps * v[3];
+    a[4] = ps * (v[4] - 2.f * tau * v[2] * v[2]);
+    a[5] = ps * (v[5] - 2.f * tau * v[3] * v[3]);
+  }
+}
+
+// reverse prologue of one wire: angle cotangents ab and the stored angle jets a -> cotangents vb of v.  It reads tau from
+// a0 / pi and never divides by s, so it stays finite where tanh saturates:
+//   vb_kk = pi s ab_kk,  vb_k = pi s ab_k - 4 tau a_k ab_kk (k = x, y),  vb_t = pi s ab_t,
+//   vb0 = pi s ab0 - 2 tau sum_{t,x,y} a_k ab_k - sum_{x,y} (2 tau a_kk + 2 a_k^2 / pi) ab_kk
+template <int NCH>
+__device__ __forceinline__ void angle_map_bwd(const float (&ab)[NCH], const float (&a)[NCH], float (&vb)[NCH]) {
+  const float tau = a[0] * (1.f / QC_PI_F);
+  const float ps = QC_PI_F * (1.f - tau * tau);
+  vb[0] = ps * ab[0];
+  if constexpr (NCH == 6) {
+    const float tt = 2.f * tau;
+    vb[1] = ps * ab[1];
+    vb[2] = ps * ab[2] - 2.f * tt * a[2] * ab[4];
+    vb[3] = ps * ab[3] - 2.f * tt * a[3] * ab[5];
+    vb[4] = ps * ab[4];
+    vb[5] = ps * ab[5];
+    vb[0] -= tt * (a[1] * ab[1] + a[2] * ab[2] + a[3] * ab[3]) +
+             (tt * a[4] + 2.f * a[2] * a[2] * (1.f / QC_PI_F)) * ab[4] +
+             (tt * a[5] + 2.f * a[3] * a[3] * (1.f / QC_PI_F)) * ab[5];
+  }
+}
+
 // ================================================================== pre network, forward jets
 // Block = 4 waves on ONE 64-point tile: lane = collocation point, wave w takes a quarter of the
 // hidden units (wave-uniform weights -> scalar loads); the four partial angle jets meet in LDS.
 // Four waves per tile (instead of one) keep >= 4 waves per SIMD in flight at B = 65 536.
 constexpr int QC_MS = 4;
 
-template <int N, int NCH>
+template <int N, int NCH, int MAP = 0, bool RF = false>
 __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                  QcLayout L, float* __restrict__ ajets, int64_t B,
                                                  const QcDraw* __restrict__ draw = nullptr, float* __restrict__ Xout = nullptr) {
@@ -80,7 +134,7 @@ __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* _
     // k_sample) and wave 0 leaves them in X for the later stages
     if (NCH == 6) qc_draw_point(0, draw->off_res + pc, 0, draw->seed, draw->step, t, x, y);
     else if (pc < draw->n_ic) qc_draw_point(1, draw->off_ic + pc, 0, draw->seed, draw->step, t, x, y);
-    else qc_draw_point(2, draw->off_bc + (pc - draw->n_ic), draw->face_pts, draw->seed, draw->step, t, x, y);
+    else qc_draw_point<RF>(2, draw->off_bc + (pc - draw->n_ic), draw->face_pts, draw->seed, draw->step, t, x, y);
     if (wave == 0 && p < B) {
       Xout[p * 3 + 0] = t;
       Xout[p * 3 + 1] = x;
@@ -127,28 +181,44 @@ __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* _
     for (int i = 0; i < N; ++i) s_part[wave][c * N + i][lane] = (c & 1) ? acc2[c >> 1][i].y : acc2[c >> 1][i].x;
   __syncthreads();
   if (p < B) {
-    for (int f = wave; f < NCH * N; f += QC_MS) {
-      float v = (s_part[0][f][lane] + s_part[1][f][lane]) + (s_part[2][f][lane] + s_part[3][f][lane]);
-      if (f < N) v += prm[L.ob2 + f];
-      ajets[(int64_t)f * B + p] = v;
+    if constexpr (MAP == 0) {
+      for (int f = wave; f < NCH * N; f += QC_MS) {
+        float v = (s_part[0][f][lane] + s_part[1][f][lane]) + (s_part[2][f][lane] + s_part[3][f][lane]);
+        if (f < N) v += prm[L.ob2 + f];
+        ajets[(int64_t)f * B + p] = v;
+      }
+    } else {
+      // the map mixes the channels of one wire: a wave finishes whole wires
+      for (int i = wave; i < N; i += QC_MS) {
+        float v[NCH], a[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int f = c * N + i;
+          v[c] = (s_part[0][f][lane] + s_part[1][f][lane]) + (s_part[2][f][lane] + s_part[3][f][lane]);
+        }
+        v[0] += prm[L.ob2 + i];
+        angle_map_fwd<NCH>(v, a);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) ajets[(int64_t)(c * N + i) * B + p] = a[c];
+      }
     }
   }
 }
 
-template <int N, int NCH>
+template <int N, int NCH, int MAP>
 __global__ void __launch_bounds__(256) k_pre_fwd(const float* __restrict__ X, const float* __restrict__ prm,
                                                  QcLayout L, float* __restrict__ ajets, int64_t B) {
-  k_pre_fwd_body<N, NCH>(blockIdx.x, X, prm, L, ajets, B);
+  k_pre_fwd_body<N, NCH, MAP>(blockIdx.x, X, prm, L, ajets, B);
 }
 
 // ================================================================== pre network, reverse pass
 // lane = hidden unit (each lane owns one row of W1 / column of W2, so weight gradients need no
 // cross-lane reduction).  The block's 64-point tile is staged in LDS and split over PS groups of HB
 // threads (16 points each, read as LDS broadcasts); the groups' accumulators meet in LDS.
-template <int N, int NCH>
+template <int N, int NCH, int MAP = 0>
 __device__ __forceinline__ void k_pre_bwd_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                           const float* __restrict__ abar, float* __restrict__ part, int64_t part_stride,
-                          int64_t row0, int64_t B, int HB, int PS) {
+                          int64_t row0, int64_t B, int HB, int PS, const float* __restrict__ aj = nullptr) {
   // six channels: the cotangents of channels (0,1), (2,3), (4,5) of one wire sit side by side in LDS (one 64-bit
   // broadcast read) and ride through the two contraction blocks as register pairs (packed multiply-adds)
   constexpr int NP2 = NCH == 6 ? 3 : 1;
@@ -161,12 +231,33 @@ __device__ __forceinline__ void k_pre_bwd_body(const int64_t bid, const float* _
     const int pp = i / 3, k = i % 3;
     sX[k][pp] = pp < cnt ? X[(base + pp) * 3 + k] : 0.f;
   }
-  for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
-    const int f = i >> 6, pp = i & 63;      // f = c * N + i
-    const int c = f / N, w = f % N;
-    const float v = pp < cnt ? abar[(int64_t)f * B + base + pp] : 0.f;
-    if (c & 1) sA2[(c >> 1) * N + w][pp].y = v;
-    else sA2[(c >> 1) * N + w][pp].x = v;
+  if constexpr (MAP == 0) {
+    for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
+      const int f = i >> 6, pp = i & 63;      // f = c * N + i
+      const int c = f / N, w = f % N;
+      const float v = pp < cnt ? abar[(int64_t)f * B + base + pp] : 0.f;
+      if (c & 1) sA2[(c >> 1) * N + w][pp].y = v;
+      else sA2[(c >> 1) * N + w][pp].x = v;
+    }
+  } else {
+    // angle cotangents pulled back through a = pi tanh(v) on load (angle_map_bwd), from the angle jets aj of the same
+    // points; the rest of the pass is the MAP = 0 pass on the cotangents of v
+    for (int i = threadIdx.x; i < N * 64; i += blockDim.x) {
+      const int w = i >> 6, pp = i & 63;
+      float ab[NCH], a[NCH], vb[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int64_t o = (int64_t)(c * N + w) * B + base + pp;
+        ab[c] = pp < cnt ? abar[o] : 0.f;
+        a[c] = pp < cnt ? aj[o] : 0.f;
+      }
+      angle_map_bwd<NCH>(ab, a, vb);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        if (c & 1) sA2[(c >> 1) * N + w][pp].y = vb[c];
+        else sA2[(c >> 1) * N + w][pp].x = vb[c];
+      }
+    }
   }
   __syncthreads();
 
@@ -262,11 +353,11 @@ __device__ __forceinline__ void k_pre_bwd_body(const int64_t bid, const float* _
   }
 }
 
-template <int N, int NCH>
+template <int N, int NCH, int MAP>
 __global__ void k_pre_bwd(const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                           const float* __restrict__ abar, float* __restrict__ part, int64_t part_stride,
-                          int64_t row0, int64_t B, int HB, int PS) {
-  k_pre_bwd_body<N, NCH>(blockIdx.x, X, prm, L, abar, part, part_stride, row0, B, HB, PS);
+                          int64_t row0, int64_t B, int HB, int PS, const float* __restrict__ aj) {
+  k_pre_bwd_body<N, NCH, MAP>(blockIdx.x, X, prm, L, abar, part, part_stride, row0, B, HB, PS, aj);
 }
 
 // ================================================================== post network + PDE + loss
@@ -417,7 +508,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
       const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
       float* row = part + (row0 + tile) * part_stride;
       if constexpr (NCH == 6) {
-        const float target = pde.problem == QC_PB_PURE_DIFFUSION ? 0.f : analytic_r(t, x, y, pde.D, pde.vx, pde.vy);
+        const float target = residual_target(pde, t, x, y);
         const float e = live ? res - target : 0.f;
         gsc = pde.w_res * e;
         if (wave == 0) {
@@ -430,9 +521,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
         }
       } else {
         const bool seg_a = p < pde.n_seg_a;
-        const float target = pde.problem == QC_PB_PURE_DIFFUSION
-                                 ? (seg_a ? analytic_u_diffusion(t, x, y, pde.D) : 0.f)
-                                 : analytic_u(t, x, y);
+        const float target = value_target(pde, seg_a, t, x, y);
         const float e = live ? u[0] - target : 0.f;
         ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
         if (wave == 0) {
@@ -633,7 +722,7 @@ __global__ void k_post_wg(const float* __restrict__ prm, QcLayout L, QcPde pde, 
 // split four ways with two LDS round trips: here each of a block's 4 waves owns one whole tile (all hidden units,
 // scalar weights, no LDS, no barrier).  Same arithmetic as the NCH = 1 instances of the kernels above; the four
 // per-quarter partial sums are still formed and added as (p0 + p1) + (p2 + p3) (same association as the m-split form).
-template <int N>
+template <int N, int MAP = 0, bool RF = false>
 __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                  QcLayout L, float* __restrict__ ajets, int64_t B,
                                                  const QcDraw* __restrict__ draw, float* __restrict__ Xout) {
@@ -646,7 +735,7 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
   float t, x, y;
   if (draw != nullptr && draw->enabled) {
     if (pc < draw->n_ic) qc_draw_point(1, draw->off_ic + pc, 0, draw->seed, draw->step, t, x, y);
-    else qc_draw_point(2, draw->off_bc + (pc - draw->n_ic), draw->face_pts, draw->seed, draw->step, t, x, y);
+    else qc_draw_point<RF>(2, draw->off_bc + (pc - draw->n_ic), draw->face_pts, draw->seed, draw->step, t, x, y);
     if (p < B) {
       Xout[p * 3 + 0] = t;
       Xout[p * 3 + 1] = x;
@@ -676,8 +765,17 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
   }
   if (p < B) {
 #pragma unroll
-    for (int i = 0; i < N; ++i)
-      ajets[(int64_t)i * B + p] = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) + prm[L.ob2 + i];
+    for (int i = 0; i < N; ++i) {
+      const float v = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) + prm[L.ob2 + i];
+      if constexpr (MAP == 0) {
+        ajets[(int64_t)i * B + p] = v;
+      } else {
+        const float vv[1] = {v};
+        float a[1];
+        angle_map_fwd<1>(vv, a);
+        ajets[(int64_t)i * B + p] = a[0];
+      }
+    }
   }
 }
 
@@ -723,8 +821,7 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
   const float u = ((up[0] + up[1]) + (up[2] + up[3])) + prm[L.ob4];
   const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   const bool seg_a = p < pde.n_seg_a;
-  const float target = pde.problem == QC_PB_PURE_DIFFUSION ? (seg_a ? analytic_u_diffusion(t, x, y, pde.D) : 0.f)
-                                                           : analytic_u(t, x, y);
+  const float target = value_target(pde, seg_a, t, x, y);
   const float e = live ? u - target : 0.f;
   const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
   const float la = qc_wave_sum_to_lane63(seg_a ? e * e * pde.inv_n_a : 0.f);
@@ -820,8 +917,7 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
   const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   float* row = part + (row0 + tile) * part_stride;
   const bool seg_a = p < pde.n_seg_a;
-  const float target = pde.problem == QC_PB_PURE_DIFFUSION ? (seg_a ? analytic_u_diffusion(t, x, y, pde.D) : 0.f)
-                                                           : analytic_u(t, x, y);
+  const float target = value_target(pde, seg_a, t, x, y);
   const float e = live ? u - target : 0.f;
   const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
   if (wt == 0 && tile_ok) {
@@ -947,7 +1043,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   float* row = part + (row0 + tile) * part_stride;
   const float res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
-  const float target = pde.problem == QC_PB_PURE_DIFFUSION ? 0.f : analytic_r(t, x, y, pde.D, pde.vx, pde.vy);
+  const float target = residual_target(pde, t, x, y);
   const float e = live ? res - target : 0.f;
   const float gsc = pde.w_res * e;
   if (wave == 0) {
@@ -1206,21 +1302,25 @@ __global__ void __launch_bounds__(256) k_post_multi(const float* __restrict__ pr
 // the value channel) are independent until the row reduction.  Launching each stage once over the blocks of BOTH
 // (the lighter value tiles first, so the launch ends on full-occupancy residual tiles; block-uniform branch) removes the side stream, its two
 // cross-queue event waits (~7 us of idle queue each) and 6 of the step's 15 launches.
-template <int N>
+// MAP: output map of the pre network (see angle_map_fwd); RF: boundary points on a random face (qc_philox.h)
+template <int N, int MAP, bool RF>
 __global__ void __launch_bounds__(256) k_pre_fwd_both(float* __restrict__ Xr, float* __restrict__ Xv,
                                                       const float* __restrict__ prm, QcLayout L, float* __restrict__ ajr,
                                                       float* __restrict__ ajv, int64_t Br, int64_t Bv, int n_val, QcDraw draw) {
-  if ((int)blockIdx.x >= n_val) k_pre_fwd_body<N, 6>(blockIdx.x - n_val, Xr, prm, L, ajr, Br, &draw, Xr);
-  else k_pre_fwd_value4<N>(blockIdx.x, Xv, prm, L, ajv, Bv, &draw, Xv);
+  if ((int)blockIdx.x >= n_val) k_pre_fwd_body<N, 6, MAP>(blockIdx.x - n_val, Xr, prm, L, ajr, Br, &draw, Xr);
+  else k_pre_fwd_value4<N, MAP, RF>(blockIdx.x, Xv, prm, L, ajv, Bv, &draw, Xv);
 }
 
-template <int N>
+// ajr / ajv: the angle jets the forward stage wrote (read with MAP = 1 only)
+template <int N, int MAP>
 __global__ void k_pre_bwd_both(const float* __restrict__ Xr, const float* __restrict__ Xv, const float* __restrict__ prm,
                                QcLayout L, const float* __restrict__ abr, const float* __restrict__ abv,
                                float* __restrict__ part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br,
-                               int64_t Bv, int HB, int PS, int n_val) {
-  if ((int)blockIdx.x >= n_val) k_pre_bwd_body<N, 6>(blockIdx.x - n_val, Xr, prm, L, abr, part, part_stride, row0_r, Br, HB, PS);
-  else k_pre_bwd_body<N, 1>(blockIdx.x, Xv, prm, L, abv, part, part_stride, row0_v, Bv, HB, PS);
+                               int64_t Bv, int HB, int PS, int n_val, const float* __restrict__ ajr,
+                               const float* __restrict__ ajv) {
+  if ((int)blockIdx.x >= n_val)
+    k_pre_bwd_body<N, 6, MAP>(blockIdx.x - n_val, Xr, prm, L, abr, part, part_stride, row0_r, Br, HB, PS, ajr);
+  else k_pre_bwd_body<N, 1, MAP>(blockIdx.x, Xv, prm, L, abv, part, part_stride, row0_v, Bv, HB, PS, ajv);
 }
 
 struct QcPostSeg {   // one pipeline's arguments of the fused (mode 2) post kernels
@@ -1304,30 +1404,36 @@ static inline bool post_fused_ok(const QcLayout& L) {
 }
 
 int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch,
-                   hipStream_t st) {
+                   hipStream_t st, int map) {
   const int grid = qc_ceil_div(B, 64);
-#define CALL(NN)                                                                                   \
-  if (nch == 6) hipLaunchKernelGGL((k_pre_fwd<NN, 6>), dim3(grid), dim3(256), 0, st, X, prm, L, ajets, B); \
-  else hipLaunchKernelGGL((k_pre_fwd<NN, 1>), dim3(grid), dim3(256), 0, st, X, prm, L, ajets, B);
+#define LAUNCH(NN, CC, MM) hipLaunchKernelGGL((k_pre_fwd<NN, CC, MM>), dim3(grid), dim3(256), 0, st, X, prm, L, ajets, B)
+#define CALL(NN)                                                     \
+  if (map) { if (nch == 6) LAUNCH(NN, 6, 1); else LAUNCH(NN, 1, 1); } \
+  else if (nch == 6) LAUNCH(NN, 6, 0);                               \
+  else LAUNCH(NN, 1, 0);
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
+#undef LAUNCH
   return QC_OK;
 }
 
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
-                   int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st) {
+                   int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, int map, const float* aj) {
   const int grid = qc_ceil_div(B, 64);
   if (L.H > 1024 || L.n > 64) return QC_ERR_UNSUPPORTED;
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
   const size_t sh = (size_t)PS * (4 + L.n) * HB * sizeof(float);
-#define CALL(NN)                                                                                               \
-  if (nch == 6) hipLaunchKernelGGL((k_pre_bwd<NN, 6>), dim3(grid), dim3(threads), sh, st, X, prm, L, abar, part, \
-                                   part_stride, row0, B, HB, PS);                                              \
-  else hipLaunchKernelGGL((k_pre_bwd<NN, 1>), dim3(grid), dim3(threads), sh, st, X, prm, L, abar, part,         \
-                          part_stride, row0, B, HB, PS);
+#define LAUNCH(NN, CC, MM)                                                                                       \
+  hipLaunchKernelGGL((k_pre_bwd<NN, CC, MM>), dim3(grid), dim3(threads), sh, st, X, prm, L, abar, part, part_stride, \
+                     row0, B, HB, PS, aj)
+#define CALL(NN)                                                     \
+  if (map) { if (nch == 6) LAUNCH(NN, 6, 1); else LAUNCH(NN, 1, 1); } \
+  else if (nch == 6) LAUNCH(NN, 6, 0);                               \
+  else LAUNCH(NN, 1, 0);
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
+#undef LAUNCH
   return QC_OK;
 }
 
@@ -1381,32 +1487,41 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
 // draw_*: when `draw` != 0 the launch first draws its own points (qc_sample_collocation_faces semantics) into Xr / Xv
 int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, float* ajr, float* ajv, int64_t Br, int64_t Bv,
                         int draw, int64_t n_ic, int64_t off_res, int64_t off_ic, int64_t off_bc, int64_t face_pts,
-                        uint64_t seed, uint64_t step, hipStream_t st) {
+                        uint64_t seed, uint64_t step, hipStream_t st, int map) {
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(qc_ceil_div(Bv, 64), 4);   // value tiles: 4 per block, one per wave
   QcDraw dr;
   dr.enabled = draw;
   dr.n_ic = n_ic; dr.off_res = off_res; dr.off_ic = off_ic; dr.off_bc = off_bc; dr.face_pts = face_pts;
   dr.seed = seed; dr.step = step;
-#define CALL(NN) \
-  hipLaunchKernelGGL((k_pre_fwd_both<NN>), dim3(nr + nv), dim3(256), 0, st, Xr, Xv, prm, L, ajr, ajv, Br, Bv, nv, dr);
+  const bool rf = draw && face_pts < 0;
+#define LAUNCH(NN, MM, RR) \
+  hipLaunchKernelGGL((k_pre_fwd_both<NN, MM, RR>), dim3(nr + nv), dim3(256), 0, st, Xr, Xv, prm, L, ajr, ajv, Br, Bv, nv, dr)
+#define CALL(NN)                                                           \
+  if (map) { if (rf) LAUNCH(NN, 1, true); else LAUNCH(NN, 1, false); }    \
+  else if (rf) LAUNCH(NN, 0, true);                                        \
+  else LAUNCH(NN, 0, false);
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
+#undef LAUNCH
   return QC_OK;
 }
 
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
                         float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
-                        hipStream_t st) {
+                        hipStream_t st, int map, const float* ajr, const float* ajv) {
   if (L.H > 1024 || L.n > 64) return QC_ERR_UNSUPPORTED;
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
   const size_t sh = (size_t)PS * (4 + L.n) * HB * sizeof(float);
-#define CALL(NN)                                                                                                   \
-  hipLaunchKernelGGL((k_pre_bwd_both<NN>), dim3(nr + nv), dim3(threads), sh, st, Xr, Xv, prm, L, abr, abv, part,    \
-                     part_stride, row0_r, row0_v, Br, Bv, HB, PS, nv);
+#define LAUNCH(NN, MM)                                                                                              \
+  hipLaunchKernelGGL((k_pre_bwd_both<NN, MM>), dim3(nr + nv), dim3(threads), sh, st, Xr, Xv, prm, L, abr, abv, part, \
+                     part_stride, row0_r, row0_v, Br, Bv, HB, PS, nv, ajr, ajv)
+#define CALL(NN) \
+  if (map) LAUNCH(NN, 1); else LAUNCH(NN, 0);
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
+#undef LAUNCH
   return QC_OK;
 }
 

@@ -28,7 +28,11 @@ __device__ __forceinline__ float u01(uint32_t v) { return (float)(v >> 8) * (1.0
 
 // segment 0: residual points in [0,1]^3; 1: IC points (t = 0); 2: boundary points: the x = 0 face
 // (trainer/diffusion_train.py:13-16), or with face_pts > 0 the four faces x=0, x=1, y=0, y=1 of the second
-// workload (train_hybrid_qpinn.py:166-176), face = global index / face_pts
+// workload (train_hybrid_qpinn.py:166-176), face = global index / face_pts.
+// RANDOM_FACE (face_pts < 0, QC_BC_RANDOM_FACE of the public header): each boundary point picks its face from the top
+// two bits of the fourth Philox word, which no coordinate uses (trainer/train.py:118-135: randint(0, 4) per point).
+// The launchers pick the instantiation from the sign of face_pts, so the other draws compile as before.
+template <bool RANDOM_FACE = false>
 __device__ __forceinline__ void qc_draw_point(int seg, int64_t gidx, int64_t face_pts, uint64_t seed, uint64_t step, float& t,
                                               float& x, float& y) {
   const U4 ctr = {(uint32_t)gidx, (uint32_t)(gidx >> 32), (uint32_t)step, (uint32_t)(step >> 32) ^ ((uint32_t)seg << 30)};
@@ -37,7 +41,7 @@ __device__ __forceinline__ void qc_draw_point(int seg, int64_t gidx, int64_t fac
   x = u01(r.y);
   y = u01(r.z);
   if (seg == 2) {
-    const int64_t face = face_pts > 0 ? gidx / face_pts : 0;
+    const int64_t face = RANDOM_FACE ? (int64_t)(r.w >> 30) : (face_pts > 0 ? gidx / face_pts : 0);
     if (face == 0) x = 0.f;
     else if (face == 1) x = 1.f;
     else if (face == 2) y = 0.f;

@@ -12,7 +12,9 @@ namespace {
 
 // segment 0: residual points in [0,1]^3; 1: IC points (t = 0); 2: boundary points: the x = 0 face
 // (trainer/diffusion_train.py:13-16), or with face_pts > 0 the four faces x=0, x=1, y=0, y=1 of the second
-// workload (train_hybrid_qpinn.py:166-176), face = global index / face_pts
+// workload (train_hybrid_qpinn.py:166-176), face = global index / face_pts; RF (face_pts < 0): a random face per
+// point (trainer/train.py:118-135, qc_philox.h)
+template <bool RF>
 __global__ void __launch_bounds__(256) k_sample(float* __restrict__ X_res, int64_t n_res, int64_t off_res,
                                                 float* __restrict__ X_val, int64_t n_ic, int64_t off_ic,
                                                 int64_t n_bc, int64_t off_bc, int64_t face_pts, uint64_t seed,
@@ -31,7 +33,7 @@ __global__ void __launch_bounds__(256) k_sample(float* __restrict__ X_res, int64
     return;
   }
   float t, x, y;
-  qc_draw_point(seg, gidx, face_pts, seed, step, t, x, y);
+  qc_draw_point<RF>(seg, gidx, face_pts, seed, step, t, x, y);
   dst[0] = t;
   dst[1] = x;
   dst[2] = y;
@@ -43,7 +45,11 @@ int qc_sample_launch(float* X_res, int64_t n_res, int64_t off_res, float* X_val,
                      int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step, hipStream_t st) {
   const int64_t total = n_res + n_ic + n_bc;
   if (total <= 0) return QC_OK;
-  hipLaunchKernelGGL(k_sample, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, n_res, off_res, X_val, n_ic,
-                     off_ic, n_bc, off_bc, bc_face_points, seed, step);
+  if (bc_face_points < 0)
+    hipLaunchKernelGGL(k_sample<true>, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, n_res, off_res, X_val, n_ic,
+                       off_ic, n_bc, off_bc, bc_face_points, seed, step);
+  else
+    hipLaunchKernelGGL(k_sample<false>, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, n_res, off_res, X_val, n_ic,
+                       off_ic, n_bc, off_bc, bc_face_points, seed, step);
   return QC_OK;
 }

@@ -50,4 +50,5 @@ struct qc_program {
   int diag_g0[QC_MAX_DIAG_RUNS], diag_g1[QC_MAX_DIAG_RUNS];   // gate ranges [g0, g1) of those runs, or (d_diag_list set)
   int* d_diag_list;                                           // ranges of this device list of gate indices
   const QcFamily* fam;  // the kernel family that runs this program (qc_internal.h), or null (n > 20: unsupported)
+  int angle_map;        // output map of the pre network that feeds this circuit in the fused step (QC_ANGLE_MAP_*)
 };

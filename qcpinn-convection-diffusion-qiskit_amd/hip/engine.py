@@ -63,7 +63,7 @@ class Circuit:
     """A device-resident gate program + its per-gate trig table and fixed-unitary table."""
 
     def __init__(self, program: GateProgram, haar: Optional[np.ndarray], device: torch.device,
-                 amplitude: bool = False):
+                 amplitude: bool = False, angle_map: int = L.QC_ANGLE_MAP_NONE):
         if device.type != "cuda":
             raise L.QcError("the HIP kernels need a GPU device (torch device type 'cuda' on ROCm); "
                             "there is no CPU fallback")
@@ -80,6 +80,11 @@ class Circuit:
         self.amplitude = bool(amplitude)
         if self.amplitude:
             L.check(self.lib.qc_program_set_encoding(self.handle, 1), "qc_program_set_encoding")
+        # output map of the pre network in front of this circuit (trainer/train.py: a = pi tanh v); the fused step reads
+        # it from the program, the separate entry points from SolverEngine.angle_map
+        self.angle_map = int(angle_map)
+        if self.angle_map != L.QC_ANGLE_MAP_NONE:
+            L.check(self.lib.qc_program_set_angle_map(self.handle, self.angle_map), "qc_program_set_angle_map")
         self.trig = torch.zeros(int(self.lib.qc_trig_bytes(self.handle)) // 4, dtype=torch.float32, device=device)
         self.umat = None
         if program.use_haar:
@@ -210,20 +215,32 @@ class SolverEngine:
         self.sigma = (1.0, 1.0, 1.0)                           # sigma_t, sigma_x, sigma_y of nn/pde.py:53-70
         self.coeffs = None      # explicit (c_t, c_x, c_y, d_xx, d_yy) of another linear operator on the same channels
         self.problem = L.QC_PROBLEM_CONVECTION_DIFFUSION      # analytic targets of the fused loss (qcpinn_hip.h)
+        self.loss_weights = (2.0, 4.0, 2.0)                    # (residual, BC, IC) weights of the fused loss
+        self.angle_map = circuit.angle_map                     # output map of the pre network, on every path
         self._fused: Dict[Tuple[int, int, int], "FusedStep"] = {}
 
     # ------------------------------------------------------------------ helpers
     def _pde(self, n_res=1, n_ic=1, n_bc=1, n_seg_a=0) -> L.QcPde:
-        # loss = 2*MSE_res + 4*MSE_bc + 2*MSE_ic (trainer/diffusion_train.py:47); d/d(err) = 2*w/N * err
+        # loss = 2*MSE_res + 4*MSE_bc + 2*MSE_ic (trainer/diffusion_train.py:47) by default; d/d(err) = 2*w/N * err
         # u_k/sigma_k and u_kk/sigma_k^2 (nn/pde.py:60-70) are scalings of channels the kernels already carry
         st, sx, sy = self.sigma
         co = self.coeffs if self.coeffs is not None else (1.0 / st, self.vx / sx, self.vy / sy, self.D / (sx * sx),
                                                           self.D / (sy * sy))
-        return L.QcPde(self.D, self.vx, self.vy, co[0], co[1], co[2], co[3], co[4], 4.0 / n_res, 1.0 / n_res, 4.0 / n_ic, 8.0 / n_bc,
-                       1.0 / n_ic, 1.0 / n_bc, self.problem, n_seg_a)
+        w_r, w_bc, w_ic = self.loss_weights
+        return L.QcPde(self.D, self.vx, self.vy, co[0], co[1], co[2], co[3], co[4], 2.0 * w_r / n_res, 1.0 / n_res,
+                       2.0 * w_ic / n_ic, 2.0 * w_bc / n_bc, 1.0 / n_ic, 1.0 / n_bc, self.problem, n_seg_a)
 
     def refresh_gates(self) -> None:
         self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
+
+    def _pre_forward(self, X, ajets, B, nch, st) -> None:
+        L.check(self.lib.qc_pre_forward_map(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, self.angle_map,
+                                            ajets.data_ptr(), B, nch, st), "qc_pre_forward_map")
+
+    def _pre_backward(self, X, ajets, abar, part, B, nch, st) -> None:
+        L.check(self.lib.qc_pre_backward_map(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
+                                             self.angle_map, ajets.data_ptr(), abar.data_ptr(), part.data_ptr(), self.NP, 0,
+                                             B, nch, st), "qc_pre_backward_map")
 
     def _X(self, X: torch.Tensor) -> torch.Tensor:
         X = _need(X, self.device, "collocation points")
@@ -241,8 +258,7 @@ class SolverEngine:
         if refresh:
             self.refresh_gates()
         ajets = torch.empty(nch, self.n, B, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_pre_forward(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
-                                        ajets.data_ptr(), B, nch, st), "qc_pre_forward")
+        self._pre_forward(X, ajets, B, nch, st)
         if nch == 1:
             qjets = self.circuit.forward_expval(ajets[0]).unsqueeze(0)
         else:
@@ -280,9 +296,7 @@ class SolverEngine:
                                  C.byref(pde), qjets.data_ptr(), None, None, _ptr(ub), _ptr(rb), qbar.data_ptr(),
                                  part.data_ptr(), self.NP, 0, B, nch, st), "qc_post(backward)")
         abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, nch)
-        L.check(self.lib.qc_pre_backward(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
-                                         abar.data_ptr(), part.data_ptr(), self.NP, 0, B, nch, st),
-                "qc_pre_backward")
+        self._pre_backward(X, ajets, abar, part, B, nch, st)
         d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
         L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st),
                 "qc_reduce_rows")
@@ -299,8 +313,7 @@ class SolverEngine:
         self.refresh_gates()
         w4k = _need(w4k, self.device, "last-layer rows")
         ajets = torch.empty(NCH, self.n, B, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_pre_forward(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
-                                        ajets.data_ptr(), B, NCH, st), "qc_pre_forward")
+        self._pre_forward(X, ajets, B, NCH, st)
         qjets = self.circuit.forward_jets(ajets)
         uj = torch.empty(K, NCH, B, dtype=torch.float32, device=self.device)
         L.check(self.lib.qc_post_multi(4, self.flat.data_ptr(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
@@ -327,8 +340,7 @@ class SolverEngine:
                                        qjets.data_ptr(), None, ub.data_ptr(), qbar.data_ptr(), part.data_ptr(), self.NP,
                                        partk.data_ptr(), KW, 0, B, st), "qc_post_multi(backward)")
         abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, NCH)
-        L.check(self.lib.qc_pre_backward(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
-                                         abar.data_ptr(), part.data_ptr(), self.NP, 0, B, NCH, st), "qc_pre_backward")
+        self._pre_backward(X, ajets, abar, part, B, NCH, st)
         d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
         L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st), "qc_reduce_rows")
         d_w4k = torch.empty(KW, dtype=torch.float32, device=self.device)
@@ -337,7 +349,8 @@ class SolverEngine:
 
     # ------------------------------------------------------------------ fused training step
     def fused(self, B_res: int, n_ic: int, n_bc: int, opt: "OptimState", counts=None) -> "FusedStep":
-        key = (B_res, n_ic, n_bc, id(opt), counts, self.problem, self.D, self.vx, self.vy, self.sigma, self.coeffs)
+        key = (B_res, n_ic, n_bc, id(opt), counts, self.problem, self.D, self.vx, self.vy, self.sigma, self.coeffs,
+               self.loss_weights)
         if key not in self._fused:
             self._fused[key] = FusedStep(self, B_res, n_ic, n_bc, opt, counts)
         return self._fused[key]
@@ -348,7 +361,10 @@ class OptimState:
     optimiser kernel advances (trainer/diffusion_train.py:81-90 without host round trips)."""
 
     def __init__(self, NP: int, lr: float, device, hist_cap: int = 0, betas=(0.9, 0.999), eps=1e-8,
-                 max_norm=1.0, factor=0.9, patience=1000, threshold=1e-4, min_lr=0.0, sched_eps=1e-8):
+                 max_norm=1.0, factor=0.9, patience=1000, threshold=1e-4, min_lr=0.0, sched_eps=1e-8,
+                 loss_weights=(2.0, 4.0, 2.0)):
+        """``max_norm`` None: no gradient clipping (+inf: the kernel's clip coefficient is then 1).  ``loss_weights``:
+        (residual, BC, IC) weights of the logged loss (trainer/diffusion_train.py:47 by default)."""
         self.device = device
         self.m = torch.zeros(NP, dtype=torch.float32, device=device)
         self.v = torch.zeros(NP, dtype=torch.float32, device=device)
@@ -358,8 +374,9 @@ class OptimState:
         self.state = torch.from_numpy(rec).to(device)
         self.hist = torch.zeros(max(hist_cap, 1), dtype=torch.float32, device=device)
         self.hist_cap = hist_cap
+        max_norm = float("inf") if max_norm is None else max_norm
         self.hyper = L.QcOptHyper(betas[0], betas[1], eps, max_norm, factor, threshold, min_lr, sched_eps,
-                                  patience, 2.0, 4.0, 2.0)
+                                  patience, *loss_weights)
 
     def read(self) -> dict:
         raw = self.state.cpu().numpy()

@@ -27,10 +27,13 @@ EXPORTS = (
     "qc_backward_jets", "qc_forward_jets_keep", "qc_backward_jets_kept", "qc_pre_forward", "qc_pre_backward", "qc_post", "qc_reduce_rows", "qc_adam_step",
     "qc_sample_collocation", "qc_sample_collocation_faces", "qc_step_workspace_bytes", "qc_fused_pinn_residual_step",
     "qc_fused_step_stage", "qc_post_multi", "qc_comm_unique_id", "qc_comm_create", "qc_comm_destroy", "qc_allreduce_grads",
+    "qc_pre_forward_map", "qc_pre_backward_map", "qc_program_set_angle_map",
 )
 
 
-QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION = 0, 1      # qc_pde.problem
+QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_PULSE = 0, 1, 2      # qc_pde.problem
+QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
+QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
 
 
 class QcError(RuntimeError):
@@ -112,6 +115,9 @@ def load() -> C.CDLL:
     lib.qc_backward_jets_kept.argtypes = [vp, vp, fp, fp, fp, fp, fp, i64, i64, i64, fp, vp]
     lib.qc_pre_forward.argtypes = [fp, fp, i32, i32, i32, fp, i64, i32, vp]
     lib.qc_pre_backward.argtypes = [fp, fp, i32, i32, i32, fp, fp, i64, i64, i64, i32, vp]
+    lib.qc_pre_forward_map.argtypes = [fp, fp, i32, i32, i32, i32, fp, i64, i32, vp]
+    lib.qc_pre_backward_map.argtypes = [fp, fp, i32, i32, i32, i32, fp, fp, fp, i64, i64, i64, i32, vp]
+    lib.qc_program_set_angle_map.argtypes = [vp, i32]
     lib.qc_post.argtypes = [i32, fp, fp, i32, i32, i32, C.POINTER(QcPde), fp, fp, fp, fp, fp, fp, fp, i64, i64,
                             i64, i32, vp]
     lib.qc_post_multi.argtypes = [i32, fp, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, i64, fp, i64, i64, i64, vp]

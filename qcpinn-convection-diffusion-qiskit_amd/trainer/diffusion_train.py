@@ -74,10 +74,15 @@ class FusedTrainer:
     like the reference (IC -> BC -> residual)."""
 
     def __init__(self, model, batch_size: int, capacity: int, sampler: str = "device", *, n_bc: int = None,
-                 bc_faces: int = 1, pde: dict = None):
-        """``n_bc`` (default ``batch_size // 3``): GLOBAL boundary points per step; ``bc_faces`` = 4 spreads them
-        evenly over the faces x=0, x=1, y=0, y=1 (second workload, train_hybrid_qpinn.py:689-697) instead of
-        the x=0 face; ``pde`` = {"D", "vx", "vy", "problem"} overrides the engine's operator / targets."""
+                 bc_faces=1, pde: dict = None, n_ic: int = None, loss_weights=(2.0, 4.0, 2.0), max_norm=1.0,
+                 optimizer=None, scheduler=None):
+        """``n_bc`` / ``n_ic`` (default ``batch_size // 3`` each): GLOBAL boundary / initial points per step;
+        ``bc_faces`` = 4 spreads the boundary points evenly over the faces x=0, x=1, y=0, y=1 (second workload,
+        train_hybrid_qpinn.py:689-697), ``"random"`` puts each on a face drawn at random (trainer/train.py:118-135),
+        instead of the x=0 face; ``pde`` = {"D", "vx", "vy", "problem"} overrides the engine's operator / targets;
+        ``loss_weights`` = (residual, BC, IC) weights of the loss; ``max_norm`` None: no gradient clipping;
+        ``optimizer`` / ``scheduler``: the torch objects the device state starts from and is mirrored into (default:
+        the model's own)."""
         # the fused step is the 3-D convection-diffusion step of trainer/diffusion_train.py:30-49 on a (t, x, y) -> u model;
         # the reference fails on any other shape (Linear(3, H) weight mismatch), and so does this trainer: a two-input
         # model keeps a zero-padded t column in W1 that the step would train, a K-output model has K last-layer rows
@@ -92,18 +97,23 @@ class FusedTrainer:
         self.eng = model._engine_for(dev)
         self.eng.sigma = (1.0, 1.0, 1.0)          # the trainers call the operator with its default scalings
         self.eng.coeffs = None
+        self.eng.loss_weights = tuple(float(w) for w in loss_weights)
         if pde:
             self.eng.D, self.eng.vx, self.eng.vy = float(pde["D"]), float(pde["vx"]), float(pde["vy"])
             self.eng.problem = int(pde["problem"])
+        self.optimizer = model.optimizer if optimizer is None else optimizer
+        self.scheduler = model.scheduler if scheduler is None else scheduler
+        self.max_norm = max_norm
         self.world, self.rank = _dist_info()
         n3 = batch_size // 3
         nb = n3 if n_bc is None else int(n_bc)
-        if bc_faces not in (1, 4) or (bc_faces == 4 and nb % 4):
-            raise ValueError("bc_faces must be 1 or 4 (with n_bc divisible by 4)")
-        self.bc_face_points = nb // 4 if bc_faces == 4 else 0
-        self.global_counts = (batch_size, n3, nb)                    # residual, IC, BC
+        ni = n3 if n_ic is None else int(n_ic)
+        if bc_faces not in (1, 4, "random") or (bc_faces == 4 and nb % 4):
+            raise ValueError("bc_faces must be 1, 4 (with n_bc divisible by 4) or 'random'")
+        self.bc_face_points = nb // 4 if bc_faces == 4 else (_lib.QC_BC_RANDOM_FACE if bc_faces == "random" else 0)
+        self.global_counts = (batch_size, ni, nb)                    # residual, IC, BC
         self.B_res = shard_count(batch_size, self.world, self.rank)
-        self.n_ic = shard_count(n3, self.world, self.rank)
+        self.n_ic = shard_count(ni, self.world, self.rank)
         self.n_bc = shard_count(nb, self.world, self.rank)
         self.bc_start = shard_slice(nb, self.world, self.rank).start
         self.opt = self._make_opt_state(capacity)
@@ -123,7 +133,7 @@ class FusedTrainer:
             dist.broadcast(t, 0)
             seed = int(t.item())
         self.fs.set_sampler(seed, shard_slice(batch_size, self.world, self.rank).start,
-                            shard_slice(n3, self.world, self.rank).start, self.bc_start, self.bc_face_points)
+                            shard_slice(ni, self.world, self.rank).start, self.bc_start, self.bc_face_points)
         # QC_DP_COLLECTIVE=rccl: the all-reduce runs INSIDE the library call (qc_comm_*: RCCL on the step's own stream,
         # one host call per step); default: torch.distributed between the two phases
         self._comm = None
@@ -164,13 +174,13 @@ class FusedTrainer:
     # -- optimiser state: continue from the torch optimiser / scheduler objects of the model
     def _make_opt_state(self, capacity):
         model = self.model
-        opt, sch = model.optimizer, model.scheduler
+        opt, sch = self.optimizer, self.scheduler
         g = opt.param_groups[0]
         st = _engine.OptimState(self.eng.NP, float(g["lr"]), self.device, hist_cap=capacity,
-                                betas=tuple(g["betas"]), eps=float(g["eps"]), max_norm=1.0,
+                                betas=tuple(g["betas"]), eps=float(g["eps"]), max_norm=self.max_norm,
                                 factor=float(sch.factor), patience=int(sch.patience),
                                 threshold=float(sch.threshold), min_lr=float(sch.min_lrs[0]),
-                                sched_eps=float(sch.eps))
+                                sched_eps=float(sch.eps), loss_weights=self.eng.loss_weights)
         steps, off = 0, 0
         for p in model.parameters():
             s = opt.state.get(p, None)
@@ -191,15 +201,15 @@ class FusedTrainer:
         off = 0
         for p in model.parameters():
             k = p.numel()
-            model.optimizer.state[p] = {
+            self.optimizer.state[p] = {
                 "step": torch.tensor(float(rec["step"])),
                 "exp_avg": self.opt.m[off:off + k].view(p.shape),
                 "exp_avg_sq": self.opt.v[off:off + k].view(p.shape),
             }
             off += k
-        for g in model.optimizer.param_groups:
+        for g in self.optimizer.param_groups:
             g["lr"] = rec["lr"]
-        sch = model.scheduler
+        sch = self.scheduler
         sch.best, sch.num_bad_epochs = rec["best"], rec["num_bad_epochs"]
         sch.last_epoch = rec["step"]
         sch._last_lr = [rec["lr"]]
@@ -215,7 +225,13 @@ class FusedTrainer:
         fs, dev = self.fs, self.device
         if self.n_ic:
             fs.X_val[: self.n_ic] = self.lo["ics"] + self.span["ics"] * torch.rand(self.n_ic, 3, device=dev)
-        if self.n_bc:
+        if self.n_bc and self.bc_face_points == _lib.QC_BC_RANDOM_FACE:      # a random face per point, one draw
+            pts = torch.rand(self.n_bc, 3, device=dev)
+            face = torch.randint(0, 4, (self.n_bc,), device=dev)
+            pts[:, 1] = torch.where(face == 0, 0.0, torch.where(face == 1, 1.0, pts[:, 1]))
+            pts[:, 2] = torch.where(face == 2, 0.0, torch.where(face == 3, 1.0, pts[:, 2]))
+            fs.X_val[self.n_ic: self.n_ic + self.n_bc] = pts
+        elif self.n_bc:
             pts = self.lo["bc1"] + self.span["bc1"] * torch.rand(self.n_bc, 3, device=dev)
             if self.bc_face_points:      # faces x=0, x=1, y=0, y=1 by GLOBAL boundary-point index
                 pts = torch.rand(self.n_bc, 3, device=dev)
