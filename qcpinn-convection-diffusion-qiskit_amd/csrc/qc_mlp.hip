@@ -119,6 +119,128 @@ __device__ __forceinline__ void angle_map_bwd(const float (&ab)[NCH], const floa
 // Four waves per tile (instead of one) keep >= 4 waves per SIMD in flight at B = 65 536.
 constexpr int QC_MS = 4;
 
+// ------------------------------------------------------------------ hidden-unit blocks of the lane = point kernels
+// A wave's hidden units m0 .. m1 - 1 are walked in compile-time blocks of UB units (then one block of 2 and one of 1
+// for the remainder).  A block's wave-uniform weights are fetched into one register set at its top: contiguous runs,
+// so a few wide scalar loads and ONE wait per block instead of a scalar-memory round trip or two per hidden unit.  With
+// PF the next full block's weights are requested before the current block's arithmetic starts and are only waited for
+// when it is done.  Fam::Blk<K> is the register set of K units, load(w, m) fills it for units m .. m + K - 1,
+// apply(w, m) does their arithmetic: every accumulator still takes its terms one hidden unit at a time in ascending m.
+template <class Fam, int UB, bool PF, class Load, class Apply>
+__device__ __forceinline__ void qc_unit_blocks(const int m0, const int m1, Load&& load, Apply&& apply) {
+  static_assert(UB == 1 || UB == 2 || UB == 4, "remainder blocks: 2, then 1");
+  int m = m0;
+  const int nblk = m1 > m0 ? (m1 - m0) / UB : 0;
+  if constexpr (PF) {
+    if (nblk > 0) {
+      typename Fam::template Blk<UB> cur;
+      load(cur, m);
+      for (int b = 1; b <= nblk; ++b) {
+        typename Fam::template Blk<UB> nxt;
+        load(nxt, b < nblk ? m + UB : m);   // the last pass re-reads its own block: in bounds, never used
+        apply(cur, m);
+        cur = nxt;
+        m += UB;
+      }
+    }
+  } else {
+    for (int b = 0; b < nblk; ++b, m += UB) {
+      typename Fam::template Blk<UB> w;
+      load(w, m);
+      apply(w, m);
+    }
+  }
+  if constexpr (UB > 2) {
+    if (m + 2 <= m1) {
+      typename Fam::template Blk<2> w;
+      load(w, m);
+      apply(w, m);
+      m += 2;
+    }
+  }
+  if constexpr (UB > 1) {
+    if (m < m1) {
+      typename Fam::template Blk<1> w;
+      load(w, m);
+      apply(w, m);
+    }
+  }
+}
+
+// block sizes by wire count: the register sets are 3 K + K + N K (pre) and N K + 2 K (post) scalar registers
+constexpr int qc_pre_ub(int n) { return n <= 4 ? 4 : (n <= 8 ? 2 : 1); }
+
+template <int N>
+struct QcPreW {
+  template <int K>
+  struct Blk { static constexpr int count = K; float w1[3 * K], b1[K], w2[N][K]; };
+};
+
+template <int N, int K>
+__device__ __forceinline__ void pre_blk_load(typename QcPreW<N>::template Blk<K>& w, const float* __restrict__ W1,
+                                             const float* __restrict__ b1, const float* __restrict__ W2, const int H,
+                                             const int m) {
+  const float* __restrict__ p1 = W1 + 3 * m;   // one base per run: constant offsets merge into wide loads
+  const float* __restrict__ pb = b1 + m;
+#pragma unroll
+  for (int j = 0; j < 3 * K; ++j) w.w1[j] = p1[j];
+#pragma unroll
+  for (int j = 0; j < K; ++j) w.b1[j] = pb[j];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const float* __restrict__ p2 = W2 + (i * H + m);
+#pragma unroll
+    for (int j = 0; j < K; ++j) w.w2[i][j] = p2[j];
+  }
+}
+
+// K hidden units of the pre network on one point: the K tanh chains first (independent, quarter-rate exp / rcp), then
+// the multiply-adds unit by unit
+template <int N, int NCH, int K>
+__device__ __forceinline__ void pre_blk_apply(const typename QcPreW<N>::template Blk<K>& w, const float t, const float x,
+                                              const float y, mf2 (&acc2)[NCH == 6 ? 3 : 1][N]) {
+  float z[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+    z[j] = qc_tanh(fmaf(w.w1[3 * j], t, fmaf(w.w1[3 * j + 1], x, fmaf(w.w1[3 * j + 2], y, w.b1[j]))));
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    if constexpr (NCH == 6) {
+      const float w0 = w.w1[3 * j], w1 = w.w1[3 * j + 1], w2 = w.w1[3 * j + 2];
+      const float d1 = 1.f - z[j] * z[j], d2 = -2.f * z[j] * d1;
+      const mf2 zc2[3] = {(mf2){z[j], d1 * w0}, (mf2){d1 * w1, d1 * w2}, (mf2){d2 * w1 * w1, d2 * w2 * w2}};
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const mf2 wi = m_dup(w.w2[i][j]);
+#pragma unroll
+        for (int cp = 0; cp < 3; ++cp) acc2[cp][i] = m_fma(wi, zc2[cp], acc2[cp][i]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) acc2[0][i].x = fmaf(w.w2[i][j], z[j], acc2[0][i].x);
+    }
+  }
+}
+
+// hidden units m0 .. m1 - 1 of the pre network accumulated into acc2
+template <int N, int NCH>
+__device__ __forceinline__ void pre_fwd_units(const float* __restrict__ W1, const float* __restrict__ b1,
+                                              const float* __restrict__ W2, const int H, const int m0, const int m1,
+                                              const float t, const float x, const float y,
+                                              mf2 (&acc2)[NCH == 6 ? 3 : 1][N]) {
+  constexpr int UB = qc_pre_ub(N);
+  qc_unit_blocks<QcPreW<N>, UB, (UB > 1)>(
+      m0, m1,
+      [&](auto& w, const int m) {
+        constexpr int K = std::remove_reference_t<decltype(w)>::count;
+        pre_blk_load<N, K>(w, W1, b1, W2, H, m);
+      },
+      [&](const auto& w, const int) {
+        constexpr int K = std::remove_reference_t<decltype(w)>::count;
+        pre_blk_apply<N, NCH, K>(w, t, x, y, acc2);
+      });
+}
+
 template <int N, int NCH, int MAP = 0, bool RF = false>
 __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                  QcLayout L, float* __restrict__ ajets, int64_t B,
@@ -157,24 +279,7 @@ __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* _
   const float* W2 = prm + L.oW2;
   const int hq = (L.H + QC_MS - 1) / QC_MS;
   const int m0 = wave * hq, m1 = (m0 + hq) < L.H ? (m0 + hq) : L.H;
-  for (int m = m0; m < m1; ++m) {
-    const float w0 = W1[3 * m], w1 = W1[3 * m + 1], w2 = W1[3 * m + 2];
-    const float h = fmaf(w0, t, fmaf(w1, x, fmaf(w2, y, b1[m])));
-    const float z = qc_tanh(h);
-    if constexpr (NCH == 6) {
-      const float d1 = 1.f - z * z, d2 = -2.f * z * d1;
-      const mf2 zc2[3] = {(mf2){z, d1 * w0}, (mf2){d1 * w1, d1 * w2}, (mf2){d2 * w1 * w1, d2 * w2 * w2}};
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        const mf2 wi = m_dup(W2[i * L.H + m]);
-#pragma unroll
-        for (int cp = 0; cp < 3; ++cp) acc2[cp][i] = m_fma(wi, zc2[cp], acc2[cp][i]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < N; ++i) acc2[0][i].x = fmaf(W2[i * L.H + m], z, acc2[0][i].x);
-    }
-  }
+  pre_fwd_units<N, NCH>(W1, b1, W2, L.H, m0, m1, t, x, y, acc2);
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
@@ -182,10 +287,29 @@ __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* _
   __syncthreads();
   if (p < B) {
     if constexpr (MAP == 0) {
-      for (int f = wave; f < NCH * N; f += QC_MS) {
-        float v = (s_part[0][f][lane] + s_part[1][f][lane]) + (s_part[2][f][lane] + s_part[3][f][lane]);
-        if (f < N) v += prm[L.ob2 + f];
-        ajets[(int64_t)f * B + p] = v;
+      // compile-time trip count (n <= 8): every LDS read of the wave's rows is in flight before the first sum
+      constexpr int NF = (NCH * N + QC_MS - 1) / QC_MS;
+      if constexpr (NF <= 12) {
+        float v[NF];
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          const int f = wave + QC_MS * j, fc = f < NCH * N ? f : 0;
+          v[j] = (s_part[0][fc][lane] + s_part[1][fc][lane]) + (s_part[2][fc][lane] + s_part[3][fc][lane]);
+        }
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          const int f = wave + QC_MS * j;
+          if (f < NCH * N) {
+            if (f < N) v[j] += prm[L.ob2 + f];
+            ajets[(int64_t)f * B + p] = v[j];
+          }
+        }
+      } else {
+        for (int f = wave; f < NCH * N; f += QC_MS) {
+          float v = (s_part[0][f][lane] + s_part[1][f][lane]) + (s_part[2][f][lane] + s_part[3][f][lane]);
+          if (f < N) v += prm[L.ob2 + f];
+          ajets[(int64_t)f * B + p] = v;
+        }
       }
     } else {
       // the map mixes the channels of one wire: a wave finishes whole wires
@@ -753,15 +877,13 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
   float part[QC_MS][N];
 #pragma unroll
   for (int k = 0; k < QC_MS; ++k) {
+    mf2 acc[1][N];
 #pragma unroll
-    for (int i = 0; i < N; ++i) part[k][i] = 0.f;
+    for (int i = 0; i < N; ++i) acc[0][i] = (mf2){0.f, 0.f};
     const int m0 = k * hq, m1 = (m0 + hq) < L.H ? (m0 + hq) : L.H;
-    for (int m = m0; m < m1; ++m) {
-      const float h = fmaf(W1[3 * m], t, fmaf(W1[3 * m + 1], x, fmaf(W1[3 * m + 2], y, b1[m])));
-      const float z = qc_tanh(h);
+    pre_fwd_units<N, 1>(W1, b1, W2, L.H, m0, m1, t, x, y, acc);
 #pragma unroll
-      for (int i = 0; i < N; ++i) part[k][i] = fmaf(W2[i * L.H + m], z, part[k][i]);
-    }
+    for (int i = 0; i < N; ++i) part[k][i] = acc[0][i].x;
   }
   if (p < B) {
 #pragma unroll
@@ -864,6 +986,38 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
 // residual blocks) 24.5 us, 2 tiles x 2 waves 27.4, 4 tiles x 1 wave (round 3) 27.9.
 constexpr int QC_POST_VALUE_TPB = 1;   // value tiles per block of the fused post stage
 
+// hidden-unit blocks of the fused post stage (qc_unit_blocks): W3 rows m .. m + K - 1 are one run of K N floats
+template <int N>
+struct QcPostW {
+  template <int K>
+  struct Blk { static constexpr int count = K; float w3[K][N], b3[K], w4[K]; };
+};
+template <int N, int K>
+__device__ __forceinline__ void post_blk_load(typename QcPostW<N>::template Blk<K>& w, const float* __restrict__ W3,
+                                              const float* __restrict__ b3, const float* __restrict__ W4, const int m) {
+  const float* __restrict__ p3 = W3 + m * N;   // one base per run: constant offsets merge into wide loads
+  const float* __restrict__ pb = b3 + m;
+  const float* __restrict__ p4 = W4 + m;
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+#pragma unroll
+    for (int i = 0; i < N; ++i) w.w3[j][i] = p3[j * N + i];
+#pragma unroll
+  for (int j = 0; j < K; ++j) w.b3[j] = pb[j];
+#pragma unroll
+  for (int j = 0; j < K; ++j) w.w4[j] = p4[j];
+}
+// one column of W3 for K consecutive hidden units (the qbar chains of the value tiles)
+struct QcColW {
+  template <int K>
+  struct Blk { static constexpr int count = K; float c[K]; };
+};
+// phase A.  (n = 3 in blocks of 4 takes the merged kernel from 80 to 102 scalar registers, 7 waves per SIMD instead of
+// 8; in blocks of 2 it needs 93 and keeps 8)
+constexpr int qc_post_ub_a(int n) { return n == 3 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 2 : 1)); }
+constexpr bool qc_post_pf(int n) { return n <= 8; }   // prefetch of the next block
+constexpr int qc_post_ub_vb(int n) { return n <= 8 ? 2 : 1; }                 // phase B of a value tile: two reductions side by side
+
 template <int N, int TPB>
 __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const float* __restrict__ X,
                                                         const float* __restrict__ prm, QcLayout L, QcPde pde,
@@ -897,14 +1051,25 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
   for (int k = 0; k < QPW; ++k) {
     up[k] = 0.f;
     const int k0 = m0 + k * hq, k1 = (k0 + hq) < m1 ? (k0 + hq) : m1;
-    for (int m = k0; m < k1; ++m) {
-      float g = b3[m];
+    qc_unit_blocks<QcPostW<N>, qc_post_ub_a(N), qc_post_pf(N)>(
+        k0, k1,
+        [&](auto& w, const int m) { post_blk_load<N, std::remove_reference_t<decltype(w)>::count>(w, W3, b3, W4, m); },
+        [&](const auto& w, const int m) {
+          constexpr int K = std::remove_reference_t<decltype(w)>::count;
+          float z[K];
 #pragma unroll
-      for (int i = 0; i < N; ++i) g = fmaf(W3[m * N + i], q[i], g);
-      const float z = qc_tanh(g);
-      s_g[m * 64 + lane] = z;
-      up[k] = fmaf(W4[m], z, up[k]);
-    }
+          for (int j = 0; j < K; ++j) {
+            float g = w.b3[j];
+#pragma unroll
+            for (int i = 0; i < N; ++i) g = fmaf(w.w3[j][i], q[i], g);
+            z[j] = qc_tanh(g);
+          }
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            s_g[(m + j) * 64 + lane] = z[j];
+            up[k] = fmaf(w.w4[j], z[j], up[k]);
+          }
+        });
   }
   float u;
   if constexpr (QPW == 4) u = (up[0] + up[1]) + (up[2] + up[3]);
@@ -936,31 +1101,59 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
   // ---------------- phase B over the same hidden units: weight gradients; gb parked in place of tanh
   float ub[1];
   expand_ub<1>(ub, ub0, 0.f, pde);
-  for (int m = m0; m < m1; ++m) {
-    const float g[1] = {0.f};   // post_cotangents reads no pre-activation for one channel
-    float gb[1], gw4;
-    post_cotangents<N, 1>(gb, gw4, g, ub, s_g[m * 64 + lane], W4[m]);
-    s_g[m * 64 + lane] = gb[0];
-    float wg[N + 2];
+  // W4 only: K values per block; the K units' reductions run side by side (each value's six steps in their own order)
+  qc_unit_blocks<QcColW, qc_post_ub_vb(N), false>(
+      m0, m1,
+      [&](auto& w, const int m) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) wg[i] = fmaf(gb[0], q[i], 0.f);
-    wg[N] = gb[0];
-    wg[N + 1] = gw4;
-    qc_wave_sum_multi_to_lane63<N + 2>(wg);
-    if (lane == 63) {
+        for (int j = 0; j < std::remove_reference_t<decltype(w)>::count; ++j) w.c[j] = W4[m + j];
+      },
+      [&](const auto& w, const int m) {
+        constexpr int K = std::remove_reference_t<decltype(w)>::count;
+        float wg[K * (N + 2)];
 #pragma unroll
-      for (int i = 0; i < N; ++i) row[L.oW3 + m * N + i] = wg[i];
-      row[L.ob3 + m] = wg[N];
-      row[L.oW4 + m] = wg[N + 1];
-    }
-  }
+        for (int j = 0; j < K; ++j) {
+          const float g[1] = {0.f};   // post_cotangents reads no pre-activation for one channel
+          float gb[1], gw4;
+          post_cotangents<N, 1>(gb, gw4, g, ub, s_g[(m + j) * 64 + lane], w.c[j]);
+          s_g[(m + j) * 64 + lane] = gb[0];
+#pragma unroll
+          for (int i = 0; i < N; ++i) wg[j * (N + 2) + i] = fmaf(gb[0], q[i], 0.f);
+          wg[j * (N + 2) + N] = gb[0];
+          wg[j * (N + 2) + N + 1] = gw4;
+        }
+        qc_wave_sum_multi_to_lane63<K * (N + 2)>(wg);
+        if (lane == 63) {
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) row[L.oW3 + (m + j) * N + i] = wg[j * (N + 2) + i];
+            row[L.ob3 + m + j] = wg[j * (N + 2) + N];
+            row[L.oW4 + m + j] = wg[j * (N + 2) + N + 1];
+          }
+        }
+      });
   __syncthreads();
   // ---------------- qbar[i] = sum over m of W3[m][i] gb(m), one chain per i
   if (live) {
     const int mh = tile_ok ? L.H : 0;
     for (int i = wt; i < N; i += WPT) {
       float qb = 0.f;
-      for (int m = 0; m < mh; ++m) qb = fmaf(W3[m * N + i], s_g[m * 64 + lane], qb);
+      // column i of W3, four hidden units per block: their scalar loads and LDS reads are issued together
+      qc_unit_blocks<QcColW, 4, true>(
+          0, mh,
+          [&](auto& w, const int m) {
+#pragma unroll
+            for (int j = 0; j < std::remove_reference_t<decltype(w)>::count; ++j) w.c[j] = W3[(m + j) * N + i];
+          },
+          [&](const auto& w, const int m) {
+            constexpr int K = std::remove_reference_t<decltype(w)>::count;
+            float gbv[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) gbv[j] = s_g[(m + j) * 64 + lane];
+#pragma unroll
+            for (int j = 0; j < K; ++j) qb = fmaf(w.c[j], gbv[j], qb);
+          });
       qbar[(int64_t)i * B + p] = qb;
     }
   }
@@ -976,6 +1169,15 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
 // s_z = [H][64] and, behind them, the u-jet exchange [4][6][64]; once every wave is past phase B the qbar exchange
 // [4][6N][64] reuses it from the start (24 KiB at H = 50, n = 4, against 36.5 KiB unaliased: six blocks per CU, not
 // four).
+
+// block sizes and prefetch of the residual tiles' two phases (qc_unit_blocks)
+template <int N> constexpr int QC_POST6_UB_A = qc_post_ub_a(N);
+template <int N> constexpr bool QC_POST6_PF_A = qc_post_pf(N);
+// (phase B in blocks of 2 needs 16 more vector registers at n = 4, 90 against 74, which costs a resident block per CU:
+// it keeps one unit per block, whose W3 row, b3 and W4 arrive behind one wait.  A prefetch of the next unit buys nothing
+// there: the compiler sinks the request below the row stores of the body's second basic block, next to its wait.)
+template <int N> constexpr int QC_POST6_UB_B = 1;
+template <int N> constexpr bool QC_POST6_PF_B = false;
 
 template <int N>
 __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
@@ -1004,34 +1206,44 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   const float* W4 = prm + L.oW4;
   const int hq = (L.H + QC_MS - 1) / QC_MS;
   const int m0 = wave * hq, m1 = (m0 + hq) < L.H ? (m0 + hq) : L.H;
-  auto preact = [&](int m, mf2 (&g2)[3]) {
-    g2[0] = (mf2){b3[m], 0.f};
+  auto preact = [&](const float (&w3)[N], const float b3m, mf2 (&g2)[3]) {
+    g2[0] = (mf2){b3m, 0.f};
     g2[1] = g2[2] = (mf2){0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-      const mf2 w = m_dup(W3[m * N + i]);
+      const mf2 w = m_dup(w3[i]);
 #pragma unroll
       for (int cp = 0; cp < 3; ++cp) g2[cp] = m_fma(w, q2[cp][i], g2[cp]);
     }
+  };
+  auto load_blk = [&](auto& w, const int m) {
+    post_blk_load<N, std::remove_reference_t<decltype(w)>::count>(w, W3, b3, W4, m);
   };
   // ---------------- phase A
   float u[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) u[c] = 0.f;
-  for (int m = m0; m < m1; ++m) {
-    mf2 g2[3];
-    preact(m, g2);
-    const float z = qc_tanh(g2[0].x);
-    s_z[m * 64 + lane] = z;
-    const float w4 = W4[m];
-    const float d1 = 1.f - z * z, d2 = -2.f * z * d1;
-    u[0] = fmaf(w4, z, u[0]);
-    u[1] = fmaf(w4, d1 * g2[0].y, u[1]);
-    u[2] = fmaf(w4, d1 * g2[1].x, u[2]);
-    u[3] = fmaf(w4, d1 * g2[1].y, u[3]);
-    u[4] = fmaf(w4, d2 * g2[1].x * g2[1].x + d1 * g2[2].x, u[4]);
-    u[5] = fmaf(w4, d2 * g2[1].y * g2[1].y + d1 * g2[2].y, u[5]);
-  }
+  qc_unit_blocks<QcPostW<N>, QC_POST6_UB_A<N>, QC_POST6_PF_A<N>>(m0, m1, load_blk, [&](const auto& w, const int m) {
+    constexpr int K = std::remove_reference_t<decltype(w)>::count;
+    mf2 g2[K][3];
+    float z[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) preact(w.w3[j], w.b3[j], g2[j]);
+#pragma unroll
+    for (int j = 0; j < K; ++j) z[j] = qc_tanh(g2[j][0].x);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      s_z[(m + j) * 64 + lane] = z[j];
+      const float w4 = w.w4[j];
+      const float d1 = 1.f - z[j] * z[j], d2 = -2.f * z[j] * d1;
+      u[0] = fmaf(w4, z[j], u[0]);
+      u[1] = fmaf(w4, d1 * g2[j][0].y, u[1]);
+      u[2] = fmaf(w4, d1 * g2[j][1].x, u[2]);
+      u[3] = fmaf(w4, d1 * g2[j][1].y, u[3]);
+      u[4] = fmaf(w4, d2 * g2[j][1].x * g2[j][1].x + d1 * g2[j][2].x, u[4]);
+      u[5] = fmaf(w4, d2 * g2[j][1].y * g2[j][1].y + d1 * g2[j][2].y, u[5]);
+    }
+  });
 #pragma unroll
   for (int c = 0; c < NCH; ++c) s_u[wave][c][lane] = u[c];
   __syncthreads();
@@ -1067,36 +1279,44 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   for (int cp = 0; cp < 3; ++cp)
 #pragma unroll
     for (int i = 0; i < N; ++i) qb2[cp][i] = (mf2){0.f, 0.f};
-  for (int m = m0; m < m1; ++m) {
-    mf2 g2[3];
-    preact(m, g2);
-    const float g[NCH] = {0.f, g2[0].y, g2[1].x, g2[1].y, g2[2].x, g2[2].y};
-    const float z = s_z[m * 64 + lane];
-    float gb[NCH], gw4;
-    post_cotangents<N, NCH>(gb, gw4, g, ub, z, W4[m]);
-    const mf2 gb2[3] = {(mf2){gb[0], gb[1]}, (mf2){gb[2], gb[3]}, (mf2){gb[4], gb[5]}};
-    float wg[N + 2];
+  // the K units' weight-gradient reductions run side by side (each value's six steps in their own order)
+  qc_unit_blocks<QcPostW<N>, QC_POST6_UB_B<N>, QC_POST6_PF_B<N>>(m0, m1, load_blk, [&](const auto& w, const int m) {
+    constexpr int K = std::remove_reference_t<decltype(w)>::count;
+    float wg[K * (N + 2)];
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      const mf2 w3 = m_dup(W3[m * N + i]);
-      mf2 acc = gb2[0] * q2[0][i];
+    for (int j = 0; j < K; ++j) {
+      mf2 g2[3];
+      preact(w.w3[j], w.b3[j], g2);
+      const float g[NCH] = {0.f, g2[0].y, g2[1].x, g2[1].y, g2[2].x, g2[2].y};
+      const float z = s_z[(m + j) * 64 + lane];
+      float gb[NCH], gw4;
+      post_cotangents<N, NCH>(gb, gw4, g, ub, z, w.w4[j]);
+      const mf2 gb2[3] = {(mf2){gb[0], gb[1]}, (mf2){gb[2], gb[3]}, (mf2){gb[4], gb[5]}};
 #pragma unroll
-      for (int cp = 0; cp < 3; ++cp) {
-        qb2[cp][i] = m_fma(w3, gb2[cp], qb2[cp][i]);
-        if (cp > 0) acc = m_fma(gb2[cp], q2[cp][i], acc);
+      for (int i = 0; i < N; ++i) {
+        const mf2 w3 = m_dup(w.w3[j][i]);
+        mf2 acc = gb2[0] * q2[0][i];
+#pragma unroll
+        for (int cp = 0; cp < 3; ++cp) {
+          qb2[cp][i] = m_fma(w3, gb2[cp], qb2[cp][i]);
+          if (cp > 0) acc = m_fma(gb2[cp], q2[cp][i], acc);
+        }
+        wg[j * (N + 2) + i] = acc.x + acc.y;
       }
-      wg[i] = acc.x + acc.y;
+      wg[j * (N + 2) + N] = gb[0];
+      wg[j * (N + 2) + N + 1] = gw4;
     }
-    wg[N] = gb[0];
-    wg[N + 1] = gw4;
-    qc_wave_sum_multi_to_lane63<N + 2>(wg);
+    qc_wave_sum_multi_to_lane63<K * (N + 2)>(wg);
     if (lane == 63) {
 #pragma unroll
-      for (int i = 0; i < N; ++i) row[L.oW3 + m * N + i] = wg[i];
-      row[L.ob3 + m] = wg[N];
-      row[L.oW4 + m] = wg[N + 1];
+      for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) row[L.oW3 + (m + j) * N + i] = wg[j * (N + 2) + i];
+        row[L.ob3 + m + j] = wg[j * (N + 2) + N];
+        row[L.oW4 + m + j] = wg[j * (N + 2) + N + 1];
+      }
     }
-  }
+  });
   __syncthreads();   // every wave is done with s_z and s_u: the qbar partials overwrite them
 #pragma unroll
   for (int cp = 0; cp < 3; ++cp)
@@ -1107,8 +1327,24 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
     }
   __syncthreads();
   if (live) {
-    for (int f = wave; f < NCH * N; f += QC_MS)
-      qbar[(int64_t)f * B + p] = (s_q[0][f][lane] + s_q[1][f][lane]) + (s_q[2][f][lane] + s_q[3][f][lane]);
+    // compile-time trip count (n <= 8): every LDS read of the wave's rows is in flight before the first sum
+    constexpr int NF = (NCH * N + QC_MS - 1) / QC_MS;
+    if constexpr (NF <= 12) {
+      float v[NF];
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int f = wave + QC_MS * j, fc = f < NCH * N ? f : 0;
+        v[j] = (s_q[0][fc][lane] + s_q[1][fc][lane]) + (s_q[2][fc][lane] + s_q[3][fc][lane]);
+      }
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int f = wave + QC_MS * j;
+        if (f < NCH * N) qbar[(int64_t)f * B + p] = v[j];
+      }
+    } else {
+      for (int f = wave; f < NCH * N; f += QC_MS)
+        qbar[(int64_t)f * B + p] = (s_q[0][f][lane] + s_q[1][f][lane]) + (s_q[2][f][lane] + s_q[3][f][lane]);
+    }
   }
 }
 
