@@ -156,6 +156,11 @@ typedef struct qc_pde {
 #define QC_PROBLEM_CONVECTION_DIFFUSION 0
 #define QC_PROBLEM_PURE_DIFFUSION 1
 #define QC_PROBLEM_GAUSSIAN_PULSE 2
+/* 3: no analytic target at all.  The targets are DATA, one float per point of the batch: what the reference's
+ *    Sampler(dim, coords, func) (data/diffusion_dataset.py:12-19) returns for ANY callable `func`, and what its train()
+ *    (trainer/diffusion_train.py:40-47) compares against whatever u and r it is handed.  Accepted only by the *_data entry
+ *    points below; the entry points above keep refusing it. */
+#define QC_PROBLEM_TABULATED 3
 
 /* mode 0: qjets -> u [B], residual [B] (nn/pde.py:71);
  * mode 1: cotangents (ubar, rbar) [B] -> qbar jets + weight-gradient partial rows;
@@ -168,6 +173,18 @@ int qc_post(int mode, const float* X_dev, const float* params_dev, int H, int n,
             const qc_pde* pde, const float* qjets_dev, float* out_u_dev, float* out_res_dev,
             const float* in_ubar_dev, const float* in_rbar_dev, float* qbar_dev, float* part_dev,
             int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream);
+
+/* qc_post mode 2 on tabulated targets (pde->problem = QC_PROBLEM_TABULATED; any other id is refused): replaces the
+ * func(x) of Sampler.sample (data/diffusion_dataset.py:16-19) by target_dev[B], read per point (value points: IC points
+ * first, then BC, like X_val), and the residual of nn/pde.py:71 by its form with a zeroth-order term,
+ *   residual = c_u u + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy)
+ * (the reaction term of the Helmholtz operator u_xx + u_yy + lambda u, nn/pde.py:73-95: c_u = lambda, d_xx = d_yy = -1).  c_u is
+ * an argument, not a field of qc_pde, whose layout is fixed.  The points themselves are not read.  out_u_dev / out_res_dev
+ * are the B-float cotangent scratch buffers of mode 2; a residual point's cotangent on u is c_u times its cotangent on the
+ * residual. */
+int qc_post_data(const float* params_dev, int H, int n, int n_theta, const qc_pde* pde, const float* qjets_dev,
+                 const float* target_dev, float c_u, float* out_u_dev, float* out_res_dev, float* qbar_dev, float* part_dev,
+                 int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream);
 
 /* K outputs behind one shared network: a post network Linear(n, H) -> Tanh -> Linear(H, K), 1 <= K <= 4 (the (u, v, p)
  * model nn/pde.py:2-27 differentiates for Navier-Stokes).  params_dev: the flat vector of the single-output layout
@@ -277,6 +294,36 @@ int qc_allreduce_grads(float* buf_dev, int64_t count, void* comm, void* stream);
 #define QC_PHASE_UPDATE 2
 #define QC_PHASE_SAMPLE 4 /* fill X_res / X_val first (see qc_sample_collocation) */
 int qc_fused_pinn_residual_step(const qc_step_desc* desc, int phases, void* stream);
+
+/* ---- the same step on a user's own problem: targets as data (QC_PROBLEM_TABULATED), batches from a resident dataset.
+ * Replaces, for a target that is not one of the three analytic problems, the Sampler(dim, coords, func) objects and the
+ * fetch_minibatch calls of trainer/diffusion_train.py:22-36 (func evaluated once, up front, on the dataset's points) and
+ * the u / r arguments of its loss (:44-47). */
+typedef struct qc_step_data {
+  float* target_res_dev;            /* [B_res] residual targets of the current batch */
+  float* target_val_dev;            /* [B_val] value targets, IC points first, then BC */
+  float  c_u;                       /* zeroth-order coefficient of the residual (see qc_post_data) */
+  /* resident dataset for QC_PHASE_SAMPLE (all NULL/0: SAMPLE is refused) */
+  const float* ds_X_res; const float* ds_r;    int64_t ds_n_res;   /* [N][3], [N] */
+  const float* ds_X_ic;  const float* ds_u_ic; int64_t ds_n_ic;
+  const float* ds_X_bc;  const float* ds_u_bc; int64_t ds_n_bc;
+} qc_step_data;
+
+/* The dataset form of qc_sample_collocation (same batch buffers, counts and GLOBAL offsets): point i of a segment
+ * (0 residual, 1 IC, 2 BC) with global index g = off + i draws the Philox4x32-10 block of the coordinate draw, counter
+ * (g lo, g hi, step lo, step hi ^ segment << 30) and key = seed, and takes row idx = (word 0 * N_seg) >> 32 of that
+ * segment's dataset: X_batch[i] = ds_X[idx], target_batch[i] = ds_target[idx] (sampling with replacement, the
+ * torch.randint minibatch of a tabulated Sampler).  1 <= N_seg < 2^31 for every non-empty batch, else QC_ERR_ARG. */
+int qc_sample_dataset(float* X_res_dev, float* target_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev,
+                      float* target_val_dev, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                      const qc_step_data* data, uint64_t seed, uint64_t step, void* stream);
+
+/* qc_fused_pinn_residual_step with desc->pde.problem = QC_PROBLEM_TABULATED (required): the post stage reads its targets
+ * from data->target_*_dev and applies data->c_u; QC_PHASE_SAMPLE fills the points AND the targets from the dataset
+ * (one launch ahead of the stages) where the analytic step draws coordinates.  Same forms, phases, workspace and flat
+ * vector.  QC_ERR_ARG before any launch: a missing target buffer of a non-empty batch; QC_PHASE_SAMPLE with an absent or
+ * empty dataset segment behind a non-empty batch, or one of 2^31 rows or more; any other problem id. */
+int qc_fused_pinn_data_step(const qc_step_desc* desc, const qc_step_data* data, int phases, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,15 @@ inline QcLayout qc_layout(int H, int n, int n_theta) {
 
 constexpr int QC_PB_CONVECTION_DIFFUSION = 0, QC_PB_PURE_DIFFUSION = 1,
               QC_PB_GAUSSIAN_PULSE = 2;   // == QC_PROBLEM_* of the public header
+constexpr int QC_PB_TABULATED = 3;        // targets read from memory (the *_data entry points), never computed in-kernel
+
+// Targets of the tabulated mode-2 post kernels: one float per point of the batch (value points: IC first, then BC), and
+// the zeroth-order coefficient of the residual c_u u + c_t u_t + ... (not part of QcPde, whose layout is public).
+struct QcTab {
+  const float* tg_res;
+  const float* tg_val;
+  float c_u;
+};
 
 struct QcPde {  // == qc_pde of the public header
   float D, vx, vy;                 // physical constants: analytic targets of mode 2
@@ -103,9 +112,11 @@ int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, floa
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
                         float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
                         hipStream_t st, int map, const float* ajr, const float* ajv);
+// `tab` (both post launchers): non-null selects the tabulated kernels (pde.problem == QC_PB_TABULATED)
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
-                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st);
+                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st,
+                     const QcTab* tab = nullptr);
 int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t,
                    int map = 0);
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
@@ -113,7 +124,8 @@ int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* ab
                    const float* aj = nullptr);
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
-                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t);
+                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t,
+                const QcTab* tab = nullptr);
 int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float* w4k, const float* qjets, float* out_u,
                       const float* ubar, float* qbar, float* part, int64_t part_stride, float* partk, int64_t partk_stride,
                       int64_t row0, int64_t B, hipStream_t);
@@ -127,6 +139,11 @@ int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState*
 int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hipStream_t);
 int qc_sample_launch(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
                      int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step, hipStream_t);
+int qc_sample_dataset_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
+                             int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
+                             const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic, int64_t ds_n_ic,
+                             const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed, uint64_t step,
+                             hipStream_t);
 // HBM family, n >= 9 (qc_circuit_hbm2.hip, qc_circuit_h2s_kernels.h): all tiles of a batch resident when the workspace allows
 void* qc_h2_create(const qc_program* pg, int absorb, int amplitude);   // amplitude: the encoding the plan is built for
 void qc_h2_destroy(void* h2);

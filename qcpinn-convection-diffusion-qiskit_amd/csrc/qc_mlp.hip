@@ -530,13 +530,17 @@ __device__ __forceinline__ void expand_ub(float (&ub)[NCH], float ub0, float gsc
   }
 }
 
-template <int N, int NCH, int MODE>
+// DATA (MODE 2 only, QC_PB_TABULATED): the point's target is tg[p] instead of the analytic function of X, and the residual
+// carries the zeroth-order term c_u u, whose cotangent on u is c_u gsc.  DATA = false is the code as it was.
+template <int N, int NCH, int MODE, bool DATA = false>
 __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                                               QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ out_res,
                                               const float* __restrict__ in_ubar, const float* __restrict__ in_rbar,
                                               float* __restrict__ qbar, float* __restrict__ part,
-                                              int64_t part_stride, int64_t row0, int64_t B) {
+                                              int64_t part_stride, int64_t row0, int64_t B,
+                                              const float* __restrict__ tg = nullptr, const float c_u = 0.f) {
+  static_assert(!DATA || MODE == 2, "tabulated targets: the fused mode only");
   // block = 4 waves on one 64-point tile; wave w owns a quarter of the hidden units
   __shared__ float s_buf[QC_MS][NCH * N][64];   // partial u jets first (NCH rows), partial qbar later
   const int lane = threadIdx.x & 63;
@@ -572,7 +576,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 #pragma unroll
     for (int c = 0; c < NCH; ++c) u[c] = 0.f;
     float ub_unit[NCH];
-    expand_ub<NCH>(ub_unit, NCH == 6 ? 0.f : 1.f, NCH == 6 ? 1.f : 0.f, pde);
+    expand_ub<NCH>(ub_unit, NCH == 6 ? (DATA ? c_u : 0.f) : 1.f, NCH == 6 ? 1.f : 0.f, pde);
     for (int m = m0; m < m1; ++m) {
       float g[NCH];
 #pragma unroll
@@ -621,6 +625,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
     }
     float res = 0.f;
     if constexpr (NCH == 6) res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
+    if constexpr (NCH == 6 && DATA) res = fmaf(c_u, u[0], res);
     if constexpr (MODE == 0) {
       if (live && wave == 0) {
         if (out_u) out_u[p] = u[0];
@@ -629,12 +634,18 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
       }
       return;
     } else {
-      const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
+      float t = 0.f, x = 0.f, y = 0.f, tgp = 0.f;
+      if constexpr (DATA) {
+        tgp = tg[pc];
+      } else {
+        t = X[pc * 3 + 0]; x = X[pc * 3 + 1]; y = X[pc * 3 + 2];
+      }
       float* row = part + (row0 + tile) * part_stride;
       if constexpr (NCH == 6) {
-        const float target = residual_target(pde, t, x, y);
+        const float target = DATA ? tgp : residual_target(pde, t, x, y);
         const float e = live ? res - target : 0.f;
         gsc = pde.w_res * e;
+        if constexpr (DATA) ub0 = c_u * gsc;   // reaches k_post_wg through out_u (W4 / b4 / hidden-layer gradients)
         if (wave == 0) {
           const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
           if (lane == 63) {
@@ -645,7 +656,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
         }
       } else {
         const bool seg_a = p < pde.n_seg_a;
-        const float target = value_target(pde, seg_a, t, x, y);
+        const float target = DATA ? tgp : value_target(pde, seg_a, t, x, y);
         const float e = live ? u[0] - target : 0.f;
         ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
         if (wave == 0) {
@@ -732,6 +743,17 @@ __global__ void __launch_bounds__(256) k_post(const float* __restrict__ X, const
                                               float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B) {
   k_post_body<N, NCH, MODE>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar, part, part_stride, row0, B);
+}
+
+// MODE 2 on tabulated targets (qc_post_data; the step's split form)
+template <int N, int NCH>
+__global__ void __launch_bounds__(256) k_post_data(const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                   const float* __restrict__ qjets, float* __restrict__ out_u,
+                                                   float* __restrict__ out_res, float* __restrict__ qbar,
+                                                   float* __restrict__ part, int64_t part_stride, int64_t row0, int64_t B,
+                                                   const float* __restrict__ tg, float c_u) {
+  k_post_body<N, NCH, 2, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, out_res, nullptr, nullptr, qbar, part,
+                               part_stride, row0, B, tg, c_u);
 }
 
 // Weight gradients of the post network: lane = hidden unit m (owns row m of W3, b3[m], W4[m]); the
@@ -902,11 +924,12 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
 }
 
 // fused (mode 2) post stage of a value tile: u, squared error against the analytic target, cotangent of <Z>
-template <int N>
+template <int N, bool DATA = false>
 __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                               QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ qbar, float* __restrict__ part,
-                                              int64_t part_stride, int64_t row0, int64_t B) {
+                                              int64_t part_stride, int64_t row0, int64_t B,
+                                              const float* __restrict__ tg = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t tile = bid * 4 + wave;
@@ -941,9 +964,14 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
     }
   }
   const float u = ((up[0] + up[1]) + (up[2] + up[3])) + prm[L.ob4];
-  const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   const bool seg_a = p < pde.n_seg_a;
-  const float target = value_target(pde, seg_a, t, x, y);
+  float target;
+  if constexpr (DATA) {
+    target = tg[pc];
+  } else {
+    const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
+    target = value_target(pde, seg_a, t, x, y);
+  }
   const float e = live ? u - target : 0.f;
   const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
   const float la = qc_wave_sum_to_lane63(seg_a ? e * e * pde.inv_n_a : 0.f);
@@ -1018,13 +1046,13 @@ constexpr int qc_post_ub_a(int n) { return n == 3 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 
 constexpr bool qc_post_pf(int n) { return n <= 8; }   // prefetch of the next block
 constexpr int qc_post_ub_vb(int n) { return n <= 8 ? 2 : 1; }                 // phase B of a value tile: two reductions side by side
 
-template <int N, int TPB>
+template <int N, int TPB, bool DATA = false>
 __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const float* __restrict__ X,
                                                         const float* __restrict__ prm, QcLayout L, QcPde pde,
                                                         const float* __restrict__ qjets, float* __restrict__ out_u,
                                                         float* __restrict__ qbar, float* __restrict__ part,
                                                         int64_t part_stride, int64_t row0, int64_t B,
-                                                        float* __restrict__ s_v) {
+                                                        float* __restrict__ s_v, const float* __restrict__ tg = nullptr) {
   constexpr int WPT = QC_MS / TPB, QPW = QC_MS / WPT;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1079,10 +1107,15 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
   if constexpr (WPT == 4) u = (s_u[lane] + s_u[64 + lane]) + (s_u[128 + lane] + s_u[192 + lane]);
   u += prm[L.ob4];
   // ---------------- error / loss sums / per-point cotangent (every wave of the tile needs ub0; wave 0 stores)
-  const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   float* row = part + (row0 + tile) * part_stride;
   const bool seg_a = p < pde.n_seg_a;
-  const float target = value_target(pde, seg_a, t, x, y);
+  float target;
+  if constexpr (DATA) {
+    target = tg[pc];
+  } else {
+    const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
+    target = value_target(pde, seg_a, t, x, y);
+  }
   const float e = live ? u - target : 0.f;
   const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
   if (wt == 0 && tile_ok) {
@@ -1179,12 +1212,15 @@ template <int N> constexpr bool QC_POST6_PF_A = qc_post_pf(N);
 template <int N> constexpr int QC_POST6_UB_B = 1;
 template <int N> constexpr bool QC_POST6_PF_B = false;
 
-template <int N>
+// DATA: target from tg[p], residual with the zeroth-order term c_u u; the point then has a cotangent c_u gsc on u
+// itself, carried through expand_ub, the b4 column of the tile row and the out_u scratch.
+template <int N, bool DATA = false>
 __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                     QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                                     float* __restrict__ out_u, float* __restrict__ out_res,
                                                     float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
-                                                    int64_t row0, int64_t B, float* __restrict__ s_dyn) {
+                                                    int64_t row0, int64_t B, float* __restrict__ s_dyn,
+                                                    const float* __restrict__ tg = nullptr, const float c_u = 0.f) {
   constexpr int NCH = 6;
   float* s_z = s_dyn;                                                        // [H][64]
   float (*s_u)[NCH][64] = reinterpret_cast<float (*)[NCH][64]>(s_dyn + L.H * 64);   // [QC_MS][NCH][64]
@@ -1252,28 +1288,37 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
     u[c] = (s_u[0][c][lane] + s_u[1][c][lane]) + (s_u[2][c][lane] + s_u[3][c][lane]);
   u[0] += prm[L.ob4];
   // ---------------- residual / error / loss sums / per-point cotangent
-  const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
   float* row = part + (row0 + tile) * part_stride;
-  const float res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
-  const float target = residual_target(pde, t, x, y);
+  float res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
+  float target;
+  if constexpr (DATA) {
+    res = fmaf(c_u, u[0], res);
+    target = tg[pc];
+  } else {
+    const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
+    target = residual_target(pde, t, x, y);
+  }
   const float e = live ? res - target : 0.f;
   const float gsc = pde.w_res * e;
+  const float ub0 = DATA ? c_u * gsc : 0.f;   // analytic problems: the loss sees u only through its derivatives
   if (wave == 0) {
     const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
+    float sb4 = 0.f;      // d loss / d b4 = sum of the points' cotangents of u
+    if constexpr (DATA) sb4 = qc_wave_sum_to_lane63(ub0);
     if (lane == 63) {
       row[L.NP + 0] = ls;
       row[L.NP + 1] = 0.f;
       row[L.NP + 2] = 0.f;
-      row[L.ob4] = 0.f;   // the loss sees u only through the residual: no cotangent on u itself
+      row[L.ob4] = sb4;
     }
     if (live) {           // the per-point cotangents (MODE 2 contract of qc_post)
-      out_u[p] = 0.f;
+      out_u[p] = ub0;
       out_res[p] = gsc;
     }
   }
   // ---------------- phase B
   float ub[NCH];
-  expand_ub<NCH>(ub, 0.f, gsc, pde);
+  expand_ub<NCH>(ub, ub0, gsc, pde);
   mf2 qb2[3][N];
 #pragma unroll
   for (int cp = 0; cp < 3; ++cp)
@@ -1368,6 +1413,21 @@ __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X,
   extern __shared__ float s_dyn[];
   if constexpr (NCH == 6) k_post_fused6_body<N>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, s_dyn);
   else k_post_fused_value_body<N, QC_POST_VALUE_TPB>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part, part_stride, row0, B, s_dyn);
+}
+
+template <int N, int NCH>
+__global__ void __launch_bounds__(256) k_post_fused_data(const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                         const float* __restrict__ qjets, float* __restrict__ out_u,
+                                                         float* __restrict__ out_res, float* __restrict__ qbar,
+                                                         float* __restrict__ part, int64_t part_stride, int64_t row0,
+                                                         int64_t B, const float* __restrict__ tg, float c_u) {
+  extern __shared__ float s_dyn[];
+  if constexpr (NCH == 6)
+    k_post_fused6_body<N, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, s_dyn,
+                                tg, c_u);
+  else
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, qbar, part, part_stride,
+                                                        row0, B, s_dyn, tg);
 }
 
 // ================================================================== K outputs behind one shared network (Navier-Stokes)
@@ -1592,6 +1652,31 @@ __global__ void __launch_bounds__(256) k_post_fused_both(const float* __restrict
                                                   part_stride, v.row0, v.B, s_dyn);
 }
 
+// the two merged point kernels on tabulated targets (QcTab): same block order as their analytic forms
+template <int N>
+__global__ void __launch_bounds__(256) k_post_both_data(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
+                                                        QcPostSeg v, float* __restrict__ part, int64_t part_stride,
+                                                        int n_val, QcTab tab) {
+  if ((int)blockIdx.x >= n_val)
+    k_post_body<N, 6, 2, true>(blockIdx.x - n_val, nullptr, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr, r.qbar, part,
+                               part_stride, r.row0, r.B, tab.tg_res, tab.c_u);
+  else
+    k_post_value4<N, true>(blockIdx.x, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B, tab.tg_val);
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) k_post_fused_both_data(const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                              QcPostSeg r, QcPostSeg v, float* __restrict__ part,
+                                                              int64_t part_stride, int n_res, QcTab tab) {
+  extern __shared__ float s_dyn[];
+  if ((int)blockIdx.x < n_res)
+    k_post_fused6_body<N, true>(blockIdx.x, nullptr, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0, r.B,
+                                s_dyn, tab.tg_res, tab.c_u);
+  else
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x - n_res, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part,
+                                                        part_stride, v.row0, v.B, s_dyn, tab.tg_val);
+}
+
 template <int N>
 __global__ void k_post_wg_both(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r, QcPostSeg v,
                                float* __restrict__ part, int64_t part_stride, int HB, int PS, int n_val) {
@@ -1675,7 +1760,7 @@ int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* ab
 
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
-                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st) {
+                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTab* tab) {
   const int tiles = qc_ceil_div(B, 64);
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   int HB, PS, threads;
@@ -1711,11 +1796,32 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
     else if (fused) LAUNCH_FUSED(NN, 1);                                 \
     else { LAUNCH(NN, 1, 2); LAUNCH_WG(NN, 1); }                         \
   }
+  /* tabulated targets (mode 2 only): the same two forms on the _data kernels */                          \
+#define LAUNCH_DATA(NN, CC)                                                                                          \
+  if (fused)                                                                                                         \
+    hipLaunchKernelGGL((k_post_fused_data<NN, CC>), dim3(CC == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)),    \
+                       dim3(256), CC == 6 ? qc_post_fused_lds_res(L) : qc_post_fused_lds_val(L), st, prm, L, pde,      \
+                       qjets, out_u, out_res, qbar, part, part_stride, row0, B, tg, tab->c_u);                        \
+  else {                                                                                                             \
+    hipLaunchKernelGGL((k_post_data<NN, CC>), dim3(tiles), dim3(256), 0, st, prm, L, pde, qjets, out_u, out_res, qbar, \
+                       part, part_stride, row0, B, tg, tab->c_u);                                                     \
+    LAUNCH_WG(NN, CC);                                                                                               \
+  }
+#define CALL_DATA(NN) \
+  if (nch == 6) { LAUNCH_DATA(NN, 6) } else { LAUNCH_DATA(NN, 1) }
+  if (tab != nullptr) {
+    if (mode != 2) return QC_ERR_ARG;
+    const float* tg = nch == 6 ? tab->tg_res : tab->tg_val;
+    QC_MLP_DISPATCH(L.n, CALL_DATA)
+    return QC_OK;
+  }
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
+#undef CALL_DATA
 #undef LAUNCH
 #undef LAUNCH_WG
 #undef LAUNCH_FUSED
+#undef LAUNCH_DATA
   return QC_OK;
 }
 
@@ -1764,7 +1870,7 @@ int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLa
 // mode-2 post stage of both pipelines: point kernel, then weight-gradient kernel
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
-                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st) {
+                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcTab* tab) {
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
   int HB, PS, threads;
@@ -1785,8 +1891,23 @@ int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, c
     hipLaunchKernelGGL((k_post_wg_both<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride, \
                        HB, PS, nv);                                                                                     \
   }
+#define CALL_DATA(NN)                                                                                                   \
+  if (fused) {                                                                                                          \
+    hipLaunchKernelGGL((k_post_fused_both_data<NN>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,       \
+                       part_stride, nr, *tab);                                                                          \
+  } else {                                                                                                              \
+    hipLaunchKernelGGL((k_post_both_data<NN>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,  \
+                       nv4, *tab);                                                                                      \
+    hipLaunchKernelGGL((k_post_wg_both<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride, \
+                       HB, PS, nv);                                                                                     \
+  }
+  if (tab != nullptr) {
+    QC_MLP_DISPATCH(L.n, CALL_DATA)
+    return QC_OK;
+  }
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
+#undef CALL_DATA
   return QC_OK;
 }
 

@@ -49,6 +49,15 @@ __device__ __forceinline__ void qc_draw_point(int seg, int64_t gidx, int64_t fac
   }
 }
 
+// Dataset mode (qc_sample_dataset, the tabulated step): the same counter and key pick a ROW of a resident dataset
+// segment of n_seg rows (1 <= n_seg < 2^31) instead of coordinates: idx = (word 0 * n_seg) >> 32, i.e. sampling with
+// replacement, the counterpart of a torch.randint minibatch (tests/tabulated_reference.py::dataset_indices).
+__device__ __forceinline__ int64_t qc_draw_index(int seg, int64_t gidx, int64_t n_seg, uint64_t seed, uint64_t step) {
+  const U4 ctr = {(uint32_t)gidx, (uint32_t)(gidx >> 32), (uint32_t)step, (uint32_t)(step >> 32) ^ ((uint32_t)seg << 30)};
+  const U4 r = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (int64_t)(((uint64_t)r.x * (uint64_t)n_seg) >> 32);
+}
+
 struct QcDraw {      // on-device sampling of one launch's points (enabled = 0: read X instead)
   int enabled;
   int64_t n_ic;      // value tiles: leading IC points

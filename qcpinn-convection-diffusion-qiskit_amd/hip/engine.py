@@ -215,6 +215,7 @@ class SolverEngine:
         self.sigma = (1.0, 1.0, 1.0)                           # sigma_t, sigma_x, sigma_y of nn/pde.py:53-70
         self.coeffs = None      # explicit (c_t, c_x, c_y, d_xx, d_yy) of another linear operator on the same channels
         self.problem = L.QC_PROBLEM_CONVECTION_DIFFUSION      # analytic targets of the fused loss (qcpinn_hip.h)
+        self.c_u = 0.0          # zeroth-order coefficient of the residual: the tabulated step only (QC_PROBLEM_TABULATED)
         self.loss_weights = (2.0, 4.0, 2.0)                    # (residual, BC, IC) weights of the fused loss
         self.angle_map = circuit.angle_map                     # output map of the pre network, on every path
         self._fused: Dict[Tuple[int, int, int], "FusedStep"] = {}
@@ -350,7 +351,7 @@ class SolverEngine:
     # ------------------------------------------------------------------ fused training step
     def fused(self, B_res: int, n_ic: int, n_bc: int, opt: "OptimState", counts=None) -> "FusedStep":
         key = (B_res, n_ic, n_bc, id(opt), counts, self.problem, self.D, self.vx, self.vy, self.sigma, self.coeffs,
-               self.loss_weights)
+               self.loss_weights, self.c_u)
         if key not in self._fused:
             self._fused[key] = FusedStep(self, B_res, n_ic, n_bc, opt, counts)
         return self._fused[key]
@@ -411,7 +412,11 @@ class OptimState:
 
 class FusedStep:
     """One ``qc_fused_pinn_residual_step`` descriptor over fixed-size resident batches.  The caller
-    fills ``X_res`` / ``X_val`` (IC points first, then BC points) and calls ``run``."""
+    fills ``X_res`` / ``X_val`` (IC points first, then BC points) and calls ``run``.
+
+    When the engine's problem is ``QC_PROBLEM_TABULATED`` the step is ``qc_fused_pinn_data_step``: the caller also fills
+    ``target_res`` / ``target_val`` (same order as the points), or hands over a resident dataset with ``set_dataset`` and
+    lets ``QC_PHASE_SAMPLE`` gather points and targets from it."""
 
     def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, counts=None):
         self.eng, self.opt = eng, opt
@@ -421,6 +426,14 @@ class FusedStep:
         f = dict(dtype=torch.float32, device=dev)
         self.X_res = torch.zeros(max(B_res, 1), 3, **f)
         self.X_val = torch.zeros(max(B_val, 1), 3, **f)
+        # targets of the current batches and the (optional) resident dataset of the tabulated step
+        self.tabulated = eng.problem == L.QC_PROBLEM_TABULATED
+        self.target_res = torch.zeros(max(B_res, 1), **f)
+        self.target_val = torch.zeros(max(B_val, 1), **f)
+        self.data = L.QcStepData()
+        self.data.target_res_dev, self.data.target_val_dev = self.target_res.data_ptr(), self.target_val.data_ptr()
+        self.data.c_u = eng.c_u
+        self._dataset = None
         self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
         self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
         rows = (B_res + 63) // 64 + (B_val + 63) // 64
@@ -464,6 +477,25 @@ class FusedStep:
         d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
         d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
 
+    def set_dataset(self, segments) -> None:
+        """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on
+        the engine's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it."""
+        t = self.data
+        if segments is None:
+            segments = ((None, None),) * 3
+        keep = []
+        for name, (X, y) in zip(("res", "ic", "bc"), segments):
+            n = 0 if X is None else int(X.shape[0])
+            if n:
+                X, y = _need(X, self.eng.device, "dataset points"), _need(y.reshape(-1), self.eng.device, "dataset targets")
+                if X.dim() != 2 or X.shape[1] != 3 or y.numel() != n:
+                    raise L.QcError(f"dataset segment '{name}': points must be (N, 3) with N targets")
+                keep += [X, y]
+            setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
+            setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], y.data_ptr() if n else None)
+            setattr(t, "ds_n_" + name, n)
+        self._dataset = keep        # the descriptor holds raw pointers: keep the tensors alive
+
     def set_comm(self, comm) -> None:
         """A communicator of ``qc_comm_create`` (or None): GRADS | UPDATE in one call then all-reduces the flat
         [gradient | 3 loss sums] vector across the ranks inside the library (RCCL, same stream)."""
@@ -472,5 +504,9 @@ class FusedStep:
     def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
         if phases & L.QC_PHASE_SAMPLE:
             self.desc.sample_step += 1          # a fresh counter block per step
+        if self.tabulated:
+            L.check(self.eng.lib.qc_fused_pinn_data_step(C.byref(self.desc), C.byref(self.data), phases,
+                                                         _stream(self.eng.device)), "qc_fused_pinn_data_step")
+            return
         L.check(self.eng.lib.qc_fused_pinn_residual_step(C.byref(self.desc), phases, _stream(self.eng.device)),
                 "qc_fused_pinn_residual_step")

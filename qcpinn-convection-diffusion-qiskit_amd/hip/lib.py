@@ -28,10 +28,12 @@ EXPORTS = (
     "qc_sample_collocation", "qc_sample_collocation_faces", "qc_step_workspace_bytes", "qc_fused_pinn_residual_step",
     "qc_fused_step_stage", "qc_post_multi", "qc_comm_unique_id", "qc_comm_create", "qc_comm_destroy", "qc_allreduce_grads",
     "qc_pre_forward_map", "qc_pre_backward_map", "qc_program_set_angle_map",
+    "qc_post_data", "qc_sample_dataset", "qc_fused_pinn_data_step",
 )
 
 
 QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_PULSE = 0, 1, 2      # qc_pde.problem
+QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc_fused_pinn_data_step only
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
 QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
 
@@ -75,6 +77,16 @@ class QcStepDesc(C.Structure):
         ("sample_bc_face_points", C.c_int64),
         ("circ_ws_dev", C.c_void_p), ("circ_ws_bytes", C.c_size_t),
         ("comm", C.c_void_p),
+    ]
+
+
+class QcStepData(C.Structure):
+    """qc_step_data: batch targets, c_u and the resident dataset of the tabulated step."""
+    _fields_ = [
+        ("target_res_dev", C.c_void_p), ("target_val_dev", C.c_void_p), ("c_u", C.c_float),
+        ("ds_X_res", C.c_void_p), ("ds_r", C.c_void_p), ("ds_n_res", C.c_int64),
+        ("ds_X_ic", C.c_void_p), ("ds_u_ic", C.c_void_p), ("ds_n_ic", C.c_int64),
+        ("ds_X_bc", C.c_void_p), ("ds_u_bc", C.c_void_p), ("ds_n_bc", C.c_int64),
     ]
 
 
@@ -132,6 +144,10 @@ def load() -> C.CDLL:
     lib.qc_amp_forward.argtypes = [fp, fp, i32, i64, i32, vp]
     lib.qc_amp_backward.argtypes = [fp, fp, fp, i32, i64, i32, vp]
     lib.qc_fused_pinn_residual_step.argtypes = [C.POINTER(QcStepDesc), i32, vp]
+    lib.qc_post_data.argtypes = [fp, i32, i32, i32, C.POINTER(QcPde), fp, fp, C.c_float, fp, fp, fp, fp, i64, i64, i64, i32, vp]
+    lib.qc_sample_dataset.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, C.POINTER(QcStepData), C.c_uint64,
+                                      C.c_uint64, vp]
+    lib.qc_fused_pinn_data_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

@@ -17,6 +17,11 @@ batches, and the flat ``[gradient | 3 loss sums]`` vector is all-reduced once pe
 (identical, replicated) optimiser update.
 
 Any other model (the reference's duck type) runs the generic torch-autograd loop below.
+
+``dataset=`` (keyword-only, a ``data.tabulated.TabulatedProblem``) trains towards the user's own targets instead of the
+analytic ones: a ``DVPDESolver`` through ``qc_fused_pinn_data_step`` (minibatches gathered from the device-resident
+dataset, targets read from memory, residual with the zeroth-order term ``c_u u``), any other model through the generic
+loop on ``torch.randint`` minibatches of the same dataset and the same residual.
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ import torch
 from ..data.diffusion_dataset import Sampler, box, r, u
 from ..hip import engine as _engine
 from ..hip import lib as _lib
-from ..nn.pde import diffusion_operator
+from ..nn.pde import _grad, diffusion_operator
 
 
 def fetch_minibatch(sampler, N):
@@ -75,14 +80,18 @@ class FusedTrainer:
 
     def __init__(self, model, batch_size: int, capacity: int, sampler: str = "device", *, n_bc: int = None,
                  bc_faces=1, pde: dict = None, n_ic: int = None, loss_weights=(2.0, 4.0, 2.0), max_norm=1.0,
-                 optimizer=None, scheduler=None):
+                 optimizer=None, scheduler=None, dataset=None):
         """``n_bc`` / ``n_ic`` (default ``batch_size // 3`` each): GLOBAL boundary / initial points per step;
         ``bc_faces`` = 4 spreads the boundary points evenly over the faces x=0, x=1, y=0, y=1 (second workload,
         train_hybrid_qpinn.py:689-697), ``"random"`` puts each on a face drawn at random (trainer/train.py:118-135),
         instead of the x=0 face; ``pde`` = {"D", "vx", "vy", "problem"} overrides the engine's operator / targets;
         ``loss_weights`` = (residual, BC, IC) weights of the loss; ``max_norm`` None: no gradient clipping;
         ``optimizer`` / ``scheduler``: the torch objects the device state starts from and is mirrored into (default:
-        the model's own)."""
+        the model's own).  ``dataset`` (a ``TabulatedProblem``): train towards its targets with its operator
+        coefficients; ``sample()`` then arms the device gather from the dataset (``sampler="torch"``: ``torch.randint``
+        indices and a copy), every rank holding the whole dataset and gathering its shard by GLOBAL point index.
+        ``pde={"problem": 3, ...}`` (optional "coeffs" = (c_t, c_x, c_y, d_xx, d_yy) and "c_u") is the tabulated step
+        without a dataset: batches and targets come through ``load_batches(..., targets=)`` only."""
         # the fused step is the 3-D convection-diffusion step of trainer/diffusion_train.py:30-49 on a (t, x, y) -> u model;
         # the reference fails on any other shape (Linear(3, H) weight mismatch), and so does this trainer: a two-input
         # model keeps a zero-padded t column in W1 that the step would train, a K-output model has K last-layer rows
@@ -98,9 +107,20 @@ class FusedTrainer:
         self.eng.sigma = (1.0, 1.0, 1.0)          # the trainers call the operator with its default scalings
         self.eng.coeffs = None
         self.eng.loss_weights = tuple(float(w) for w in loss_weights)
+        # a tabulated step leaves the engine as it found it: the descriptor built below keeps what it needs
+        before = (self.eng.problem, self.eng.c_u)
         if pde:
             self.eng.D, self.eng.vx, self.eng.vy = float(pde["D"]), float(pde["vx"]), float(pde["vy"])
             self.eng.problem = int(pde["problem"])
+            if self.eng.problem == _lib.QC_PROBLEM_TABULATED:
+                self.eng.coeffs = tuple(float(c) for c in pde["coeffs"]) if "coeffs" in pde else None
+                self.eng.c_u = float(pde.get("c_u", 0.0))
+        self.dataset = None
+        if dataset is not None:
+            self.dataset = dataset.to(dev)
+            self.eng.problem = _lib.QC_PROBLEM_TABULATED
+            self.eng.coeffs, self.eng.c_u = self.dataset.coeffs, self.dataset.c_u
+        self.tabulated = self.eng.problem == _lib.QC_PROBLEM_TABULATED
         self.optimizer = model.optimizer if optimizer is None else optimizer
         self.scheduler = model.scheduler if scheduler is None else scheduler
         self.max_norm = max_norm
@@ -118,6 +138,13 @@ class FusedTrainer:
         self.bc_start = shard_slice(nb, self.world, self.rank).start
         self.opt = self._make_opt_state(capacity)
         self.fs = self.eng.fused(self.B_res, self.n_ic, self.n_bc, self.opt, self.global_counts)
+        if self.tabulated:
+            (self.eng.problem, self.eng.c_u), self.eng.coeffs = before, None
+        if self.dataset is not None:
+            for what, n_batch, n_rows in zip(("residual", "initial", "boundary"), self.global_counts, self.dataset.sizes()):
+                if n_batch > 0 and n_rows == 0:
+                    raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
+            self.fs.set_dataset(self.dataset.segments())
         self.lo = {k: box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.span = {k: box(k, dev)[1:2] - box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.eng.refresh_gates()
@@ -219,10 +246,22 @@ class FusedTrainer:
         """IC -> BC -> residual, uniform in the reference's boxes (trainer/diffusion_train.py:9-20,34-36).
         With the device sampler this only arms the next ``step()``."""
         self._explicit = False
+        if self.tabulated and self.dataset is None:
+            raise ValueError("a tabulated step without dataset= has nothing to sample from: use load_batches(..., targets=)")
         if self.sampler == "device":
             return
         self._explicit = True
         fs, dev = self.fs, self.device
+        if self.dataset is not None:     # torch.randint minibatches, IC -> BC -> residual like the draws below
+            (Xr, rr), (Xi, ui), (Xb, ub) = self.dataset.segments()
+            for X, y, n, dX, dy, o in ((Xi, ui, self.n_ic, fs.X_val, fs.target_val, 0),
+                                       (Xb, ub, self.n_bc, fs.X_val, fs.target_val, self.n_ic),
+                                       (Xr, rr, self.B_res, fs.X_res, fs.target_res, 0)):
+                if n:
+                    idx = torch.randint(0, X.shape[0], (n,), device=dev)
+                    dX[o:o + n] = X[idx]
+                    dy[o:o + n] = y[idx]
+            return
         if self.n_ic:
             fs.X_val[: self.n_ic] = self.lo["ics"] + self.span["ics"] * torch.rand(self.n_ic, 3, device=dev)
         if self.n_bc and self.bc_face_points == _lib.QC_BC_RANDOM_FACE:      # a random face per point, one draw
@@ -242,8 +281,13 @@ class FusedTrainer:
         if self.B_res:
             fs.X_res[: self.B_res] = self.lo["dom"] + self.span["dom"] * torch.rand(self.B_res, 3, device=dev)
 
-    def load_batches(self, X_ic, X_bc, X_res):
-        """Use given GLOBAL batches (parity tests): this rank takes its contiguous shard."""
+    def load_batches(self, X_ic, X_bc, X_res, targets=None):
+        """Use given GLOBAL batches (parity tests): this rank takes its contiguous shard.  ``targets`` =
+        (u_ic, u_bc, r_res), one value per point: required by, and only accepted for, a tabulated step."""
+        if targets is not None and not self.tabulated:
+            raise ValueError("targets need a tabulated step: construct the trainer with dataset= or pde={'problem': 3, ...}")
+        if targets is None and self.tabulated:
+            raise ValueError("a tabulated step needs targets=(u_ic, u_bc, r_res) with its batches")
         self._explicit = True
         fs, dev = self.fs, self.device
         s_ic = shard_slice(X_ic.shape[0], self.world, self.rank)
@@ -255,6 +299,16 @@ class FusedTrainer:
             fs.X_val[self.n_ic: self.n_ic + self.n_bc] = X_bc[s_bc].to(dev)
         if self.B_res:
             fs.X_res[: self.B_res] = X_res[s_rs].to(dev)
+        if targets is not None:
+            u_ic, u_bc, r_res = (torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in targets)
+            if (u_ic.numel(), u_bc.numel(), r_res.numel()) != (X_ic.shape[0], X_bc.shape[0], X_res.shape[0]):
+                raise ValueError("targets=(u_ic, u_bc, r_res) must hold one value per point of (X_ic, X_bc, X_res)")
+            if self.n_ic:
+                fs.target_val[: self.n_ic] = u_ic[s_ic].to(dev)
+            if self.n_bc:
+                fs.target_val[self.n_ic: self.n_ic + self.n_bc] = u_bc[s_bc].to(dev)
+            if self.B_res:
+                fs.target_res[: self.B_res] = r_res[s_rs].to(dev)
 
     def step(self):
         draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
@@ -271,9 +325,9 @@ class FusedTrainer:
         return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
 
 
-def _train_fused(model, batch_size, batches=None):
+def _train_fused(model, batch_size, batches=None, dataset=None):
     steps = model.epochs + 1
-    tr = FusedTrainer(model, batch_size, capacity=steps)
+    tr = FusedTrainer(model, batch_size, capacity=steps, dataset=dataset)
     t0 = time.time()
     model.logger.print(f"Starting training for {model.epochs} epochs...")
     model.logger.print(f"Batch size: {batch_size}")
@@ -283,7 +337,7 @@ def _train_fused(model, batch_size, batches=None):
         if batches is None:
             tr.sample()
         else:
-            tr.load_batches(*batches[it])
+            tr.load_batches(*batches[it][:3], targets=batches[it][3] if len(batches[it]) > 3 else None)
         tr.step()
         if it % pe == 0 or it == 0:
             # the reference logs the loss of iteration `it` BEFORE its optimiser step; the fused step has
@@ -306,12 +360,43 @@ def _train_fused(model, batch_size, batches=None):
 
 
 # ---------------------------------------------------------------------------------------------
-def _train_generic(model, batch_size):
-    """The reference algorithm for any duck-typed model, on torch autograd."""
+class _RowSampler:
+    """``Sampler`` over one segment of a TabulatedProblem: a ``torch.randint`` minibatch of its rows and targets."""
+
+    def __init__(self, X, y):
+        self.X, self.y = X, y.reshape(-1, 1)
+
+    def sample(self, N):
+        idx = torch.randint(0, self.X.shape[0], (N,))
+        return self.X[idx], self.y[idx]
+
+
+def tabulated_operator(model, t, x, y, coeffs, c_u):
+    """(u, c_u u + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy)) of a torch model by autograd."""
+    c_t, c_x, c_y, d_xx, d_yy = coeffs
+    for v in (t, x, y):
+        v.requires_grad_(True)
+    uu = model(torch.cat((t, x, y), 1))
+    u_x, u_y = _grad(uu, x), _grad(uu, y)
+    return uu, c_u * uu + c_t * _grad(uu, t) + c_x * u_x + c_y * u_y - (d_xx * _grad(u_x, x) + d_yy * _grad(u_y, y))
+
+
+def _train_generic(model, batch_size, dataset=None):
+    """The reference algorithm for any duck-typed model, on torch autograd.  With ``dataset``: the same loop on
+    torch.randint minibatches of its segments (IC -> BC -> residual) and its operator."""
     dev = model.device
-    ics = Sampler(3, box("ics", dev), u, name="Initial Condition", device=dev)
-    bc1 = Sampler(3, box("bc1", dev), u, name="Dirichlet BC1", device=dev)
-    res = Sampler(3, box("dom", dev), r, name="Forcing", device=dev)
+    if dataset is not None:
+        dataset = dataset.to(dev if dev is not None else "cpu")
+        for what, n_batch, n_rows in zip(("residual", "initial", "boundary"), (batch_size, batch_size // 3, batch_size // 3),
+                                         dataset.sizes()):
+            if n_batch > 0 and n_rows == 0:
+                raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
+        ics, bc1, res = _RowSampler(dataset.X_ic, dataset.u_ic), _RowSampler(dataset.X_bc, dataset.u_bc), \
+            _RowSampler(dataset.X_res, dataset.r)
+    else:
+        ics = Sampler(3, box("ics", dev), u, name="Initial Condition", device=dev)
+        bc1 = Sampler(3, box("bc1", dev), u, name="Dirichlet BC1", device=dev)
+        res = Sampler(3, box("dom", dev), r, name="Forcing", device=dev)
     t0 = time.time()
     model.logger.print(f"Starting training for {model.epochs} epochs...")
     model.logger.print(f"Batch size: {batch_size}")
@@ -325,7 +410,10 @@ def _train_generic(model, batch_size):
         X_rs, r_rs = fetch_minibatch(res, batch_size)
         pred_bc = model.forward(X_bc)
         pred_ic = model.forward(X_ic)
-        _, pred_r = diffusion_operator(model, X_rs[:, 0:1], X_rs[:, 1:2], X_rs[:, 2:3])
+        if dataset is not None:
+            _, pred_r = tabulated_operator(model, X_rs[:, 0:1], X_rs[:, 1:2], X_rs[:, 2:3], dataset.coeffs, dataset.c_u)
+        else:
+            _, pred_r = diffusion_operator(model, X_rs[:, 0:1], X_rs[:, 1:2], X_rs[:, 2:3])
         l_r, l_bc, l_ic = model.loss_fn(pred_r, r_rs), model.loss_fn(pred_bc, u_bc), model.loss_fn(pred_ic, u_ic)
         loss = 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic
         fwd_times.append(time.time() - t_it)
@@ -346,12 +434,14 @@ def _train_generic(model, batch_size):
     model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
 
 
-def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None):
+def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None):
     """``batches`` (keyword-only, not in the reference): a per-iteration list of
-    ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests."""
+    ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests; with a dataset each entry carries a
+    fourth element, the targets ``(u_ic, u_bc, r_res)``.  ``dataset`` (keyword-only): a ``TabulatedProblem`` whose targets
+    and operator replace the analytic problem (module docstring)."""
     if hasattr(model, "_engine_for") and hasattr(model, "quantum_layer"):
-        _train_fused(model, batch_size, batches)
+        _train_fused(model, batch_size, batches, dataset)
     else:
         if batches is not None:
             raise ValueError("explicit batches are only supported for DVPDESolver models")
-        _train_generic(model, batch_size)
+        _train_generic(model, batch_size, dataset)
