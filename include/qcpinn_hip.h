@@ -325,6 +325,45 @@ int qc_sample_dataset(float* X_res_dev, float* target_res_dev, int64_t n_res, in
  * empty dataset segment behind a non-empty batch, or one of 2^31 rows or more; any other problem id. */
 int qc_fused_pinn_data_step(const qc_step_desc* desc, const qc_step_data* data, int phases, void* stream);
 
+/* ---- the tabulated step with the OPERATOR as data too: one coefficient row per residual point, next to its target,
+ *   res_p = c_u[p] u + c_3[p] u^3 + c_t[p] u_t + c_x[p] u_x + c_y[p] u_y - (d_xx[p] u_xx + d_yy[p] u_yy).
+ * Covers velocity / diffusivity fields v(x, y), D(x); derivative conditions (a Neumann point is the row (0, 0, 1, 0, 0, 0, 0)
+ * with the prescribed flux as its target; Robin: c_u and one derivative column); and the cubic term of
+ * klein_gordon_operator, u_tt + alpha u_xx + beta u + gamma u**3 (nn/pde.py:28-41): with (t, x) on the x / y slots
+ * d_xx = -1, d_yy = -alpha, c_u = beta, c_3 = gamma.  A per-point loss weight w is the row AND its target scaled by sqrt(w).
+ * Value points keep comparing u with their target. */
+#define QC_COEF_COLS 7   /* c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 -- signs as in qc_post_data, c_3 multiplies u^3 */
+typedef struct qc_step_coef {
+  float* coef_res_dev;      /* [7][B_res] batch-minor: the rows of the CURRENT residual batch */
+  const float* ds_coef;     /* [ds_n_res][7] row-major, beside data->ds_X_res / ds_r: gathered with them under SAMPLE */
+} qc_step_coef;
+
+/* qc_post mode 2 on residual points (nch = 6) with per-point operator rows coef_dev[7][B] and targets target_dev[B]
+ * (pde->problem = QC_PROBLEM_TABULATED; pde->c_t .. d_yy are not read, w_res and inv_n_res are).  cot_dev[6][B] receives the
+ * per-point cotangents of the six channels of u: with g = w_res (res - target),
+ *   (c_u + 3 c_3 u^2) g,  g c_t,  g c_x,  g c_y,  -d_xx g,  -d_yy g.
+ * The b4 column of a tile row is the sum of the first; the three loss columns are those of qc_post_data. */
+int qc_post_coef(const float* params_dev, int H, int n, int n_theta, const qc_pde* pde, const float* qjets_dev,
+                 const float* target_dev, const float* coef_dev, float* cot_dev, float* qbar_dev, float* part_dev,
+                 int64_t part_stride, int64_t row0, int64_t B, void* stream);
+
+/* qc_sample_dataset that also gathers the operator rows of the residual points, in the same launch and with the same
+ * Philox index (so the same batches as qc_sample_dataset on the same seed): coef_res_dev[k * n_res + i] =
+ * coef->ds_coef[idx * 7 + k].  coef_res_dev and coef->ds_coef may be NULL only with n_res = 0. */
+int qc_sample_dataset_coef(float* X_res_dev, float* target_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev,
+                           float* target_val_dev, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                           float* coef_res_dev, const qc_step_data* data, const qc_step_coef* coef, uint64_t seed,
+                           uint64_t step, void* stream);
+
+/* qc_fused_pinn_data_step with the residual operator read from coef->coef_res_dev: desc->pde.c_t .. d_yy and data->c_u
+ * are not read.  Value tiles, targets, phases, both forms, circuit families, encodings, workspace and flat vector are those
+ * of the data step (the split form's [6][B_res] cotangent scratch is the head of abar_res_dev).  QC_PHASE_SAMPLE fills
+ * points, targets and coefficient rows in one launch.  QC_ERR_ARG before any launch: coef NULL; coef_res_dev NULL with
+ * B_res > 0; QC_PHASE_SAMPLE with ds_coef NULL and B_res > 0; whatever qc_fused_pinn_data_step refuses.  With B_res = 0
+ * both pointers may be NULL. */
+int qc_fused_pinn_coef_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef, int phases,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,10 @@ struct QcTab {
   float c_u;
 };
 
+// Per-point operator rows of the coefficient step (qc_post_coef): columns c_u, c_t, c_x, c_y, d_xx, d_yy, c_3, stored
+// batch-minor [QC_COEF_COLS][B] next to the residual targets.  == QC_COEF_COLS of the public header.
+constexpr int QC_COEF_N = 7;
+
 struct QcPde {  // == qc_pde of the public header
   float D, vx, vy;                 // physical constants: analytic targets of mode 2
   float c_t, c_x, c_y, d_xx, d_yy; // operator coefficients (sigma scalings folded in)
@@ -112,11 +116,12 @@ int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, floa
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
                         float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
                         hipStream_t st, int map, const float* ajr, const float* ajv);
-// `tab` (both post launchers): non-null selects the tabulated kernels (pde.problem == QC_PB_TABULATED)
+// `tab` (both post launchers): non-null selects the tabulated kernels (pde.problem == QC_PB_TABULATED); with `coef`
+// ([7][B_res], needs `tab`) the residual points take their operator from it and ubr / out_u is a [6][B] cotangent scratch
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
                      int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st,
-                     const QcTab* tab = nullptr);
+                     const QcTab* tab = nullptr, const float* coef = nullptr);
 int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t,
                    int map = 0);
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
@@ -125,7 +130,7 @@ int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* ab
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t,
-                const QcTab* tab = nullptr);
+                const QcTab* tab = nullptr, const float* coef = nullptr);
 int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float* w4k, const float* qjets, float* out_u,
                       const float* ubar, float* qbar, float* part, int64_t part_stride, float* partk, int64_t partk_stride,
                       int64_t row0, int64_t B, hipStream_t);
@@ -143,7 +148,7 @@ int qc_sample_dataset_launch(float* X_res, float* tg_res, int64_t n_res, int64_t
                              int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
                              const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic, int64_t ds_n_ic,
                              const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed, uint64_t step,
-                             hipStream_t);
+                             hipStream_t, float* coef_res = nullptr, const float* ds_coef = nullptr);
 // HBM family, n >= 9 (qc_circuit_hbm2.hip, qc_circuit_h2s_kernels.h): all tiles of a batch resident when the workspace allows
 void* qc_h2_create(const qc_program* pg, int absorb, int amplitude);   // amplitude: the encoding the plan is built for
 void qc_h2_destroy(void* h2);

@@ -532,15 +532,22 @@ __device__ __forceinline__ void expand_ub(float (&ub)[NCH], float ub0, float gsc
 
 // DATA (MODE 2 only, QC_PB_TABULATED): the point's target is tg[p] instead of the analytic function of X, and the residual
 // carries the zeroth-order term c_u u, whose cotangent on u is c_u gsc.  DATA = false is the code as it was.
-template <int N, int NCH, int MODE, bool DATA = false>
+// COEF (with DATA, residual points only): the operator is the point's own row coef[k][p], k = c_u, c_t, c_x, c_y, d_xx,
+// d_yy, c_3 (QC_COEF_N), with the cubic term c_3 u^3; pde.c_* / d_* and c_u are not read.  The unit cotangent of the
+// reverse pass is then per lane, and the cubic term adds a second direction, the unit cotangent of u alone (N more
+// accumulators): its weight 3 c_3 u^2 is only known after the loop.  out_u receives all six channel cotangents [6][B]
+// (the weight-gradient kernel runs in its gen mode on them); out_res is not written.
+template <int N, int NCH, int MODE, bool DATA = false, bool COEF = false>
 __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                                               QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ out_res,
                                               const float* __restrict__ in_ubar, const float* __restrict__ in_rbar,
                                               float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B,
-                                              const float* __restrict__ tg = nullptr, const float c_u = 0.f) {
+                                              const float* __restrict__ tg = nullptr, const float c_u = 0.f,
+                                              const float* __restrict__ coef = nullptr) {
   static_assert(!DATA || MODE == 2, "tabulated targets: the fused mode only");
+  static_assert(!COEF || (DATA && NCH == 6), "per-point operators: tabulated residual points only");
   // block = 4 waves on one 64-point tile; wave w owns a quarter of the hidden units
   __shared__ float s_buf[QC_MS][NCH * N][64];   // partial u jets first (NCH rows), partial qbar later
   const int lane = threadIdx.x & 63;
@@ -554,6 +561,11 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int i = 0; i < N; ++i) q[c][i] = qjets[((int64_t)c * N + i) * B + pc];
+  float cf[COEF ? QC_COEF_N : 1];
+  if constexpr (COEF) {
+#pragma unroll
+    for (int k = 0; k < QC_COEF_N; ++k) cf[k] = coef[(int64_t)k * B + pc];
+  }
   const float* W3 = prm + L.oW3;
   const float* b3 = prm + L.ob3;
   const float* W4 = prm + L.oW4;
@@ -561,6 +573,12 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
   const int m0 = wave * hq, m1 = (m0 + hq) < L.H ? (m0 + hq) : L.H;
 
   float ub0 = 0.f, gsc = 0.f;  // cotangent of u, and of the residual
+  float k3 = 0.f;              // COEF: 3 c_3 u^2, the weight of the second direction
+  float qbu0[COEF ? N : 1];    // COEF: reverse pass of the unit cotangent of u alone
+  if constexpr (COEF) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) qbu0[i] = 0.f;
+  }
   // MODE 2: the reverse pass is linear in its single non-zero cotangent (the residual's for residual points,
   // u's for value points), so it is accumulated for a UNIT cotangent inside the forward loop and scaled
   // afterwards - the pre-activations and tanh are formed once per hidden unit, not twice.
@@ -576,7 +594,11 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 #pragma unroll
     for (int c = 0; c < NCH; ++c) u[c] = 0.f;
     float ub_unit[NCH];
-    expand_ub<NCH>(ub_unit, NCH == 6 ? (DATA ? c_u : 0.f) : 1.f, NCH == 6 ? 1.f : 0.f, pde);
+    if constexpr (COEF) {
+      ub_unit[0] = cf[0]; ub_unit[1] = cf[1]; ub_unit[2] = cf[2]; ub_unit[3] = cf[3]; ub_unit[4] = -cf[4]; ub_unit[5] = -cf[5];
+    } else {
+      expand_ub<NCH>(ub_unit, NCH == 6 ? (DATA ? c_u : 0.f) : 1.f, NCH == 6 ? 1.f : 0.f, pde);
+    }
     for (int m = m0; m < m1; ++m) {
       float g[NCH];
 #pragma unroll
@@ -606,6 +628,11 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 #pragma unroll
           for (int c = 0; c < NCH; ++c) qbu[c][i] = fmaf(w3, gb[c], qbu[c][i]);
         }
+        if constexpr (COEF) {   // post_cotangents of ub = (1, 0, ..): gb[0] = w4 d1 and nothing else
+          const float g0 = w4 * (1.f - z * z);
+#pragma unroll
+          for (int i = 0; i < N; ++i) qbu0[i] = fmaf(W3[m * N + i], g0, qbu0[i]);
+        }
       }
     }
 #pragma unroll
@@ -624,8 +651,14 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
       return;
     }
     float res = 0.f;
-    if constexpr (NCH == 6) res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
-    if constexpr (NCH == 6 && DATA) res = fmaf(c_u, u[0], res);
+    if constexpr (COEF) {
+      res = cf[1] * u[1] + cf[2] * u[2] + cf[3] * u[3] - (cf[4] * u[4] + cf[5] * u[5]);
+      res = fmaf(fmaf(cf[6] * u[0], u[0], cf[0]), u[0], res);
+      k3 = 3.f * cf[6] * u[0] * u[0];
+    } else if constexpr (NCH == 6) {
+      res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
+    }
+    if constexpr (NCH == 6 && DATA && !COEF) res = fmaf(c_u, u[0], res);
     if constexpr (MODE == 0) {
       if (live && wave == 0) {
         if (out_u) out_u[p] = u[0];
@@ -645,7 +678,8 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
         const float target = DATA ? tgp : residual_target(pde, t, x, y);
         const float e = live ? res - target : 0.f;
         gsc = pde.w_res * e;
-        if constexpr (DATA) ub0 = c_u * gsc;   // reaches k_post_wg through out_u (W4 / b4 / hidden-layer gradients)
+        if constexpr (COEF) ub0 = (cf[0] + k3) * gsc;
+        else if constexpr (DATA) ub0 = c_u * gsc;   // reaches k_post_wg through out_u (W4 / b4 / hidden-layer gradients)
         if (wave == 0) {
           const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
           if (lane == 63) {
@@ -669,7 +703,16 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
           }
         }
       }
-      if (live && wave == 0) {  // hand the per-point cotangents to k_post_wg
+      if constexpr (COEF) {
+        if (live && wave == 0) {  // the six channel cotangents, for k_post_wg in its gen mode
+          out_u[p] = ub0;
+          out_u[B + p] = gsc * cf[1];
+          out_u[2 * B + p] = gsc * cf[2];
+          out_u[3 * B + p] = gsc * cf[3];
+          out_u[4 * B + p] = -cf[4] * gsc;
+          out_u[5 * B + p] = -cf[5] * gsc;
+        }
+      } else if (live && wave == 0) {  // hand the per-point cotangents to k_post_wg
         out_u[p] = ub0;
         if constexpr (NCH == 6) out_res[p] = gsc;
       }
@@ -684,7 +727,10 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
-      for (int i = 0; i < N; ++i) s_buf[wave][c * N + i][lane] = scale * qbu[c][i];
+      for (int i = 0; i < N; ++i) {
+        if constexpr (COEF) s_buf[wave][c * N + i][lane] = scale * (c == 0 ? fmaf(k3, qbu0[i], qbu[c][i]) : qbu[c][i]);
+        else s_buf[wave][c * N + i][lane] = scale * qbu[c][i];
+      }
     __syncthreads();
     if (live) {
       for (int f = wave; f < NCH * N; f += QC_MS)
@@ -754,6 +800,17 @@ __global__ void __launch_bounds__(256) k_post_data(const float* __restrict__ prm
                                                    const float* __restrict__ tg, float c_u) {
   k_post_body<N, NCH, 2, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, out_res, nullptr, nullptr, qbar, part,
                                part_stride, row0, B, tg, c_u);
+}
+
+// MODE 2 with per-point operator rows (qc_post_coef; residual points of the coefficient step's split form)
+template <int N>
+__global__ void __launch_bounds__(256) k_post_coef(const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                   const float* __restrict__ qjets, float* __restrict__ cot,
+                                                   float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
+                                                   int64_t row0, int64_t B, const float* __restrict__ tg,
+                                                   const float* __restrict__ coef) {
+  k_post_body<N, 6, 2, true, true>(blockIdx.x, nullptr, prm, L, pde, qjets, cot, nullptr, nullptr, nullptr, qbar, part,
+                                   part_stride, row0, B, tg, 0.f, coef);
 }
 
 // Weight gradients of the post network: lane = hidden unit m (owns row m of W3, b3[m], W4[m]); the
@@ -1214,13 +1271,17 @@ template <int N> constexpr bool QC_POST6_PF_B = false;
 
 // DATA: target from tg[p], residual with the zeroth-order term c_u u; the point then has a cotangent c_u gsc on u
 // itself, carried through expand_ub, the b4 column of the tile row and the out_u scratch.
-template <int N, bool DATA = false>
+// COEF (with DATA): the point's own operator row coef[k][p] (see k_post_body), loaded ahead of phase A; u is known
+// before phase B, so the cubic term only changes the residual and ub0.  out_u receives the six channel cotangents [6][B].
+template <int N, bool DATA = false, bool COEF = false>
 __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                     QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                                     float* __restrict__ out_u, float* __restrict__ out_res,
                                                     float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
                                                     int64_t row0, int64_t B, float* __restrict__ s_dyn,
-                                                    const float* __restrict__ tg = nullptr, const float c_u = 0.f) {
+                                                    const float* __restrict__ tg = nullptr, const float c_u = 0.f,
+                                                    const float* __restrict__ coef = nullptr) {
+  static_assert(!COEF || DATA, "per-point operators: tabulated targets only");
   constexpr int NCH = 6;
   float* s_z = s_dyn;                                                        // [H][64]
   float (*s_u)[NCH][64] = reinterpret_cast<float (*)[NCH][64]>(s_dyn + L.H * 64);   // [QC_MS][NCH][64]
@@ -1237,6 +1298,11 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
 #pragma unroll
     for (int i = 0; i < N; ++i)
       q2[cp][i] = (mf2){qjets[((int64_t)(2 * cp) * N + i) * B + pc], qjets[((int64_t)(2 * cp + 1) * N + i) * B + pc]};
+  float cf[COEF ? QC_COEF_N : 1];   // seven coalesced loads, first used after phase A
+  if constexpr (COEF) {
+#pragma unroll
+    for (int k = 0; k < QC_COEF_N; ++k) cf[k] = coef[(int64_t)k * B + pc];
+  }
   const float* W3 = prm + L.oW3;
   const float* b3 = prm + L.ob3;
   const float* W4 = prm + L.oW4;
@@ -1289,10 +1355,16 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   u[0] += prm[L.ob4];
   // ---------------- residual / error / loss sums / per-point cotangent
   float* row = part + (row0 + tile) * part_stride;
-  float res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
+  float res;
+  if constexpr (COEF) {
+    res = cf[1] * u[1] + cf[2] * u[2] + cf[3] * u[3] - (cf[4] * u[4] + cf[5] * u[5]);
+    res = fmaf(fmaf(cf[6] * u[0], u[0], cf[0]), u[0], res);
+  } else {
+    res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
+  }
   float target;
   if constexpr (DATA) {
-    res = fmaf(c_u, u[0], res);
+    if constexpr (!COEF) res = fmaf(c_u, u[0], res);
     target = tg[pc];
   } else {
     const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
@@ -1300,7 +1372,9 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   }
   const float e = live ? res - target : 0.f;
   const float gsc = pde.w_res * e;
-  const float ub0 = DATA ? c_u * gsc : 0.f;   // analytic problems: the loss sees u only through its derivatives
+  // analytic problems: the loss sees u only through its derivatives
+  float ub0 = DATA ? c_u * gsc : 0.f;
+  if constexpr (COEF) ub0 = fmaf(3.f * cf[6] * u[0], u[0], cf[0]) * gsc;
   if (wave == 0) {
     const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
     float sb4 = 0.f;      // d loss / d b4 = sum of the points' cotangents of u
@@ -1311,14 +1385,27 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
       row[L.NP + 2] = 0.f;
       row[L.ob4] = sb4;
     }
-    if (live) {           // the per-point cotangents (MODE 2 contract of qc_post)
+    if constexpr (COEF) {
+      if (live) {           // the six channel cotangents (qc_post_coef)
+        out_u[p] = ub0;
+        out_u[B + p] = gsc * cf[1];
+        out_u[2 * B + p] = gsc * cf[2];
+        out_u[3 * B + p] = gsc * cf[3];
+        out_u[4 * B + p] = -cf[4] * gsc;
+        out_u[5 * B + p] = -cf[5] * gsc;
+      }
+    } else if (live) {    // the per-point cotangents (MODE 2 contract of qc_post)
       out_u[p] = ub0;
       out_res[p] = gsc;
     }
   }
   // ---------------- phase B
   float ub[NCH];
-  expand_ub<NCH>(ub, ub0, gsc, pde);
+  if constexpr (COEF) {
+    ub[0] = ub0; ub[1] = gsc * cf[1]; ub[2] = gsc * cf[2]; ub[3] = gsc * cf[3]; ub[4] = -cf[4] * gsc; ub[5] = -cf[5] * gsc;
+  } else {
+    expand_ub<NCH>(ub, ub0, gsc, pde);
+  }
   mf2 qb2[3][N];
 #pragma unroll
   for (int cp = 0; cp < 3; ++cp)
@@ -1428,6 +1515,17 @@ __global__ void __launch_bounds__(256) k_post_fused_data(const float* __restrict
   else
     k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, qbar, part, part_stride,
                                                         row0, B, s_dyn, tg);
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) k_post_fused_coef(const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                         const float* __restrict__ qjets, float* __restrict__ cot,
+                                                         float* __restrict__ qbar, float* __restrict__ part,
+                                                         int64_t part_stride, int64_t row0, int64_t B,
+                                                         const float* __restrict__ tg, const float* __restrict__ coef) {
+  extern __shared__ float s_dyn[];
+  k_post_fused6_body<N, true, true>(blockIdx.x, nullptr, prm, L, pde, qjets, cot, nullptr, qbar, part, part_stride, row0, B,
+                                    s_dyn, tg, 0.f, coef);
 }
 
 // ================================================================== K outputs behind one shared network (Navier-Stokes)
@@ -1686,6 +1784,42 @@ __global__ void k_post_wg_both(const float* __restrict__ prm, QcLayout L, QcPde 
     k_post_wg_body<N, 1>(blockIdx.x, prm, L, pde, v.qjets, v.ub, nullptr, part, part_stride, v.row0, v.B, HB, PS);
 }
 
+// the merged kernels of the coefficient step: residual tiles on the COEF bodies (r.ub = the [6][B] cotangent scratch,
+// r.rb unused), value tiles on the DATA code; the weight-gradient kernel reads the residual cotangents in its gen mode
+template <int N>
+__global__ void __launch_bounds__(256) k_post_both_coef(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
+                                                        QcPostSeg v, float* __restrict__ part, int64_t part_stride,
+                                                        int n_val, QcTab tab, const float* __restrict__ coef) {
+  if ((int)blockIdx.x >= n_val)
+    k_post_body<N, 6, 2, true, true>(blockIdx.x - n_val, nullptr, prm, L, pde, r.qjets, r.ub, nullptr, nullptr, nullptr, r.qbar,
+                                     part, part_stride, r.row0, r.B, tab.tg_res, 0.f, coef);
+  else
+    k_post_value4<N, true>(blockIdx.x, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B, tab.tg_val);
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) k_post_fused_both_coef(const float* __restrict__ prm, QcLayout L, QcPde pde,
+                                                              QcPostSeg r, QcPostSeg v, float* __restrict__ part,
+                                                              int64_t part_stride, int n_res, QcTab tab,
+                                                              const float* __restrict__ coef) {
+  extern __shared__ float s_dyn[];
+  if ((int)blockIdx.x < n_res)
+    k_post_fused6_body<N, true, true>(blockIdx.x, nullptr, prm, L, pde, r.qjets, r.ub, nullptr, r.qbar, part, part_stride,
+                                      r.row0, r.B, s_dyn, tab.tg_res, 0.f, coef);
+  else
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x - n_res, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part,
+                                                        part_stride, v.row0, v.B, s_dyn, tab.tg_val);
+}
+
+template <int N>
+__global__ void k_post_wg_both_coef(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r, QcPostSeg v,
+                                    float* __restrict__ part, int64_t part_stride, int HB, int PS, int n_val) {
+  if ((int)blockIdx.x >= n_val)
+    k_post_wg_body<N, 6>(blockIdx.x - n_val, prm, L, pde, r.qjets, r.ub, nullptr, part, part_stride, r.row0, r.B, HB, PS, 1);
+  else
+    k_post_wg_body<N, 1>(blockIdx.x, prm, L, pde, v.qjets, v.ub, nullptr, part, part_stride, v.row0, v.B, HB, PS);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
@@ -1697,6 +1831,15 @@ __global__ void k_post_wg_both(const float* __restrict__ prm, QcLayout L, QcPde 
     case 10: { CALL(10) } break; case 11: { CALL(11) } break; case 12: { CALL(12) } break;         \
     case 13: { CALL(13) } break; case 14: { CALL(14) } break; case 15: { CALL(15) } break;         \
     case 16: { CALL(16) } break;                                                                   \
+    default: return QC_ERR_UNSUPPORTED;                                                            \
+  }
+
+// the merged launches of the coefficient step: the merged form exists for the register family only (n = 2 .. 5), so its
+// kernels are instantiated for those widths alone (the weight-gradient kernel would need scratch memory from n = 13)
+#define QC_MLP_DISPATCH_MERGED(n, CALL)                                                            \
+  switch (n) {                                                                                     \
+    case 2: { CALL(2) } break;  case 3: { CALL(3) } break;                                         \
+    case 4: { CALL(4) } break;  case 5: { CALL(5) } break;                                         \
     default: return QC_ERR_UNSUPPORTED;                                                            \
   }
 
@@ -1760,7 +1903,8 @@ int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* ab
 
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
-                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTab* tab) {
+                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTab* tab,
+                const float* coef) {
   const int tiles = qc_ceil_div(B, 64);
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   int HB, PS, threads;
@@ -1809,6 +1953,22 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
   }
 #define CALL_DATA(NN) \
   if (nch == 6) { LAUNCH_DATA(NN, 6) } else { LAUNCH_DATA(NN, 1) }
+  /* per-point operator rows (residual points): out_u = the [6][B] cotangents, the pair's second kernel in gen mode */ \
+#define CALL_COEF(NN)                                                                                                \
+  if (fused)                                                                                                         \
+    hipLaunchKernelGGL((k_post_fused_coef<NN>), dim3(tiles), dim3(256), qc_post_fused_lds_res(L), st, prm, L, pde,    \
+                       qjets, out_u, qbar, part, part_stride, row0, B, tab->tg_res, coef);                            \
+  else {                                                                                                             \
+    hipLaunchKernelGGL((k_post_coef<NN>), dim3(tiles), dim3(256), 0, st, prm, L, pde, qjets, out_u, qbar, part,       \
+                       part_stride, row0, B, tab->tg_res, coef);                                                      \
+    hipLaunchKernelGGL((k_post_wg<NN, 6>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets, (const float*)out_u, \
+                       (const float*)nullptr, part, part_stride, row0, B, HB, PS, 1);                                 \
+  }
+  if (coef != nullptr) {
+    if (mode != 2 || nch != 6 || tab == nullptr) return QC_ERR_ARG;
+    QC_MLP_DISPATCH(L.n, CALL_COEF)
+    return QC_OK;
+  }
   if (tab != nullptr) {
     if (mode != 2) return QC_ERR_ARG;
     const float* tg = nch == 6 ? tab->tg_res : tab->tg_val;
@@ -1818,6 +1978,7 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
 #undef CALL_DATA
+#undef CALL_COEF
 #undef LAUNCH
 #undef LAUNCH_WG
 #undef LAUNCH_FUSED
@@ -1870,7 +2031,8 @@ int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLa
 // mode-2 post stage of both pipelines: point kernel, then weight-gradient kernel
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
-                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcTab* tab) {
+                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcTab* tab,
+                     const float* coef) {
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
   int HB, PS, threads;
@@ -1901,6 +2063,22 @@ int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, c
     hipLaunchKernelGGL((k_post_wg_both<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride, \
                        HB, PS, nv);                                                                                     \
   }
+  /* coefficient step: ubr is the [6][Br] cotangent scratch of the residual tiles */                                     \
+#define CALL_COEF(NN)                                                                                                   \
+  if (fused) {                                                                                                          \
+    hipLaunchKernelGGL((k_post_fused_both_coef<NN>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,       \
+                       part_stride, nr, *tab, coef);                                                                    \
+  } else {                                                                                                              \
+    hipLaunchKernelGGL((k_post_both_coef<NN>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,  \
+                       nv4, *tab, coef);                                                                                \
+    hipLaunchKernelGGL((k_post_wg_both_coef<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part,        \
+                       part_stride, HB, PS, nv);                                                                        \
+  }
+  if (coef != nullptr) {
+    if (tab == nullptr) return QC_ERR_ARG;
+    QC_MLP_DISPATCH_MERGED(L.n, CALL_COEF)
+    return QC_OK;
+  }
   if (tab != nullptr) {
     QC_MLP_DISPATCH(L.n, CALL_DATA)
     return QC_OK;
@@ -1908,6 +2086,7 @@ int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, c
   QC_MLP_DISPATCH(L.n, CALL)
 #undef CALL
 #undef CALL_DATA
+#undef CALL_COEF
   return QC_OK;
 }
 

@@ -74,16 +74,54 @@ __global__ void __launch_bounds__(256) k_sample_dataset(float* __restrict__ X_re
   dstT[out] = ds.tg[idx];
 }
 
+// The same gather for the coefficient step: a residual point also copies its operator row, ds_coef[idx][7] ->
+// coef_res[7][n_res] (batch-minor).  Same segments, counters and index, hence the same batches as k_sample_dataset.
+__global__ void __launch_bounds__(256) k_sample_dataset_coef(float* __restrict__ X_res, float* __restrict__ tg_res,
+                                                             int64_t n_res, int64_t off_res, float* __restrict__ X_val,
+                                                             float* __restrict__ tg_val, int64_t n_ic, int64_t off_ic,
+                                                             int64_t n_bc, int64_t off_bc, QcDsSeg d_res, QcDsSeg d_ic,
+                                                             QcDsSeg d_bc, uint64_t seed, uint64_t step,
+                                                             float* __restrict__ coef_res, const float* __restrict__ ds_coef) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int seg;
+  int64_t out, gidx;
+  float *dstX, *dstT;
+  QcDsSeg ds;
+  if (i < n_res) {
+    seg = 0; out = i; gidx = off_res + i; dstX = X_res; dstT = tg_res; ds = d_res;
+  } else if (i < n_res + n_ic) {
+    seg = 1; out = i - n_res; gidx = off_ic + out; dstX = X_val; dstT = tg_val; ds = d_ic;
+  } else if (i < n_res + n_ic + n_bc) {
+    seg = 2; out = i - n_res; gidx = off_bc + (out - n_ic); dstX = X_val; dstT = tg_val; ds = d_bc;
+  } else {
+    return;
+  }
+  const int64_t idx = qc_draw_index(seg, gidx, ds.n, seed, step);   // < ds.n: the product's high word
+  dstX[out * 3 + 0] = ds.X[idx * 3 + 0];
+  dstX[out * 3 + 1] = ds.X[idx * 3 + 1];
+  dstX[out * 3 + 2] = ds.X[idx * 3 + 2];
+  dstT[out] = ds.tg[idx];
+  if (seg == 0) {
+#pragma unroll
+    for (int k = 0; k < QC_COEF_N; ++k) coef_res[(int64_t)k * n_res + out] = ds_coef[idx * QC_COEF_N + k];
+  }
+}
+
 }  // namespace
 
 int qc_sample_dataset_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
                              int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
                              const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic, int64_t ds_n_ic,
                              const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed, uint64_t step,
-                             hipStream_t st) {
+                             hipStream_t st, float* coef_res, const float* ds_coef) {
   const int64_t total = n_res + n_ic + n_bc;
   if (total <= 0) return QC_OK;
   const QcDsSeg a = {dsX_res, ds_r, ds_n_res}, b = {dsX_ic, ds_u_ic, ds_n_ic}, c = {dsX_bc, ds_u_bc, ds_n_bc};
+  if (coef_res != nullptr && ds_coef != nullptr) {   // the coefficient step: rows, targets and operator rows in one launch
+    hipLaunchKernelGGL(k_sample_dataset_coef, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, tg_res, n_res, off_res,
+                       X_val, tg_val, n_ic, off_ic, n_bc, off_bc, a, b, c, seed, step, coef_res, ds_coef);
+    return QC_OK;
+  }
   hipLaunchKernelGGL(k_sample_dataset, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, tg_res, n_res, off_res, X_val,
                      tg_val, n_ic, off_ic, n_bc, off_bc, a, b, c, seed, step);
   return QC_OK;

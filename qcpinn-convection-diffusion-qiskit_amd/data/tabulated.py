@@ -8,6 +8,16 @@ targets in-kernel.  A ``TabulatedProblem`` is the general case for that step: th
 once, up front, the three segments live on the device, and every training step gathers its minibatch from them on the
 device (``qc_sample_dataset``: sampling with replacement, like a ``torch.randint`` minibatch) and reads the targets from
 memory (``qc_fused_pinn_data_step``).  ``from_functions`` is the counterpart of ``Sampler(..., func)``.
+
+``coef_res`` makes the operator data too, one row per residual point (``qc_fused_pinn_coef_step``):
+
+    residual_p = c_u[p] u + c_3[p] u^3 + c_t[p] u_t + c_x[p] u_x + c_y[p] u_y - (d_xx[p] u_xx + d_yy[p] u_yy),
+
+rows ``(c_u, c_t, c_x, c_y, d_xx, d_yy, c_3)`` (``COEF_COLUMNS``; ``coef_table`` builds them from scalars, arrays or
+callables of X).  A velocity or diffusivity field is a column that varies; a Neumann point is the row
+``(0, 0, 1, 0, 0, 0, 0)`` with the prescribed flux as its target; the reference's ``klein_gordon_operator``
+(nn/pde.py:28-41) with (t, x) on the x / y slots is ``d_xx=-1, d_yy=-alpha, c_u=beta, c_3=gamma``.  There is no weight
+column: a per-point loss weight ``w`` is the row and its target both scaled by ``sqrt(w)``.
 """
 from __future__ import annotations
 
@@ -16,6 +26,41 @@ import torch
 from .diffusion_dataset import box
 
 MAX_ROWS = 2 ** 31 - 1      # the device gather forms (32-bit word * rows) >> 32
+COEF_COLUMNS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")     # column order of a coefficient row
+_SCALARS = {"c_t": 1.0, "c_x": 1.0, "c_y": 1.0, "d_xx": 0.01, "d_yy": 0.01, "c_u": 0.0}
+
+
+def coef_table(X, **columns):
+    """The (N, 7) float32 coefficient table of the points ``X`` (N, 3): each keyword of ``COEF_COLUMNS`` is a scalar, an
+    (N,) / (N, 1) array or a callable of X returning one; columns not given are 0."""
+    X = torch.as_tensor(X)
+    unknown = set(columns) - set(COEF_COLUMNS)
+    if unknown:
+        raise ValueError(f"unknown coefficient column(s) {sorted(unknown)}: the columns are {COEF_COLUMNS}")
+    N = int(X.shape[0])
+    out = torch.zeros(N, len(COEF_COLUMNS), dtype=torch.float32)
+    for k, name in enumerate(COEF_COLUMNS):
+        v = columns.get(name, 0.0)
+        if callable(v):
+            v = v(X)
+        v = torch.as_tensor(v, dtype=torch.float32).cpu()
+        if v.dim() > 0:
+            v = v.reshape(-1)
+            if v.shape[0] != N:
+                raise ValueError(f"coefficient column {name}: {N} points but {v.shape[0]} values")
+        out[:, k] = v
+    return out
+
+
+def _coef_rows(coef, n_res):
+    coef = torch.as_tensor(coef)
+    if coef.dtype != torch.float32:
+        raise ValueError(f"coefficient table: must be a float32 tensor, got {coef.dtype}")
+    if coef.dim() != 2 or coef.shape[1] != len(COEF_COLUMNS):
+        raise ValueError(f"coefficient table: must have shape (N, 7) = {COEF_COLUMNS} rows, got {tuple(coef.shape)}")
+    if coef.shape[0] != n_res:
+        raise ValueError(f"coefficient table: {n_res} residual points but {coef.shape[0]} rows")
+    return coef.contiguous()
 
 
 def _segment(name, X, y):
@@ -39,18 +84,33 @@ def _segment(name, X, y):
 class TabulatedProblem:
     """Residual points with forcing values ``r``, initial points with ``u_ic``, boundary points with ``u_bc``."""
 
-    def __init__(self, X_res, r, X_ic, u_ic, X_bc, u_bc, *, c_t=1.0, c_x=1.0, c_y=1.0, d_xx=0.01, d_yy=0.01, c_u=0.0):
+    def __init__(self, X_res, r, X_ic, u_ic, X_bc, u_bc, *, c_t=None, c_x=None, c_y=None, d_xx=None, d_yy=None, c_u=None,
+                 coef_res=None):
+        """Scalar coefficients (defaults c_t = c_x = c_y = 1, d_xx = d_yy = 0.01, c_u = 0): one operator for every residual
+        point.  ``coef_res`` (N_res, 7) float32 instead: one row per residual point; giving it together with any scalar
+        coefficient is an error."""
         self.X_res, self.r = _segment("residual segment", X_res, r)
         self.X_ic, self.u_ic = _segment("initial segment", X_ic, u_ic)
         self.X_bc, self.u_bc = _segment("boundary segment", X_bc, u_bc)
-        self.coeffs = tuple(float(c) for c in (c_t, c_x, c_y, d_xx, d_yy))
-        self.c_u = float(c_u)
+        given = {k: v for k, v in dict(c_t=c_t, c_x=c_x, c_y=c_y, d_xx=d_xx, d_yy=d_yy, c_u=c_u).items() if v is not None}
+        self.coef_res = None
+        if coef_res is not None:
+            if given:
+                raise ValueError(f"coef_res holds the whole operator per point: do not also give {sorted(given)}")
+            self.coef_res = _coef_rows(coef_res, self.X_res.shape[0])
+            if self.coef_res.device != self.X_res.device:
+                raise ValueError("coefficient table: must be on the device of the residual points")
+        sc = {**_SCALARS, **given}
+        self.coeffs = tuple(float(sc[k]) for k in ("c_t", "c_x", "c_y", "d_xx", "d_yy"))
+        self.c_u = float(sc["c_u"])
 
     @classmethod
-    def from_functions(cls, u_ic, u_bc, r, n_res, n_ic, n_bc, generator=None, **coeffs):
+    def from_functions(cls, u_ic, u_bc, r, n_res, n_ic, n_bc, generator=None, coef=None, **coeffs):
         """Evaluate the callables ``u_ic(X)``, ``u_bc(X)``, ``r(X)`` (X: (N, 3) rows (t, x, y) -> (N,) or (N, 1)) on
         uniform points of the trainer's three boxes (trainer/diffusion_train.py:9-20: t = 0 face, x = 0 face, unit cube),
-        drawn IC -> BC -> residual from ``generator`` (default: torch's CPU generator)."""
+        drawn IC -> BC -> residual from ``generator`` (default: torch's CPU generator).  ``coef``: a callable
+        X -> (N, 7) coefficient rows (e.g. ``lambda X: coef_table(X, c_t=1.0, c_x=vx, c_y=vy, ...)``), evaluated on
+        the residual points."""
         segs = []
         for name, n, f in (("ics", n_ic, u_ic), ("bc1", n_bc, u_bc), ("dom", n_res, r)):
             b = box(name, "cpu")
@@ -58,6 +118,8 @@ class TabulatedProblem:
             y = torch.as_tensor(f(X), dtype=torch.float32) if n else torch.zeros(0)
             segs.append((X, y))
         (Xi, ui), (Xb, ub), (Xr, rr) = segs
+        if coef is not None:
+            coeffs["coef_res"] = torch.as_tensor(coef(Xr), dtype=torch.float32)
         return cls(Xr, rr, Xi, ui, Xb, ub, **coeffs)
 
     # ---- the three segments in the order the samplers use: residual, IC, BC
@@ -73,5 +135,7 @@ class TabulatedProblem:
         if all(X.device == device and y.device == device for X, y in self.segments()):
             return self
         c = dict(zip(("c_t", "c_x", "c_y", "d_xx", "d_yy"), self.coeffs), c_u=self.c_u)
+        if self.coef_res is not None:
+            c = dict(coef_res=self.coef_res.to(device))
         (Xr, rr), (Xi, ui), (Xb, ub) = [(X.to(device), y.to(device)) for X, y in self.segments()]
         return TabulatedProblem(Xr, rr, Xi, ui, Xb, ub, **c)

@@ -216,6 +216,7 @@ class SolverEngine:
         self.coeffs = None      # explicit (c_t, c_x, c_y, d_xx, d_yy) of another linear operator on the same channels
         self.problem = L.QC_PROBLEM_CONVECTION_DIFFUSION      # analytic targets of the fused loss (qcpinn_hip.h)
         self.c_u = 0.0          # zeroth-order coefficient of the residual: the tabulated step only (QC_PROBLEM_TABULATED)
+        self.coef_mode = False  # tabulated step with one operator row per residual point (qc_fused_pinn_coef_step)
         self.loss_weights = (2.0, 4.0, 2.0)                    # (residual, BC, IC) weights of the fused loss
         self.angle_map = circuit.angle_map                     # output map of the pre network, on every path
         self._fused: Dict[Tuple[int, int, int], "FusedStep"] = {}
@@ -351,7 +352,7 @@ class SolverEngine:
     # ------------------------------------------------------------------ fused training step
     def fused(self, B_res: int, n_ic: int, n_bc: int, opt: "OptimState", counts=None) -> "FusedStep":
         key = (B_res, n_ic, n_bc, id(opt), counts, self.problem, self.D, self.vx, self.vy, self.sigma, self.coeffs,
-               self.loss_weights, self.c_u)
+               self.loss_weights, self.c_u, self.coef_mode)
         if key not in self._fused:
             self._fused[key] = FusedStep(self, B_res, n_ic, n_bc, opt, counts)
         return self._fused[key]
@@ -416,7 +417,9 @@ class FusedStep:
 
     When the engine's problem is ``QC_PROBLEM_TABULATED`` the step is ``qc_fused_pinn_data_step``: the caller also fills
     ``target_res`` / ``target_val`` (same order as the points), or hands over a resident dataset with ``set_dataset`` and
-    lets ``QC_PHASE_SAMPLE`` gather points and targets from it."""
+    lets ``QC_PHASE_SAMPLE`` gather points and targets from it.  In the engine's coefficient mode (``coef_mode``, tabulated
+    only) the step is ``qc_fused_pinn_coef_step``: ``coef_res`` [7][B_res] holds the operator rows of the residual batch
+    (c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 per point), filled by the caller or gathered from the dataset's table."""
 
     def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, counts=None):
         self.eng, self.opt = eng, opt
@@ -434,6 +437,13 @@ class FusedStep:
         self.data.target_res_dev, self.data.target_val_dev = self.target_res.data_ptr(), self.target_val.data_ptr()
         self.data.c_u = eng.c_u
         self._dataset = None
+        self.coef_mode = bool(eng.coef_mode)
+        if self.coef_mode and not self.tabulated:
+            raise L.QcError("per-point operator rows need the tabulated step (problem = QC_PROBLEM_TABULATED)")
+        if self.coef_mode:
+            self.coef_res = torch.zeros(L.QC_COEF_COLS, max(B_res, 1), **f)
+            self.coef = L.QcStepCoef()
+            self.coef.coef_res_dev, self.coef.ds_coef = (self.coef_res.data_ptr() if B_res else None), None
         self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
         self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
         rows = (B_res + 63) // 64 + (B_val + 63) // 64
@@ -477,10 +487,14 @@ class FusedStep:
         d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
         d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
 
-    def set_dataset(self, segments) -> None:
+    def set_dataset(self, segments, coef=None) -> None:
         """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on
-        the engine's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it."""
+        the engine's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it.
+        ``coef``: the (N_res, 7) float32 operator table beside the residual segment (coefficient mode only, where a
+        non-empty residual segment needs it)."""
         t = self.data
+        if coef is not None and not self.coef_mode:
+            raise L.QcError("a coefficient table needs a step in coefficient mode")
         if segments is None:
             segments = ((None, None),) * 3
         keep = []
@@ -494,6 +508,16 @@ class FusedStep:
             setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
             setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], y.data_ptr() if n else None)
             setattr(t, "ds_n_" + name, n)
+        if self.coef_mode:
+            n_res = int(t.ds_n_res)
+            if coef is not None and n_res:
+                coef = _need(coef, self.eng.device, "dataset coefficient table")
+                if coef.dim() != 2 or tuple(coef.shape) != (n_res, L.QC_COEF_COLS):
+                    raise L.QcError(f"dataset coefficient table must be ({n_res}, {L.QC_COEF_COLS}), got {tuple(coef.shape)}")
+                keep.append(coef)
+                self.coef.ds_coef = coef.data_ptr()
+            else:
+                self.coef.ds_coef = None
         self._dataset = keep        # the descriptor holds raw pointers: keep the tensors alive
 
     def set_comm(self, comm) -> None:
@@ -504,6 +528,10 @@ class FusedStep:
     def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
         if phases & L.QC_PHASE_SAMPLE:
             self.desc.sample_step += 1          # a fresh counter block per step
+        if self.coef_mode:
+            L.check(self.eng.lib.qc_fused_pinn_coef_step(C.byref(self.desc), C.byref(self.data), C.byref(self.coef), phases,
+                                                         _stream(self.eng.device)), "qc_fused_pinn_coef_step")
+            return
         if self.tabulated:
             L.check(self.eng.lib.qc_fused_pinn_data_step(C.byref(self.desc), C.byref(self.data), phases,
                                                          _stream(self.eng.device)), "qc_fused_pinn_data_step")

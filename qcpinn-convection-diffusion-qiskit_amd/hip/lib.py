@@ -29,11 +29,13 @@ EXPORTS = (
     "qc_fused_step_stage", "qc_post_multi", "qc_comm_unique_id", "qc_comm_create", "qc_comm_destroy", "qc_allreduce_grads",
     "qc_pre_forward_map", "qc_pre_backward_map", "qc_program_set_angle_map",
     "qc_post_data", "qc_sample_dataset", "qc_fused_pinn_data_step",
+    "qc_post_coef", "qc_sample_dataset_coef", "qc_fused_pinn_coef_step",
 )
 
 
 QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_PULSE = 0, 1, 2      # qc_pde.problem
 QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc_fused_pinn_data_step only
+QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 (qc_step_coef)
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
 QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
 
@@ -88,6 +90,11 @@ class QcStepData(C.Structure):
         ("ds_X_ic", C.c_void_p), ("ds_u_ic", C.c_void_p), ("ds_n_ic", C.c_int64),
         ("ds_X_bc", C.c_void_p), ("ds_u_bc", C.c_void_p), ("ds_n_bc", C.c_int64),
     ]
+
+
+class QcStepCoef(C.Structure):
+    """qc_step_coef: the [7][B_res] operator rows of the current residual batch and the dataset's [N_res][7] table."""
+    _fields_ = [("coef_res_dev", C.c_void_p), ("ds_coef", C.c_void_p)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -148,6 +155,10 @@ def load() -> C.CDLL:
     lib.qc_sample_dataset.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, C.POINTER(QcStepData), C.c_uint64,
                                       C.c_uint64, vp]
     lib.qc_fused_pinn_data_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), i32, vp]
+    lib.qc_post_coef.argtypes = [fp, i32, i32, i32, C.POINTER(QcPde), fp, fp, fp, fp, fp, fp, i64, i64, i64, vp]
+    lib.qc_sample_dataset_coef.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, fp, C.POINTER(QcStepData),
+                                           C.POINTER(QcStepCoef), C.c_uint64, C.c_uint64, vp]
+    lib.qc_fused_pinn_coef_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

@@ -21,7 +21,9 @@ Any other model (the reference's duck type) runs the generic torch-autograd loop
 ``dataset=`` (keyword-only, a ``data.tabulated.TabulatedProblem``) trains towards the user's own targets instead of the
 analytic ones: a ``DVPDESolver`` through ``qc_fused_pinn_data_step`` (minibatches gathered from the device-resident
 dataset, targets read from memory, residual with the zeroth-order term ``c_u u``), any other model through the generic
-loop on ``torch.randint`` minibatches of the same dataset and the same residual.
+loop on ``torch.randint`` minibatches of the same dataset and the same residual.  A dataset with a coefficient table
+(``dataset.coef_res``: one operator row per residual point, with a cubic term) takes ``qc_fused_pinn_coef_step`` in the
+same way; nothing else changes for the caller.
 """
 from __future__ import annotations
 
@@ -91,7 +93,9 @@ class FusedTrainer:
         coefficients; ``sample()`` then arms the device gather from the dataset (``sampler="torch"``: ``torch.randint``
         indices and a copy), every rank holding the whole dataset and gathering its shard by GLOBAL point index.
         ``pde={"problem": 3, ...}`` (optional "coeffs" = (c_t, c_x, c_y, d_xx, d_yy) and "c_u") is the tabulated step
-        without a dataset: batches and targets come through ``load_batches(..., targets=)`` only."""
+        without a dataset: batches and targets come through ``load_batches(..., targets=)`` only.  A dataset with
+        ``coef_res`` (or ``pde={"problem": 3, "coef": True, ...}`` without one) selects the coefficient step: one operator
+        row per residual point, gathered with the batch or given through ``load_batches(..., targets=, coef=)``."""
         # the fused step is the 3-D convection-diffusion step of trainer/diffusion_train.py:30-49 on a (t, x, y) -> u model;
         # the reference fails on any other shape (Linear(3, H) weight mismatch), and so does this trainer: a two-input
         # model keeps a zero-padded t column in W1 that the step would train, a K-output model has K last-layer rows
@@ -109,17 +113,21 @@ class FusedTrainer:
         self.eng.loss_weights = tuple(float(w) for w in loss_weights)
         # a tabulated step leaves the engine as it found it: the descriptor built below keeps what it needs
         before = (self.eng.problem, self.eng.c_u)
+        self.eng.coef_mode = False
         if pde:
             self.eng.D, self.eng.vx, self.eng.vy = float(pde["D"]), float(pde["vx"]), float(pde["vy"])
             self.eng.problem = int(pde["problem"])
             if self.eng.problem == _lib.QC_PROBLEM_TABULATED:
                 self.eng.coeffs = tuple(float(c) for c in pde["coeffs"]) if "coeffs" in pde else None
                 self.eng.c_u = float(pde.get("c_u", 0.0))
+                self.eng.coef_mode = bool(pde.get("coef", False))
         self.dataset = None
         if dataset is not None:
             self.dataset = dataset.to(dev)
             self.eng.problem = _lib.QC_PROBLEM_TABULATED
             self.eng.coeffs, self.eng.c_u = self.dataset.coeffs, self.dataset.c_u
+            self.eng.coef_mode = self.dataset.coef_res is not None
+        self.coef_mode = self.eng.coef_mode
         self.tabulated = self.eng.problem == _lib.QC_PROBLEM_TABULATED
         self.optimizer = model.optimizer if optimizer is None else optimizer
         self.scheduler = model.scheduler if scheduler is None else scheduler
@@ -140,11 +148,12 @@ class FusedTrainer:
         self.fs = self.eng.fused(self.B_res, self.n_ic, self.n_bc, self.opt, self.global_counts)
         if self.tabulated:
             (self.eng.problem, self.eng.c_u), self.eng.coeffs = before, None
+        self.eng.coef_mode = False
         if self.dataset is not None:
             for what, n_batch, n_rows in zip(("residual", "initial", "boundary"), self.global_counts, self.dataset.sizes()):
                 if n_batch > 0 and n_rows == 0:
                     raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
-            self.fs.set_dataset(self.dataset.segments())
+            self.fs.set_dataset(self.dataset.segments(), self.dataset.coef_res)
         self.lo = {k: box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.span = {k: box(k, dev)[1:2] - box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.eng.refresh_gates()
@@ -261,6 +270,8 @@ class FusedTrainer:
                     idx = torch.randint(0, X.shape[0], (n,), device=dev)
                     dX[o:o + n] = X[idx]
                     dy[o:o + n] = y[idx]
+                    if self.coef_mode and X is Xr:
+                        fs.coef_res[:, :n] = self.dataset.coef_res[idx].t()
             return
         if self.n_ic:
             fs.X_val[: self.n_ic] = self.lo["ics"] + self.span["ics"] * torch.rand(self.n_ic, 3, device=dev)
@@ -281,9 +292,14 @@ class FusedTrainer:
         if self.B_res:
             fs.X_res[: self.B_res] = self.lo["dom"] + self.span["dom"] * torch.rand(self.B_res, 3, device=dev)
 
-    def load_batches(self, X_ic, X_bc, X_res, targets=None):
+    def load_batches(self, X_ic, X_bc, X_res, targets=None, coef=None):
         """Use given GLOBAL batches (parity tests): this rank takes its contiguous shard.  ``targets`` =
-        (u_ic, u_bc, r_res), one value per point: required by, and only accepted for, a tabulated step."""
+        (u_ic, u_bc, r_res), one value per point: required by, and only accepted for, a tabulated step.  ``coef``: the
+        (B_res, 7) operator rows of ``X_res``: required by, and only accepted for, a coefficient step."""
+        if coef is not None and not self.coef_mode:
+            raise ValueError("coef needs a coefficient step: a dataset with coef_res, or pde={'problem': 3, 'coef': True, ...}")
+        if coef is None and self.coef_mode:
+            raise ValueError("a coefficient step needs coef=(B_res, 7) operator rows with its batches")
         if targets is not None and not self.tabulated:
             raise ValueError("targets need a tabulated step: construct the trainer with dataset= or pde={'problem': 3, ...}")
         if targets is None and self.tabulated:
@@ -309,6 +325,12 @@ class FusedTrainer:
                 fs.target_val[self.n_ic: self.n_ic + self.n_bc] = u_bc[s_bc].to(dev)
             if self.B_res:
                 fs.target_res[: self.B_res] = r_res[s_rs].to(dev)
+        if coef is not None:
+            coef = torch.as_tensor(coef, dtype=torch.float32)
+            if tuple(coef.shape) != (X_res.shape[0], _lib.QC_COEF_COLS):
+                raise ValueError(f"coef must be ({X_res.shape[0]}, {_lib.QC_COEF_COLS}): one operator row per point of X_res")
+            if self.B_res:
+                fs.coef_res[:, : self.B_res] = coef[s_rs].to(dev).t()
 
     def step(self):
         draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
@@ -337,7 +359,8 @@ def _train_fused(model, batch_size, batches=None, dataset=None):
         if batches is None:
             tr.sample()
         else:
-            tr.load_batches(*batches[it][:3], targets=batches[it][3] if len(batches[it]) > 3 else None)
+            tr.load_batches(*batches[it][:3], targets=batches[it][3] if len(batches[it]) > 3 else None,
+                            coef=batches[it][4] if len(batches[it]) > 4 else None)
         tr.step()
         if it % pe == 0 or it == 0:
             # the reference logs the loss of iteration `it` BEFORE its optimiser step; the fused step has
@@ -363,22 +386,34 @@ def _train_fused(model, batch_size, batches=None, dataset=None):
 class _RowSampler:
     """``Sampler`` over one segment of a TabulatedProblem: a ``torch.randint`` minibatch of its rows and targets."""
 
-    def __init__(self, X, y):
-        self.X, self.y = X, y.reshape(-1, 1)
+    def __init__(self, X, y, coef=None):
+        self.X, self.y, self.coef = X, y.reshape(-1, 1), coef
+        self.rows = None        # the coefficient rows of the last minibatch (residual segment of a coefficient dataset)
 
     def sample(self, N):
         idx = torch.randint(0, self.X.shape[0], (N,))
+        if self.coef is not None:
+            self.rows = self.coef[idx]
         return self.X[idx], self.y[idx]
 
 
-def tabulated_operator(model, t, x, y, coeffs, c_u):
-    """(u, c_u u + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy)) of a torch model by autograd."""
-    c_t, c_x, c_y, d_xx, d_yy = coeffs
+def tabulated_operator(model, t, x, y, coeffs, c_u, coef=None):
+    """(u, c_u u + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy)) of a torch model by autograd.  With ``coef``
+    ((N, 7) rows c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 of the N points): the per-point operator with the cubic term
+    c_3 u^3 instead; ``coeffs`` and ``c_u`` are then not read."""
+    c_3 = 0.0
+    if coef is not None:
+        c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 = (coef[:, k:k + 1] for k in range(7))
+    else:
+        c_t, c_x, c_y, d_xx, d_yy = coeffs
     for v in (t, x, y):
         v.requires_grad_(True)
     uu = model(torch.cat((t, x, y), 1))
     u_x, u_y = _grad(uu, x), _grad(uu, y)
-    return uu, c_u * uu + c_t * _grad(uu, t) + c_x * u_x + c_y * u_y - (d_xx * _grad(u_x, x) + d_yy * _grad(u_y, y))
+    res = c_u * uu + c_t * _grad(uu, t) + c_x * u_x + c_y * u_y - (d_xx * _grad(u_x, x) + d_yy * _grad(u_y, y))
+    if coef is not None:
+        res = res + c_3 * uu ** 3
+    return uu, res
 
 
 def _train_generic(model, batch_size, dataset=None):
@@ -392,7 +427,7 @@ def _train_generic(model, batch_size, dataset=None):
             if n_batch > 0 and n_rows == 0:
                 raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
         ics, bc1, res = _RowSampler(dataset.X_ic, dataset.u_ic), _RowSampler(dataset.X_bc, dataset.u_bc), \
-            _RowSampler(dataset.X_res, dataset.r)
+            _RowSampler(dataset.X_res, dataset.r, dataset.coef_res)
     else:
         ics = Sampler(3, box("ics", dev), u, name="Initial Condition", device=dev)
         bc1 = Sampler(3, box("bc1", dev), u, name="Dirichlet BC1", device=dev)
@@ -411,7 +446,8 @@ def _train_generic(model, batch_size, dataset=None):
         pred_bc = model.forward(X_bc)
         pred_ic = model.forward(X_ic)
         if dataset is not None:
-            _, pred_r = tabulated_operator(model, X_rs[:, 0:1], X_rs[:, 1:2], X_rs[:, 2:3], dataset.coeffs, dataset.c_u)
+            _, pred_r = tabulated_operator(model, X_rs[:, 0:1], X_rs[:, 1:2], X_rs[:, 2:3], dataset.coeffs, dataset.c_u,
+                                           res.rows)
         else:
             _, pred_r = diffusion_operator(model, X_rs[:, 0:1], X_rs[:, 1:2], X_rs[:, 2:3])
         l_r, l_bc, l_ic = model.loss_fn(pred_r, r_rs), model.loss_fn(pred_bc, u_bc), model.loss_fn(pred_ic, u_ic)
