@@ -233,13 +233,13 @@ static bool problem_ok(int pb) { return pb >= QC_PROBLEM_CONVECTION_DIFFUSION &&
 static bool step_desc_ok(const qc_step_desc* d) {
   return problem_ok(d->pde.problem) && d->sample_bc_face_points >= QC_BC_RANDOM_FACE;
 }
-// what the tabulated step needs of its descriptor pair: problem id 3, a target buffer behind every non-empty batch, and
-// under QC_PHASE_SAMPLE a dataset segment (1 <= rows < 2^31) behind every non-empty batch
+// what the tabulated step needs of its descriptor pair (the problem id is QcTarget::ok's): a target buffer behind every
+// non-empty batch, and under QC_PHASE_SAMPLE a dataset segment (1 <= rows < 2^31) behind every non-empty batch
 static bool dataset_seg_ok(int64_t n_batch, const float* X, const float* tg, int64_t n) {
   return n_batch <= 0 || (X && tg && n >= 1 && n < ((int64_t)1 << 31));
 }
 static bool step_data_ok(const qc_step_desc* d, const qc_step_data* t, int phases) {
-  if (!t || d->pde.problem != QC_PROBLEM_TABULATED || d->n_ic < 0 || d->n_ic > d->B_val) return false;
+  if (!t || d->n_ic < 0 || d->n_ic > d->B_val) return false;
   if ((d->B_res > 0 && !t->target_res_dev) || (d->B_val > 0 && !t->target_val_dev)) return false;
   if (!(phases & QC_PHASE_SAMPLE)) return true;
   return dataset_seg_ok(d->B_res, t->ds_X_res, t->ds_r, t->ds_n_res) && dataset_seg_ok(d->n_ic, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic) &&
@@ -493,25 +493,25 @@ int qc_pre_backward(const float* X, const float* prm, int H, int n, int n_theta,
                              stream);
 }
 
-// qc_post, and with `tab` qc_post_data (mode 2 on tabulated targets: X is not read); with `coef` too, qc_post_coef
-// (out_u = the [6][B] cotangents, out_res not used)
+// qc_post, and by `tg` qc_post_data (mode 2 on tabulated targets: X is not read) or qc_post_coef (out_u = the [6][B]
+// cotangents, out_res not used)
 static int post_impl(int mode, const float* X, const float* prm, int H, int n, int n_theta, const qc_pde* pde,
                      const float* qjets, float* out_u, float* out_res, const float* in_ubar, const float* in_rbar,
                      float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream,
-                     const QcTab* tab, const float* coef = nullptr) {
+                     const QcTarget& tg) {
   int rc = check_mlp(H, n, n_theta, B, nch);
   if (rc) return rc;
   const QcLayout L = make_layout(H, n, n_theta);
-  if (mode < 0 || mode > 4 || (!X && !tab) || !prm || !pde || !qjets) return QC_ERR_ARG;
-  // the analytic targets are defined for 0..2 only; the tabulated ones for QC_PROBLEM_TABULATED only
-  if (mode == 2 && !(tab ? pde->problem == QC_PROBLEM_TABULATED : problem_ok(pde->problem))) return QC_ERR_ARG;
+  const bool analytic = tg.kind == QC_TARGET_ANALYTIC;
+  if (mode < 0 || mode > 4 || (!X && analytic) || !prm || !pde || !qjets) return QC_ERR_ARG;
+  // the analytic targets are defined for 0..2 only; the tabulated ones by the rule of their type
+  if ((mode == 2 && analytic && !problem_ok(pde->problem)) || !tg.ok(mode, nch, pde->problem)) return QC_ERR_ARG;
   if (mode >= 3 && nch != 6) return QC_ERR_ARG;          // general jets: six channels only
   if (mode >= 1 && mode <= 3 && (!qbar || !part || row0 < 0 || part_stride < L.NP + (mode == 2 ? 3 : 0))) return QC_ERR_ARG;
-  if (coef && (!tab || mode != 2 || nch != 6)) return QC_ERR_ARG;
-  if (mode == 2 && (!out_u || (nch == 6 && !out_res && !coef))) return QC_ERR_ARG;  // per-point cotangent scratch
+  if (mode == 2 && (!out_u || (nch == 6 && !out_res && tg.kind != QC_TARGET_COEF))) return QC_ERR_ARG;  // per-point cotangent scratch
   if ((mode == 3 && !in_ubar) || (mode == 4 && !out_u)) return QC_ERR_ARG;
   rc = qc_mlp_post(mode, X, prm, L, to_pde(pde), qjets, out_u, out_res, in_ubar, in_rbar, qbar, part, part_stride,
-                   row0, B, nch, (hipStream_t)stream, tab, coef);
+                   row0, B, nch, (hipStream_t)stream, tg);
   return rc ? rc : after_launch();
 }
 
@@ -519,25 +519,23 @@ int qc_post(int mode, const float* X, const float* prm, int H, int n, int n_thet
             const float* qjets, float* out_u, float* out_res, const float* in_ubar, const float* in_rbar,
             float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream) {
   return post_impl(mode, X, prm, H, n, n_theta, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar, part, part_stride, row0,
-                   B, nch, stream, nullptr);
+                   B, nch, stream, QcTarget{});
 }
 
 int qc_post_data(const float* prm, int H, int n, int n_theta, const qc_pde* pde, const float* qjets, const float* target,
                  float c_u, float* out_u, float* out_res, float* qbar, float* part, int64_t part_stride, int64_t row0,
                  int64_t B, int nch, void* stream) {
   if (!target) return QC_ERR_ARG;
-  const QcTab tab = {target, target, c_u};
   return post_impl(2, nullptr, prm, H, n, n_theta, pde, qjets, out_u, out_res, nullptr, nullptr, qbar, part, part_stride,
-                   row0, B, nch, stream, &tab);
+                   row0, B, nch, stream, QcTarget::tabulated(target, target, c_u));
 }
 
 int qc_post_coef(const float* prm, int H, int n, int n_theta, const qc_pde* pde, const float* qjets, const float* target,
                  const float* coef, float* cot, float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B,
                  void* stream) {
   if (!target || !coef || !cot) return QC_ERR_ARG;
-  const QcTab tab = {target, target, 0.f};
   return post_impl(2, nullptr, prm, H, n, n_theta, pde, qjets, cot, nullptr, nullptr, nullptr, qbar, part, part_stride, row0, B,
-                   6, stream, &tab, coef);
+                   6, stream, QcTarget::with_coef(target, target, coef));
 }
 
 int qc_post_multi(int mode, const float* prm, int H, int n, int n_theta, int K, const float* w4k, const float* qjets,
@@ -587,32 +585,36 @@ int qc_sample_collocation(float* X_res, int64_t n_res, int64_t off_res, float* X
   return qc_sample_collocation_faces(X_res, n_res, off_res, X_val, n_ic, off_ic, n_bc, off_bc, 0, seed, step, stream);
 }
 
-int qc_sample_dataset(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
-                      int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const qc_step_data* t, uint64_t seed,
-                      uint64_t step, void* stream) {
-  if (!t || n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0) return QC_ERR_ARG;
+// the gather behind both exports: rows and targets of the three batches, and with a table (ds_coef -> coef_res) the
+// residual rows' operator coefficients; the plain form is the coefficient form with no table
+static int sample_dataset_impl(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
+                               int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const float* ds_coef,
+                               const qc_step_data* t, uint64_t seed, uint64_t step, void* stream) {
+  if (n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0) return QC_ERR_ARG;
   if ((n_res > 0 && (!X_res || !target_res)) || (n_ic + n_bc > 0 && (!X_val || !target_val))) return QC_ERR_ARG;
   if (!dataset_seg_ok(n_res, t->ds_X_res, t->ds_r, t->ds_n_res) || !dataset_seg_ok(n_ic, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic) ||
       !dataset_seg_ok(n_bc, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc)) return QC_ERR_ARG;
   qc_sample_dataset_launch(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, t->ds_X_res,
                            t->ds_r, t->ds_n_res, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc, seed,
-                           step, (hipStream_t)stream);
+                           step, (hipStream_t)stream, coef_res, ds_coef);
   return after_launch();
+}
+
+int qc_sample_dataset(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
+                      int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const qc_step_data* t, uint64_t seed,
+                      uint64_t step, void* stream) {
+  if (!t) return QC_ERR_ARG;
+  return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, nullptr, nullptr,
+                             t, seed, step, stream);
 }
 
 int qc_sample_dataset_coef(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
                            int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const qc_step_data* t,
                            const qc_step_coef* cf, uint64_t seed, uint64_t step, void* stream) {
-  if (!t || !cf || n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0) return QC_ERR_ARG;
-  if ((n_res > 0 && (!X_res || !target_res || !coef_res || !cf->ds_coef)) || (n_ic + n_bc > 0 && (!X_val || !target_val)))
-    return QC_ERR_ARG;
-  if (!dataset_seg_ok(n_res, t->ds_X_res, t->ds_r, t->ds_n_res) || !dataset_seg_ok(n_ic, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic) ||
-      !dataset_seg_ok(n_bc, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc)) return QC_ERR_ARG;
+  if (!t || !cf || (n_res > 0 && (!coef_res || !cf->ds_coef))) return QC_ERR_ARG;
   // (n_res = 0 with null coefficient pointers: the plain gather, no residual rows to copy)
-  qc_sample_dataset_launch(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, t->ds_X_res,
-                           t->ds_r, t->ds_n_res, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc, seed,
-                           step, (hipStream_t)stream, n_res > 0 ? coef_res : nullptr, n_res > 0 ? cf->ds_coef : nullptr);
-  return after_launch();
+  return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
+                             n_res > 0 ? coef_res : nullptr, n_res > 0 ? cf->ds_coef : nullptr, t, seed, step, stream);
 }
 
 // ---- merged residual + value stages of the fused step (register family, angle encoding)
@@ -624,8 +626,7 @@ static bool merged_ok(const qc_step_desc* d) {
          d->qbar_val_dev && d->abar_val_dev;
 }
 
-static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool draw = false, const QcTab* tab = nullptr,
-                        const float* coef = nullptr) {
+static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool draw, const QcTarget& tg) {
   const QcLayout L = make_layout(d->H, d->n, d->n_theta);
   const int64_t rows_res = qc_ceil_div(d->B_res, 64);
   const QcTrig* trig = (const QcTrig*)d->trig_dev;
@@ -644,11 +645,11 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
                                   d->ajets_val_dev, d->qjets_val_dev, d->B_val, st);
     case QC_STAGE_POST:
       // abar_* are written only by the adjoint sweep: their heads serve as per-point cotangent scratch here (two
-      // B_res-float rows; with `coef` the [6][B_res] channel cotangents, of abar_res' 6 n B_res floats)
+      // B_res-float rows; with a coefficient table the [6][B_res] channel cotangents, of abar_res' 6 n B_res floats)
       return qc_mlp_post_both(prm, L, pde, (const float*)d->X_res_dev, d->qjets_res_dev, d->abar_res_dev,
                               d->abar_res_dev + d->B_res, d->qbar_res_dev, 0, d->B_res, (const float*)d->X_val_dev,
                               d->qjets_val_dev, d->abar_val_dev, d->qbar_val_dev, rows_res, d->B_val, d->part_dev,
-                              d->part_stride, st, tab, coef);
+                              d->part_stride, st, tg);
     case QC_STAGE_CIRCUIT_BWD:
       return qc_reg_circ_bwd_both(d->prog, trig, d->umat_dev, d->ajets_res_dev, d->qbar_res_dev, d->abar_res_dev, 0, d->B_res,
                                   chi_store, d->ajets_val_dev, d->qbar_val_dev, d->abar_val_dev, rows_res, d->B_val,
@@ -668,7 +669,7 @@ int qc_fused_step_stage(const qc_step_desc* d, int stage, void* stream) {
   if (!merged_ok(d)) return QC_ERR_UNSUPPORTED;
   int rc = check_mlp(d->H, d->n, d->n_theta, d->B_res, 6);
   if (rc) return rc;
-  if ((rc = merged_stage(d, stage, (hipStream_t)stream))) return rc;
+  if ((rc = merged_stage(d, stage, (hipStream_t)stream, false, QcTarget{}))) return rc;
   return after_launch();
 }
 
@@ -683,7 +684,7 @@ struct QcPipe {
 };
 
 // pre -> [amplitudes] -> circuit -> post -> circuit adjoint -> [amplitude adjoint] -> pre adjoint, on one stream
-static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, const QcTab* tab, const float* coef) {
+static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, const QcTarget& tg) {
   const qc_program* p = d->prog;
   const int n = d->n, H = d->H;
   const QcTrig* trig = (const QcTrig*)d->trig_dev;
@@ -697,8 +698,7 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
   if ((rc = p->fam->fwd(p, trig, d->umat_dev, cin, q.qjets, q.B, q.nch, q.store, st)) || (rc = after_launch())) return rc;
   // abar is written only by the adjoint sweep below: its head serves as per-point cotangent scratch here
   if ((rc = post_impl(2, q.X, d->params_dev, H, n, d->n_theta, &d->pde, q.qjets, q.abar, q.nch == 6 ? q.abar + q.B : nullptr,
-                      nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tab,
-                      q.nch == 6 ? coef : nullptr))) return rc;
+                      nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tg))) return rc;
   if ((rc = p->fam->bwd(p, trig, d->umat_dev, cin, q.qbar, cout, part_theta, d->part_stride, q.row0, q.B, q.nch, q.store, st)) ||
       (rc = after_launch())) return rc;
   if (q.u && (rc = qc_amp_backward(q.ajets, q.ub, q.abar, n, q.B, q.nch, st))) return rc;
@@ -713,18 +713,19 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
 // residual points' operator rows come from cf->coef_res_dev, gathered with the rows and targets under QC_PHASE_SAMPLE.
 static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phases, void* stream,
                       const qc_step_coef* cf = nullptr) {
+  if (!d) return QC_ERR_ARG;
   const bool tabulated = data != nullptr;
-  if (cf && (!d || !data || (d->B_res > 0 && (!cf->coef_res_dev || ((phases & QC_PHASE_SAMPLE) && !cf->ds_coef)))))
-    return QC_ERR_ARG;
-  const float* coef = (cf && d->B_res > 0) ? cf->coef_res_dev : nullptr;
-  if (!d || !(tabulated ? step_data_ok(d, data, phases) && d->sample_bc_face_points >= QC_BC_RANDOM_FACE : step_desc_ok(d)))
+  const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
+  if (table && (!cf->coef_res_dev || ((phases & QC_PHASE_SAMPLE) && !cf->ds_coef))) return QC_ERR_ARG;
+  if (!(tabulated ? step_data_ok(d, data, phases) && d->sample_bc_face_points >= QC_BC_RANDOM_FACE : step_desc_ok(d)))
     return QC_ERR_ARG;
   if (!d->prog || !d->trig_dev || !d->params_dev || !d->part_dev || !d->flat_dev) return QC_ERR_ARG;
   const int n = d->n, H = d->H;
   if (d->prog->n_qubits != n || d->prog->n_params != d->n_theta) return QC_ERR_ARG;
-  QcTab tab_v = {nullptr, nullptr, 0.f};
-  if (tabulated) tab_v = {data->target_res_dev, data->target_val_dev, data->c_u};
-  const QcTab* tab = tabulated ? &tab_v : nullptr;
+  const QcTarget tg = !tabulated ? QcTarget{}
+                      : table    ? QcTarget::with_coef(data->target_res_dev, data->target_val_dev, cf->coef_res_dev)
+                                 : QcTarget::tabulated(data->target_res_dev, data->target_val_dev, data->c_u);
+  if (!tg.ok(2, 6, d->pde.problem)) return QC_ERR_ARG;
   int rc = check_mlp(H, n, d->n_theta, d->B_res > 0 ? d->B_res : 1, 6);
   if (rc) return rc;
   const QcLayout L = make_layout(H, n, d->n_theta);
@@ -741,16 +742,12 @@ static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phase
 
   // (in the merged form below the first stage draws the points itself)
   const bool draw_in_stage = !tabulated && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);
-  if (coef && (phases & QC_PHASE_SAMPLE)) {
-    if ((rc = qc_sample_dataset_coef((float*)d->X_res_dev, data->target_res_dev, d->B_res, d->sample_off_res,
-                                     (float*)d->X_val_dev, data->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic,
-                                     d->sample_off_bc, cf->coef_res_dev, data, cf, d->sample_seed, d->sample_step, st)))
-      return rc;
-  } else if (tabulated && (phases & QC_PHASE_SAMPLE)) {
-    if ((rc = qc_sample_dataset((float*)d->X_res_dev, data->target_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev,
-                                data->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc, data,
-                                d->sample_seed, d->sample_step, st))) return rc;
-  } else if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage) {
+  if (tabulated && (phases & QC_PHASE_SAMPLE)) {   // dataset gather, with or without the table
+    if ((rc = sample_dataset_impl((float*)d->X_res_dev, data->target_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev,
+                                  data->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
+                                  table ? cf->coef_res_dev : nullptr, table ? cf->ds_coef : nullptr, data, d->sample_seed,
+                                  d->sample_step, st))) return rc;
+  } else if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage) {   // coordinate draw
     if ((rc = qc_sample_collocation_faces((float*)d->X_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev, d->n_ic,
                                           d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
                                           d->sample_bc_face_points, d->sample_seed, d->sample_step, st))) return rc;
@@ -761,7 +758,7 @@ static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phase
   const bool merged = (phases & QC_PHASE_GRADS) && merged_ok(d);
   if (merged) {
     for (int stage = 0; stage < QC_STAGE_COUNT; ++stage)
-      if ((rc = merged_stage(d, stage, st, draw_in_stage && stage == QC_STAGE_PRE_FWD, tab, coef))) return rc;
+      if ((rc = merged_stage(d, stage, st, draw_in_stage && stage == QC_STAGE_PRE_FWD, tg))) return rc;
     if ((rc = after_launch())) return rc;
   }
   if ((phases & QC_PHASE_GRADS) && !merged) {
@@ -780,8 +777,8 @@ static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phase
                         ws.ub_val, d->B_val, rows_res, 1, ws.val};
     const QcPipe res = {d->X_res_dev, d->ajets_res_dev, d->qjets_res_dev, d->qbar_res_dev, d->abar_res_dev, ws.u_res,
                         ws.ub_res, d->B_res, 0, 6, ws.res};
-    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, tab, nullptr))) return rc;
-    if (d->B_res > 0 && (rc = run_pipeline(d, res, st, tab, coef))) return rc;
+    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, tg.value_side()))) return rc;
+    if (d->B_res > 0 && (rc = run_pipeline(d, res, st, tg))) return rc;
     if (side) {
       hipError_t e = hipEventRecord(side->join, sv);
       if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);

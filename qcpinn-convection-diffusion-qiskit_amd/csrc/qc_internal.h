@@ -40,6 +40,33 @@ struct QcTab {
 // batch-minor [QC_COEF_COLS][B] next to the residual targets.  == QC_COEF_COLS of the public header.
 constexpr int QC_COEF_N = 7;
 
+// Where a post stage takes its targets and its operator from: analytic (functions of X, the operator of QcPde),
+// tabulated (tab), or tabulated with a coefficient table [QC_COEF_N][B_res] for the residual points (tab.c_u is then not
+// read).  The post launchers and everything above them pass this one value; the kernels receive nothing, tab, or tab and
+// coef as their last arguments.
+enum QcTargetKind { QC_TARGET_ANALYTIC = 0, QC_TARGET_TAB, QC_TARGET_COEF };
+struct QcTarget {
+  QcTargetKind kind = QC_TARGET_ANALYTIC;
+  QcTab tab = {nullptr, nullptr, 0.f};
+  const float* coef = nullptr;
+
+  static QcTarget tabulated(const float* tg_res, const float* tg_val, float c_u) {
+    return {QC_TARGET_TAB, {tg_res, tg_val, c_u}, nullptr};
+  }
+  static QcTarget with_coef(const float* tg_res, const float* tg_val, const float* coef) {
+    return {QC_TARGET_COEF, {tg_res, tg_val, 0.f}, coef};
+  }
+  // the value points of a step have no operator: the same targets without the table
+  QcTarget value_side() const { return kind == QC_TARGET_COEF ? tabulated(tab.tg_res, tab.tg_val, tab.c_u) : *this; }
+  // THE validity rule: a coefficient table needs tabulated targets (it has them by construction), mode 2 and six
+  // channels; tabulated targets need mode 2 and problem id 3
+  bool ok(int mode, int nch, int problem) const {
+    if (kind == QC_TARGET_ANALYTIC) return true;
+    if (mode != 2 || problem != QC_PB_TABULATED) return false;
+    return kind != QC_TARGET_COEF || (nch == 6 && coef != nullptr);
+  }
+};
+
 struct QcPde {  // == qc_pde of the public header
   float D, vx, vy;                 // physical constants: analytic targets of mode 2
   float c_t, c_x, c_y, d_xx, d_yy; // operator coefficients (sigma scalings folded in)
@@ -116,12 +143,12 @@ int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, floa
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
                         float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
                         hipStream_t st, int map, const float* ajr, const float* ajv);
-// `tab` (both post launchers): non-null selects the tabulated kernels (pde.problem == QC_PB_TABULATED); with `coef`
-// ([7][B_res], needs `tab`) the residual points take their operator from it and ubr / out_u is a [6][B] cotangent scratch
+// `tg` (both post launchers, checked with QcTarget::ok): the tabulated kinds select the kernels that read their targets
+// from memory; with a coefficient table ubr / out_u is a [6][B] cotangent scratch and rbr / out_res is not used
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
                      int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st,
-                     const QcTab* tab = nullptr, const float* coef = nullptr);
+                     const QcTarget& tg);
 int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t,
                    int map = 0);
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
@@ -130,7 +157,7 @@ int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* ab
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t,
-                const QcTab* tab = nullptr, const float* coef = nullptr);
+                const QcTarget& tg);
 int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float* w4k, const float* qjets, float* out_u,
                       const float* ubar, float* qbar, float* part, int64_t part_stride, float* partk, int64_t partk_stride,
                       int64_t row0, int64_t B, hipStream_t);

@@ -20,6 +20,7 @@
 // NCH = 1 : boundary / initial-condition points, value channel only.
 #include "qc_internal.h"
 #include "qc_philox.h"
+#include <tuple>
 
 namespace {
 
@@ -781,36 +782,42 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
   }
 }
 
-template <int N, int NCH, int MODE>
+// Target kind of a mode-2 point kernel = its TRAILING arguments: none (analytic targets, computed from X), a QcTab
+// (qc_post_data, the data step), or a QcTab and the coefficient table (qc_post_coef, the coefficient step).  One kernel
+// template per launch shape takes them as a pack, so the analytic instantiations carry no argument for them.  QcKind
+// names the DATA / COEF flags of the bodies and picks what the bodies take out of the pack, where they take it: null /
+// zero for what the kind does not have or does not read (c_u beside a coefficient table).
+template <class... TG>
+struct QcKind {
+  static_assert(sizeof...(TG) <= 2, "(), (QcTab) or (QcTab, const float*)");
+  static constexpr bool data = sizeof...(TG) >= 1, coef = sizeof...(TG) == 2;
+  static __device__ __forceinline__ const float* tg_res(const TG&... t) {
+    if constexpr (data) return std::get<0>(std::tie(t...)).tg_res; else return nullptr;
+  }
+  static __device__ __forceinline__ const float* tg_val(const TG&... t) {
+    if constexpr (data) return std::get<0>(std::tie(t...)).tg_val; else return nullptr;
+  }
+  static __device__ __forceinline__ float c_u(const TG&... t) {
+    if constexpr (data && !coef) return std::get<0>(std::tie(t...)).c_u; else return 0.f;
+  }
+  static __device__ __forceinline__ const float* table(const TG&... t) {
+    if constexpr (coef) return std::get<1>(std::tie(t...)); else return nullptr;
+  }
+};
+
+// With target arguments (MODE 2 only) X, in_ubar and in_rbar are not read; with a coefficient table (six channels only)
+// out_u is the [6][B] cotangent scratch and out_res is not written.
+template <int N, int NCH, int MODE, class... TG>
 __global__ void __launch_bounds__(256) k_post(const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                                               QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ out_res,
                                               const float* __restrict__ in_ubar, const float* __restrict__ in_rbar,
                                               float* __restrict__ qbar, float* __restrict__ part,
-                                              int64_t part_stride, int64_t row0, int64_t B) {
-  k_post_body<N, NCH, MODE>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar, part, part_stride, row0, B);
-}
-
-// MODE 2 on tabulated targets (qc_post_data; the step's split form)
-template <int N, int NCH>
-__global__ void __launch_bounds__(256) k_post_data(const float* __restrict__ prm, QcLayout L, QcPde pde,
-                                                   const float* __restrict__ qjets, float* __restrict__ out_u,
-                                                   float* __restrict__ out_res, float* __restrict__ qbar,
-                                                   float* __restrict__ part, int64_t part_stride, int64_t row0, int64_t B,
-                                                   const float* __restrict__ tg, float c_u) {
-  k_post_body<N, NCH, 2, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, out_res, nullptr, nullptr, qbar, part,
-                               part_stride, row0, B, tg, c_u);
-}
-
-// MODE 2 with per-point operator rows (qc_post_coef; residual points of the coefficient step's split form)
-template <int N>
-__global__ void __launch_bounds__(256) k_post_coef(const float* __restrict__ prm, QcLayout L, QcPde pde,
-                                                   const float* __restrict__ qjets, float* __restrict__ cot,
-                                                   float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
-                                                   int64_t row0, int64_t B, const float* __restrict__ tg,
-                                                   const float* __restrict__ coef) {
-  k_post_body<N, 6, 2, true, true>(blockIdx.x, nullptr, prm, L, pde, qjets, cot, nullptr, nullptr, nullptr, qbar, part,
-                                   part_stride, row0, B, tg, 0.f, coef);
+                                              int64_t part_stride, int64_t row0, int64_t B, TG... tg) {
+  using K = QcKind<TG...>;
+  k_post_body<N, NCH, MODE, K::data, K::coef>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar, part,
+                                              part_stride, row0, B, NCH == 6 ? K::tg_res(tg...) : K::tg_val(tg...),
+                                              K::c_u(tg...), K::table(tg...));
 }
 
 // Weight gradients of the post network: lane = hidden unit m (owns row m of W3, b3[m], W4[m]); the
@@ -1492,40 +1499,20 @@ static inline size_t qc_post_fused_lds_val(const QcLayout& L) {
   return (size_t)QC_POST_VALUE_TPB * (L.H + QC_MS / QC_POST_VALUE_TPB) * 64 * sizeof(float);
 }
 
-template <int N, int NCH>
+template <int N, int NCH, class... TG>
 __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                                                     QcPde pde, const float* __restrict__ qjets, float* __restrict__ out_u,
                                                     float* __restrict__ out_res, float* __restrict__ qbar,
-                                                    float* __restrict__ part, int64_t part_stride, int64_t row0, int64_t B) {
+                                                    float* __restrict__ part, int64_t part_stride, int64_t row0, int64_t B,
+                                                    TG... tg) {
   extern __shared__ float s_dyn[];
-  if constexpr (NCH == 6) k_post_fused6_body<N>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, s_dyn);
-  else k_post_fused_value_body<N, QC_POST_VALUE_TPB>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part, part_stride, row0, B, s_dyn);
-}
-
-template <int N, int NCH>
-__global__ void __launch_bounds__(256) k_post_fused_data(const float* __restrict__ prm, QcLayout L, QcPde pde,
-                                                         const float* __restrict__ qjets, float* __restrict__ out_u,
-                                                         float* __restrict__ out_res, float* __restrict__ qbar,
-                                                         float* __restrict__ part, int64_t part_stride, int64_t row0,
-                                                         int64_t B, const float* __restrict__ tg, float c_u) {
-  extern __shared__ float s_dyn[];
+  using K = QcKind<TG...>;
   if constexpr (NCH == 6)
-    k_post_fused6_body<N, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, s_dyn,
-                                tg, c_u);
+    k_post_fused6_body<N, K::data, K::coef>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B,
+                                            s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...));
   else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x, nullptr, prm, L, pde, qjets, out_u, qbar, part, part_stride,
-                                                        row0, B, s_dyn, tg);
-}
-
-template <int N>
-__global__ void __launch_bounds__(256) k_post_fused_coef(const float* __restrict__ prm, QcLayout L, QcPde pde,
-                                                         const float* __restrict__ qjets, float* __restrict__ cot,
-                                                         float* __restrict__ qbar, float* __restrict__ part,
-                                                         int64_t part_stride, int64_t row0, int64_t B,
-                                                         const float* __restrict__ tg, const float* __restrict__ coef) {
-  extern __shared__ float s_dyn[];
-  k_post_fused6_body<N, true, true>(blockIdx.x, nullptr, prm, L, pde, qjets, cot, nullptr, qbar, part, part_stride, row0, B,
-                                    s_dyn, tg, 0.f, coef);
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part, part_stride,
+                                                           row0, B, s_dyn, K::tg_val(tg...));
 }
 
 // ================================================================== K outputs behind one shared network (Navier-Stokes)
@@ -1726,96 +1713,42 @@ struct QcPostSeg {   // one pipeline's arguments of the fused (mode 2) post kern
   int64_t row0, B;
 };
 
-template <int N>
+// The merged point kernels by target kind (QcKind).  With a coefficient table: residual tiles on the COEF bodies (r.ub =
+// the [6][B] cotangent scratch, r.rb unused), value tiles on the DATA code.
+template <int N, class... TG>
 __global__ void __launch_bounds__(256) k_post_both(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
                                                    QcPostSeg v, float* __restrict__ part, int64_t part_stride,
-                                                   int n_val) {
+                                                   int n_val, TG... tg) {
+  using K = QcKind<TG...>;
   if ((int)blockIdx.x >= n_val)
-    k_post_body<N, 6, 2>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr, r.qbar, part, part_stride,
-                         r.row0, r.B);
+    k_post_body<N, 6, 2, K::data, K::coef>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr, r.qbar,
+                                           part, part_stride, r.row0, r.B, K::tg_res(tg...), K::c_u(tg...), K::table(tg...));
   else
-    k_post_value4<N>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B);
+    k_post_value4<N, K::data>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B, K::tg_val(tg...));
 }
 
 // fused post stage: here the residual tiles come first and the (shorter) value blocks fill the slots after them
-template <int N>
+template <int N, class... TG>
 __global__ void __launch_bounds__(256) k_post_fused_both(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
                                                          QcPostSeg v, float* __restrict__ part, int64_t part_stride,
-                                                         int n_res) {
+                                                         int n_res, TG... tg) {
   extern __shared__ float s_dyn[];
+  using K = QcKind<TG...>;
   if ((int)blockIdx.x < n_res)
-    k_post_fused6_body<N>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0, r.B, s_dyn);
+    k_post_fused6_body<N, K::data, K::coef>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0,
+                                            r.B, s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...));
   else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part,
-                                                  part_stride, v.row0, v.B, s_dyn);
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part,
+                                                           part_stride, v.row0, v.B, s_dyn, K::tg_val(tg...));
 }
 
-// the two merged point kernels on tabulated targets (QcTab): same block order as their analytic forms
-template <int N>
-__global__ void __launch_bounds__(256) k_post_both_data(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
-                                                        QcPostSeg v, float* __restrict__ part, int64_t part_stride,
-                                                        int n_val, QcTab tab) {
-  if ((int)blockIdx.x >= n_val)
-    k_post_body<N, 6, 2, true>(blockIdx.x - n_val, nullptr, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr, r.qbar, part,
-                               part_stride, r.row0, r.B, tab.tg_res, tab.c_u);
-  else
-    k_post_value4<N, true>(blockIdx.x, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B, tab.tg_val);
-}
-
-template <int N>
-__global__ void __launch_bounds__(256) k_post_fused_both_data(const float* __restrict__ prm, QcLayout L, QcPde pde,
-                                                              QcPostSeg r, QcPostSeg v, float* __restrict__ part,
-                                                              int64_t part_stride, int n_res, QcTab tab) {
-  extern __shared__ float s_dyn[];
-  if ((int)blockIdx.x < n_res)
-    k_post_fused6_body<N, true>(blockIdx.x, nullptr, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0, r.B,
-                                s_dyn, tab.tg_res, tab.c_u);
-  else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x - n_res, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part,
-                                                        part_stride, v.row0, v.B, s_dyn, tab.tg_val);
-}
-
-template <int N>
+// GEN (the coefficient step): the residual tiles read their six channel cotangents from r.ub (gen mode of the body)
+template <int N, bool GEN>
 __global__ void k_post_wg_both(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r, QcPostSeg v,
                                float* __restrict__ part, int64_t part_stride, int HB, int PS, int n_val) {
   if ((int)blockIdx.x >= n_val)
-    k_post_wg_body<N, 6>(blockIdx.x - n_val, prm, L, pde, r.qjets, r.ub, r.rb, part, part_stride, r.row0, r.B, HB, PS);
-  else
-    k_post_wg_body<N, 1>(blockIdx.x, prm, L, pde, v.qjets, v.ub, nullptr, part, part_stride, v.row0, v.B, HB, PS);
-}
-
-// the merged kernels of the coefficient step: residual tiles on the COEF bodies (r.ub = the [6][B] cotangent scratch,
-// r.rb unused), value tiles on the DATA code; the weight-gradient kernel reads the residual cotangents in its gen mode
-template <int N>
-__global__ void __launch_bounds__(256) k_post_both_coef(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
-                                                        QcPostSeg v, float* __restrict__ part, int64_t part_stride,
-                                                        int n_val, QcTab tab, const float* __restrict__ coef) {
-  if ((int)blockIdx.x >= n_val)
-    k_post_body<N, 6, 2, true, true>(blockIdx.x - n_val, nullptr, prm, L, pde, r.qjets, r.ub, nullptr, nullptr, nullptr, r.qbar,
-                                     part, part_stride, r.row0, r.B, tab.tg_res, 0.f, coef);
-  else
-    k_post_value4<N, true>(blockIdx.x, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B, tab.tg_val);
-}
-
-template <int N>
-__global__ void __launch_bounds__(256) k_post_fused_both_coef(const float* __restrict__ prm, QcLayout L, QcPde pde,
-                                                              QcPostSeg r, QcPostSeg v, float* __restrict__ part,
-                                                              int64_t part_stride, int n_res, QcTab tab,
-                                                              const float* __restrict__ coef) {
-  extern __shared__ float s_dyn[];
-  if ((int)blockIdx.x < n_res)
-    k_post_fused6_body<N, true, true>(blockIdx.x, nullptr, prm, L, pde, r.qjets, r.ub, nullptr, r.qbar, part, part_stride,
-                                      r.row0, r.B, s_dyn, tab.tg_res, 0.f, coef);
-  else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, true>(blockIdx.x - n_res, nullptr, prm, L, pde, v.qjets, v.ub, v.qbar, part,
-                                                        part_stride, v.row0, v.B, s_dyn, tab.tg_val);
-}
-
-template <int N>
-__global__ void k_post_wg_both_coef(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r, QcPostSeg v,
-                                    float* __restrict__ part, int64_t part_stride, int HB, int PS, int n_val) {
-  if ((int)blockIdx.x >= n_val)
-    k_post_wg_body<N, 6>(blockIdx.x - n_val, prm, L, pde, r.qjets, r.ub, nullptr, part, part_stride, r.row0, r.B, HB, PS, 1);
+    k_post_wg_body<N, 6>(blockIdx.x - n_val, prm, L, pde, r.qjets, r.ub, GEN ? nullptr : r.rb, part, part_stride, r.row0, r.B,
+                         HB, PS, GEN ? 1 : 0);
   else
     k_post_wg_body<N, 1>(blockIdx.x, prm, L, pde, v.qjets, v.ub, nullptr, part, part_stride, v.row0, v.B, HB, PS);
 }
@@ -1823,25 +1756,22 @@ __global__ void k_post_wg_both_coef(const float* __restrict__ prm, QcLayout L, Q
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
-#define QC_MLP_DISPATCH(n, CALL)                                                                   \
-  switch (n) {                                                                                     \
-    case 1: { CALL(1) } break;  case 2: { CALL(2) } break;  case 3: { CALL(3) } break;             \
-    case 4: { CALL(4) } break;  case 5: { CALL(5) } break;  case 6: { CALL(6) } break;             \
-    case 7: { CALL(7) } break;  case 8: { CALL(8) } break;  case 9: { CALL(9) } break;             \
-    case 10: { CALL(10) } break; case 11: { CALL(11) } break; case 12: { CALL(12) } break;         \
-    case 13: { CALL(13) } break; case 14: { CALL(14) } break; case 15: { CALL(15) } break;         \
-    case 16: { CALL(16) } break;                                                                   \
-    default: return QC_ERR_UNSUPPORTED;                                                            \
-  }
-
-// the merged launches of the coefficient step: the merged form exists for the register family only (n = 2 .. 5), so its
-// kernels are instantiated for those widths alone (the weight-gradient kernel would need scratch memory from n = 13)
-#define QC_MLP_DISPATCH_MERGED(n, CALL)                                                            \
-  switch (n) {                                                                                     \
-    case 2: { CALL(2) } break;  case 3: { CALL(3) } break;                                         \
-    case 4: { CALL(4) } break;  case 5: { CALL(5) } break;                                         \
-    default: return QC_ERR_UNSUPPORTED;                                                            \
-  }
+// The wire count as a compile-time value: f(qc_int<N>) for the N in LO .. HI that equals n, QC_ERR_UNSUPPORTED outside.
+// The range is the set of instantiations a launcher builds.  It is walked from HI down: the compiler emits the kernels of
+// the calls it meets last first, so the code object holds them in ascending N, as it always has (where identical kernels
+// lie is worth 0.5 % of the step at config 2: DESIGN.md, "Target kinds").
+template <int V> using qc_int = std::integral_constant<int, V>;
+template <int LO, class F, int... I>
+static inline int qc_dispatch_seq(const int n, F&& f, std::integer_sequence<int, I...>) {
+  constexpr int HI = LO + (int)sizeof...(I) - 1;
+  const bool hit = ((n == HI - I ? (f(qc_int<HI - I>{}), true) : false) || ...);
+  return hit ? QC_OK : QC_ERR_UNSUPPORTED;
+}
+template <int LO, int HI, class F>
+static inline int qc_dispatch_n(const int n, F&& f) {
+  return qc_dispatch_seq<LO>(n, f, std::make_integer_sequence<int, HI - LO + 1>{});
+}
+constexpr int QC_MLP_NMAX = 16;   // every kernel of this file exists for n = 1 .. 16
 
 // lane = hidden unit kernels: HB lanes per group (one per hidden unit), PS groups share the tile's 64
 // points.  Narrow hidden layers pack groups back to back (HB = H: 5 groups of 50 fill 250 of 256 lanes
@@ -1870,15 +1800,14 @@ static inline bool post_fused_ok(const QcLayout& L) {
 int qc_mlp_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch,
                    hipStream_t st, int map) {
   const int grid = qc_ceil_div(B, 64);
-#define LAUNCH(NN, CC, MM) hipLaunchKernelGGL((k_pre_fwd<NN, CC, MM>), dim3(grid), dim3(256), 0, st, X, prm, L, ajets, B)
-#define CALL(NN)                                                     \
-  if (map) { if (nch == 6) LAUNCH(NN, 6, 1); else LAUNCH(NN, 1, 1); } \
-  else if (nch == 6) LAUNCH(NN, 6, 0);                               \
-  else LAUNCH(NN, 1, 0);
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-#undef LAUNCH
-  return QC_OK;
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c, auto m) {
+      hipLaunchKernelGGL((k_pre_fwd<n(), c(), m()>), dim3(grid), dim3(256), 0, st, X, prm, L, ajets, B);
+    };
+    if (map) { if (nch == 6) launch(qc_int<6>{}, qc_int<1>{}); else launch(qc_int<1>{}, qc_int<1>{}); }
+    else if (nch == 6) launch(qc_int<6>{}, qc_int<0>{});
+    else launch(qc_int<1>{}, qc_int<0>{});
+  });
 }
 
 int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part,
@@ -1888,102 +1817,75 @@ int qc_mlp_pre_bwd(const float* X, const float* prm, QcLayout L, const float* ab
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
   const size_t sh = (size_t)PS * (4 + L.n) * HB * sizeof(float);
-#define LAUNCH(NN, CC, MM)                                                                                       \
-  hipLaunchKernelGGL((k_pre_bwd<NN, CC, MM>), dim3(grid), dim3(threads), sh, st, X, prm, L, abar, part, part_stride, \
-                     row0, B, HB, PS, aj)
-#define CALL(NN)                                                     \
-  if (map) { if (nch == 6) LAUNCH(NN, 6, 1); else LAUNCH(NN, 1, 1); } \
-  else if (nch == 6) LAUNCH(NN, 6, 0);                               \
-  else LAUNCH(NN, 1, 0);
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-#undef LAUNCH
-  return QC_OK;
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c, auto m) {
+      hipLaunchKernelGGL((k_pre_bwd<n(), c(), m()>), dim3(grid), dim3(threads), sh, st, X, prm, L, abar, part, part_stride,
+                         row0, B, HB, PS, aj);
+    };
+    if (map) { if (nch == 6) launch(qc_int<6>{}, qc_int<1>{}); else launch(qc_int<1>{}, qc_int<1>{}); }
+    else if (nch == 6) launch(qc_int<6>{}, qc_int<0>{});
+    else launch(qc_int<1>{}, qc_int<0>{});
+  });
+}
+
+// The mode as a compile-time value, for the instantiations that exist: modes 3 and 4 with six channels only, and with a
+// target argument mode 2 only.
+template <int NCH, bool DATA, class F>
+static inline void qc_post_mode(const int mode, F&& f) {
+  if constexpr (!DATA) {
+    if (mode == 0) return f(qc_int<0>{});
+    if (mode == 1) return f(qc_int<1>{});
+    if constexpr (NCH == 6) {
+      if (mode == 3) return f(qc_int<3>{});
+      if (mode == 4) return f(qc_int<4>{});
+    }
+  }
+  f(qc_int<2>{});
 }
 
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
-                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTab* tab,
-                const float* coef) {
-  const int tiles = qc_ceil_div(B, 64);
+                float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg) {
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
+  if (!tg.ok(mode, nch, pde.problem)) return QC_ERR_ARG;
+  const int tiles = qc_ceil_div(B, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
   const size_t sh = (size_t)PS * (L.n + 2) * HB * sizeof(float);
-  // cotangent sources of the weight-gradient kernel: given (mode 1) or produced by the point kernel (mode 2)
+  // cotangent sources of the weight-gradient kernel: given (modes 1, 3) or produced by the point kernel (mode 2); one
+  // per derivative channel (its gen mode) in mode 3 and behind the point kernel of a coefficient table
   const float* ub_src = (mode == 1 || mode == 3) ? in_ubar : out_u;
-  const float* rb_src = mode == 1 ? in_rbar : out_res;
-  const int gen = mode == 3 ? 1 : 0;
-  const bool fused = post_fused_ok(L);
-#define LAUNCH(NN, CC, MM)                                                                              \
-  hipLaunchKernelGGL((k_post<NN, CC, MM>), dim3(tiles), dim3(256), 0, st, X, prm, L, pde, qjets, out_u,  \
-                     out_res, in_ubar, in_rbar, qbar, part, part_stride, row0, B)
-#define LAUNCH_WG(NN, CC)                                                                               \
-  hipLaunchKernelGGL((k_post_wg<NN, CC>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets,        \
-                     ub_src, (CC == 6 ? rb_src : nullptr), part, part_stride, row0, B, HB, PS, gen)
-  /* the step's form (mode 2): one kernel, lane = point in both phases; QC_POST_SPLIT=1 keeps the pair */ \
-#define LAUNCH_FUSED(NN, CC)                                                                                         \
-  hipLaunchKernelGGL((k_post_fused<NN, CC>), dim3(CC == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)),           \
-                     dim3(256), CC == 6 ? qc_post_fused_lds_res(L) : qc_post_fused_lds_val(L), st, X, prm, L, pde,     \
-                     qjets, out_u, out_res, qbar, part, part_stride, row0, B)
-#define CALL(NN)                                                         \
-  if (nch == 6) {                                                        \
-    if (mode == 0) LAUNCH(NN, 6, 0);                                     \
-    else if (mode == 1) { LAUNCH(NN, 6, 1); LAUNCH_WG(NN, 6); }          \
-    else if (mode == 3) { LAUNCH(NN, 6, 3); LAUNCH_WG(NN, 6); }          \
-    else if (mode == 4) LAUNCH(NN, 6, 4);                                \
-    else if (fused) LAUNCH_FUSED(NN, 6);                                 \
-    else { LAUNCH(NN, 6, 2); LAUNCH_WG(NN, 6); }                         \
-  } else {                                                               \
-    if (mode == 0) LAUNCH(NN, 1, 0);                                     \
-    else if (mode == 1) { LAUNCH(NN, 1, 1); LAUNCH_WG(NN, 1); }          \
-    else if (fused) LAUNCH_FUSED(NN, 1);                                 \
-    else { LAUNCH(NN, 1, 2); LAUNCH_WG(NN, 1); }                         \
-  }
-  /* tabulated targets (mode 2 only): the same two forms on the _data kernels */                          \
-#define LAUNCH_DATA(NN, CC)                                                                                          \
-  if (fused)                                                                                                         \
-    hipLaunchKernelGGL((k_post_fused_data<NN, CC>), dim3(CC == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)),    \
-                       dim3(256), CC == 6 ? qc_post_fused_lds_res(L) : qc_post_fused_lds_val(L), st, prm, L, pde,      \
-                       qjets, out_u, out_res, qbar, part, part_stride, row0, B, tg, tab->c_u);                        \
-  else {                                                                                                             \
-    hipLaunchKernelGGL((k_post_data<NN, CC>), dim3(tiles), dim3(256), 0, st, prm, L, pde, qjets, out_u, out_res, qbar, \
-                       part, part_stride, row0, B, tg, tab->c_u);                                                     \
-    LAUNCH_WG(NN, CC);                                                                                               \
-  }
-#define CALL_DATA(NN) \
-  if (nch == 6) { LAUNCH_DATA(NN, 6) } else { LAUNCH_DATA(NN, 1) }
-  /* per-point operator rows (residual points): out_u = the [6][B] cotangents, the pair's second kernel in gen mode */ \
-#define CALL_COEF(NN)                                                                                                \
-  if (fused)                                                                                                         \
-    hipLaunchKernelGGL((k_post_fused_coef<NN>), dim3(tiles), dim3(256), qc_post_fused_lds_res(L), st, prm, L, pde,    \
-                       qjets, out_u, qbar, part, part_stride, row0, B, tab->tg_res, coef);                            \
-  else {                                                                                                             \
-    hipLaunchKernelGGL((k_post_coef<NN>), dim3(tiles), dim3(256), 0, st, prm, L, pde, qjets, out_u, qbar, part,       \
-                       part_stride, row0, B, tab->tg_res, coef);                                                      \
-    hipLaunchKernelGGL((k_post_wg<NN, 6>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets, (const float*)out_u, \
-                       (const float*)nullptr, part, part_stride, row0, B, HB, PS, 1);                                 \
-  }
-  if (coef != nullptr) {
-    if (mode != 2 || nch != 6 || tab == nullptr) return QC_ERR_ARG;
-    QC_MLP_DISPATCH(L.n, CALL_COEF)
-    return QC_OK;
-  }
-  if (tab != nullptr) {
-    if (mode != 2) return QC_ERR_ARG;
-    const float* tg = nch == 6 ? tab->tg_res : tab->tg_val;
-    QC_MLP_DISPATCH(L.n, CALL_DATA)
-    return QC_OK;
-  }
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-#undef CALL_DATA
-#undef CALL_COEF
-#undef LAUNCH
-#undef LAUNCH_WG
-#undef LAUNCH_FUSED
-#undef LAUNCH_DATA
-  return QC_OK;
+  const float* rb_src = mode == 1 ? in_rbar : (tg.kind == QC_TARGET_COEF ? nullptr : out_res);
+  const int gen = (mode == 3 || tg.kind == QC_TARGET_COEF) ? 1 : 0;
+  // the step's form (mode 2): one kernel, lane = point in both phases; QC_POST_SPLIT=1 and wide hidden layers keep the pair
+  const bool fused = mode == 2 && post_fused_ok(L);
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L);
+  // the one launch sequence, for n wires, nch channels and the target arguments t (none: analytic)
+  auto launch = [&](auto n, auto c, const auto&... t) {
+    constexpr int N = n(), NCH = c();
+    if (fused) {
+      hipLaunchKernelGGL((k_post_fused<N, NCH, std::decay_t<decltype(t)>...>),
+                         dim3(NCH == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)), dim3(256), NCH == 6 ? shr : shv, st, X,
+                         prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, t...);
+      return;
+    }
+    qc_post_mode<NCH, (sizeof...(t) > 0)>(mode, [&](auto m) {
+      hipLaunchKernelGGL((k_post<N, NCH, m(), std::decay_t<decltype(t)>...>), dim3(tiles), dim3(256), 0, st, X, prm, L, pde,
+                         qjets, out_u, out_res, in_ubar, in_rbar, qbar, part, part_stride, row0, B, t...);
+    });
+    if (mode >= 1 && mode <= 3)
+      hipLaunchKernelGGL((k_post_wg<N, NCH>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets, ub_src,
+                         (NCH == 6 ? rb_src : nullptr), part, part_stride, row0, B, HB, PS, gen);
+  };
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto by_nch = [&](const auto&... t) {
+      if (nch == 6) launch(n, qc_int<6>{}, t...);
+      else launch(n, qc_int<1>{}, t...);
+    };
+    if (tg.kind == QC_TARGET_COEF) launch(n, qc_int<6>{}, tg.tab, tg.coef);   // residual points only (QcTarget::ok)
+    else if (tg.kind == QC_TARGET_TAB) by_nch(tg.tab);
+    else by_nch();
+  });
 }
 
 // ------------------------------------------------------------------ merged residual + value launches (fused step)
@@ -1997,16 +1899,15 @@ int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, floa
   dr.n_ic = n_ic; dr.off_res = off_res; dr.off_ic = off_ic; dr.off_bc = off_bc; dr.face_pts = face_pts;
   dr.seed = seed; dr.step = step;
   const bool rf = draw && face_pts < 0;
-#define LAUNCH(NN, MM, RR) \
-  hipLaunchKernelGGL((k_pre_fwd_both<NN, MM, RR>), dim3(nr + nv), dim3(256), 0, st, Xr, Xv, prm, L, ajr, ajv, Br, Bv, nv, dr)
-#define CALL(NN)                                                           \
-  if (map) { if (rf) LAUNCH(NN, 1, true); else LAUNCH(NN, 1, false); }    \
-  else if (rf) LAUNCH(NN, 0, true);                                        \
-  else LAUNCH(NN, 0, false);
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-#undef LAUNCH
-  return QC_OK;
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto m, auto r) {
+      hipLaunchKernelGGL((k_pre_fwd_both<n(), m(), r()>), dim3(nr + nv), dim3(256), 0, st, Xr, Xv, prm, L, ajr, ajv, Br, Bv, nv,
+                         dr);
+    };
+    if (map) { if (rf) launch(qc_int<1>{}, std::true_type{}); else launch(qc_int<1>{}, std::false_type{}); }
+    else if (rf) launch(qc_int<0>{}, std::true_type{});
+    else launch(qc_int<0>{}, std::false_type{});
+  });
 }
 
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
@@ -2017,77 +1918,50 @@ int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLa
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
   const size_t sh = (size_t)PS * (4 + L.n) * HB * sizeof(float);
-#define LAUNCH(NN, MM)                                                                                              \
-  hipLaunchKernelGGL((k_pre_bwd_both<NN, MM>), dim3(nr + nv), dim3(threads), sh, st, Xr, Xv, prm, L, abr, abv, part, \
-                     part_stride, row0_r, row0_v, Br, Bv, HB, PS, nv, ajr, ajv)
-#define CALL(NN) \
-  if (map) LAUNCH(NN, 1); else LAUNCH(NN, 0);
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-#undef LAUNCH
-  return QC_OK;
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto m) {
+      hipLaunchKernelGGL((k_pre_bwd_both<n(), m()>), dim3(nr + nv), dim3(threads), sh, st, Xr, Xv, prm, L, abr, abv, part,
+                         part_stride, row0_r, row0_v, Br, Bv, HB, PS, nv, ajr, ajv);
+    };
+    if (map) launch(qc_int<1>{}); else launch(qc_int<0>{});
+  });
 }
 
-// mode-2 post stage of both pipelines: point kernel, then weight-gradient kernel
+// mode-2 post stage of both pipelines: the fused kernel, or point kernel and weight-gradient kernel
 int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr,
                      float* qbr, int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv,
-                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcTab* tab,
-                     const float* coef) {
+                     int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcTarget& tg) {
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
+  if (!tg.ok(2, 6, pde.problem)) return QC_ERR_ARG;
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
   const size_t sh = (size_t)PS * (L.n + 2) * HB * sizeof(float);
   const int nv4 = qc_ceil_div(nv, 4);   // point kernel: 4 value tiles per block, one per wave
+  // (with a coefficient table ubr is the [6][Br] cotangent scratch of the residual tiles)
   const QcPostSeg r = {Xr, qjr, ubr, rbr, qbr, row0_r, Br}, v = {Xv, qjv, ubv, nullptr, qbv, row0_v, Bv};
   const bool fused = post_fused_ok(L);
   // fused: residual blocks, then value blocks of QC_POST_VALUE_TPB tiles; one dynamic LDS size serves both bodies
   const int nvf = qc_ceil_div(nv, QC_POST_VALUE_TPB);
   const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L), shf = shr > shv ? shr : shv;
-#define CALL(NN)                                                                                                        \
-  if (fused) {                                                                                                          \
-    hipLaunchKernelGGL((k_post_fused_both<NN>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,            \
-                       part_stride, nr);                                                                                \
-  } else {                                                                                                              \
-    hipLaunchKernelGGL((k_post_both<NN>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride, nv4); \
-    hipLaunchKernelGGL((k_post_wg_both<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride, \
-                       HB, PS, nv);                                                                                     \
-  }
-#define CALL_DATA(NN)                                                                                                   \
-  if (fused) {                                                                                                          \
-    hipLaunchKernelGGL((k_post_fused_both_data<NN>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,       \
-                       part_stride, nr, *tab);                                                                          \
-  } else {                                                                                                              \
-    hipLaunchKernelGGL((k_post_both_data<NN>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,  \
-                       nv4, *tab);                                                                                      \
-    hipLaunchKernelGGL((k_post_wg_both<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride, \
-                       HB, PS, nv);                                                                                     \
-  }
-  /* coefficient step: ubr is the [6][Br] cotangent scratch of the residual tiles */                                     \
-#define CALL_COEF(NN)                                                                                                   \
-  if (fused) {                                                                                                          \
-    hipLaunchKernelGGL((k_post_fused_both_coef<NN>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,       \
-                       part_stride, nr, *tab, coef);                                                                    \
-  } else {                                                                                                              \
-    hipLaunchKernelGGL((k_post_both_coef<NN>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,  \
-                       nv4, *tab, coef);                                                                                \
-    hipLaunchKernelGGL((k_post_wg_both_coef<NN>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part,        \
-                       part_stride, HB, PS, nv);                                                                        \
-  }
-  if (coef != nullptr) {
-    if (tab == nullptr) return QC_ERR_ARG;
-    QC_MLP_DISPATCH_MERGED(L.n, CALL_COEF)
-    return QC_OK;
-  }
-  if (tab != nullptr) {
-    QC_MLP_DISPATCH(L.n, CALL_DATA)
-    return QC_OK;
-  }
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-#undef CALL_DATA
-#undef CALL_COEF
-  return QC_OK;
+  // the one launch sequence, for n wires and the target arguments t (none: analytic)
+  auto launch = [&](auto n, const auto&... t) {
+    constexpr int N = n();
+    if (fused) {
+      hipLaunchKernelGGL((k_post_fused_both<N, std::decay_t<decltype(t)>...>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde,
+                         r, v, part, part_stride, nr, t...);
+    } else {
+      hipLaunchKernelGGL((k_post_both<N, std::decay_t<decltype(t)>...>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v,
+                         part, part_stride, nv4, t...);
+      hipLaunchKernelGGL((k_post_wg_both<N, QcKind<std::decay_t<decltype(t)>...>::coef>), dim3(nr + nv), dim3(threads), sh, st,
+                         prm, L, pde, r, v, part, part_stride, HB, PS, nv);
+    }
+  };
+  // the merged form exists for the register family only (n = 2 .. 5), so the kernels of the youngest kind are built for
+  // those widths alone (the weight-gradient kernel would need scratch memory from n = 13)
+  if (tg.kind == QC_TARGET_COEF) return qc_dispatch_n<2, 5>(L.n, [&](auto n) { launch(n, tg.tab, tg.coef); });
+  if (tg.kind == QC_TARGET_TAB) return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) { launch(n, tg.tab); });
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) { launch(n); });
 }
 
 // K-output post stage (k_post_multi): mode 4 forward / mode 3 reverse, six channels
@@ -2096,12 +1970,11 @@ int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float
                       int64_t row0, int64_t B, hipStream_t st) {
   if (K < 1 || K > QC_KMAX || L.H > 1024) return QC_ERR_UNSUPPORTED;
   const int tiles = qc_ceil_div(B, 64);
-#define CALL(NN)                                                                                                     \
-  if (mode == 4) hipLaunchKernelGGL((k_post_multi<NN, 4>), dim3(tiles), dim3(256), 0, st, prm, L, K, w4k, qjets, out_u, \
-                                    ubar, qbar, part, part_stride, partk, partk_stride, row0, B);                      \
-  else hipLaunchKernelGGL((k_post_multi<NN, 3>), dim3(tiles), dim3(256), 0, st, prm, L, K, w4k, qjets, out_u, ubar,     \
-                          qbar, part, part_stride, partk, partk_stride, row0, B);
-  QC_MLP_DISPATCH(L.n, CALL)
-#undef CALL
-  return QC_OK;
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto m) {
+      hipLaunchKernelGGL((k_post_multi<n(), m()>), dim3(tiles), dim3(256), 0, st, prm, L, K, w4k, qjets, out_u, ubar, qbar, part,
+                         part_stride, partk, partk_stride, row0, B);
+    };
+    if (mode == 4) launch(qc_int<4>{}); else launch(qc_int<3>{});
+  });
 }

@@ -35,6 +35,10 @@ CASES = {
     "hbm_cascade9": ("cascade", 9, 1, "angle", 65, 3, 2),            # HBM family
     "amp_cascade4": ("cascade", 4, 1, "amplitude", 40, 10, 10),      # amplitude encoding
     "reg_cascade4_H129": ("cascade", 4, 1, "angle", 70, 30, 20),     # merged, H > 128: point + weight-gradient kernel pair
+    # the ends of the merged form's range of wire counts.  Two tiles in both pipelines, the second holding one point; the
+    # first value tile mixes IC and BC: the smallest merged shape with every tail
+    "reg_cascade2": ("cascade", 2, 1, "angle", 65, 1, 64),
+    "reg_cascade5": ("cascade", 5, 1, "angle", 65, 1, 64),
 }
 CASE_H = {"reg_cascade4_H129": 129}     # hidden width of a case (default H)
 

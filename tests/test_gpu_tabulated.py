@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 H = T.H
 TOL_G, TOL_L = 2e-4, 1e-4
 THETA_MIN = 20 * TOL_G
-MERGED = ("reg_cascade4", "reg_cascade4_H129")
+MERGED = ("reg_cascade4", "reg_cascade4_H129", "reg_cascade2", "reg_cascade5")
 
 
 def _model(gpu_device, ans, n, L, enc, flat=None, hidden=H):
