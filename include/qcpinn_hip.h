@@ -364,6 +364,65 @@ int qc_sample_dataset_coef(float* X_res_dev, float* target_res_dev, int64_t n_re
 int qc_fused_pinn_coef_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef, int phases,
                             void* stream);
 
+/* ---- residual-adaptive sampling of the dataset's residual rows (RAD / RAR: Wu et al. 2023, Lu et al. 2021): every so many
+ * steps the residual is evaluated on the whole candidate pool, and the residual batch is then drawn with probability
+ * proportional to |res|^power / mean + floor instead of uniformly.  Three calls, all enqueued on `stream`, no host read:
+ * scores of the rows, scores -> an integer CDF, and the gather (or the step) that draws from it.  IC and BC rows stay
+ * uniform.  The loss is not reweighted.
+ *
+ * Scores.  score_dev[j] = | res_j - ds_r[j] | in fp32 for the rows row0 <= j < row0 + rows of data's residual segment
+ * (1 <= rows, row0 + rows <= ds_n_res; the other entries of score_dev [ds_n_res] are not touched), res_j the residual the
+ * step applies under the current parameters and trig table: coef NULL, that of qc_post_data with data->c_u and desc->pde;
+ * else the per-row form of qc_fused_pinn_coef_step on the rows of coef->ds_coef (coef_res_dev is not read).  It runs the
+ * forward half of the residual pipeline over chunks of at most B_res rows through the step's own residual scratch:
+ * ajets_res_dev, qjets_res_dev, the head of qbar_res_dev ([6][chunk] channels of u) and circ_ws_dev.  Between steps all
+ * of these are scratch.  QC_ERR_ARG before any launch: B_res = 0; a NULL buffer; rows or row0 out of range; a problem id
+ * other than QC_PROBLEM_TABULATED; coef given with ds_coef NULL; a workspace the step itself would refuse. */
+int qc_dataset_scores(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef, int64_t row0,
+                      int64_t rows, float* score_dev, void* stream);
+
+/* Scores -> CDF, every bit defined (integers behind the power, so no result depends on a summation order):
+ *  1. p_j = score_j^power, 1 <= power <= 4, by left-to-right fp32 multiplication; a p_j that is NaN or negative counts as 0,
+ *     one above FLT_MAX as FLT_MAX.
+ *  2. M = max_j p_j.  M = 0: q_j = 1 for every row (uniform).  Otherwise s = 23 - ilogb M and q_j = floor(p_j 2^s) as a
+ *     64-bit integer, so that the largest lies in [2^23, 2^24); the scaling and the truncation are exact.
+ *  3. Q = sum_j q_j; a = (uint64)((double)floor_c * (double)Q / (double)n_rows), raised to 1 when floor_c > 0 and the
+ *     quotient truncates to 0; w_j = q_j + a.  floor_c = 0 is sampling proportional to the residual alone; a row with
+ *     w_j = 0 is never drawn.  0 <= floor_c <= QC_ADAPT_FLOOR_MAX (the CDF then stays below 2^64 for every n_rows < 2^31).
+ *  4. cdf_j = sum of w_i over i <= j (uint64), and a coarse table with one entry per QC_ADAPT_BLOCK rows,
+ *     coarse[b] = cdf[min(n_rows, (b + 1) QC_ADAPT_BLOCK) - 1].
+ * adapt_dev: 8-byte aligned, qc_adapt_bytes of n_rows bytes: a 64-byte record {uint64 total = cdf[n_rows - 1], q_sum = Q,
+ * add = a; float max_p = M; int32 shift = s (0 when M = 0); pad}, then cdf[n_rows], then coarse[ceil(n_rows / QC_ADAPT_BLOCK)].
+ * QC_ERR_ARG: a NULL or misaligned buffer, n_rows outside [1, 2^31), power outside 1..4, floor_c negative, not finite or
+ * above QC_ADAPT_FLOOR_MAX.  qc_adapt_bytes returns 0 for an n_rows outside that range. */
+#define QC_ADAPT_BLOCK 1024
+#define QC_ADAPT_FLOOR_MAX 256.0f
+size_t qc_adapt_bytes(int64_t n_rows);
+int qc_adapt_build(const float* score_dev, int64_t n_rows, int power, float floor_c, void* adapt_dev, void* stream);
+
+typedef struct qc_step_adapt {
+  const void* adapt_dev;   /* the buffer qc_adapt_build filled (or one of the same layout; only cdf and coarse are read) */
+  int64_t n_rows;          /* == data->ds_n_res */
+} qc_step_adapt;
+
+/* qc_sample_dataset_coef with the residual rows drawn from the CDF: same launch shape, segments, counters and IC / BC
+ * draws, so the value batches are bit-identical to the uniform gather's on the same seed.  Residual point i with global
+ * index g = off_res + i takes the Philox block it takes there (segment 0 counter, key = seed), forms
+ * r64 = word 0 << 32 | word 1 and t = the high 64 bits of r64 * T, T = cdf[n_rows - 1], and copies row
+ * idx = min{j : cdf_j > t} (coarse table first, then one block of the CDF).  coef NULL (then coef_res_dev is not written):
+ * rows and targets only.  QC_ERR_ARG: adapt NULL, adapt_dev NULL or misaligned, adapt->n_rows != data->ds_n_res, and
+ * whatever qc_sample_dataset_coef refuses. */
+int qc_sample_dataset_adaptive(float* X_res_dev, float* target_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev,
+                               float* target_val_dev, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                               float* coef_res_dev, const qc_step_data* data, const qc_step_coef* coef,
+                               const qc_step_adapt* adapt, uint64_t seed, uint64_t step, void* stream);
+
+/* qc_fused_pinn_data_step (coef NULL) or qc_fused_pinn_coef_step whose QC_PHASE_SAMPLE is that gather: still one launch
+ * ahead of the stages, and nothing else in the step differs.  QC_ERR_ARG before any launch: adapt NULL, adapt_dev NULL or
+ * misaligned, adapt->n_rows != data->ds_n_res, B_res = 0, and whatever the data or the coefficient step refuses. */
+int qc_fused_pinn_adaptive_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef,
+                                const qc_step_adapt* adapt, int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

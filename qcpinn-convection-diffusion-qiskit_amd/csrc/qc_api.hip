@@ -585,15 +585,45 @@ int qc_sample_collocation(float* X_res, int64_t n_res, int64_t off_res, float* X
   return qc_sample_collocation_faces(X_res, n_res, off_res, X_val, n_ic, off_ic, n_bc, off_bc, 0, seed, step, stream);
 }
 
+// ---- residual-adaptive sampling: the caller's buffer {64-byte record, cdf[n_rows], coarse[ceil(n_rows / QC_ADAPT_BLOCK)]}
+static const uint64_t* adapt_cdf(const qc_step_adapt* ad) { return (const uint64_t*)((const char*)ad->adapt_dev + sizeof(QcAdaptRec)); }
+// a buffer (8-byte aligned) over exactly the rows of the dataset's residual segment
+static bool adapt_ok(const qc_step_adapt* ad, const qc_step_data* t) {
+  return ad && t && ad->adapt_dev && ((uintptr_t)ad->adapt_dev & 7) == 0 && ad->n_rows >= 1 && ad->n_rows < ((int64_t)1 << 31) &&
+         ad->n_rows == t->ds_n_res;
+}
+
+size_t qc_adapt_bytes(int64_t n_rows) {
+  if (n_rows < 1 || n_rows >= ((int64_t)1 << 31)) return 0;
+  return sizeof(QcAdaptRec) + sizeof(uint64_t) * ((size_t)n_rows + (size_t)((n_rows + QC_ADAPT_BLOCK - 1) / QC_ADAPT_BLOCK));
+}
+
+int qc_adapt_build(const float* score, int64_t n_rows, int power, float floor_c, void* adapt, void* stream) {
+  if (!score || !adapt || ((uintptr_t)adapt & 7) != 0 || n_rows < 1 || n_rows >= ((int64_t)1 << 31)) return QC_ERR_ARG;
+  if (power < 1 || power > 4 || !(floor_c >= 0.f) || !(floor_c <= QC_ADAPT_FLOOR_MAX)) return QC_ERR_ARG;
+  const int rc = qc_adapt_build_launch(score, n_rows, power, floor_c, adapt, (hipStream_t)stream);
+  return rc ? hip_fail(hipGetLastError()) : after_launch();
+}
+
 // the gather behind both exports: rows and targets of the three batches, and with a table (ds_coef -> coef_res) the
 // residual rows' operator coefficients; the plain form is the coefficient form with no table
 static int sample_dataset_impl(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
                                int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const float* ds_coef,
-                               const qc_step_data* t, uint64_t seed, uint64_t step, void* stream) {
+                               const qc_step_data* t, uint64_t seed, uint64_t step, void* stream,
+                               const qc_step_adapt* ad = nullptr) {
   if (n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0) return QC_ERR_ARG;
+  if (ad && !adapt_ok(ad, t)) return QC_ERR_ARG;
   if ((n_res > 0 && (!X_res || !target_res)) || (n_ic + n_bc > 0 && (!X_val || !target_val))) return QC_ERR_ARG;
   if (!dataset_seg_ok(n_res, t->ds_X_res, t->ds_r, t->ds_n_res) || !dataset_seg_ok(n_ic, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic) ||
       !dataset_seg_ok(n_bc, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc)) return QC_ERR_ARG;
+  if (ad) {   // residual rows from the CDF; the value rows as below
+    const uint64_t* cdf = adapt_cdf(ad);
+    qc_sample_dataset_adaptive_launch(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
+                                      t->ds_X_res, t->ds_r, t->ds_n_res, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic, t->ds_X_bc,
+                                      t->ds_u_bc, t->ds_n_bc, seed, step, (hipStream_t)stream, coef_res, ds_coef, cdf,
+                                      cdf + ad->n_rows);
+    return after_launch();
+  }
   qc_sample_dataset_launch(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, t->ds_X_res,
                            t->ds_r, t->ds_n_res, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc, seed,
                            step, (hipStream_t)stream, coef_res, ds_coef);
@@ -615,6 +645,16 @@ int qc_sample_dataset_coef(float* X_res, float* target_res, int64_t n_res, int64
   // (n_res = 0 with null coefficient pointers: the plain gather, no residual rows to copy)
   return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
                              n_res > 0 ? coef_res : nullptr, n_res > 0 ? cf->ds_coef : nullptr, t, seed, step, stream);
+}
+
+int qc_sample_dataset_adaptive(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
+                               int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const qc_step_data* t,
+                               const qc_step_coef* cf, const qc_step_adapt* ad, uint64_t seed, uint64_t step, void* stream) {
+  if (!t || !ad) return QC_ERR_ARG;
+  const bool table = cf && n_res > 0;   // without a table (cf NULL): rows and targets only
+  if (table && (!coef_res || !cf->ds_coef)) return QC_ERR_ARG;
+  return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
+                             table ? coef_res : nullptr, table ? cf->ds_coef : nullptr, t, seed, step, stream, ad);
 }
 
 // ---- merged residual + value stages of the fused step (register family, angle encoding)
@@ -711,9 +751,11 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
 // rows and targets from its resident dataset AHEAD of the stages, in the merged form too (the merged pre stage then runs
 // with its own draw off, so its instantiations are the analytic step's).  With `cf` too, qc_fused_pinn_coef_step: the
 // residual points' operator rows come from cf->coef_res_dev, gathered with the rows and targets under QC_PHASE_SAMPLE.
+// With `ad`, qc_fused_pinn_adaptive_step: that gather draws its residual rows from the CDF; nothing else differs.
 static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phases, void* stream,
-                      const qc_step_coef* cf = nullptr) {
+                      const qc_step_coef* cf = nullptr, const qc_step_adapt* ad = nullptr) {
   if (!d) return QC_ERR_ARG;
+  if (ad && (d->B_res <= 0 || !adapt_ok(ad, data))) return QC_ERR_ARG;
   const bool tabulated = data != nullptr;
   const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
   if (table && (!cf->coef_res_dev || ((phases & QC_PHASE_SAMPLE) && !cf->ds_coef))) return QC_ERR_ARG;
@@ -746,7 +788,7 @@ static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phase
     if ((rc = sample_dataset_impl((float*)d->X_res_dev, data->target_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev,
                                   data->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
                                   table ? cf->coef_res_dev : nullptr, table ? cf->ds_coef : nullptr, data, d->sample_seed,
-                                  d->sample_step, st))) return rc;
+                                  d->sample_step, st, ad))) return rc;
   } else if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage) {   // coordinate draw
     if ((rc = qc_sample_collocation_faces((float*)d->X_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev, d->n_ic,
                                           d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
@@ -822,6 +864,53 @@ int qc_fused_pinn_coef_step(const qc_step_desc* d, const qc_step_data* data, con
                             void* stream) {
   if (!data || !coef) return QC_ERR_ARG;
   return fused_step(d, data, phases, stream, coef);
+}
+
+int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef,
+                                const qc_step_adapt* adapt, int phases, void* stream) {
+  if (!data || !adapt) return QC_ERR_ARG;
+  return fused_step(d, data, phases, stream, coef, adapt);
+}
+
+// Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pre network,
+// [amplitudes,] circuit, qc_post mode 4) over chunks of at most B_res rows through the step's residual scratch, then
+// |res - r| per row.  Between steps those buffers hold nothing that is read again.
+int qc_dataset_scores(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, int64_t row0, int64_t rows,
+                      float* score, void* stream) {
+  if (!d || !t || !score || d->B_res <= 0) return QC_ERR_ARG;
+  if (!t->ds_X_res || !t->ds_r || t->ds_n_res < 1 || t->ds_n_res >= ((int64_t)1 << 31)) return QC_ERR_ARG;
+  if (row0 < 0 || rows < 1 || row0 > t->ds_n_res || rows > t->ds_n_res - row0) return QC_ERR_ARG;
+  if (cf && !cf->ds_coef) return QC_ERR_ARG;
+  if (d->pde.problem != QC_PROBLEM_TABULATED) return QC_ERR_ARG;
+  if (!d->prog || !d->trig_dev || !d->params_dev || !d->ajets_res_dev || !d->qjets_res_dev || !d->qbar_res_dev) return QC_ERR_ARG;
+  const qc_program* p = d->prog;
+  const int n = d->n, H = d->H;
+  if (p->n_qubits != n || p->n_params != d->n_theta || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
+  if (!p->fam) return QC_ERR_UNSUPPORTED;
+  int rc = check_mlp(H, n, d->n_theta, d->B_res, 6);
+  if (rc) return rc;
+  if (p->amplitude && (!d->circ_ws_dev || d->circ_ws_bytes < qc_step_workspace_bytes(p, d->B_res, d->B_val))) return QC_ERR_ARG;
+  const QcStepLayout ws = step_layout(p, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
+  if (!ws.fits) return QC_ERR_ARG;
+  // forward only: nothing is kept.  The HBM family runs a chunk in as many groups of tiles as its scratch holds (a
+  // forward tile is never larger than the forward-and-adjoint tile the step sized it for), so no chunk needs shrinking
+  const QcCircStore store = {ws.res.p, ws.res.bytes, false};
+  hipStream_t st = (hipStream_t)stream;
+  const QcPde pde = to_pde(&d->pde);
+  float* uj = d->qbar_res_dev;   // [6][c]
+  for (int64_t r = row0; r < row0 + rows; r += d->B_res) {
+    const int64_t c = row0 + rows - r < d->B_res ? row0 + rows - r : d->B_res;
+    const float* X = t->ds_X_res + 3 * r;
+    if ((rc = qc_pre_forward_map(X, d->params_dev, H, n, d->n_theta, p->angle_map, d->ajets_res_dev, c, 6, st))) return rc;
+    if (ws.u_res && (rc = qc_amp_forward(d->ajets_res_dev, ws.u_res, n, c, 6, st))) return rc;
+    if ((rc = p->fam->fwd(p, (const QcTrig*)d->trig_dev, d->umat_dev, ws.u_res ? ws.u_res : d->ajets_res_dev, d->qjets_res_dev, c,
+                          6, store, st)) || (rc = after_launch())) return rc;
+    if ((rc = post_impl(4, X, d->params_dev, H, n, d->n_theta, &d->pde, d->qjets_res_dev, uj, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, 0, 0, c, 6, st, QcTarget{}))) return rc;
+    qc_adapt_score_launch(uj, c, pde, t->c_u, cf ? cf->ds_coef + (size_t)QC_COEF_N * r : nullptr, t->ds_r + r, score + r, st);
+    if ((rc = after_launch())) return rc;
+  }
+  return QC_OK;
 }
 
 }  // extern "C"

@@ -67,6 +67,17 @@ struct QcTarget {
   }
 };
 
+// Residual-adaptive sampling (qc_adapt.hip, k_sample_dataset_adaptive): the caller's buffer holds this record, then the
+// inclusive uint64 CDF of the rows' integer weights, then one coarse entry per QC_ADAPT_ROWS rows (the CDF at the last row
+// of each block of rows).  == the layout documented at qc_adapt_bytes in the public header.
+constexpr int QC_ADAPT_ROWS = 1024;   // == QC_ADAPT_BLOCK
+struct QcAdaptRec {
+  uint64_t total, q_sum, add;   // cdf[n - 1]; sum of the quantised powers; the floor term added to every row
+  float max_p;                  // M = max_j p_j
+  int32_t shift;                // s = 23 - ilogb(M) (0 when M = 0)
+  int32_t pad[8];
+};
+
 struct QcPde {  // == qc_pde of the public header
   float D, vx, vy;                 // physical constants: analytic targets of mode 2
   float c_t, c_x, c_y, d_xx, d_yy; // operator coefficients (sigma scalings folded in)
@@ -176,6 +187,18 @@ int qc_sample_dataset_launch(float* X_res, float* tg_res, int64_t n_res, int64_t
                              const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic, int64_t ds_n_ic,
                              const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed, uint64_t step,
                              hipStream_t, float* coef_res = nullptr, const float* ds_coef = nullptr);
+// the gather with the residual row drawn from the CDF (`cdf` [ds_n_res], `coarse` behind it); coef_res / ds_coef may be null
+int qc_sample_dataset_adaptive_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
+                                      int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
+                                      const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic,
+                                      int64_t ds_n_ic, const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed,
+                                      uint64_t step, hipStream_t, float* coef_res, const float* ds_coef, const uint64_t* cdf,
+                                      const uint64_t* coarse);
+// qc_adapt.hip: |res - target| of c rows from their [6][c] channels (coef_rows [c][7] or null: the scalar operator), and
+// scores -> record, CDF and coarse table
+int qc_adapt_score_launch(const float* uj, int64_t c, QcPde pde, float c_u, const float* coef_rows, const float* tg,
+                          float* score, hipStream_t);
+int qc_adapt_build_launch(const float* score, int64_t n, int power, float floor_c, void* adapt, hipStream_t);
 // HBM family, n >= 9 (qc_circuit_hbm2.hip, qc_circuit_h2s_kernels.h): all tiles of a batch resident when the workspace allows
 void* qc_h2_create(const qc_program* pg, int absorb, int amplitude);   // amplitude: the encoding the plan is built for
 void qc_h2_destroy(void* h2);

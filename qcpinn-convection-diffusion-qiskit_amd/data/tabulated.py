@@ -24,6 +24,7 @@ from __future__ import annotations
 import torch
 
 from .diffusion_dataset import box
+from ..hip.lib import QC_ADAPT_FLOOR_MAX
 
 MAX_ROWS = 2 ** 31 - 1      # the device gather forms (32-bit word * rows) >> 32
 COEF_COLUMNS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")     # column order of a coefficient row
@@ -79,6 +80,57 @@ def _segment(name, X, y):
     if X.shape[0] > MAX_ROWS:
         raise ValueError(f"{name}: at most {MAX_ROWS} rows per segment, got {X.shape[0]}")
     return X.contiguous(), y.contiguous()
+
+
+class AdaptiveSampling:
+    """Residual-adaptive sampling of a dataset's residual rows (RAD / RAR: Wu et al. 2023, Lu et al. 2021): every ``every``
+    steps, starting with the first, the residual e_j = |res_j - r_j| is evaluated on ALL residual rows under the current
+    parameters, and until the next evaluation the residual batch is drawn with probability proportional to
+
+        e_j^power / mean_i(e_i^power) + floor
+
+    instead of uniformly (``qc_dataset_scores``, ``qc_adapt_build``, ``qc_fused_pinn_adaptive_step``; the exact integer
+    rule is in include/qcpinn_hip.h).  ``power`` in 1..4 sharpens the concentration; ``floor`` >= 0 is the share kept for
+    uniform coverage (0: proportional to the residual alone, rows of zero residual are then never drawn; 1: about half of
+    the batch uniform).  IC and BC rows stay uniform and the loss is not reweighted."""
+
+    def __init__(self, power: int = 1, floor: float = 1.0, every: int = 100):
+        if isinstance(power, bool) or not isinstance(power, int) or not 1 <= power <= 4:
+            raise ValueError(f"adaptive sampling: power must be an integer in 1..4, got {power!r}")
+        floor = float(floor)
+        if not (0.0 <= floor <= QC_ADAPT_FLOOR_MAX):
+            raise ValueError(f"adaptive sampling: floor must be a finite number in [0, {QC_ADAPT_FLOOR_MAX:g}], got {floor!r}")
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"adaptive sampling: every must be a positive integer, got {every!r}")
+        self.power, self.floor, self.every = power, floor, every
+
+    def __repr__(self):
+        return f"AdaptiveSampling(power={self.power}, floor={self.floor}, every={self.every})"
+
+
+def adaptive_cdf(score, power: int, floor: float):
+    """The integer CDF of ``qc_adapt_build`` with torch ops: (N,) float32 scores -> (N,) int64 inclusive sums of
+    w_j = q_j + a (the generic training loop draws from it with ``torch.searchsorted``).  torch has no uint64 sums: where
+    the device's CDF can pass 2^63 (N (2^24 + a) >= 2^63: more than 2^31 rows at floor 256) this raises ValueError."""
+    e = torch.as_tensor(score, dtype=torch.float32).reshape(-1)
+    p = e.clone()
+    for _ in range(int(power) - 1):
+        p = p * e
+    p = torch.where(p > 0, p, torch.zeros_like(p)).clamp(max=torch.finfo(torch.float32).max)
+    N = p.numel()
+    M = p.max()
+    if float(M) == 0.0:
+        q = torch.ones(N, dtype=torch.int64, device=p.device)
+    else:
+        s = 23 - (int(torch.frexp(M)[1]) - 1)                  # 23 - ilogb(M)
+        q = torch.floor(torch.ldexp(p.double(), torch.tensor(s, device=p.device))).to(torch.int64)
+    Q = int(q.sum())
+    a = int(float(torch.tensor(floor, dtype=torch.float32)) * float(Q) / float(N))
+    if floor > 0 and a == 0:
+        a = 1
+    if N * (2 ** 24 + a) >= 2 ** 63:
+        raise ValueError(f"adaptive sampling: {N} rows at floor {floor} overflow torch's int64 cumulative sum")
+    return torch.cumsum(q + a, 0)
 
 
 class TabulatedProblem:

@@ -444,6 +444,8 @@ class FusedStep:
             self.coef_res = torch.zeros(L.QC_COEF_COLS, max(B_res, 1), **f)
             self.coef = L.QcStepCoef()
             self.coef.coef_res_dev, self.coef.ds_coef = (self.coef_res.data_ptr() if B_res else None), None
+        self.scores = self.adapt_buf = None
+        self.adapt = None       # QcStepAdapt once set_adaptive armed residual-adaptive sampling
         self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
         self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
         rows = (B_res + 63) // 64 + (B_val + 63) // 64
@@ -519,6 +521,46 @@ class FusedStep:
             else:
                 self.coef.ds_coef = None
         self._dataset = keep        # the descriptor holds raw pointers: keep the tensors alive
+        if self.adapt is not None:      # a CDF belongs to the rows it was built for: a uniform one over the new rows
+            self.set_adaptive(self.adapt_power, self.adapt_floor)
+
+    def set_adaptive(self, power: int = 1, floor: float = 1.0) -> None:
+        """Residual-adaptive sampling of the dataset's residual rows (after ``set_dataset``): allocates the score tensor
+        [ds_n_res] and the CDF buffer, and makes QC_PHASE_SAMPLE draw the residual batch from that CDF
+        (``qc_fused_pinn_adaptive_step``).  The CDF starts uniform; ``rescore()`` refreshes it.  A later ``set_dataset``
+        re-arms it for the new rows (uniform again until the next ``rescore()``); ``clear_adaptive()`` turns it off."""
+        n_rows = int(self.data.ds_n_res)
+        if not self.tabulated or n_rows < 1 or self.B_res < 1:
+            raise L.QcError("adaptive sampling needs a tabulated step with residual points and a dataset with residual rows")
+        dev = self.eng.device
+        self.adapt_power, self.adapt_floor = int(power), float(floor)
+        self.scores = torch.zeros(n_rows, dtype=torch.float32, device=dev)
+        need = int(self.eng.lib.qc_adapt_bytes(n_rows))
+        self.adapt_buf = torch.zeros((need + 7) // 8, dtype=torch.int64, device=dev)        # 8-byte aligned
+        self.adapt = L.QcStepAdapt(self.adapt_buf.data_ptr(), n_rows)
+        self._build_cdf()       # zero scores: uniform weights
+
+    def clear_adaptive(self) -> None:
+        """Back to the uniform gather."""
+        self.adapt = self.scores = self.adapt_buf = None
+
+    def _build_cdf(self) -> None:
+        L.check(self.eng.lib.qc_adapt_build(self.scores.data_ptr(), self.adapt.n_rows, self.adapt_power, self.adapt_floor,
+                                            self.adapt_buf.data_ptr(), _stream(self.eng.device)), "qc_adapt_build")
+
+    def rescore(self) -> None:
+        """Enqueue, on the step's stream, the scores |res - r| of every residual row of the dataset under the current
+        parameters and the CDF built from them.  No host read; the step's residual scratch is used between steps."""
+        L.check(self.eng.lib.qc_dataset_scores(C.byref(self.desc), C.byref(self.data), C.byref(self.coef) if self.coef_mode else None,
+                                               0, self.adapt.n_rows, self.scores.data_ptr(), _stream(self.eng.device)),
+                "qc_dataset_scores")
+        self._build_cdf()
+
+    def adaptive_state(self) -> dict:
+        """The 64-byte record of the CDF buffer (a host read)."""
+        raw = self.adapt_buf[:8].cpu().numpy()
+        return {"total": int(raw[0]), "q_sum": int(raw[1]), "add": int(raw[2]), "max_p": float(raw[3:4].view(np.float32)[0]),
+                "shift": int(raw[3:4].view(np.int32)[1])}
 
     def set_comm(self, comm) -> None:
         """A communicator of ``qc_comm_create`` (or None): GRADS | UPDATE in one call then all-reduces the flat
@@ -528,6 +570,12 @@ class FusedStep:
     def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
         if phases & L.QC_PHASE_SAMPLE:
             self.desc.sample_step += 1          # a fresh counter block per step
+        if self.adapt is not None:
+            L.check(self.eng.lib.qc_fused_pinn_adaptive_step(C.byref(self.desc), C.byref(self.data),
+                                                             C.byref(self.coef) if self.coef_mode else None,
+                                                             C.byref(self.adapt), phases, _stream(self.eng.device)),
+                    "qc_fused_pinn_adaptive_step")
+            return
         if self.coef_mode:
             L.check(self.eng.lib.qc_fused_pinn_coef_step(C.byref(self.desc), C.byref(self.data), C.byref(self.coef), phases,
                                                          _stream(self.eng.device)), "qc_fused_pinn_coef_step")

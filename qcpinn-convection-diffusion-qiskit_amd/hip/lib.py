@@ -30,12 +30,15 @@ EXPORTS = (
     "qc_pre_forward_map", "qc_pre_backward_map", "qc_program_set_angle_map",
     "qc_post_data", "qc_sample_dataset", "qc_fused_pinn_data_step",
     "qc_post_coef", "qc_sample_dataset_coef", "qc_fused_pinn_coef_step",
+    "qc_dataset_scores", "qc_adapt_bytes", "qc_adapt_build", "qc_sample_dataset_adaptive", "qc_fused_pinn_adaptive_step",
 )
 
 
 QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_PULSE = 0, 1, 2      # qc_pde.problem
 QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc_fused_pinn_data_step only
 QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 (qc_step_coef)
+QC_ADAPT_BLOCK = 1024            # rows per entry of the coarse table of an adaptive-sampling buffer (qc_adapt_bytes)
+QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
 QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
 
@@ -95,6 +98,11 @@ class QcStepData(C.Structure):
 class QcStepCoef(C.Structure):
     """qc_step_coef: the [7][B_res] operator rows of the current residual batch and the dataset's [N_res][7] table."""
     _fields_ = [("coef_res_dev", C.c_void_p), ("ds_coef", C.c_void_p)]
+
+
+class QcStepAdapt(C.Structure):
+    """qc_step_adapt: the buffer of qc_adapt_build ({64-byte record, cdf[n_rows], coarse[ceil(n_rows / 1024)]}) and its rows."""
+    _fields_ = [("adapt_dev", C.c_void_p), ("n_rows", C.c_int64)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -159,6 +167,14 @@ def load() -> C.CDLL:
     lib.qc_sample_dataset_coef.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, fp, C.POINTER(QcStepData),
                                            C.POINTER(QcStepCoef), C.c_uint64, C.c_uint64, vp]
     lib.qc_fused_pinn_coef_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef), i32, vp]
+    lib.qc_dataset_scores.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef), i64, i64, fp, vp]
+    lib.qc_adapt_bytes.restype = C.c_size_t
+    lib.qc_adapt_bytes.argtypes = [i64]
+    lib.qc_adapt_build.argtypes = [fp, i64, i32, C.c_float, vp, vp]
+    lib.qc_sample_dataset_adaptive.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, fp, C.POINTER(QcStepData),
+                                               C.POINTER(QcStepCoef), C.POINTER(QcStepAdapt), C.c_uint64, C.c_uint64, vp]
+    lib.qc_fused_pinn_adaptive_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef),
+                                                C.POINTER(QcStepAdapt), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]
@@ -166,7 +182,7 @@ def load() -> C.CDLL:
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qc_error_string", "qc_trig_bytes", "qc_circuit_workspace_bytes", "qc_circuit_workspace_bytes_batch",
-                        "qc_step_workspace_bytes"):
+                        "qc_step_workspace_bytes", "qc_adapt_bytes"):
             fn.restype = i32
     _lib = lib
     return lib

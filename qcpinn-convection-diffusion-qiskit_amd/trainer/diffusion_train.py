@@ -24,6 +24,12 @@ dataset, targets read from memory, residual with the zeroth-order term ``c_u u``
 loop on ``torch.randint`` minibatches of the same dataset and the same residual.  A dataset with a coefficient table
 (``dataset.coef_res``: one operator row per residual point, with a cubic term) takes ``qc_fused_pinn_coef_step`` in the
 same way; nothing else changes for the caller.
+
+``adaptive=`` (keyword-only, a ``data.tabulated.AdaptiveSampling``, with ``dataset=``) draws the residual batch from the
+dataset's residual rows with probability proportional to |res|^power / mean + floor instead of uniformly, the residual
+re-evaluated on all rows every ``every`` steps: on the device for a ``DVPDESolver`` (``qc_dataset_scores``,
+``qc_adapt_build``, ``qc_fused_pinn_adaptive_step``: still one call per iteration, no host read), with torch ops and
+``torch.searchsorted`` on the same integer weights for any other model.
 """
 from __future__ import annotations
 
@@ -82,7 +88,7 @@ class FusedTrainer:
 
     def __init__(self, model, batch_size: int, capacity: int, sampler: str = "device", *, n_bc: int = None,
                  bc_faces=1, pde: dict = None, n_ic: int = None, loss_weights=(2.0, 4.0, 2.0), max_norm=1.0,
-                 optimizer=None, scheduler=None, dataset=None):
+                 optimizer=None, scheduler=None, dataset=None, adaptive=None):
         """``n_bc`` / ``n_ic`` (default ``batch_size // 3`` each): GLOBAL boundary / initial points per step;
         ``bc_faces`` = 4 spreads the boundary points evenly over the faces x=0, x=1, y=0, y=1 (second workload,
         train_hybrid_qpinn.py:689-697), ``"random"`` puts each on a face drawn at random (trainer/train.py:118-135),
@@ -95,7 +101,10 @@ class FusedTrainer:
         ``pde={"problem": 3, ...}`` (optional "coeffs" = (c_t, c_x, c_y, d_xx, d_yy) and "c_u") is the tabulated step
         without a dataset: batches and targets come through ``load_batches(..., targets=)`` only.  A dataset with
         ``coef_res`` (or ``pde={"problem": 3, "coef": True, ...}`` without one) selects the coefficient step: one operator
-        row per residual point, gathered with the batch or given through ``load_batches(..., targets=, coef=)``."""
+        row per residual point, gathered with the batch or given through ``load_batches(..., targets=, coef=)``.
+        ``adaptive`` (an ``AdaptiveSampling``; needs ``dataset`` and the device sampler): residual rows are drawn in
+        proportion to their current residual, rescored on sampled step 0 and then every ``adaptive.every`` sampled steps inside ``step()``
+        (enqueued ahead of the step on its stream; every rank scores the whole dataset itself)."""
         # the fused step is the 3-D convection-diffusion step of trainer/diffusion_train.py:30-49 on a (t, x, y) -> u model;
         # the reference fails on any other shape (Linear(3, H) weight mismatch), and so does this trainer: a two-input
         # model keeps a zero-padded t column in W1 that the step would train, a K-output model has K last-layer rows
@@ -103,6 +112,7 @@ class FusedTrainer:
             raise ValueError("train() / FusedTrainer need classic_network = [3, H, 1] (got input_dim = %s, n_out = %s): the "
                              "convection-diffusion step takes (t, x, y) points and one output"
                              % (getattr(model, "input_dim", None), getattr(model, "n_out", None)))
+        _check_adaptive(adaptive, dataset, batch_size, sampler)
         dev = model._resolve_device(model.device)
         if dev is None or dev.type != "cuda":
             raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
@@ -154,6 +164,9 @@ class FusedTrainer:
                 if n_batch > 0 and n_rows == 0:
                     raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
             self.fs.set_dataset(self.dataset.segments(), self.dataset.coef_res)
+        self.adaptive, self._steps = adaptive, 0
+        if adaptive is not None:
+            self.fs.set_adaptive(adaptive.power, adaptive.floor)
         self.lo = {k: box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.span = {k: box(k, dev)[1:2] - box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.eng.refresh_gates()
@@ -332,8 +345,28 @@ class FusedTrainer:
             if self.B_res:
                 fs.coef_res[:, : self.B_res] = coef[s_rs].to(dev).t()
 
+    def dataset_scores(self):
+        """The fp32 scores |res_j - r_j| of the dataset's residual rows as of the last rescoring (a device tensor; its
+        mean is a held-out residual metric).  Adaptive sampling only."""
+        if self.adaptive is None:
+            raise ValueError("dataset_scores() needs adaptive= sampling")
+        return self.fs.scores
+
+    def adaptive_state(self):
+        """{"total", "q_sum", "add", "max_p", "shift"} of the current CDF (reads 64 bytes back)."""
+        if self.adaptive is None:
+            raise ValueError("adaptive_state() needs adaptive= sampling")
+        return self.fs.adaptive_state()
+
     def step(self):
         draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
+        if self.adaptive is not None:
+            # scores of all residual rows and their CDF, enqueued ahead of the step on its stream: nothing is read back
+            # (steps on explicit batches draw nothing and do not count towards the cadence)
+            if draw:
+                if self._steps % self.adaptive.every == 0:
+                    self.fs.rescore()
+                self._steps += 1
         if self.world == 1 or self._comm is not None:
             self.fs.run(draw | _lib.QC_PHASE_GRADS | _lib.QC_PHASE_UPDATE)
         else:
@@ -347,9 +380,23 @@ class FusedTrainer:
         return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
 
 
-def _train_fused(model, batch_size, batches=None, dataset=None):
+def _check_adaptive(adaptive, dataset, batch_size, sampler="device"):
+    """The argument errors of ``adaptive=``, the same for the fused and the generic loop."""
+    if adaptive is None:
+        return
+    if not hasattr(adaptive, "power") or not hasattr(adaptive, "floor") or not hasattr(adaptive, "every"):
+        raise ValueError("adaptive= must be a data.tabulated.AdaptiveSampling")
+    if dataset is None:
+        raise ValueError("adaptive= samples the residual rows of a dataset: give dataset= too")
+    if dataset.sizes()[0] == 0 or batch_size <= 0:
+        raise ValueError("adaptive= needs residual points: the dataset's residual segment (or the residual batch) is empty")
+    if sampler == "torch":
+        raise ValueError("adaptive= draws on the device: it cannot be combined with sampler='torch'")
+
+
+def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None):
     steps = model.epochs + 1
-    tr = FusedTrainer(model, batch_size, capacity=steps, dataset=dataset)
+    tr = FusedTrainer(model, batch_size, capacity=steps, dataset=dataset, adaptive=adaptive)
     t0 = time.time()
     model.logger.print(f"Starting training for {model.epochs} epochs...")
     model.logger.print(f"Batch size: {batch_size}")
@@ -389,9 +436,16 @@ class _RowSampler:
     def __init__(self, X, y, coef=None):
         self.X, self.y, self.coef = X, y.reshape(-1, 1), coef
         self.rows = None        # the coefficient rows of the last minibatch (residual segment of a coefficient dataset)
+        self.cdf = None         # adaptive sampling: the (N,) int64 CDF of the rows' integer weights
+        self.idx = None         # the rows of the last minibatch
 
     def sample(self, N):
-        idx = torch.randint(0, self.X.shape[0], (N,))
+        if self.cdf is not None:      # row min{j : cdf_j > t}, t uniform in [0, cdf[-1])
+            t = torch.randint(0, int(self.cdf[-1]), (N,))
+            idx = torch.searchsorted(self.cdf, t.to(self.cdf.device), right=True).to(self.X.device)
+        else:
+            idx = torch.randint(0, self.X.shape[0], (N,))
+        self.idx = idx
         if self.coef is not None:
             self.rows = self.coef[idx]
         return self.X[idx], self.y[idx]
@@ -416,9 +470,27 @@ def tabulated_operator(model, t, x, y, coeffs, c_u, coef=None):
     return uu, res
 
 
-def _train_generic(model, batch_size, dataset=None):
+def _rescore_generic(model, dataset, res, adaptive, chunk=65536):
+    """Scores |res_j - r_j| of all residual rows of ``dataset`` by torch autograd (no gradient reaches the parameters) and
+    the integer CDF of qc_adapt_build on them, left in ``res.cdf``."""
+    from ..data.tabulated import adaptive_cdf
+    out = []
+    for k in range(0, dataset.X_res.shape[0], chunk):
+        X = dataset.X_res[k:k + chunk]
+        rows = None if dataset.coef_res is None else dataset.coef_res[k:k + chunk]
+        with torch.enable_grad():
+            _, pr = tabulated_operator(model, X[:, 0:1].clone(), X[:, 1:2].clone(), X[:, 2:3].clone(), dataset.coeffs,
+                                       dataset.c_u, rows)
+        out.append((pr.detach().reshape(-1) - dataset.r[k:k + chunk]).abs().float())
+    res.scores = torch.cat(out)
+    res.cdf = adaptive_cdf(res.scores, adaptive.power, adaptive.floor)
+
+
+def _train_generic(model, batch_size, dataset=None, adaptive=None):
     """The reference algorithm for any duck-typed model, on torch autograd.  With ``dataset``: the same loop on
-    torch.randint minibatches of its segments (IC -> BC -> residual) and its operator."""
+    torch.randint minibatches of its segments (IC -> BC -> residual) and its operator; with ``adaptive`` the residual
+    rows are drawn from the CDF of their residuals, rescored every ``adaptive.every`` iterations."""
+    _check_adaptive(adaptive, dataset, batch_size)
     dev = model.device
     if dataset is not None:
         dataset = dataset.to(dev if dev is not None else "cpu")
@@ -438,6 +510,8 @@ def _train_generic(model, batch_size, dataset=None):
     fwd_times = []
     for it in range(model.epochs + 1):
         t_it = time.time()
+        if adaptive is not None and it % adaptive.every == 0:
+            _rescore_generic(model, dataset, res, adaptive)
         if model.optimizer is not None:
             model.optimizer.zero_grad()
         X_ic, u_ic = fetch_minibatch(ics, batch_size // 3)
@@ -470,14 +544,16 @@ def _train_generic(model, batch_size, dataset=None):
     model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
 
 
-def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None):
+def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None,
+          adaptive=None):
     """``batches`` (keyword-only, not in the reference): a per-iteration list of
     ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests; with a dataset each entry carries a
     fourth element, the targets ``(u_ic, u_bc, r_res)``.  ``dataset`` (keyword-only): a ``TabulatedProblem`` whose targets
-    and operator replace the analytic problem (module docstring)."""
+    and operator replace the analytic problem (module docstring).  ``adaptive`` (keyword-only): an ``AdaptiveSampling``
+    for the residual rows of ``dataset`` (module docstring)."""
     if hasattr(model, "_engine_for") and hasattr(model, "quantum_layer"):
-        _train_fused(model, batch_size, batches, dataset)
+        _train_fused(model, batch_size, batches, dataset, adaptive)
     else:
         if batches is not None:
             raise ValueError("explicit batches are only supported for DVPDESolver models")
-        _train_generic(model, batch_size, dataset)
+        _train_generic(model, batch_size, dataset, adaptive)
