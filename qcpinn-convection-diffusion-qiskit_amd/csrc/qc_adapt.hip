@@ -1,5 +1,5 @@
 // Residual-adaptive sampling of the dataset's residual rows (RAD: Wu et al. 2023; RAR: Lu et al. 2021): the score of a
-// row from the six channels of u, and scores -> the integer CDF that k_sample_dataset_adaptive (qc_sample.hip) searches.
+// row from the six channels of u, and scores -> the integer CDF that the CDF rules of k_gather (qc_sample.hip) search.
 // The definitions are those of include/qcpinn_hip.h (qc_dataset_scores, qc_adapt_build); tests/adaptive_reference.py
 // restates them in numpy.  Everything behind the fp32 power is integer arithmetic, so no result depends on the order of a
 // reduction.  The scan is three launches (block totals, scan of the totals, per-block scan plus offset): no block ever

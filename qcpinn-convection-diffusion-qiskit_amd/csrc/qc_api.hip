@@ -13,6 +13,7 @@ static_assert(sizeof(QcPde) == sizeof(qc_pde), "qc_pde layout");
 static_assert(QC_PB_CONVECTION_DIFFUSION == QC_PROBLEM_CONVECTION_DIFFUSION && QC_PB_PURE_DIFFUSION == QC_PROBLEM_PURE_DIFFUSION &&
               QC_PB_GAUSSIAN_PULSE == QC_PROBLEM_GAUSSIAN_PULSE && QC_PB_TABULATED == QC_PROBLEM_TABULATED, "problem ids");
 static_assert(QC_COEF_N == QC_COEF_COLS, "coefficient columns");
+static_assert(QC_FACE_RANDOM == QC_BC_RANDOM_FACE, "boundary rule");
 static_assert(sizeof(QcOptHyper) == sizeof(qc_opt_hyper), "qc_opt_hyper layout");
 
 static thread_local int g_last_hip = 0;
@@ -228,24 +229,6 @@ int qc_program_set_encoding(qc_program* p, int amplitude) {
 
 static bool angle_map_ok(int m) { return m == QC_ANGLE_MAP_NONE || m == QC_ANGLE_MAP_TANH_PI; }
 static bool problem_ok(int pb) { return pb >= QC_PROBLEM_CONVECTION_DIFFUSION && pb <= QC_PROBLEM_GAUSSIAN_PULSE; }
-// what the fused step's analytic targets and boundary draw accept (both step entry points check it, so the merged and
-// the two-stream forms refuse the same descriptors)
-static bool step_desc_ok(const qc_step_desc* d) {
-  return problem_ok(d->pde.problem) && d->sample_bc_face_points >= QC_BC_RANDOM_FACE;
-}
-// what the tabulated step needs of its descriptor pair (the problem id is QcTarget::ok's): a target buffer behind every
-// non-empty batch, and under QC_PHASE_SAMPLE a dataset segment (1 <= rows < 2^31) behind every non-empty batch
-static bool dataset_seg_ok(int64_t n_batch, const float* X, const float* tg, int64_t n) {
-  return n_batch <= 0 || (X && tg && n >= 1 && n < ((int64_t)1 << 31));
-}
-static bool step_data_ok(const qc_step_desc* d, const qc_step_data* t, int phases) {
-  if (!t || d->n_ic < 0 || d->n_ic > d->B_val) return false;
-  if ((d->B_res > 0 && !t->target_res_dev) || (d->B_val > 0 && !t->target_val_dev)) return false;
-  if (!(phases & QC_PHASE_SAMPLE)) return true;
-  return dataset_seg_ok(d->B_res, t->ds_X_res, t->ds_r, t->ds_n_res) && dataset_seg_ok(d->n_ic, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic) &&
-         dataset_seg_ok(d->B_val - d->n_ic, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc);
-}
-
 int qc_program_set_angle_map(qc_program* p, int angle_map) {
   if (!p || !angle_map_ok(angle_map)) return QC_ERR_ARG;
   p->angle_map = angle_map;
@@ -570,14 +553,42 @@ int qc_adam_step(float* flat, int NP, float* prm, float* m, float* v, void* stat
   return after_launch();
 }
 
+// The one place that fills batches: the source's rule, the launch its kind selects, the launch status
+static int fill_batches(const QcBatches& b, const QcSource& s, void* stream) {
+  if (!s.ok(b)) return QC_ERR_ARG;
+  if (s.kind == QC_SOURCE_DRAW) qc_sample_launch(b, s.face_pts, (hipStream_t)stream);
+  else qc_gather_launch(b, s, (hipStream_t)stream);
+  return after_launch();
+}
+// Source of a step or of a gather from the optional records of the public header: no data: the coordinate draw; data:
+// its dataset's rows, with `cf` the operator rows as well (into coef_res), with `ad` the residual rows from its CDF
+// (the caller's buffer {64-byte record, cdf[n_rows], coarse[ceil(n_rows / QC_ADAPT_BLOCK)]})
+static QcSource make_source(const qc_step_data* t, const qc_step_coef* cf, float* coef_res, const qc_step_adapt* ad,
+                            int64_t face_pts = 0) {
+  QcSource s;
+  s.face_pts = face_pts;
+  if (!t) return s;
+  s.kind = QC_SOURCE_ROWS;
+  s.res = {t->ds_X_res, t->ds_r, t->ds_n_res};
+  s.ic = {t->ds_X_ic, t->ds_u_ic, t->ds_n_ic};
+  s.bc = {t->ds_X_bc, t->ds_u_bc, t->ds_n_bc};
+  if (cf) { s.table = true; s.coef_res = coef_res; s.ds_coef = cf->ds_coef; }
+  if (ad) {
+    s.kind = QC_SOURCE_CDF;
+    s.cdf_rows = ad->n_rows;
+    if (ad->adapt_dev) {
+      s.cdf = (const uint64_t*)((const char*)ad->adapt_dev + sizeof(QcAdaptRec));
+      s.coarse = s.cdf + ad->n_rows;
+    }
+  }
+  return s;
+}
+
 int qc_sample_collocation_faces(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
                                 int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step,
                                 void* stream) {
-  if (n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0 || bc_face_points < QC_BC_RANDOM_FACE)
-    return QC_ERR_ARG;
-  if ((n_res > 0 && !X_res) || (n_ic + n_bc > 0 && !X_val)) return QC_ERR_ARG;
-  qc_sample_launch(X_res, n_res, off_res, X_val, n_ic, off_ic, n_bc, off_bc, bc_face_points, seed, step, (hipStream_t)stream);
-  return after_launch();
+  return fill_batches({X_res, nullptr, n_res, off_res, X_val, nullptr, n_ic, off_ic, n_bc, off_bc, seed, step},
+                      make_source(nullptr, nullptr, nullptr, nullptr, bc_face_points), stream);
 }
 
 int qc_sample_collocation(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
@@ -585,14 +596,7 @@ int qc_sample_collocation(float* X_res, int64_t n_res, int64_t off_res, float* X
   return qc_sample_collocation_faces(X_res, n_res, off_res, X_val, n_ic, off_ic, n_bc, off_bc, 0, seed, step, stream);
 }
 
-// ---- residual-adaptive sampling: the caller's buffer {64-byte record, cdf[n_rows], coarse[ceil(n_rows / QC_ADAPT_BLOCK)]}
-static const uint64_t* adapt_cdf(const qc_step_adapt* ad) { return (const uint64_t*)((const char*)ad->adapt_dev + sizeof(QcAdaptRec)); }
-// a buffer (8-byte aligned) over exactly the rows of the dataset's residual segment
-static bool adapt_ok(const qc_step_adapt* ad, const qc_step_data* t) {
-  return ad && t && ad->adapt_dev && ((uintptr_t)ad->adapt_dev & 7) == 0 && ad->n_rows >= 1 && ad->n_rows < ((int64_t)1 << 31) &&
-         ad->n_rows == t->ds_n_res;
-}
-
+// ---- residual-adaptive sampling
 size_t qc_adapt_bytes(int64_t n_rows) {
   if (n_rows < 1 || n_rows >= ((int64_t)1 << 31)) return 0;
   return sizeof(QcAdaptRec) + sizeof(uint64_t) * ((size_t)n_rows + (size_t)((n_rows + QC_ADAPT_BLOCK - 1) / QC_ADAPT_BLOCK));
@@ -605,56 +609,30 @@ int qc_adapt_build(const float* score, int64_t n_rows, int power, float floor_c,
   return rc ? hip_fail(hipGetLastError()) : after_launch();
 }
 
-// the gather behind both exports: rows and targets of the three batches, and with a table (ds_coef -> coef_res) the
-// residual rows' operator coefficients; the plain form is the coefficient form with no table
-static int sample_dataset_impl(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
-                               int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const float* ds_coef,
-                               const qc_step_data* t, uint64_t seed, uint64_t step, void* stream,
-                               const qc_step_adapt* ad = nullptr) {
-  if (n_res < 0 || n_ic < 0 || n_bc < 0 || off_res < 0 || off_ic < 0 || off_bc < 0) return QC_ERR_ARG;
-  if (ad && !adapt_ok(ad, t)) return QC_ERR_ARG;
-  if ((n_res > 0 && (!X_res || !target_res)) || (n_ic + n_bc > 0 && (!X_val || !target_val))) return QC_ERR_ARG;
-  if (!dataset_seg_ok(n_res, t->ds_X_res, t->ds_r, t->ds_n_res) || !dataset_seg_ok(n_ic, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic) ||
-      !dataset_seg_ok(n_bc, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc)) return QC_ERR_ARG;
-  if (ad) {   // residual rows from the CDF; the value rows as below
-    const uint64_t* cdf = adapt_cdf(ad);
-    qc_sample_dataset_adaptive_launch(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
-                                      t->ds_X_res, t->ds_r, t->ds_n_res, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic, t->ds_X_bc,
-                                      t->ds_u_bc, t->ds_n_bc, seed, step, (hipStream_t)stream, coef_res, ds_coef, cdf,
-                                      cdf + ad->n_rows);
-    return after_launch();
-  }
-  qc_sample_dataset_launch(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, t->ds_X_res,
-                           t->ds_r, t->ds_n_res, t->ds_X_ic, t->ds_u_ic, t->ds_n_ic, t->ds_X_bc, t->ds_u_bc, t->ds_n_bc, seed,
-                           step, (hipStream_t)stream, coef_res, ds_coef);
-  return after_launch();
-}
-
+// the three gathers: rows and targets of the three batches; with a table the residual rows' operator coefficients as
+// well (coef_res and ds_coef may be NULL only with n_res = 0); with a CDF the residual rows drawn from it
 int qc_sample_dataset(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
                       int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const qc_step_data* t, uint64_t seed,
                       uint64_t step, void* stream) {
   if (!t) return QC_ERR_ARG;
-  return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, nullptr, nullptr,
-                             t, seed, step, stream);
+  return fill_batches({X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, seed, step},
+                      make_source(t, nullptr, nullptr, nullptr), stream);
 }
 
 int qc_sample_dataset_coef(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
                            int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const qc_step_data* t,
                            const qc_step_coef* cf, uint64_t seed, uint64_t step, void* stream) {
-  if (!t || !cf || (n_res > 0 && (!coef_res || !cf->ds_coef))) return QC_ERR_ARG;
-  // (n_res = 0 with null coefficient pointers: the plain gather, no residual rows to copy)
-  return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
-                             n_res > 0 ? coef_res : nullptr, n_res > 0 ? cf->ds_coef : nullptr, t, seed, step, stream);
+  if (!t || !cf) return QC_ERR_ARG;
+  return fill_batches({X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, seed, step},
+                      make_source(t, cf, coef_res, nullptr), stream);
 }
 
 int qc_sample_dataset_adaptive(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
                                int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const qc_step_data* t,
                                const qc_step_coef* cf, const qc_step_adapt* ad, uint64_t seed, uint64_t step, void* stream) {
-  if (!t || !ad) return QC_ERR_ARG;
-  const bool table = cf && n_res > 0;   // without a table (cf NULL): rows and targets only
-  if (table && (!coef_res || !cf->ds_coef)) return QC_ERR_ARG;
-  return sample_dataset_impl(X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc,
-                             table ? coef_res : nullptr, table ? cf->ds_coef : nullptr, t, seed, step, stream, ad);
+  if (!t || !ad) return QC_ERR_ARG;   // without a table (cf NULL): rows and targets only
+  return fill_batches({X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, seed, step},
+                      make_source(t, cf, coef_res, ad), stream);
 }
 
 // ---- merged residual + value stages of the fused step (register family, angle encoding)
@@ -664,6 +642,31 @@ static bool merged_ok(const qc_step_desc* d) {
          d->circ_ws_dev && d->circ_ws_bytes >= qc_family_reg.store_bytes(d->prog, 6, d->B_res) && d->X_res_dev && d->ajets_res_dev &&
          d->qjets_res_dev && d->qbar_res_dev && d->abar_res_dev && d->X_val_dev && d->ajets_val_dev && d->qjets_val_dev &&
          d->qbar_val_dev && d->abar_val_dev;
+}
+
+// the step's batches as the sampler sees them (targets: those of `t`, or none)
+static QcBatches step_batches(const qc_step_desc* d, const qc_step_data* t) {
+  return {(float*)d->X_res_dev, t ? t->target_res_dev : nullptr, d->B_res, d->sample_off_res,
+          (float*)d->X_val_dev, t ? t->target_val_dev : nullptr, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
+          d->sample_seed, d->sample_step};
+}
+
+// What fused_step, qc_fused_step_stage and qc_dataset_scores ask of a descriptor (non-null) before anything else of
+// theirs that can coincide with it, in the order all three had it, so every refusal keeps its code: program and core
+// buffers, n / n_theta, [umat behind U4 gates,] [`supported`: what the caller needs of the kernel family,] the network's
+// shape, and with amplitude encoding the step workspace
+static int check_step_desc(const qc_step_desc* d, bool need_umat, bool (*supported)(const qc_step_desc*)) {
+  if (!d->prog || !d->trig_dev || !d->params_dev) return QC_ERR_ARG;
+  if (d->prog->n_qubits != d->n || d->prog->n_params != d->n_theta) return QC_ERR_ARG;
+  if (need_umat && d->prog->n_u4 > 0 && !d->umat_dev) return QC_ERR_ARG;
+  if (supported && !supported(d)) return QC_ERR_UNSUPPORTED;
+  const int rc = check_mlp(d->H, d->n, d->n_theta, d->B_res > 0 ? d->B_res : 1, 6);
+  if (rc) return rc;
+  // amplitude encoding: the circuit kernels run on the initial-amplitude jets u(a) and return cotangents w.r.t. them,
+  // both kept in the step workspace
+  if (d->prog->amplitude && (!d->circ_ws_dev || d->circ_ws_bytes < qc_step_workspace_bytes(d->prog, d->B_res, d->B_val)))
+    return QC_ERR_ARG;
+  return QC_OK;
 }
 
 static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool draw, const QcTarget& tg) {
@@ -676,10 +679,8 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
   memcpy(&pde, &d->pde, sizeof(pde));
   switch (stage) {
     case QC_STAGE_PRE_FWD:
-      return qc_mlp_pre_fwd_both((float*)d->X_res_dev, (float*)d->X_val_dev, prm, L, d->ajets_res_dev, d->ajets_val_dev,
-                                 d->B_res, d->B_val, draw ? 1 : 0, d->n_ic, d->sample_off_res, d->sample_off_ic,
-                                 d->sample_off_bc, d->sample_bc_face_points, d->sample_seed, d->sample_step, st,
-                                 d->prog->angle_map);
+      return qc_mlp_pre_fwd_both(step_batches(d, nullptr), draw ? 1 : 0, d->sample_bc_face_points, prm, L, d->ajets_res_dev,
+                                 d->ajets_val_dev, st, d->prog->angle_map);
     case QC_STAGE_CIRCUIT_FWD:
       return qc_reg_circ_fwd_both(d->prog, trig, d->umat_dev, d->ajets_res_dev, d->qjets_res_dev, d->B_res, chi_store,
                                   d->ajets_val_dev, d->qjets_val_dev, d->B_val, st);
@@ -703,11 +704,10 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
 }
 
 int qc_fused_step_stage(const qc_step_desc* d, int stage, void* stream) {
-  if (!d || !d->prog || !d->trig_dev || !d->params_dev || !d->part_dev) return QC_ERR_ARG;
-  if (d->prog->n_qubits != d->n || d->prog->n_params != d->n_theta) return QC_ERR_ARG;
-  if (stage < 0 || stage >= QC_STAGE_COUNT || !step_desc_ok(d)) return QC_ERR_ARG;
-  if (!merged_ok(d)) return QC_ERR_UNSUPPORTED;
-  int rc = check_mlp(d->H, d->n, d->n_theta, d->B_res, 6);
+  if (!d || !d->part_dev || stage < 0 || stage >= QC_STAGE_COUNT) return QC_ERR_ARG;
+  // analytic targets and the coordinate draw only, like qc_fused_pinn_residual_step
+  if (!problem_ok(d->pde.problem) || d->sample_bc_face_points < QC_BC_RANDOM_FACE) return QC_ERR_ARG;
+  int rc = check_step_desc(d, false, merged_ok);
   if (rc) return rc;
   if ((rc = merged_stage(d, stage, (hipStream_t)stream, false, QcTarget{}))) return rc;
   return after_launch();
@@ -723,7 +723,17 @@ struct QcPipe {
   QcCircStore store;
 };
 
-// pre -> [amplitudes] -> circuit -> post -> circuit adjoint -> [amplitude adjoint] -> pre adjoint, on one stream
+// the forward half of a pipeline: pre network -> [amplitudes] -> circuit, and the launch status
+static int pipe_forward(const qc_step_desc* d, const QcPipe& q, hipStream_t st) {
+  const qc_program* p = d->prog;
+  int rc;
+  if ((rc = qc_pre_forward_map(q.X, d->params_dev, d->H, d->n, d->n_theta, p->angle_map, q.ajets, q.B, q.nch, st))) return rc;
+  if (q.u && (rc = qc_amp_forward(q.ajets, q.u, d->n, q.B, q.nch, st))) return rc;
+  rc = p->fam->fwd(p, (const QcTrig*)d->trig_dev, d->umat_dev, q.u ? q.u : q.ajets, q.qjets, q.B, q.nch, q.store, st);
+  return rc ? rc : after_launch();
+}
+
+// forward half -> post -> circuit adjoint -> [amplitude adjoint] -> pre adjoint, on one stream
 static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, const QcTarget& tg) {
   const qc_program* p = d->prog;
   const int n = d->n, H = d->H;
@@ -731,11 +741,9 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
   float* part_theta = d->part_dev + make_layout(H, n, d->n_theta).oTh;
   if (!q.X || !q.ajets || !q.qjets || !q.qbar || !q.abar || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
   int rc;
-  if ((rc = qc_pre_forward_map(q.X, d->params_dev, H, n, d->n_theta, p->angle_map, q.ajets, q.B, q.nch, st))) return rc;
-  if (q.u && (rc = qc_amp_forward(q.ajets, q.u, n, q.B, q.nch, st))) return rc;
+  if ((rc = pipe_forward(d, q, st))) return rc;
   const float* cin = q.u ? q.u : q.ajets;
   float* cout = q.u ? q.ub : q.abar;
-  if ((rc = p->fam->fwd(p, trig, d->umat_dev, cin, q.qjets, q.B, q.nch, q.store, st)) || (rc = after_launch())) return rc;
   // abar is written only by the adjoint sweep below: its head serves as per-point cotangent scratch here
   if ((rc = post_impl(2, q.X, d->params_dev, H, n, d->n_theta, &d->pde, q.qjets, q.abar, q.nch == 6 ? q.abar + q.B : nullptr,
                       nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tg))) return rc;
@@ -746,54 +754,28 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
                              q.row0, q.B, q.nch, st);
 }
 
-// The step behind both step entry points.  `data` = null: qc_fused_pinn_residual_step (analytic targets, coordinate
-// draw).  Otherwise qc_fused_pinn_data_step: the targets of both batches come from `data`, and QC_PHASE_SAMPLE gathers
-// rows and targets from its resident dataset AHEAD of the stages, in the merged form too (the merged pre stage then runs
-// with its own draw off, so its instantiations are the analytic step's).  With `cf` too, qc_fused_pinn_coef_step: the
-// residual points' operator rows come from cf->coef_res_dev, gathered with the rows and targets under QC_PHASE_SAMPLE.
-// With `ad`, qc_fused_pinn_adaptive_step: that gather draws its residual rows from the CDF; nothing else differs.
-static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phases, void* stream,
-                      const qc_step_coef* cf = nullptr, const qc_step_adapt* ad = nullptr) {
-  if (!d) return QC_ERR_ARG;
-  if (ad && (d->B_res <= 0 || !adapt_ok(ad, data))) return QC_ERR_ARG;
-  const bool tabulated = data != nullptr;
-  const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
-  if (table && (!cf->coef_res_dev || ((phases & QC_PHASE_SAMPLE) && !cf->ds_coef))) return QC_ERR_ARG;
-  if (!(tabulated ? step_data_ok(d, data, phases) && d->sample_bc_face_points >= QC_BC_RANDOM_FACE : step_desc_ok(d)))
-    return QC_ERR_ARG;
-  if (!d->prog || !d->trig_dev || !d->params_dev || !d->part_dev || !d->flat_dev) return QC_ERR_ARG;
-  const int n = d->n, H = d->H;
-  if (d->prog->n_qubits != n || d->prog->n_params != d->n_theta) return QC_ERR_ARG;
-  const QcTarget tg = !tabulated ? QcTarget{}
-                      : table    ? QcTarget::with_coef(data->target_res_dev, data->target_val_dev, cf->coef_res_dev)
-                                 : QcTarget::tabulated(data->target_res_dev, data->target_val_dev, data->c_u);
-  if (!tg.ok(2, 6, d->pde.problem)) return QC_ERR_ARG;
-  int rc = check_mlp(H, n, d->n_theta, d->B_res > 0 ? d->B_res : 1, 6);
+// The step behind the four step entry points, which differ in `tg`, where the post stage takes its targets and its
+// operator from, and in `src`, where QC_PHASE_SAMPLE takes the batches `b` from.  The dataset kinds gather rows and targets
+// (and operator rows) AHEAD of the stages, in the merged form too (the merged pre stage then runs with its own draw off,
+// so its instantiations are the analytic step's); nothing else in the step depends on the source.
+static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches& b, const QcSource& src, int phases,
+                      void* stream) {
+  if (!d->part_dev || !d->flat_dev || !src.holds(b)) return QC_ERR_ARG;
+  if ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem)) return QC_ERR_ARG;
+  int rc = check_step_desc(d, false, nullptr);
   if (rc) return rc;
+  const int n = d->n, H = d->H;
   const QcLayout L = make_layout(H, n, d->n_theta);
   const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
   const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
   const int64_t rows = rows_res + rows_val;
   if (rows <= 0 || rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  // amplitude encoding: the circuit kernels run on the initial-amplitude jets u(a) and return cotangents w.r.t. them,
-  // both kept in the step workspace
-  if (d->prog->amplitude && (!d->circ_ws_dev || d->circ_ws_bytes < qc_step_workspace_bytes(d->prog, d->B_res, d->B_val)))
-    return QC_ERR_ARG;
   const QcStepLayout ws = step_layout(d->prog, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
 
   // (in the merged form below the first stage draws the points itself)
-  const bool draw_in_stage = !tabulated && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);
-  if (tabulated && (phases & QC_PHASE_SAMPLE)) {   // dataset gather, with or without the table
-    if ((rc = sample_dataset_impl((float*)d->X_res_dev, data->target_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev,
-                                  data->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
-                                  table ? cf->coef_res_dev : nullptr, table ? cf->ds_coef : nullptr, data, d->sample_seed,
-                                  d->sample_step, st, ad))) return rc;
-  } else if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage) {   // coordinate draw
-    if ((rc = qc_sample_collocation_faces((float*)d->X_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev, d->n_ic,
-                                          d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc,
-                                          d->sample_bc_face_points, d->sample_seed, d->sample_step, st))) return rc;
-  }
+  const bool draw_in_stage = src.kind == QC_SOURCE_DRAW && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);
+  if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage && (rc = fill_batches(b, src, st))) return rc;
   // register family, angle encoding, both pipelines present, final-state store available: every stage is ONE launch
   // over the value tiles and the residual tiles together (no side stream, 9 launches per step); QC_NO_MERGE=1 keeps
   // the two-stream form below
@@ -851,61 +833,65 @@ static int fused_step(const qc_step_desc* d, const qc_step_data* data, int phase
   return QC_OK;
 }
 
+// the four entry points: targets, batches and source from the records each was given (the kind of step is decided here)
+static int step_from(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_adapt* ad, int phases,
+                     void* stream) {
+  if (!d) return QC_ERR_ARG;
+  const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
+  const QcTarget tg = !t      ? QcTarget{}
+                      : table ? QcTarget::with_coef(t->target_res_dev, t->target_val_dev, cf->coef_res_dev)
+                              : QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u);
+  return fused_step(d, tg, step_batches(d, t), make_source(t, cf, cf ? cf->coef_res_dev : nullptr, ad, d->sample_bc_face_points),
+                    phases, stream);
+}
+
 int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream) {
-  return fused_step(d, nullptr, phases, stream);
+  return step_from(d, nullptr, nullptr, nullptr, phases, stream);
 }
 
 int qc_fused_pinn_data_step(const qc_step_desc* d, const qc_step_data* data, int phases, void* stream) {
   if (!data) return QC_ERR_ARG;
-  return fused_step(d, data, phases, stream);
+  return step_from(d, data, nullptr, nullptr, phases, stream);
 }
 
 int qc_fused_pinn_coef_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef, int phases,
                             void* stream) {
   if (!data || !coef) return QC_ERR_ARG;
-  return fused_step(d, data, phases, stream, coef);
+  return step_from(d, data, coef, nullptr, phases, stream);
 }
 
 int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef,
                                 const qc_step_adapt* adapt, int phases, void* stream) {
-  if (!data || !adapt) return QC_ERR_ARG;
-  return fused_step(d, data, phases, stream, coef, adapt);
+  if (!d || !data || !adapt || d->B_res <= 0) return QC_ERR_ARG;
+  return step_from(d, data, coef, adapt, phases, stream);
 }
 
-// Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pre network,
-// [amplitudes,] circuit, qc_post mode 4) over chunks of at most B_res rows through the step's residual scratch, then
-// |res - r| per row.  Between steps those buffers hold nothing that is read again.
+// Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pipe_forward, then
+// qc_post mode 4) over chunks of at most B_res rows through the step's residual scratch, then |res - r| per row.  Between
+// steps those buffers hold nothing that is read again.
 int qc_dataset_scores(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, int64_t row0, int64_t rows,
                       float* score, void* stream) {
   if (!d || !t || !score || d->B_res <= 0) return QC_ERR_ARG;
-  if (!t->ds_X_res || !t->ds_r || t->ds_n_res < 1 || t->ds_n_res >= ((int64_t)1 << 31)) return QC_ERR_ARG;
+  if (!QcDsSeg{t->ds_X_res, t->ds_r, t->ds_n_res}.serves(1)) return QC_ERR_ARG;
   if (row0 < 0 || rows < 1 || row0 > t->ds_n_res || rows > t->ds_n_res - row0) return QC_ERR_ARG;
   if (cf && !cf->ds_coef) return QC_ERR_ARG;
   if (d->pde.problem != QC_PROBLEM_TABULATED) return QC_ERR_ARG;
-  if (!d->prog || !d->trig_dev || !d->params_dev || !d->ajets_res_dev || !d->qjets_res_dev || !d->qbar_res_dev) return QC_ERR_ARG;
-  const qc_program* p = d->prog;
-  const int n = d->n, H = d->H;
-  if (p->n_qubits != n || p->n_params != d->n_theta || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
-  if (!p->fam) return QC_ERR_UNSUPPORTED;
-  int rc = check_mlp(H, n, d->n_theta, d->B_res, 6);
+  if (!d->ajets_res_dev || !d->qjets_res_dev || !d->qbar_res_dev) return QC_ERR_ARG;
+  int rc = check_step_desc(d, true, [](const qc_step_desc* e) { return e->prog->fam != nullptr; });
   if (rc) return rc;
-  if (p->amplitude && (!d->circ_ws_dev || d->circ_ws_bytes < qc_step_workspace_bytes(p, d->B_res, d->B_val))) return QC_ERR_ARG;
-  const QcStepLayout ws = step_layout(p, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
+  const QcStepLayout ws = step_layout(d->prog, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
   if (!ws.fits) return QC_ERR_ARG;
-  // forward only: nothing is kept.  The HBM family runs a chunk in as many groups of tiles as its scratch holds (a
-  // forward tile is never larger than the forward-and-adjoint tile the step sized it for), so no chunk needs shrinking
-  const QcCircStore store = {ws.res.p, ws.res.bytes, false};
   hipStream_t st = (hipStream_t)stream;
   const QcPde pde = to_pde(&d->pde);
   float* uj = d->qbar_res_dev;   // [6][c]
   for (int64_t r = row0; r < row0 + rows; r += d->B_res) {
     const int64_t c = row0 + rows - r < d->B_res ? row0 + rows - r : d->B_res;
-    const float* X = t->ds_X_res + 3 * r;
-    if ((rc = qc_pre_forward_map(X, d->params_dev, H, n, d->n_theta, p->angle_map, d->ajets_res_dev, c, 6, st))) return rc;
-    if (ws.u_res && (rc = qc_amp_forward(d->ajets_res_dev, ws.u_res, n, c, 6, st))) return rc;
-    if ((rc = p->fam->fwd(p, (const QcTrig*)d->trig_dev, d->umat_dev, ws.u_res ? ws.u_res : d->ajets_res_dev, d->qjets_res_dev, c,
-                          6, store, st)) || (rc = after_launch())) return rc;
-    if ((rc = post_impl(4, X, d->params_dev, H, n, d->n_theta, &d->pde, d->qjets_res_dev, uj, nullptr, nullptr, nullptr, nullptr,
+    // forward only: nothing is kept.  The HBM family runs a chunk in as many groups of tiles as its scratch holds (a
+    // forward tile is never larger than the forward-and-adjoint tile the step sized it for), so no chunk needs shrinking
+    const QcPipe q = {t->ds_X_res + 3 * r, d->ajets_res_dev, d->qjets_res_dev, nullptr, nullptr, ws.u_res, nullptr, c, 0, 6,
+                      {ws.res.p, ws.res.bytes, false}};
+    if ((rc = pipe_forward(d, q, st))) return rc;
+    if ((rc = post_impl(4, q.X, d->params_dev, d->H, d->n, d->n_theta, &d->pde, q.qjets, uj, nullptr, nullptr, nullptr, nullptr,
                         nullptr, 0, 0, c, 6, st, QcTarget{}))) return rc;
     qc_adapt_score_launch(uj, c, pde, t->c_u, cf ? cf->ds_coef + (size_t)QC_COEF_N * r : nullptr, t->ds_r + r, score + r, st);
     if ((rc = after_launch())) return rc;

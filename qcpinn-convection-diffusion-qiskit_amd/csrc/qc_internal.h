@@ -67,7 +67,65 @@ struct QcTarget {
   }
 };
 
-// Residual-adaptive sampling (qc_adapt.hip, k_sample_dataset_adaptive): the caller's buffer holds this record, then the
+// Where a step's three batches go, and the counters that draw them: the residual rows, then the value rows, IC first and
+// BC behind them (X_val, tg_val); off_* is the GLOBAL index of the first point of each batch (data parallelism).  The
+// target pointers are null for the coordinate draw, which has no targets to fill.
+struct QcBatches {
+  float *X_res, *tg_res;
+  int64_t n_res, off_res;
+  float *X_val, *tg_val;
+  int64_t n_ic, off_ic, n_bc, off_bc;
+  uint64_t seed, step;
+};
+
+// One segment of the tabulated step's resident dataset; it serves a batch that is empty, or with 1 <= n < 2^31 rows.
+struct QcDsSeg {
+  const float* X;   // [n][3]
+  const float* tg;  // [n]
+  int64_t n;
+  bool serves(int64_t n_batch) const { return n_batch <= 0 || (X && tg && n >= 1 && n < ((int64_t)1 << 31)); }
+};
+
+// Where those batches come from: coordinates drawn in the boxes of the three analytic problems (face_pts: the boundary
+// faces, from QC_FACE_RANDOM up), rows of a resident dataset drawn uniformly, or the same with the residual row
+// drawn from the integer CDF of qc_adapt_build (cdf over cdf_rows rows, coarse table behind it).  With `table` (a
+// qc_step_coef was given) a residual point also copies its operator row, ds_coef[idx][QC_COEF_N] -> coef_res.  The
+// sampler's launchers and everything above them pass this one value; qc_sample.hip maps it to a kernel.
+enum QcSourceKind { QC_SOURCE_DRAW = 0, QC_SOURCE_ROWS, QC_SOURCE_CDF };
+constexpr int64_t QC_FACE_RANDOM = -1;   // == QC_BC_RANDOM_FACE of the public header: the smallest face_pts
+struct QcSource {
+  QcSourceKind kind = QC_SOURCE_DRAW;
+  int64_t face_pts = 0;
+  QcDsSeg res = {}, ic = {}, bc = {};
+  bool table = false;
+  float* coef_res = nullptr;
+  const float* ds_coef = nullptr;
+  const uint64_t *cdf = nullptr, *coarse = nullptr;
+  int64_t cdf_rows = 0;
+
+  // THE validity rule, in two steps.  holds(): what a step asks of batches that are already filled (a call without
+  // QC_PHASE_SAMPLE asks no more): a known boundary rule; of dataset kinds a split of the value batch, a target buffer
+  // behind every non-empty batch, and a CDF buffer that is 8-byte aligned and lies over exactly the rows of the residual
+  // segment (1 <= rows < 2^31).
+  bool holds(const QcBatches& b) const {
+    if (face_pts < QC_FACE_RANDOM) return false;
+    if (kind == QC_SOURCE_DRAW) return true;
+    if (b.n_ic < 0 || b.n_bc < 0 || (b.n_res > 0 && !b.tg_res) || (b.n_ic + b.n_bc > 0 && !b.tg_val)) return false;
+    return kind != QC_SOURCE_CDF ||
+           (cdf && ((uintptr_t)cdf & 7) == 0 && cdf_rows >= 1 && cdf_rows < ((int64_t)1 << 31) && cdf_rows == res.n);
+  }
+  // ok(): what filling them asks on top: counts and offsets from 0, a point buffer and a dataset segment behind every
+  // non-empty batch, and the coefficient pair whole where a table is wanted (n_res = 0: neither pointer is read)
+  bool ok(const QcBatches& b) const {
+    if (!holds(b) || b.n_res < 0 || b.n_ic < 0 || b.n_bc < 0 || b.off_res < 0 || b.off_ic < 0 || b.off_bc < 0) return false;
+    if ((b.n_res > 0 && !b.X_res) || (b.n_ic + b.n_bc > 0 && !b.X_val)) return false;
+    if (kind == QC_SOURCE_DRAW) return true;
+    if (table && b.n_res > 0 && (!coef_res || !ds_coef)) return false;
+    return res.serves(b.n_res) && ic.serves(b.n_ic) && bc.serves(b.n_bc);
+  }
+};
+
+// Residual-adaptive sampling (qc_adapt.hip, the CDF rules of k_gather): the caller's buffer holds this record, then the
 // inclusive uint64 CDF of the rows' integer weights, then one coarse entry per QC_ADAPT_ROWS rows (the CDF at the last row
 // of each block of rows).  == the layout documented at qc_adapt_bytes in the public header.
 constexpr int QC_ADAPT_ROWS = 1024;   // == QC_ADAPT_BLOCK
@@ -148,9 +206,8 @@ int qc_reg_circ_bwd_both(const qc_program* pg, const QcTrig* trig, const float* 
 
 // ---- launchers, one group per .hip file
 // `map`: output map of the pre network (QC_ANGLE_MAP_*); its reverse pass reads the forward pass's angle jets aj / ajr / ajv
-int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, float* ajr, float* ajv, int64_t Br, int64_t Bv,
-                        int draw, int64_t n_ic, int64_t off_res, int64_t off_ic, int64_t off_bc, int64_t face_pts,
-                        uint64_t seed, uint64_t step, hipStream_t st, int map);
+int qc_mlp_pre_fwd_both(const QcBatches& b, int draw, int64_t face_pts, const float* prm, QcLayout L, float* ajr, float* ajv,
+                        hipStream_t st, int map);
 int qc_mlp_pre_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
                         float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
                         hipStream_t st, int map, const float* ajr, const float* ajv);
@@ -180,20 +237,9 @@ int qc_opt_adam_fold(const float* part, int64_t stride, int RS, float* flat, int
 int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState* state, QcOptHyper hp,
                 float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t);
 int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hipStream_t);
-int qc_sample_launch(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
-                     int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step, hipStream_t);
-int qc_sample_dataset_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
-                             int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
-                             const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic, int64_t ds_n_ic,
-                             const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed, uint64_t step,
-                             hipStream_t, float* coef_res = nullptr, const float* ds_coef = nullptr);
-// the gather with the residual row drawn from the CDF (`cdf` [ds_n_res], `coarse` behind it); coef_res / ds_coef may be null
-int qc_sample_dataset_adaptive_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
-                                      int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
-                                      const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic,
-                                      int64_t ds_n_ic, const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed,
-                                      uint64_t step, hipStream_t, float* coef_res, const float* ds_coef, const uint64_t* cdf,
-                                      const uint64_t* coarse);
+// qc_sample.hip: fill the batches `b` from a source that QcSource::ok passed: the coordinate draw, or the dataset kinds
+int qc_sample_launch(const QcBatches& b, int64_t bc_face_points, hipStream_t);
+int qc_gather_launch(const QcBatches& b, const QcSource& s, hipStream_t);
 // qc_adapt.hip: |res - target| of c rows from their [6][c] channels (coef_rows [c][7] or null: the scalar operator), and
 // scores -> record, CDF and coarse table
 int qc_adapt_score_launch(const float* uj, int64_t c, QcPde pde, float c_u, const float* coef_rows, const float* tg,

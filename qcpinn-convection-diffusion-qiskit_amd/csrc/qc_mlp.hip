@@ -1890,14 +1890,12 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
 
 // ------------------------------------------------------------------ merged residual + value launches (fused step)
 // draw_*: when `draw` != 0 the launch first draws its own points (qc_sample_collocation_faces semantics) into Xr / Xv
-int qc_mlp_pre_fwd_both(float* Xr, float* Xv, const float* prm, QcLayout L, float* ajr, float* ajv, int64_t Br, int64_t Bv,
-                        int draw, int64_t n_ic, int64_t off_res, int64_t off_ic, int64_t off_bc, int64_t face_pts,
-                        uint64_t seed, uint64_t step, hipStream_t st, int map) {
+int qc_mlp_pre_fwd_both(const QcBatches& b, int draw, int64_t face_pts, const float* prm, QcLayout L, float* ajr, float* ajv,
+                        hipStream_t st, int map) {
+  float *Xr = b.X_res, *Xv = b.X_val;
+  const int64_t Br = b.n_res, Bv = b.n_ic + b.n_bc;
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(qc_ceil_div(Bv, 64), 4);   // value tiles: 4 per block, one per wave
-  QcDraw dr;
-  dr.enabled = draw;
-  dr.n_ic = n_ic; dr.off_res = off_res; dr.off_ic = off_ic; dr.off_bc = off_bc; dr.face_pts = face_pts;
-  dr.seed = seed; dr.step = step;
+  const QcDraw dr = {draw, b.n_ic, b.off_res, b.off_ic, b.off_bc, face_pts, b.seed, b.step};
   const bool rf = draw && face_pts < 0;
   return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
     auto launch = [&](auto m, auto r) {

@@ -8,7 +8,39 @@
 #include "qc_internal.h"
 #include "qc_philox.h"
 
+#include <tuple>
+
 namespace {
+
+// Thread i of a launch over n_res + n_ic + n_bc points: its segment (0 residual, 1 IC, 2 BC; -1: past the last point),
+// its row `out` of that segment's output buffers (value rows and value targets are laid out IC first, then BC, like
+// X_val), its global index, where its point goes, the targets of its batch, and in dataset mode the resident segment it
+// copies from.  Returned by value: handed out through a reference, `ds` went through scratch memory in the CDF gathers.
+struct QcSlot {
+  int seg;
+  int64_t out, gidx;
+  float *X, *tg;   // X_batch + 3 * out; the batch's target buffer (indexed by out)
+  QcDsSeg ds;
+};
+__device__ __forceinline__ QcSlot qc_slot(int64_t i, float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val,
+                                          float* tg_val, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                                          QcDsSeg d_res = {}, QcDsSeg d_ic = {}, QcDsSeg d_bc = {}) {
+  QcSlot s;
+  int64_t local;
+  if (i < n_res) {
+    local = i;
+    s = {0, local, off_res + local, X_res + local * 3, tg_res, d_res};
+  } else if (i < n_res + n_ic) {
+    local = i - n_res;
+    s = {1, local, off_ic + local, X_val + local * 3, tg_val, d_ic};
+  } else if (i < n_res + n_ic + n_bc) {
+    local = i - n_res - n_ic;
+    s = {2, n_ic + local, off_bc + local, X_val + (n_ic + local) * 3, tg_val, d_bc};
+  } else {
+    s.seg = -1;
+  }
+  return s;
+}
 
 // segment 0: residual points in [0,1]^3; 1: IC points (t = 0); 2: boundary points: the x = 0 face
 // (trainer/diffusion_train.py:13-16), or with face_pts > 0 the four faces x=0, x=1, y=0, y=1 of the second
@@ -19,111 +51,64 @@ __global__ void __launch_bounds__(256) k_sample(float* __restrict__ X_res, int64
                                                 float* __restrict__ X_val, int64_t n_ic, int64_t off_ic,
                                                 int64_t n_bc, int64_t off_bc, int64_t face_pts, uint64_t seed,
                                                 uint64_t step) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int seg;
-  int64_t local, gidx;
-  float* dst;
-  if (i < n_res) {
-    seg = 0; local = i; gidx = off_res + local; dst = X_res + local * 3;
-  } else if (i < n_res + n_ic) {
-    seg = 1; local = i - n_res; gidx = off_ic + local; dst = X_val + local * 3;
-  } else if (i < n_res + n_ic + n_bc) {
-    seg = 2; local = i - n_res - n_ic; gidx = off_bc + local; dst = X_val + (n_ic + local) * 3;
-  } else {
-    return;
-  }
+  const QcSlot s = qc_slot((int64_t)blockIdx.x * 256 + threadIdx.x, X_res, nullptr, n_res, off_res, X_val, nullptr, n_ic,
+                           off_ic, n_bc, off_bc);
+  if (s.seg < 0) return;
   float t, x, y;
-  qc_draw_point<RF>(seg, gidx, face_pts, seed, step, t, x, y);
-  dst[0] = t;
-  dst[1] = x;
-  dst[2] = y;
+  qc_draw_point<RF>(s.seg, s.gidx, face_pts, seed, step, t, x, y);
+  s.X[0] = t;
+  s.X[1] = x;
+  s.X[2] = y;
 }
 
-// Dataset mode of the same launch (the tabulated step): point i of a segment copies row idx of that segment's resident
-// dataset and its target, idx drawn by qc_draw_index from the counter the coordinate draw uses.  Value rows and value
-// targets are laid out IC first, then BC, like X_val.
-struct QcDsSeg {
-  const float* X;   // [n][3]
-  const float* tg;  // [n]
-  int64_t n;
-};
-
-__global__ void __launch_bounds__(256) k_sample_dataset(float* __restrict__ X_res, float* __restrict__ tg_res, int64_t n_res,
-                                                        int64_t off_res, float* __restrict__ X_val,
-                                                        float* __restrict__ tg_val, int64_t n_ic, int64_t off_ic,
-                                                        int64_t n_bc, int64_t off_bc, QcDsSeg d_res, QcDsSeg d_ic,
-                                                        QcDsSeg d_bc, uint64_t seed, uint64_t step) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int seg;
-  int64_t out, gidx;
-  float *dstX, *dstT;
-  QcDsSeg ds;
-  if (i < n_res) {
-    seg = 0; out = i; gidx = off_res + i; dstX = X_res; dstT = tg_res; ds = d_res;
-  } else if (i < n_res + n_ic) {
-    seg = 1; out = i - n_res; gidx = off_ic + out; dstX = X_val; dstT = tg_val; ds = d_ic;
-  } else if (i < n_res + n_ic + n_bc) {
-    seg = 2; out = i - n_res; gidx = off_bc + (out - n_ic); dstX = X_val; dstT = tg_val; ds = d_bc;
-  } else {
-    return;
+// The search of the CDF gather (residual-adaptive sampling, the integer CDF of qc_adapt_build): min{j : cdf[j] > t}, in the
+// coarse table `top` (nb entries, one per QC_ADAPT_ROWS rows) first, then in that block of the CDF.  t >= cdf[N - 1] (only
+// with cdf[N - 1] = 0, no row has weight, which qc_adapt_build never leaves) takes the last row, in bounds.
+__device__ __forceinline__ int64_t qc_cdf_search(uint64_t t, const uint64_t* __restrict__ cdf, const uint64_t* top, int64_t N,
+                                                 int64_t nb) {
+  int64_t lo = 0, hi = nb - 1;          // first block whose last CDF entry exceeds t (the last block if none does)
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (top[mid] > t) hi = mid;
+    else lo = mid + 1;
   }
-  const int64_t idx = qc_draw_index(seg, gidx, ds.n, seed, step);   // < ds.n: the product's high word
-  dstX[out * 3 + 0] = ds.X[idx * 3 + 0];
-  dstX[out * 3 + 1] = ds.X[idx * 3 + 1];
-  dstX[out * 3 + 2] = ds.X[idx * 3 + 2];
-  dstT[out] = ds.tg[idx];
+  hi = (lo + 1) * QC_ADAPT_ROWS < N ? (lo + 1) * QC_ADAPT_ROWS - 1 : N - 1;
+  lo *= QC_ADAPT_ROWS;                  // first row of that block whose CDF entry exceeds t
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (cdf[mid] > t) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
 }
 
-// The same gather for the coefficient step: a residual point also copies its operator row, ds_coef[idx][7] ->
-// coef_res[7][n_res] (batch-minor).  Same segments, counters and index, hence the same batches as k_sample_dataset.
-__global__ void __launch_bounds__(256) k_sample_dataset_coef(float* __restrict__ X_res, float* __restrict__ tg_res,
-                                                             int64_t n_res, int64_t off_res, float* __restrict__ X_val,
-                                                             float* __restrict__ tg_val, int64_t n_ic, int64_t off_ic,
-                                                             int64_t n_bc, int64_t off_bc, QcDsSeg d_res, QcDsSeg d_ic,
-                                                             QcDsSeg d_bc, uint64_t seed, uint64_t step,
-                                                             float* __restrict__ coef_res, const float* __restrict__ ds_coef) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int seg;
-  int64_t out, gidx;
-  float *dstX, *dstT;
-  QcDsSeg ds;
-  if (i < n_res) {
-    seg = 0; out = i; gidx = off_res + i; dstX = X_res; dstT = tg_res; ds = d_res;
-  } else if (i < n_res + n_ic) {
-    seg = 1; out = i - n_res; gidx = off_ic + out; dstX = X_val; dstT = tg_val; ds = d_ic;
-  } else if (i < n_res + n_ic + n_bc) {
-    seg = 2; out = i - n_res; gidx = off_bc + (out - n_ic); dstX = X_val; dstT = tg_val; ds = d_bc;
-  } else {
-    return;
-  }
-  const int64_t idx = qc_draw_index(seg, gidx, ds.n, seed, step);   // < ds.n: the product's high word
-  dstX[out * 3 + 0] = ds.X[idx * 3 + 0];
-  dstX[out * 3 + 1] = ds.X[idx * 3 + 1];
-  dstX[out * 3 + 2] = ds.X[idx * 3 + 2];
-  dstT[out] = ds.tg[idx];
-  if (seg == 0) {
-#pragma unroll
-    for (int k = 0; k < QC_COEF_N; ++k) coef_res[(int64_t)k * n_res + out] = ds_coef[idx * QC_COEF_N + k];
-  }
+// Dataset mode of the same launch (the tabulated step), ONE template for every QcSource of rows: point i of a segment
+// copies row idx of that segment's resident dataset and its target.  ROWS is the rule for idx.  Uniform: qc_draw_index
+// on the counter the coordinate draw uses.  The two CDF rules: a residual point searches the CDF (qc_cdf_search), IC and
+// BC points draw as before, so the value batches are those of the uniform gather; the blocks that hold residual points
+// first stage the coarse table in shared memory (at most QC_ADAPT_LDS_MAX entries), or with QC_ROWS_CDF_GLOBAL every
+// search reads it where it lies.
+// `src` is the source's optional pointers as a trailing pack, so the plain gather carries no argument for them:
+// nothing; (coef_res, ds_coef): a residual point also copies its operator row, ds_coef[idx][7] -> coef_res[7][n_res]
+// (batch-minor); (coef_res, ds_coef, cdf, coarse) for the CDF rules, where coef_res / ds_coef may be null.
+template <int K, class... P>
+__device__ __forceinline__ auto qc_src(P*... src) {   // pointer K of the pack, null behind its end
+  if constexpr (K < sizeof...(P)) return std::get<K>(std::tie(src...));
+  else return nullptr;
 }
-
-// The same gather with the residual row drawn from the integer CDF of qc_adapt_build (residual-adaptive sampling):
-// r64 = word 0 << 32 | word 1 of the block the uniform gather draws, t = umul64hi(r64, T) with T = cdf[N - 1], and
-// idx = min{j : cdf[j] > t}: the coarse table (one entry per QC_ADAPT_ROWS rows) first, then that block of the CDF.  IC and
-// BC points draw as in k_sample_dataset, so the value batches are those of the uniform step.  LDS: the blocks that hold
-// residual points stage the coarse table (nb entries, at most QC_ADAPT_LDS_MAX; larger tables are searched in global memory) in shared memory first.  coef_res / ds_coef may be
-// null.  T = 0 (no row has weight; qc_adapt_build never leaves that) takes the last row, in bounds.
+enum QcRows { QC_ROWS_UNIFORM = 0, QC_ROWS_CDF_LDS, QC_ROWS_CDF_GLOBAL };
 constexpr int QC_ADAPT_LDS_MAX = 4096;   // coarse entries staged in LDS (32 KB): datasets up to 4 Mi residual rows
 
-template <bool LDS>
-__global__ void __launch_bounds__(256) k_sample_dataset_adaptive(float* __restrict__ X_res, float* __restrict__ tg_res,
-                                                                 int64_t n_res, int64_t off_res, float* __restrict__ X_val,
-                                                                 float* __restrict__ tg_val, int64_t n_ic, int64_t off_ic,
-                                                                 int64_t n_bc, int64_t off_bc, QcDsSeg d_res, QcDsSeg d_ic,
-                                                                 QcDsSeg d_bc, uint64_t seed, uint64_t step,
-                                                                 float* __restrict__ coef_res, const float* __restrict__ ds_coef,
-                                                                 const uint64_t* __restrict__ cdf,
-                                                                 const uint64_t* __restrict__ coarse) {
+template <QcRows ROWS, class... P>
+__global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float* __restrict__ tg_res, int64_t n_res,
+                                                int64_t off_res, float* __restrict__ X_val, float* __restrict__ tg_val,
+                                                int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, QcDsSeg d_res,
+                                                QcDsSeg d_ic, QcDsSeg d_bc, uint64_t seed, uint64_t step,
+                                                P* __restrict__... src) {
+  constexpr bool CDF = ROWS != QC_ROWS_UNIFORM, LDS = ROWS == QC_ROWS_CDF_LDS, TABLE = sizeof...(P) >= 2;
+  float* coef_res = qc_src<0>(src...);
+  const float* ds_coef = qc_src<1>(src...);
+  const uint64_t *cdf = qc_src<2>(src...), *coarse = qc_src<3>(src...);
   __shared__ uint64_t sh[LDS ? QC_ADAPT_LDS_MAX : 1];
   const int64_t N = d_res.n;
   const int64_t nb = (N + QC_ADAPT_ROWS - 1) / QC_ADAPT_ROWS;
@@ -131,105 +116,64 @@ __global__ void __launch_bounds__(256) k_sample_dataset_adaptive(float* __restri
     for (int64_t b = threadIdx.x; b < nb; b += 256) sh[b] = coarse[b];
     __syncthreads();
   }
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int seg;
-  int64_t out, gidx;
-  float *dstX, *dstT;
-  QcDsSeg ds;
-  if (i < n_res) {
-    seg = 0; out = i; gidx = off_res + i; dstX = X_res; dstT = tg_res; ds = d_res;
-  } else if (i < n_res + n_ic) {
-    seg = 1; out = i - n_res; gidx = off_ic + out; dstX = X_val; dstT = tg_val; ds = d_ic;
-  } else if (i < n_res + n_ic + n_bc) {
-    seg = 2; out = i - n_res; gidx = off_bc + (out - n_ic); dstX = X_val; dstT = tg_val; ds = d_bc;
-  } else {
-    return;
-  }
+  const QcSlot s = qc_slot((int64_t)blockIdx.x * 256 + threadIdx.x, X_res, tg_res, n_res, off_res, X_val, tg_val, n_ic,
+                           off_ic, n_bc, off_bc, d_res, d_ic, d_bc);
+  if (s.seg < 0) return;
   int64_t idx;
-  if (seg == 0) {
-    const U4 ctr = {(uint32_t)gidx, (uint32_t)(gidx >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
+  if (CDF && s.seg == 0) {   // t = umul64hi(r64, cdf[N - 1]), r64 = word 0 << 32 | word 1 of the uniform gather's block
+    const U4 ctr = {(uint32_t)s.gidx, (uint32_t)(s.gidx >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
     const U4 r = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint64_t t = __umul64hi(((uint64_t)r.x << 32) | r.y, cdf[N - 1]);
-    const uint64_t* top = LDS ? sh : coarse;
-    int64_t lo = 0, hi = nb - 1;          // first block whose last CDF entry exceeds t (the last block if none does)
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (top[mid] > t) hi = mid;
-      else lo = mid + 1;
-    }
-    hi = (lo + 1) * QC_ADAPT_ROWS < N ? (lo + 1) * QC_ADAPT_ROWS - 1 : N - 1;
-    lo *= QC_ADAPT_ROWS;                  // first row of that block whose CDF entry exceeds t
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (cdf[mid] > t) hi = mid;
-      else lo = mid + 1;
-    }
-    idx = lo;
+    idx = qc_cdf_search(__umul64hi(((uint64_t)r.x << 32) | r.y, cdf[N - 1]), cdf, LDS ? sh : coarse, N, nb);
   } else {
-    idx = qc_draw_index(seg, gidx, ds.n, seed, step);   // < ds.n: the product's high word
+    idx = qc_draw_index(s.seg, s.gidx, s.ds.n, seed, step);   // < ds.n: the product's high word
   }
-  dstX[out * 3 + 0] = ds.X[idx * 3 + 0];
-  dstX[out * 3 + 1] = ds.X[idx * 3 + 1];
-  dstX[out * 3 + 2] = ds.X[idx * 3 + 2];
-  dstT[out] = ds.tg[idx];
-  if (seg == 0 && coef_res != nullptr) {
+  s.X[0] = s.ds.X[idx * 3 + 0];
+  s.X[1] = s.ds.X[idx * 3 + 1];
+  s.X[2] = s.ds.X[idx * 3 + 2];
+  s.tg[s.out] = s.ds.tg[idx];
+  if (TABLE && s.seg == 0 && (!CDF || coef_res != nullptr)) {
 #pragma unroll
-    for (int k = 0; k < QC_COEF_N; ++k) coef_res[(int64_t)k * n_res + out] = ds_coef[idx * QC_COEF_N + k];
+    for (int k = 0; k < QC_COEF_N; ++k) coef_res[(int64_t)k * n_res + s.out] = ds_coef[idx * QC_COEF_N + k];
   }
 }
+
+// Implicit instantiations are emitted in order of first use, and where identical kernels lie in the object has been
+// measured (DESIGN section 6 "Batch sources"): the two uniform gathers are named here, ahead of qc_sample_launch, so the
+// order stays uniform, uniform with a table, k_sample<true>, k_sample<false>, CDF from LDS, CDF from global memory.
+constexpr auto k_gather_rows = k_gather<QC_ROWS_UNIFORM>;
+constexpr auto k_gather_rows_coef = k_gather<QC_ROWS_UNIFORM, float, const float>;
+template <QcRows ROWS>
+constexpr auto k_gather_cdf = k_gather<ROWS, float, const float, const uint64_t, const uint64_t>;
 
 }  // namespace
 
-int qc_sample_dataset_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
-                             int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
-                             const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic, int64_t ds_n_ic,
-                             const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed, uint64_t step,
-                             hipStream_t st, float* coef_res, const float* ds_coef) {
-  const int64_t total = n_res + n_ic + n_bc;
+int qc_sample_launch(const QcBatches& b, int64_t bc_face_points, hipStream_t st) {
+  const int64_t total = b.n_res + b.n_ic + b.n_bc;
   if (total <= 0) return QC_OK;
-  const QcDsSeg a = {dsX_res, ds_r, ds_n_res}, b = {dsX_ic, ds_u_ic, ds_n_ic}, c = {dsX_bc, ds_u_bc, ds_n_bc};
-  if (coef_res != nullptr && ds_coef != nullptr) {   // the coefficient step: rows, targets and operator rows in one launch
-    hipLaunchKernelGGL(k_sample_dataset_coef, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, tg_res, n_res, off_res,
-                       X_val, tg_val, n_ic, off_ic, n_bc, off_bc, a, b, c, seed, step, coef_res, ds_coef);
-    return QC_OK;
+  hipLaunchKernelGGL((bc_face_points < 0 ? k_sample<true> : k_sample<false>), dim3(qc_ceil_div(total, 256)), dim3(256), 0, st,
+                     b.X_res, b.n_res, b.off_res, b.X_val, b.n_ic, b.off_ic, b.n_bc, b.off_bc, bc_face_points, b.seed, b.step);
+  return QC_OK;
+}
+
+// the dataset kinds of QcSource (validated with QcSource::ok): one launch, the kernel by kind, table and table size
+int qc_gather_launch(const QcBatches& b, const QcSource& s, hipStream_t st) {
+  const int64_t total = b.n_res + b.n_ic + b.n_bc;
+  if (total <= 0) return QC_OK;
+  auto launch = [&](auto kernel, auto... src) {
+    hipLaunchKernelGGL(kernel, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, b.X_res, b.tg_res, b.n_res, b.off_res, b.X_val,
+                       b.tg_val, b.n_ic, b.off_ic, b.n_bc, b.off_bc, s.res, s.ic, s.bc, b.seed, b.step, src...);
+  };
+  const bool table = s.table && b.n_res > 0;   // no residual rows: none to copy an operator row for
+  float* coef_res = table ? s.coef_res : nullptr;
+  const float* ds_coef = table ? s.ds_coef : nullptr;
+  if (s.kind != QC_SOURCE_CDF) {
+    if (table) launch(k_gather_rows_coef, coef_res, ds_coef);   // rows, targets and operator rows in one launch
+    else launch(k_gather_rows);
+  } else if ((s.res.n + QC_ADAPT_ROWS - 1) / QC_ADAPT_ROWS <= QC_ADAPT_LDS_MAX) {
+    // measured faster than the search from global memory alone
+    launch(k_gather_cdf<QC_ROWS_CDF_LDS>, coef_res, ds_coef, s.cdf, s.coarse);
+  } else {
+    launch(k_gather_cdf<QC_ROWS_CDF_GLOBAL>, coef_res, ds_coef, s.cdf, s.coarse);
   }
-  hipLaunchKernelGGL(k_sample_dataset, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, tg_res, n_res, off_res, X_val,
-                     tg_val, n_ic, off_ic, n_bc, off_bc, a, b, c, seed, step);
-  return QC_OK;
-}
-
-int qc_sample_launch(float* X_res, int64_t n_res, int64_t off_res, float* X_val, int64_t n_ic, int64_t off_ic,
-                     int64_t n_bc, int64_t off_bc, int64_t bc_face_points, uint64_t seed, uint64_t step, hipStream_t st) {
-  const int64_t total = n_res + n_ic + n_bc;
-  if (total <= 0) return QC_OK;
-  if (bc_face_points < 0)
-    hipLaunchKernelGGL(k_sample<true>, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, n_res, off_res, X_val, n_ic,
-                       off_ic, n_bc, off_bc, bc_face_points, seed, step);
-  else
-    hipLaunchKernelGGL(k_sample<false>, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, n_res, off_res, X_val, n_ic,
-                       off_ic, n_bc, off_bc, bc_face_points, seed, step);
-  return QC_OK;
-}
-
-// (defined last: the kernels that existed keep their places in the object file, DESIGN section 6 "Target kinds")
-int qc_sample_dataset_adaptive_launch(float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val, float* tg_val,
-                                      int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const float* dsX_res,
-                                      const float* ds_r, int64_t ds_n_res, const float* dsX_ic, const float* ds_u_ic,
-                                      int64_t ds_n_ic, const float* dsX_bc, const float* ds_u_bc, int64_t ds_n_bc, uint64_t seed,
-                                      uint64_t step, hipStream_t st, float* coef_res, const float* ds_coef, const uint64_t* cdf,
-                                      const uint64_t* coarse) {
-  const int64_t total = n_res + n_ic + n_bc;
-  if (total <= 0) return QC_OK;
-  const QcDsSeg a = {dsX_res, ds_r, ds_n_res}, b = {dsX_ic, ds_u_ic, ds_n_ic}, c = {dsX_bc, ds_u_bc, ds_n_bc};
-  const bool table = coef_res != nullptr && ds_coef != nullptr;
-  const int64_t nb = (ds_n_res + QC_ADAPT_ROWS - 1) / QC_ADAPT_ROWS;
-  if (nb <= QC_ADAPT_LDS_MAX)   // measured faster than the search from global memory alone
-    hipLaunchKernelGGL(k_sample_dataset_adaptive<true>, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, tg_res, n_res,
-                       off_res, X_val, tg_val, n_ic, off_ic, n_bc, off_bc, a, b, c, seed, step, table ? coef_res : nullptr,
-                       table ? ds_coef : nullptr, cdf, coarse);
-  else
-    hipLaunchKernelGGL(k_sample_dataset_adaptive<false>, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, X_res, tg_res, n_res,
-                       off_res, X_val, tg_val, n_ic, off_ic, n_bc, off_bc, a, b, c, seed, step, table ? coef_res : nullptr,
-                       table ? ds_coef : nullptr, cdf, coarse);
   return QC_OK;
 }

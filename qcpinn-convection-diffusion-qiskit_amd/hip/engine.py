@@ -478,6 +478,7 @@ class FusedStep:
         d.sample_seed, d.sample_step = 0, 0
         d.sample_bc_face_points = 0
         self.desc = d
+        self._bind()
 
     def set_sampler(self, seed: int, off_res: int = 0, off_ic: int = 0, off_bc: int = 0,
                     bc_face_points: int = 0) -> None:
@@ -538,11 +539,13 @@ class FusedStep:
         need = int(self.eng.lib.qc_adapt_bytes(n_rows))
         self.adapt_buf = torch.zeros((need + 7) // 8, dtype=torch.int64, device=dev)        # 8-byte aligned
         self.adapt = L.QcStepAdapt(self.adapt_buf.data_ptr(), n_rows)
+        self._bind()
         self._build_cdf()       # zero scores: uniform weights
 
     def clear_adaptive(self) -> None:
         """Back to the uniform gather."""
         self.adapt = self.scores = self.adapt_buf = None
+        self._bind()
 
     def _build_cdf(self) -> None:
         L.check(self.eng.lib.qc_adapt_build(self.scores.data_ptr(), self.adapt.n_rows, self.adapt_power, self.adapt_floor,
@@ -567,22 +570,20 @@ class FusedStep:
         [gradient | 3 loss sums] vector across the ranks inside the library (RCCL, same stream)."""
         self.desc.comm = comm
 
+    def _bind(self) -> None:
+        """THE place that maps what the step was given (an armed CDF, coefficient mode, a tabulated problem, none of them)
+        to one of the four exports and its arguments ahead of ``phases``; re-run when adaptive sampling is (dis)armed."""
+        data, coef = C.byref(self.data), C.byref(self.coef) if self.coef_mode else None
+        if self.adapt is not None:
+            name, args = "qc_fused_pinn_adaptive_step", (data, coef, C.byref(self.adapt))
+        elif self.coef_mode:
+            name, args = "qc_fused_pinn_coef_step", (data, coef)
+        else:
+            name, args = ("qc_fused_pinn_data_step", (data,)) if self.tabulated else ("qc_fused_pinn_residual_step", ())
+        self._entry = name, getattr(self.eng.lib, name), (C.byref(self.desc), *args)
+
     def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
         if phases & L.QC_PHASE_SAMPLE:
             self.desc.sample_step += 1          # a fresh counter block per step
-        if self.adapt is not None:
-            L.check(self.eng.lib.qc_fused_pinn_adaptive_step(C.byref(self.desc), C.byref(self.data),
-                                                             C.byref(self.coef) if self.coef_mode else None,
-                                                             C.byref(self.adapt), phases, _stream(self.eng.device)),
-                    "qc_fused_pinn_adaptive_step")
-            return
-        if self.coef_mode:
-            L.check(self.eng.lib.qc_fused_pinn_coef_step(C.byref(self.desc), C.byref(self.data), C.byref(self.coef), phases,
-                                                         _stream(self.eng.device)), "qc_fused_pinn_coef_step")
-            return
-        if self.tabulated:
-            L.check(self.eng.lib.qc_fused_pinn_data_step(C.byref(self.desc), C.byref(self.data), phases,
-                                                         _stream(self.eng.device)), "qc_fused_pinn_data_step")
-            return
-        L.check(self.eng.lib.qc_fused_pinn_residual_step(C.byref(self.desc), phases, _stream(self.eng.device)),
-                "qc_fused_pinn_residual_step")
+        name, fn, args = self._entry
+        L.check(fn(*args, phases, _stream(self.eng.device)), name)

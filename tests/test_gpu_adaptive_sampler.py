@@ -54,9 +54,9 @@ def _bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def _check(dev, arr, ten, table, parts, n_res, off, with_table):
+def _check(dev, arr, ten, table, parts, n_res, off, with_table, n_val=(4, 3)):
     tab_dev = torch.from_numpy(table).to(dev) if with_table else None
-    counts, offs = (n_res, 4, 3), (off, 2, 6)
+    counts, offs = (n_res, *n_val), (off, 2, 6)
     got = _adaptive_gather(dev, ten, tab_dev, parts, counts, offs)
     k = AR.indices(parts[1], off, n_res, SEED, STEP)
     (X, r) = arr[0]
@@ -96,6 +96,34 @@ def test_rows_targets_and_operator_rows_match_the_restatement(N, gpu_device):
                 assert np.unique(k).size > 100 and not np.array_equal(arr[0][1][k], plain[1])      # not the uniform draw
                 seen += 1
     assert seen == (2 if N > 3 else 0)
+
+
+@pytest.mark.parametrize("with_table", [False, True], ids=["rows", "table"])
+@pytest.mark.parametrize("counts", [(65, 300, 200), (257, 0, 3), (255, 1, 0)], ids=lambda c: "x".join(map(str, c)))
+def test_blocks_of_value_points_only_and_empty_batches(counts, with_table, gpu_device):
+    """Launch shapes no other case has: blocks that hold value points only (65 + 300 + 200 points: the second and third
+    block of 256 skip the staging of the coarse table and its barrier), a residual batch that ends one point into the
+    second block with no IC points behind it, and a last block filled to its last thread with no BC points.  1025 rows:
+    two coarse entries, the second over a single row that holds a third of the weight.  The uniform gathers (the other
+    instantiations of the same kernel) fill the same shapes, against the numpy restatement of their draw."""
+    from test_gpu_coef import _expected_coef, _gather_coef
+    N = AR.BLOCK + 1
+    arr, ten = _dataset(gpu_device, (N, N_IC, N_BC), seed=21)
+    table = CR.coef_star(arr[0][0])
+    g = np.random.default_rng(22)
+    w = g.integers(0, 2 ** 20, N, dtype=np.uint64) * (g.random(N) < 0.7).astype(np.uint64)
+    w[-1] = w[:-1].sum() // np.uint64(2)
+    parts = AR.from_cdf(np.cumsum(w, dtype=np.uint64))
+    assert parts[2].size == 2
+    off = (1 << 32) + 7
+    k, plain = _check(gpu_device, arr, ten, table, parts, counts[0], off, with_table, counts[1:])
+    assert (w[k] > 0).all() and (k == N - 1).any() and (k < N - 1).any()
+    offs = (off, 2, 6)
+    L = pkg("hip.lib")
+    want = _expected_coef(arr, table, offs, counts, SEED, STEP)
+    got = _gather_coef(L.load(), L, gpu_device, _step_data(L, ten), torch.from_numpy(table).to(gpu_device), counts, offs, SEED, STEP)
+    for a, b in zip(list(plain) + got, want[:4] + want):
+        assert _bits(a, b)
 
 
 def test_flat_spots_and_single_hot_rows(gpu_device):
