@@ -25,15 +25,64 @@
 
 namespace {
 
+// A run-time flag of the stand-alone kernels that a merged step kernel knows when it is compiled: AB = 0 / 1 fixes it
+// (no register, no branch, no select where it is read), AB = -1 forwards the run-time argument.
+template <int AB>
+__device__ __forceinline__ bool qc_flag(int rt) {
+  if constexpr (AB < 0) return rt != 0;
+  else return AB != 0;
+}
+
+// Hides a pointer's provenance from the optimiser: loads through the result are not merged with
+// earlier loads, so values recomputed from them do not stay live in registers in between.
+template <class T>
+__device__ __forceinline__ const T* qc_launder(const T* p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+// The same for wave-uniform read-only tables (trig, phase tables, U4 blocks), through the constant address space:
+// always scalar loads, requested where the result is used - never hoisted out of a loop around the caller and held
+// (or spilled to VGPR lanes) across it.
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* qc_const(const T* p) {
+  return (const __attribute__((address_space(4))) T*)qc_launder(p);
+}
+// ... and not before the state the table is applied to exists, every amplitude of it: the request cannot move up past
+// the gate in front of it either (one anchored amplitude would only pull that amplitude's arithmetic up with it)
+template <class T, int N>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* qc_const_at(const T* p, const SV<N>& v) {
+#define QC_A4_(o) "v"(v.a[o]), "v"(v.a[o + 1]), "v"(v.a[o + 2]), "v"(v.a[o + 3])
+  if constexpr (N == 2) asm volatile("" : "+s"(p) : QC_A4_(0));
+  if constexpr (N == 3) asm volatile("" : "+s"(p) : QC_A4_(0), QC_A4_(4));
+  if constexpr (N >= 4) asm volatile("" : "+s"(p) : QC_A4_(0), QC_A4_(4), QC_A4_(8), QC_A4_(12));
+  if constexpr (N == 5) asm volatile("" : "+s"(p) : QC_A4_(16), QC_A4_(20), QC_A4_(24), QC_A4_(28));
+#undef QC_A4_
+  static_assert(N >= 2 && N <= 5, "register family");
+  return (const __attribute__((address_space(4))) T*)p;
+}
+// a wave-uniform / per-lane integer as an opaque value: what is derived from it is recomputed at its use instead of
+// being hoisted out of a loop and held
+__device__ __forceinline__ int64_t qc_opaque_s(int64_t v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+__device__ __forceinline__ int qc_opaque_v(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // ------------------------------------------------------------------ program policies
 // DynProg<N>: the gate program is run-time data (scalar switch per gate, any ansatz).
 template <int NQ>
 struct DynProg {
   static constexpr int N = NQ;
+  static constexpr bool lead_rx = true;   // (run-time data: either form of the embedding may be asked for)
+  __device__ static __forceinline__ int lead_slot(const QcGate* __restrict__ prog, int w) { return prog[w].slot; }
+  template <int AB = -1, bool PIN = false>
   __device__ static __forceinline__ void fwd(SV<NQ> (&v)[1], const QcGate* __restrict__ prog,
                                              const QcTrig* __restrict__ trig, const float* __restrict__ umat,
                                              int n_gates, int absorb) {
-    for (int g = absorb ? NQ : 0; g < n_gates; ++g) {
+    for (int g = qc_flag<AB>(absorb) ? NQ : 0; g < n_gates; ++g) {
       const QcGate gt = prog[g];
       const QcTrig tr = trig[g];
       qc_apply_gate<NQ, 1, false>(v, gt, tr.c, tr.s, umat);
@@ -41,10 +90,11 @@ struct DynProg {
   }
   // Reverse sweep for one (chi, lam) pair: accumulates Im<lam|G|chi> per parameter slot into
   // acc_wave[slot] (LDS, one row per wave), then un-applies the gate on both.
+  template <int AB = -1>
   __device__ static __forceinline__ void bwd(SV<NQ> (&cl)[2], const QcGate* __restrict__ prog,
                                              const QcTrig* __restrict__ trig, const float* __restrict__ umat,
                                              int n_gates, float* __restrict__ acc_wave, int lane, int absorb) {
-    const int g_first = absorb ? NQ : 0;
+    const int g_first = qc_flag<AB>(absorb) ? NQ : 0;
     for (int g = n_gates - 1; g >= g_first; --g) {
       const QcGate gt = prog[g];
       const QcTrig tr = trig[g];
@@ -65,8 +115,7 @@ struct SGate {
 };
 
 template <int NQ, int K, bool ADJ, int OP, int BA, int BB, int SLOT>
-__device__ __forceinline__ void qc_static_gate(SV<NQ> (&v)[K], const float c, const float s_in,
-                                               const float* __restrict__ umat) {
+__device__ __forceinline__ void qc_static_gate(SV<NQ> (&v)[K], const float c, const float s_in) {
   const float s = ADJ ? -s_in : s_in;
 #pragma unroll
   for (int q = 0; q < K; ++q) {
@@ -76,8 +125,7 @@ __device__ __forceinline__ void qc_static_gate(SV<NQ> (&v)[K], const float c, co
     else if constexpr (OP == QC_H) g_h<NQ, BA>(v[q]);
     else if constexpr (OP == QC_CNOT) g_cnot<NQ, BA, BB>(v[q]);
     else if constexpr (OP == QC_CRX) g_crx<NQ, BA, BB>(v[q], c, s);
-    else if constexpr (OP == QC_CRZ) g_crz<NQ, BA, BB>(v[q], c, s);
-    else if constexpr (OP == QC_U4) g_u4<NQ, BA, BB>(v[q], umat + (SLOT * 2 + (ADJ ? 1 : 0)) * 32);
+    else if constexpr (OP == QC_CRZ) g_crz<NQ, BA, BB>(v[q], c, s);   // (QC_U4: StatProg::gate)
   }
 }
 
@@ -99,20 +147,33 @@ struct StatProg {
   struct Trig {
     float c[SP::G], s[SP::G];
   };
-  template <int I>
-  __device__ static __forceinline__ void load_one(Trig& t, const QcTrig* __restrict__ trig) {
+  using CMat = const __attribute__((address_space(4))) float*;
+  // the first N gates are RX(theta_w) on wire w with N distinct slots: the layer the embedding can absorb (qc_api.hip)
+  static constexpr bool lead_rx_layer() {
+    if (SP::G < N) return false;
+    for (int w = 0; w < N; ++w) {
+      if (SP::g[w].op != QC_RX || SP::g[w].ba != N - 1 - w || SP::g[w].slot < 0) return false;
+      for (int u = 0; u < w; ++u)
+        if (SP::g[u].slot == SP::g[w].slot) return false;
+    }
+    return true;
+  }
+  static constexpr bool lead_rx = lead_rx_layer();
+  __device__ static __forceinline__ int lead_slot(const QcGate* __restrict__, int w) { return SP::g[w < SP::G ? w : 0].slot; }
+  // AB = 1: the absorbed layer's gates are not run, so their entries are not fetched either
+  template <int I, int AB, class TP>
+  __device__ static __forceinline__ void load_one(Trig& t, TP trig) {
     constexpr SGate g = SP::g[I];
     t.c[I] = 1.f;
     t.s[I] = 0.f;
-    if constexpr (g.op != QC_U4 && g.slot >= 0 && !fused(I)) {
+    if constexpr (g.op != QC_U4 && g.slot >= 0 && !fused(I) && !(AB == 1 && I < N)) {
       t.c[I] = trig[I].c;
       t.s[I] = trig[I].s;
     }
   }
-  template <int... Is>
-  __device__ static __forceinline__ void load_all(Trig& t, const QcTrig* __restrict__ trig,
-                                                  std::integer_sequence<int, Is...>) {
-    (load_one<Is>(t, trig), ...);
+  template <int AB, class TP, int... Is>
+  __device__ static __forceinline__ void load_all(Trig& t, TP trig, std::integer_sequence<int, Is...>) {
+    (load_one<Is, AB>(t, trig), ...);
     __builtin_amdgcn_sched_barrier(0);
   }
   // ---- runs of >= 2 consecutive diagonal gates (RZ / CRZ) are ONE table multiply (tables: qc_fill_diag_tables)
@@ -131,15 +192,22 @@ struct StatProg {
     return r;
   }
   static_assert(run_ordinal(SP::G) <= QC_MAX_DIAG_RUNS, "more fused diagonal runs than the host records (qc_find_diag_runs)");
-  template <int I, bool ADJ, int K>
+  // PIN: the table is requested here, inside the run that consumes it, and not before the state it is applied to
+  // exists (2^N SGPR pairs: not held across the neighbouring gates).  The forward-only kernels, with room for every
+  // table at once, leave the requests to the compiler (!PIN): it issues them in front of the sweep.
+  template <int I, bool ADJ, int K, bool PIN = true>
   __device__ static __forceinline__ void apply_table(SV<N> (&v)[K], const QcTrig* __restrict__ trig) {
-    const QcTrig* tab = trig + SP::G + run_ordinal(I) * (1 << N);
+    constexpr int off = SP::G + run_ordinal(I) * (1 << N);
+    auto run = [&](auto tab) {
 #pragma unroll
-    for (int k = 0; k < (1 << N); ++k) {
-      const float dr = tab[k].c, di = ADJ ? -tab[k].s : tab[k].s;   // adjacent in the table: one SGPR pair
+      for (int k = 0; k < (1 << N); ++k) {
+        const float dr = tab[k].c, di = ADJ ? -tab[k].s : tab[k].s;   // adjacent in the table: one SGPR pair
 #pragma unroll
-      for (int q = 0; q < K; ++q) v[q].a[k] = qc_cmul(dr, di, v[q].a[k]);
-    }
+        for (int q = 0; q < K; ++q) v[q].a[k] = qc_cmul(dr, di, v[q].a[k]);
+      }
+    };
+    if constexpr (PIN) run(qc_const_at(trig, v[0]) + off);
+    else run(trig + off);
   }
   // gradient terms of the gates H, H+1, ..., E-1 of one run from t[k] = Im(conj(lam_k) chi_k) (invariant under
   // the other diagonal gates of the run): signed by the target bit, masked by the control bit
@@ -163,46 +231,65 @@ struct StatProg {
       run_grads<H + 1, E>(t, gacc);
     }
   }
-  template <int I>
+  // one non-diagonal gate; PIN: the 32 scalars of a U4 block are requested here, inside the gate that consumes them
+  template <int I, int K, bool ADJ, bool PIN = true>
+  __device__ static __forceinline__ void gate(SV<N> (&v)[K], const Trig& t, const float* __restrict__ umat) {
+    constexpr SGate g = SP::g[I];
+    if constexpr (g.op == QC_U4) {
+      constexpr int off = (g.slot * 2 + (ADJ ? 1 : 0)) * 32;
+      if constexpr (PIN) {
+        const CMat u = qc_const_at(umat, v[0]) + off;
+#pragma unroll
+        for (int q = 0; q < K; ++q) g_u4<N, g.ba, g.bb>(v[q], u);
+      } else {
+#pragma unroll
+        for (int q = 0; q < K; ++q) g_u4<N, g.ba, g.bb>(v[q], umat + off);
+      }
+    } else {
+      qc_static_gate<N, K, ADJ, g.op, g.ba, g.bb, g.slot>(v, t.c[I], t.s[I]);
+    }
+  }
+  template <int I, int AB, bool PIN>
   __device__ static __forceinline__ void fwd_one(SV<N> (&v)[1], const Trig& t, const float* __restrict__ umat,
                                                  int absorb, const QcTrig* __restrict__ trig) {
-    constexpr SGate g = SP::g[I];
     if constexpr (I < N) {
-      if (absorb) return;   // leading RX layer folded into the embedding angles
+      if (qc_flag<AB>(absorb)) return;   // leading RX layer folded into the embedding angles
     }
     if constexpr (fused(I)) {
       if constexpr (I == run_begin(I)) {
-        apply_table<I, false, 1>(v, trig);
+        apply_table<I, false, 1, PIN>(v, trig);
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
-      qc_static_gate<N, 1, false, g.op, g.ba, g.bb, g.slot>(v, t.c[I], t.s[I], umat);
+      gate<I, 1, false, PIN>(v, t, umat);
       __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from interleaving whole gates (register pressure)
     }
   }
-  template <int... Is>
+  template <int AB, bool PIN, int... Is>
   __device__ static __forceinline__ void fwd_all(SV<N> (&v)[1], const Trig& t, const float* __restrict__ umat,
                                                  int absorb, const QcTrig* __restrict__ trig,
                                                  std::integer_sequence<int, Is...>) {
-    (fwd_one<Is>(v, t, umat, absorb, trig), ...);
+    (fwd_one<Is, AB, PIN>(v, t, umat, absorb, trig), ...);
   }
+  template <int AB = -1, bool PIN = false>
   __device__ static __forceinline__ void fwd(SV<N> (&v)[1], const QcGate* __restrict__, const QcTrig* __restrict__ trig,
                                              const float* __restrict__ umat, int, int absorb) {
     Trig t;
-    load_all(t, trig, std::make_integer_sequence<int, SP::G>{});
-    fwd_all(v, t, umat, absorb, trig, std::make_integer_sequence<int, SP::G>{});
+    if constexpr (PIN) load_all<AB>(t, qc_const(trig), std::make_integer_sequence<int, SP::G>{});
+    else load_all<AB>(t, trig, std::make_integer_sequence<int, SP::G>{});
+    fwd_all<AB, PIN>(v, t, umat, absorb, trig, std::make_integer_sequence<int, SP::G>{});
   }
   // Reverse sweep.  Parameter slots are compile-time constants here, so the wave totals of the
   // gradient terms stay in registers (gacc[slot], valid in lane 63) and reach LDS once, after the
   // sweep, instead of one LDS read-modify-write round trip per gate.
-  template <int J>
+  template <int J, int AB>
   __device__ static __forceinline__ void bwd_one(SV<N> (&cl)[2], const Trig& t, const float* __restrict__ umat,
                                                  float (&gacc)[SP::P > 0 ? SP::P : 1], int absorb,
                                                  const QcTrig* __restrict__ trig) {
     constexpr int I = SP::G - 1 - J;
     constexpr SGate g = SP::g[I];
     if constexpr (I < N) {
-      if (absorb) return;
+      if (qc_flag<AB>(absorb)) return;
     }
     if constexpr (fused(I)) {
       if constexpr (I == run_end(I) - 1) {   // first gate of the run met by the reverse sweep
@@ -219,16 +306,17 @@ struct StatProg {
     } else {
       if constexpr (g.op != QC_U4 && g.slot >= 0)
         gacc[g.slot] += qc_wave_sum_to_lane63(qc_static_grad<N, g.op, g.ba, g.bb>(cl[1], cl[0]));
-      qc_static_gate<N, 2, true, g.op, g.ba, g.bb, g.slot>(cl, t.c[I], t.s[I], umat);
+      gate<I, 2, true>(cl, t, umat);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  template <int... Js>
+  template <int AB, int... Js>
   __device__ static __forceinline__ void bwd_all(SV<N> (&cl)[2], const Trig& t, const float* __restrict__ umat,
                                                  float (&gacc)[SP::P > 0 ? SP::P : 1], int absorb,
                                                  const QcTrig* __restrict__ trig, std::integer_sequence<int, Js...>) {
-    (bwd_one<Js>(cl, t, umat, gacc, absorb, trig), ...);
+    (bwd_one<Js, AB>(cl, t, umat, gacc, absorb, trig), ...);
   }
+  template <int AB = -1>
   __device__ static __forceinline__ void bwd(SV<N> (&cl)[2], const QcGate* __restrict__, const QcTrig* __restrict__ trig,
                                              const float* __restrict__ umat, int, float* __restrict__ acc_wave,
                                              int lane, int absorb) {
@@ -236,24 +324,27 @@ struct StatProg {
 #pragma unroll
     for (int k = 0; k < (SP::P > 0 ? SP::P : 1); ++k) gacc[k] = 0.f;
     Trig t;
-    load_all(t, trig, std::make_integer_sequence<int, SP::G>{});
-    bwd_all(cl, t, umat, gacc, absorb, trig, std::make_integer_sequence<int, SP::G>{});
+    load_all<AB>(t, qc_const(trig), std::make_integer_sequence<int, SP::G>{});
+    bwd_all<AB>(cl, t, umat, gacc, absorb, trig, std::make_integer_sequence<int, SP::G>{});
+    const int k0 = qc_opaque_v(0);   // (one address, constant offsets; the lane test rebuilt here, not held as a mask)
+    const bool last = qc_opaque_v(lane) == 63;
 #pragma unroll
     for (int k = 0; k < SP::P; ++k)
-      if (lane == 63) acc_wave[k] += gacc[k];   // lane 63 holds the wave totals
+      if (last) acc_wave[k0 + k] += gacc[k];   // lane 63 holds the wave totals
   }
 };
 
 // half-angle (cos, sin) of wire w's embedding rotation for one point
+template <int AB = -1>
 __device__ __forceinline__ void qc_wire_sincos(float& c, float& s, const float* __restrict__ a, int64_t B, int64_t p, int w,
                                                const QcTrig* __restrict__ trig, int absorb) {
   // absorb: gate w is RX(theta_w) on wire w, applied right after RX(a_w): one rotation by a_w + theta_w
-  const float h = 0.5f * (a[(int64_t)w * B + p] + (absorb ? trig[w].th : 0.f));
+  const float h = 0.5f * (a[(int64_t)w * B + p] + (qc_flag<AB>(absorb) ? trig[w].th : 0.f));
   sincosf(h, &s, &c);
 }
 // `cs` != nullptr: the block already holds them in LDS as [cos | sin][N][64] (each of the jet kernels' six waves
 // needs the same 2N values for its 64 points: waves 0..N-1 compute one wire each instead of all six computing all)
-template <int N>
+template <int N, int AB = -1>
 __device__ __forceinline__ void load_sincos(float (&ca)[N], float (&sa)[N], const float* __restrict__ a,
                                             int64_t B, int64_t p, const QcTrig* __restrict__ trig, int absorb,
                                             const float* cs = nullptr) {
@@ -263,19 +354,29 @@ __device__ __forceinline__ void load_sincos(float (&ca)[N], float (&sa)[N], cons
       ca[w] = cs[w * 64 + (threadIdx.x & 63)];
       sa[w] = cs[(N + w) * 64 + (threadIdx.x & 63)];
     } else {
-      qc_wire_sincos(ca[w], sa[w], a, B, p, w, trig, absorb);
+      qc_wire_sincos<AB>(ca[w], sa[w], a, B, p, w, trig, absorb);
     }
+  }
+}
+
+// the block's [cos | sin][N][64] table in LDS, unconditionally (no second, computing path in the caller's code)
+template <int N>
+__device__ __forceinline__ void load_sincos_lds(float (&ca)[N], float (&sa)[N], const float* cs) {
+#pragma unroll
+  for (int w = 0; w < N; ++w) {
+    ca[w] = cs[w * 64 + (threadIdx.x & 63)];
+    sa[w] = cs[(N + w) * 64 + (threadIdx.x & 63)];
   }
 }
 
 // Embedding series of channel `ch`'s direction for this lane's point: P0 = phi, P1 = d phi,
 // P2 = d2 phi (only as far as the channel needs).
-template <int N>
+template <int N, int AB = -1>
 __device__ __forceinline__ void channel_series(QcPk<(1 << N)>& P0, QcPk<(1 << N)>& P1, QcPk<(1 << N)>& P2,
                                                int ch, const float* __restrict__ ajets, int64_t B, int64_t pc,
                                                const QcTrig* __restrict__ trig, int absorb, const float* cs = nullptr) {
   float ca[N], sa[N], da[N], dda[N];
-  load_sincos<N>(ca, sa, ajets, B, pc, trig, absorb, cs);
+  load_sincos<N, AB>(ca, sa, ajets, B, pc, trig, absorb, cs);
   const int dirch = ch == 0 ? 0 : (ch <= 3 ? ch : ch - 2);  // channel holding the first derivative
 #pragma unroll
   for (int w = 0; w < N; ++w) {
@@ -289,7 +390,7 @@ __device__ __forceinline__ void channel_series(QcPk<(1 << N)>& P0, QcPk<(1 << N)
 
 // Initial vector of channel `ch`.  amp != 0: amplitude encoding — `ajets` then holds the jets of the
 // (normalised, zero-padded) initial amplitudes themselves (qc_amp.hip): amplitude k = feature k, real.
-template <int N>
+template <int N, int AB = -1>
 __device__ __forceinline__ void build_channel(SV<N>& v, int ch, const float* __restrict__ ajets, int64_t B,
                                               int64_t pc, int amp, const QcTrig* __restrict__ trig, int absorb,
                                               const float* cs = nullptr) {
@@ -302,17 +403,10 @@ __device__ __forceinline__ void build_channel(SV<N>& v, int ch, const float* __r
     return;
   }
   QcPk<(1 << N)> P0, P1, P2;
-  channel_series<N>(P0, P1, P2, ch, ajets, B, pc, trig, absorb, cs);
+  channel_series<N, AB>(P0, P1, P2, ch, ajets, B, pc, trig, absorb, cs);
   if (ch == 0) qc_phase_load<N>(v, P0);
   else if (ch <= 3) qc_phase_load<N>(v, P1);
   else qc_phase_load<N>(v, P2);
-}
-
-// Hides a pointer's provenance from the optimiser: loads through the result are not merged with
-// earlier loads, so values recomputed from them do not stay live in registers in between.
-__device__ __forceinline__ const float* qc_launder(const float* p) {
-  asm volatile("" : "+s"(p));
-  return p;
 }
 
 // ================================================================== value channel only
@@ -349,13 +443,16 @@ __global__ void __launch_bounds__(256) k_value_fwd(const QcGate* __restrict__ pr
   k_value_fwd_body<PG, 4>(blockIdx.x, prog, trig, umat, n_gates, angles, expval, B, amp);
 }
 
-template <class PG, int WPB>
+// AB >= 0 (the merged step's 3-wave stage): angle encoding, the absorb flag = AB at compile time, `amp` not read
+template <class PG, int WPB, int AB = -1>
 __device__ __forceinline__ void k_value_bwd_body(const int64_t bid, const QcGate* __restrict__ prog, const QcTrig* __restrict__ trig,
                                                    const float* __restrict__ umat, int n_gates, int n_params,
                                                    const float* __restrict__ angles, const float* __restrict__ cot,
                                                    float* __restrict__ d_angles, float* __restrict__ part,
                                                    int64_t part_stride, int64_t row0, int64_t B, int amp) {
   constexpr int N = PG::N;
+  const bool ampl = AB < 0 && (amp & 1);
+  const int absorb = AB < 0 ? amp >> 1 : AB;
   extern __shared__ float smem[];  // [WPB waves][n_params]
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   for (int i = threadIdx.x; i < WPB * n_params; i += 64 * WPB) smem[i] = 0.f;
@@ -367,8 +464,8 @@ __device__ __forceinline__ void k_value_bwd_body(const int64_t bid, const QcGate
   SV<N> cl[2];  // [0] = chi, [1] = lambda
   {
     SV<N> v[1];
-    build_channel<N>(v[0], 0, angles, B, pc, amp & 1, trig, amp >> 1);
-    PG::fwd(v, prog, trig, umat, n_gates, amp >> 1);
+    build_channel<N, AB>(v[0], 0, angles, B, pc, ampl, trig, absorb);
+    PG::template fwd<AB, true>(v, prog, trig, umat, n_gates, absorb);   // (pinned requests: the adjoint kernels have no room)
     cl[0] = v[0];
   }
   float qb[N];
@@ -380,25 +477,25 @@ __device__ __forceinline__ void k_value_bwd_body(const int64_t bid, const QcGate
 #pragma unroll
     for (int k = 0; k < (1 << N); ++k) cl[1].a[k] = qc_dup(d[k]) * cl[0].a[k];
   }
-  PG::bwd(cl, prog, trig, umat, n_gates, smem + wave * n_params, lane, amp >> 1);
+  PG::template bwd<AB>(cl, prog, trig, umat, n_gates, smem + wave * n_params, lane, absorb);
   float T[N];
-  if (amp & 1) {   // d L / d(initial amplitude k) = 2 Re Lambda_k  (the initial amplitudes are real)
+  if (ampl) {   // d L / d(initial amplitude k) = 2 Re Lambda_k  (the initial amplitudes are real)
 #pragma unroll
     for (int w = 0; w < N; ++w) T[w] = 2.f * cl[1].a[w].x;
   } else {
     QcPk<(1 << N)> Q0, Q1, Q2;
-    channel_series<N>(Q0, Q1, Q2, 0, qc_launder(angles), B, pc, trig, amp >> 1);
+    channel_series<N, AB>(Q0, Q1, Q2, 0, qc_launder(angles), B, pc, trig, absorb);
     qc_embed_ip<N>(T, cl[1], Q0);
   }
   if (live) {
 #pragma unroll
     for (int w = 0; w < N; ++w) d_angles[(int64_t)w * B + p] = T[w];
   }
-  if (amp >> 1) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
+  if (qc_flag<AB>(absorb)) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
 #pragma unroll
     for (int w = 0; w < N; ++w) {
       const float tot = qc_wave_sum_to_lane63(live ? T[w] : 0.f);
-      if (lane == 63) smem[wave * n_params + prog[w].slot] += tot;
+      if (lane == 63) smem[wave * n_params + (AB < 0 ? prog[w].slot : PG::lead_slot(prog, w))] += tot;
     }
   }
   __syncthreads();
@@ -549,7 +646,7 @@ __device__ __forceinline__ void k_jets_bwd_body(const int64_t bid, const QcGate*
   } else {
     SV<N> v[1];
     build_channel<N>(v[0], ch, ajets, B, pc, amp & 1, trig, amp >> 1);
-    PG::fwd(v, prog, trig, umat, n_gates, amp >> 1);
+    PG::template fwd<-1, true>(v, prog, trig, umat, n_gates, amp >> 1);
     cl[0] = v[0];
   }
   // The other channels' final states: through LDS when this launch computed them, straight from the
@@ -692,20 +789,23 @@ __global__ void __launch_bounds__(384, QC_JB_WAVES) k_jets_bwd(const QcGate* __r
 //     turn comes (second in its wave), instead of 160 extra global loads and five extra D-vector builds up front;
 //   * 2 block barriers instead of 3, per-gate wave reductions accumulate over both channels in registers of the
 //     same wave, cross-wave traffic in the tail shrinks to the one row that sums over all channels.
-template <class PG>
+// Angle encoding only; ABSORB (leading RX layer folded into the embedding) is fixed when the kernel is compiled.
+// `row_of()` returns the tile's partial row and n_params; it is asked for after the last barrier, so that what it is
+// computed from (part, its stride, the first row, the tile index) is not held through the sweeps.
+struct QcPartRow {
+  float* row;
+  int n_params;
+};
+template <class PG, bool ABSORB, class ROW>
 __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate* __restrict__ prog, const QcTrig* __restrict__ trig,
                                                    const float* __restrict__ umat, int n_gates, int n_params,
                                                    const float* __restrict__ ajets, const float* __restrict__ qbar,
-                                                   float* __restrict__ abar, float* __restrict__ part,
-                                                   int64_t part_stride, int64_t row0, int64_t B,
-                                                   const float* __restrict__ chi_store, int amp, int stagger = 0) {
+                                                   float* __restrict__ abar, const ROW row_of, int64_t B,
+                                                   const float* __restrict__ chi_store) {
   constexpr int N = PG::N;
   constexpr int A2 = 2 << N;
   constexpr int NA = 1 << N;
-  // diagnostic (timing only, results wrong): bit 7 of the flags = every block reads the final states of tile 0, i.e.
-  // from cache - what the stage would take if its 56 MB of final states did not have to come from HBM / Infinity Cache
-  const bool same_tile = (amp & 0x80) != 0;
-  amp &= 0x7f;
+  constexpr int AB = ABSORB ? 1 : 0;
   extern __shared__ float smem[];
   float* s_l0 = smem;                          // [3 waves][A2][64]: shares of lam_0
   float* s_t0 = s_l0 + 3 * A2 * 64;            // [2][N][64]: waves 1, 2: their channels' terms of abar[0]
@@ -717,14 +817,8 @@ __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate
   const bool live = p < B;
   const int64_t pc = live ? p : B - 1;
   for (int i = threadIdx.x; i < 3 * n_params; i += 192) s_acc[i] = 0.f;
-  // every second tile can start late (stagger x 8 128 cycles): the whole grid is resident in one round, so all waves
-  // load at the same time and then all sweep at the same time (HBM and VALU take turns instead of overlapping)
-  if (stagger > 0 && (bid & 1)) {
-#pragma unroll 1
-    for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
   // wires wv, wv + 3, ... of the embedding half-angles
-  for (int w = wv; w < N; w += 3) qc_wire_sincos(s_cs[w * 64 + lane], s_cs[(N + w) * 64 + lane], ajets, B, pc, w, trig, amp >> 1);
+  for (int w = wv; w < N; w += 3) qc_wire_sincos<AB>(s_cs[w * 64 + lane], s_cs[(N + w) * 64 + lane], ajets, B, pc, w, trig, AB);
   // the point index as an opaque value: addresses derived from it are recomputed at their use instead of being hoisted
   // above the two-channel loop and held (or spilled) for the whole kernel
   auto pcf = [&]() {
@@ -732,18 +826,20 @@ __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate
     asm volatile("" : "+v"(v));
     return v;
   };
+  // the wave index as an opaque value, for the same reason (it and the channel numbers are rebuilt per sweep and in
+  // the tail from the thread index, a register that lives anyway)
+  auto wvf = [&]() { return __builtin_amdgcn_readfirstlane(qc_opaque_v((int)threadIdx.x) >> 6); };
   const int cha = wv == 0 ? 1 : wv + 1;        // first channel of this wave: t, x, y
   const int chb = wv == 0 ? 0 : wv + 3;        // second: value, xx, yy
 
   const qf2* chi2 = reinterpret_cast<const qf2*>(chi_store);
   qf2* s_l02 = reinterpret_cast<qf2*>(s_l0);     // [3 waves][amplitude][64]
-  auto pcs = [&]() { return same_tile ? (int64_t)(threadIdx.x & 63) : pcf(); };   // point index for final-state reads
-  auto load_chi = [&](SV<N>& v, int c) { qc_chi_read<N>(v, chi_store, c, pcs()); };
+  auto load_chi = [&](SV<N>& v, int c) { qc_chi_read<N>(v, chi_store, c, pcf()); };
   auto dvec = [&](int c, QcPk<NA>& d) {
     float qb[N];
-    const int64_t pq = pcf();
+    const int64_t pq = pcf(), Bq = qc_opaque_s(B);   // (row addresses rebuilt per call, not held between calls)
 #pragma unroll
-    for (int w = 0; w < N; ++w) qb[w] = live ? qbar[((int64_t)c * N + w) * B + pq] : 0.f;
+    for (int w = 0; w < N; ++w) qb[w] = live ? qbar[((int64_t)c * N + w) * Bq + pq] : 0.f;
     qc_sign_sums<N>(d, qb);
   };
 
@@ -765,7 +861,7 @@ __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate
         cl[1].a[k] *= qc_dup(da_[k]);
       }
     } else {                  // lam_x = D_x chi_0 + 2 D_xx chi_x (the same for y)
-      const int64_t pqs = pcs();
+      const int64_t pqs = pcf();
 #pragma unroll
       for (int k = 0; k < NA; ++k)
         mine[k * 64 + lane] = qc_pk_fma(qc_dup(da_[k]), cl[0].a[k], qc_dup(d[k]) * chi2[qc_chi_pair<A2>(chb, k, pqs)]);
@@ -784,32 +880,34 @@ __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate
 
 #pragma unroll 1
   for (int half = 0; half < 2; ++half) {
-    const int ch = half == 0 ? cha : chb;
+    const int wq = wvf();
+    const int chb = wq == 0 ? 0 : wq + 3;
+    const int ch = half == 0 ? (wq == 0 ? 1 : wq + 1) : chb;
     if (half == 1) {
       load_chi(cl[0], chb);
-      if (wv == 0) {          // lam_0: the three shares
+      if (wq == 0) {          // lam_0: the three shares
 #pragma unroll
         for (int k = 0; k < NA; ++k)
           cl[1].a[k] = (s_l02[k * 64 + lane] + s_l02[(NA + k) * 64 + lane]) + s_l02[(2 * NA + k) * 64 + lane];
       } else {                // lam_xx = D_xx chi_0
         dvec(chb, d);
-        const int64_t pqs = pcs();
+        const int64_t pqs = pcf();
 #pragma unroll
         for (int k = 0; k < NA; ++k) cl[1].a[k] = qc_dup(d[k]) * chi2[qc_chi_pair<A2>(0, k, pqs)];
       }
     }
-    PG::bwd(cl, prog, trig, umat, n_gates, s_acc + wv * n_params, lane, amp >> 1);
+    PG::template bwd<AB>(cl, prog, trig, umat, n_gates, s_acc + wq * n_params, lane, AB);
 
     // cotangents of the angle jets in the frame pulled back through the embedding (qc_gates.h)
     float ca[N], sa[N], da[N], dda[N];
-    const int64_t pq = pcf();
-    load_sincos<N>(ca, sa, aj, B, pq, trig, amp >> 1, s_cs);
+    const int64_t pq = pcf(), Bq = qc_opaque_s(B);
+    load_sincos_lds<N>(ca, sa, s_cs);
     qc_unembed<N>(cl[1], ca, sa);
     const int dirch = ch == 0 ? 0 : (ch <= 3 ? ch : ch - 2);
 #pragma unroll
     for (int w = 0; w < N; ++w) {
-      da[w] = ch >= 1 ? aj[((int64_t)dirch * N + w) * B + pq] : 0.f;
-      dda[w] = ch >= 4 ? aj[((int64_t)ch * N + w) * B + pq] : 0.f;
+      da[w] = ch >= 1 ? aj[((int64_t)dirch * N + w) * Bq + pq] : 0.f;
+      dda[w] = ch >= 4 ? aj[((int64_t)ch * N + w) * Bq + pq] : 0.f;
     }
     float T[N];
     if (ch == 0) {
@@ -833,33 +931,35 @@ __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate
       qc_pull_ip0<N>(T, cl[1]);
       if (live) {
 #pragma unroll
-        for (int w = 0; w < N; ++w) abar[((int64_t)ch * N + w) * B + p] = T[w];   // abar[xx] = ip0(mu_xx)
+        for (int w = 0; w < N; ++w) abar[((int64_t)ch * N + w) * Bq + p] = T[w];   // abar[xx] = ip0(mu_xx)
       }
     }
   }
+  const int wt = wvf();
   if (live) {
 #pragma unroll
-    for (int w = 0; w < N; ++w) abar[((int64_t)cha * N + w) * B + p] = t_a1[w];
+    for (int w = 0; w < N; ++w) abar[((int64_t)(wt == 0 ? 1 : wt + 1) * N + w) * B + p] = t_a1[w];
   }
-  if (wv != 0) {
+  if (wt != 0) {
 #pragma unroll
-    for (int w = 0; w < N; ++w) s_t0[((wv - 1) * N + w) * 64 + lane] = t_own[w];
+    for (int w = 0; w < N; ++w) s_t0[((wt - 1) * N + w) * 64 + lane] = t_own[w];
   }
   __syncthreads();
-  if (wv == 0) {
+  if (wt == 0) {
 #pragma unroll
     for (int w = 0; w < N; ++w) {
       const float r = (t_own[w] + s_t0[w * 64 + lane]) + s_t0[(N + w) * 64 + lane];
       if (live) abar[(int64_t)w * B + p] = r;
-      if (amp >> 1) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
+      if constexpr (ABSORB) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
         const float tot = qc_wave_sum_to_lane63(live ? r : 0.f);
-        if (lane == 63) s_acc[prog[w].slot] += tot;
+        if (lane == 63) s_acc[PG::lead_slot(prog, w)] += tot;
       }
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < n_params; i += 192)
-    part[(row0 + bid) * part_stride + i] = (s_acc[i] + s_acc[n_params + i]) + s_acc[2 * n_params + i];
+  const QcPartRow pr = row_of();
+  float* __restrict__ row = pr.row;
+  for (int i = threadIdx.x; i < pr.n_params; i += 192) row[i] = (s_acc[i] + s_acc[pr.n_params + i]) + s_acc[2 * pr.n_params + i];
 }
 
 // ---- residual + value tiles in one launch (see qc_mlp.hip): blocks [0, n_val) run the value-channel kernel on
@@ -888,21 +988,59 @@ __global__ void __launch_bounds__(384, QC_JB_WAVES) k_circ_bwd_both(
                             row0_v, Bv, amp);
 }
 
-// the same stage with 3-wave blocks (k_jets_bwd2_body); angle encoding only (the merged step's precondition)
-template <class PG>
-__global__ void __launch_bounds__(192, 4) k_circ_bwd_both2(
-    const QcGate* __restrict__ prog, const QcTrig* __restrict__ trig, const float* __restrict__ umat, int n_gates, int n_params,
-    const float* __restrict__ ajets, const float* __restrict__ qbar, float* __restrict__ abar, int64_t row0_r, int64_t Br,
-    const float* __restrict__ chi_store, const float* __restrict__ angles, const float* __restrict__ cot,
-    float* __restrict__ d_angles, int64_t row0_v, int64_t Bv, float* __restrict__ part, int64_t part_stride, int amp, int n_val) {
-  const int stagger = (amp >> 8) & 0xff;   // (launcher: bits 8.. of the flags word)
-  amp &= 0xff;
-  if ((int)blockIdx.x >= n_val)
-    k_jets_bwd2_body<PG>(blockIdx.x - n_val, prog, trig, umat, n_gates, n_params, ajets, qbar, abar, part, part_stride, row0_r, Br,
-                         chi_store, amp, stagger);
-  else
-    k_value_bwd_body<PG, 3>(blockIdx.x, prog, trig, umat, n_gates, n_params, angles, cot, d_angles, part, part_stride,
-                            row0_v, Bv, amp);
+// the same stage with 3-wave blocks (k_jets_bwd2_body); angle encoding only (the merged step's precondition), the
+// absorb flag a template parameter.  The arguments of the two bodies travel as two by-value records inside the one
+// kernel argument, and a block reads only what its own body needs, inside its branch: the argument is read through the
+// kernel-argument segment itself (explicit arguments start at its offset 0, AMDGPU ABI) behind an opaque pointer, so
+// the requests cannot be merged into one wide load at the kernel's entry and held (or spilled) by both bodies.
+struct QcBwdResArgs {
+  const float* ajets;
+  const float* qbar;
+  float* abar;
+  const float* chi_store;
+  int64_t row0, B;
+};
+struct QcBwdValArgs {
+  const float* angles;
+  const float* cot;
+  float* d_angles;
+  int64_t row0, B;
+};
+struct QcBwd2Args {
+  const QcGate* prog;
+  const QcTrig* trig;
+  const float* umat;
+  int n_gates, n_params;
+  float* part;
+  int64_t part_stride;
+  int n_val;
+  QcBwdResArgs res;
+  QcBwdValArgs val;
+};
+template <class PG, bool ABSORB>
+__global__ void __launch_bounds__(192, 4) k_circ_bwd_both2(const QcBwd2Args) {
+  using Args = const __attribute__((address_space(4))) QcBwd2Args*;
+  const Args a0 = (Args)__builtin_amdgcn_kernarg_segment_ptr();
+  auto args = [&]() {
+    Args a = a0;
+    asm volatile("" : "+s"(a));
+    return a;
+  };
+  const int n_val = a0->n_val;
+  if ((int)blockIdx.x >= n_val) {
+    const Args a = args();
+    k_jets_bwd2_body<PG, ABSORB>(
+        blockIdx.x - n_val, a->prog, a->trig, a->umat, a->n_gates, a->n_params, a->res.ajets, a->res.qbar, a->res.abar,
+        [&]() {
+          const Args t = args();
+          return QcPartRow{t->part + (t->res.row0 + ((int)blockIdx.x - t->n_val)) * t->part_stride, t->n_params};
+        },
+        a->res.B, a->res.chi_store);
+  } else {
+    const Args a = args();
+    k_value_bwd_body<PG, 3, ABSORB ? 1 : 0>(blockIdx.x, a->prog, a->trig, a->umat, a->n_gates, a->n_params, a->val.angles,
+                                            a->val.cot, a->val.d_angles, a->part, a->part_stride, a->val.row0, a->val.B, 0);
+  }
 }
 
 }  // namespace
@@ -985,18 +1123,21 @@ struct RegLaunch {
                            const float* angles, const float* cot, float* d_angles, int64_t row0_v, int64_t Bv, float* part,
                            int64_t part_stride, hipStream_t st) {
     static const bool six = [] { const char* e = getenv("QC_BWD6"); return e && e[0] == '1'; }();   // A/B: the six-wave form
-    static const int stagger = [] { const char* e = getenv("QC_BWD2_STAGGER"); return e ? atoi(e) & 0xff : 0; }();
     if (!six && !pg->amplitude) {
       const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 192);
-      // QC_BWD2_LDS_KB=k (diagnostic, A/B): k KB of unused dynamic LDS per block lower the blocks per CU, so that the grid
-      // runs in more than one round and the load phases of later blocks overlap the sweeps of earlier ones
-      static const int same_tile = [] { const char* e = getenv("QC_BWD2_SAMETILE"); return (e && e[0] == '1') ? 0x80 : 0; }();
-      static const size_t pad = [] { const char* e = getenv("QC_BWD2_LDS_KB"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();
-      const size_t sh = ((size_t)3 * (2u << PG::N) * 64 + (size_t)4 * PG::N * 64 + (size_t)3 * pg->n_params) * sizeof(float) + pad;
-      if (pad) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_circ_bwd_both2<PG>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(k_circ_bwd_both2<PG>, dim3(nr + nv), dim3(192), sh, st, pg->d_gates, trig, umat, pg->n_gates,
-                         pg->n_params, ajets, qbar, abar, row0_r, Br, chi_store, angles, cot, d_angles, row0_v, Bv, part,
-                         part_stride, qc_embed_flags(pg) | (stagger << 8) | same_tile, nv);
+      const size_t sh = ((size_t)3 * (2u << PG::N) * 64 + (size_t)4 * PG::N * 64 + (size_t)3 * pg->n_params) * sizeof(float);
+      const QcBwd2Args args = {pg->d_gates, trig, umat, pg->n_gates, pg->n_params, part, part_stride, nv,
+                               {ajets, qbar, abar, chi_store, row0_r, Br}, {angles, cot, d_angles, row0_v, Bv}};
+      const bool absorb = (qc_embed_flags(pg) & 2) != 0;
+      if constexpr (PG::lead_rx) {   // (a program without the layer never asks for the absorbed form)
+        if (absorb) {
+          hipLaunchKernelGGL((k_circ_bwd_both2<PG, true>), dim3(nr + nv), dim3(192), sh, st, args);
+          return QC_OK;
+        }
+      } else if (absorb) {
+        return QC_ERR_UNSUPPORTED;
+      }
+      hipLaunchKernelGGL((k_circ_bwd_both2<PG, false>), dim3(nr + nv), dim3(192), sh, st, args);
       return QC_OK;
     }
     const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 384);
