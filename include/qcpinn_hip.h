@@ -423,6 +423,72 @@ int qc_sample_dataset_adaptive(float* X_res_dev, float* target_res_dev, int64_t 
 int qc_fused_pinn_adaptive_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef,
                                 const qc_step_adapt* adapt, int phases, void* stream);
 
+/* ---- systems of equations behind one shared network: a model with K outputs (W4[K][H], b4[K]) trained on n_eq
+ * residuals, the operator given as DATA, one term list per step.  Replaces navier_stokes_2D_operator (nn/pde.py:2-27: u, v, p
+ * from one network, continuity and two momentum equations), the three MSEs, autograd and the optimiser of its training
+ * loop by one fused step; Burgers systems, shallow water, Gray-Scott and Lotka-Volterra have the same shape.
+ *   res_e(p) = sum over the terms t with t.eq == e of
+ *              t.coef * q[t.out][t.chan](p) * (t.mul0 >= 0 ? u[t.mul0](p) : 1) * (t.mul1 >= 0 ? u[t.mul1](p) : 1),
+ * q[k][c] channel c (value, t, x, y, xx, yy) of output k and u[k] = q[k][0].  Navier-Stokes takes 14 terms; two
+ * multipliers cover cubic reactions such as u v^2.  The loss columns stay three:
+ *   L_r = sum_e w_eq[e] mean_p (res_e - r_e)^2,   L_bc, L_ic = sum_k w_out[k] mean (u_k - target_k)^2
+ * over the BC / IC points (w_out[k] = 0: output k is not prescribed there, e.g. the pressure), and the loss is
+ * w_res L_r + w_bc L_bc + w_ic L_ic of qc_opt_hyper as in every other step.
+ * Flat parameter layout (= model.parameters() of the K-output model): W1 b1 W2 b2 | W3 b3 W4[K][H] b4[K] | theta,
+ * NP_K = NP + (K - 1)(H + 1) entries; K = 1 is the layout at the head of this file. */
+#define QC_KMAX 4         /* outputs */
+#define QC_EQMAX 4        /* equations */
+#define QC_TERMS_MAX 32   /* terms of all equations together */
+typedef struct qc_sys_term {
+  int32_t eq, out, chan;   /* 0 <= eq < n_eq, 0 <= out < K, 0 <= chan <= 5 */
+  int32_t mul0, mul1;      /* -1 (no factor) or an output 0 .. K - 1 */
+  float coef;              /* finite */
+} qc_sys_term;
+
+typedef struct qc_step_system {
+  int32_t K, n_eq, n_terms;
+  qc_sys_term terms[QC_TERMS_MAX];
+  float w_eq[QC_EQMAX], w_out[QC_KMAX];   /* finite; entries from n_eq / K on are not read */
+  float* target_res_dev;   /* [n_eq][B_res] batch-minor residual targets of the current batch, or NULL: zero */
+  float* target_val_dev;   /* [K][B_val] batch-minor value targets, IC points first, then BC (required with B_val > 0) */
+  /* resident dataset for QC_PHASE_SAMPLE: the point arrays of qc_step_data and row-major target tables */
+  const float* ds_X_res; const float* ds_r;    int64_t ds_n_res;   /* [N][3], [N][n_eq] or NULL (zero targets: then
+                                                                      target_res_dev is not written) */
+  const float* ds_X_ic;  const float* ds_u_ic; int64_t ds_n_ic;    /* [N][3], [N][K] */
+  const float* ds_X_bc;  const float* ds_u_bc; int64_t ds_n_bc;
+} qc_step_system;
+
+/* The post stage of the system step alone (the analogue of qc_post_data / qc_post_coef): ONE kernel per 64-point tile for
+ * the hidden layer, the channels of the K outputs, residuals, loss columns, cotangents and the reverse pass.
+ * params_dev: the K-row flat layout.  nch = 6, residual points: target_dev = [n_eq][B] or NULL (zero); per point and
+ * equation g_e = pde->w_res w_eq[e] (res_e - r_e), loss column 0 gets sum_e w_eq[e] (res_e - r_e)^2 pde->inv_n_res.
+ * nch = 1, value points (the first pde->n_seg_a are IC points): target_dev = [K][B], required; the cotangent of u_k is
+ * (w_val_a | w_val_b) w_out[k] (u_k - target_k), loss columns 2 (IC) / 1 (BC) get w_out[k] (u_k - target_k)^2 inv_n_a | inv_n_b.
+ * Writes qbar_dev [nch][n][B] and, in row row0 + tile of part_dev, the columns of W3, b3, W4[K][H], b4[K] and the three
+ * loss columns at NP_K .. NP_K + 2 (part_stride >= NP_K + 3); nothing else.  sys->target_* and sys->ds_* are not read.
+ * QC_ERR_ARG: K, n_eq, n_terms or a term field out of range, a non-finite coef / w_eq / w_out, a NULL buffer. */
+int qc_post_system(const float* params_dev, int H, int n, int n_theta, const qc_step_system* sys, const qc_pde* pde,
+                   const float* qjets_dev, const float* target_dev, float* qbar_dev, float* part_dev, int64_t part_stride,
+                   int64_t row0, int64_t B, int nch, void* stream);
+
+/* qc_sample_dataset for a system's dataset: the same Philox counter and the same row index, so for the same seed, step and
+ * offsets the same rows; target rows are written batch-minor, target_res_dev[e * n_res + i] = ds_r[idx * n_eq + e],
+ * target_val_dev[k * (n_ic + n_bc) + i] = ds_u[idx * K + k].  With sys->ds_r or target_res_dev NULL the residual
+ * targets are not written.  The buffers are arguments; sys->target_* are not read.  QC_ERR_ARG as qc_sample_dataset,
+ * and for K or n_eq out of range. */
+int qc_sample_dataset_system(float* X_res_dev, float* target_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev,
+                             float* target_val_dev, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                             const qc_step_system* sys, uint64_t seed, uint64_t step, void* stream);
+
+/* The fused step on a system: same descriptor, phases (QC_PHASE_SAMPLE gathers points and target rows from sys->ds_*),
+ * workspace rules and comm handling as qc_fused_pinn_data_step; params_dev, m_dev, v_dev hold NP_K entries, flat_dev =
+ * [grad[NP_K] | L_r, L_bc, L_ic].  desc->pde supplies w_res, inv_n_res, w_val_*, inv_n_* and n_seg_a (its operator
+ * coefficients and problem id are not read).  All circuit families and both encodings; the step runs in the two-stream form.
+ * QC_ERR_ARG before any launch: sys NULL; K, n_eq or n_terms out of range; a term field out of range; a non-finite coef,
+ * w_eq or w_out; target_val_dev NULL with B_val > 0; QC_PHASE_SAMPLE with an absent or empty segment behind a non-empty
+ * batch, or one of 2^31 rows or more; part_stride < NP_K + 3; whatever qc_fused_pinn_data_step refuses of the descriptor. */
+int qc_fused_pinn_system_step(const qc_step_desc* desc, const qc_step_system* sys, int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

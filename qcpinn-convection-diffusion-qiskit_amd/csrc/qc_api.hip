@@ -4,6 +4,8 @@
 #include "qc_wave_sched.h"
 #include "../../include/qcpinn_hip.h"
 
+#include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -15,6 +17,9 @@ static_assert(QC_PB_CONVECTION_DIFFUSION == QC_PROBLEM_CONVECTION_DIFFUSION && Q
 static_assert(QC_COEF_N == QC_COEF_COLS, "coefficient columns");
 static_assert(QC_FACE_RANDOM == QC_BC_RANDOM_FACE, "boundary rule");
 static_assert(sizeof(QcOptHyper) == sizeof(qc_opt_hyper), "qc_opt_hyper layout");
+static_assert(QC_SYS_K == QC_KMAX && QC_SYS_EQ == QC_EQMAX && QC_SYS_TERMS == QC_TERMS_MAX, "system limits");
+static_assert(sizeof(QcSysTerm) == sizeof(qc_sys_term) && ((sizeof(QcSys) + 7) & ~(size_t)7) == offsetof(qc_step_system, target_res_dev),
+              "qc_step_system head");
 
 static thread_local int g_last_hip = 0;
 
@@ -713,6 +718,65 @@ int qc_fused_step_stage(const qc_step_desc* d, int stage, void* stream) {
   return after_launch();
 }
 
+// ---- systems: K outputs, the operator as a term list
+// THE validity rule of a system's operator: counts in range, every term field in range, finite coefficients and weights
+static bool sys_ok(const qc_step_system* s) {
+  if (!s || s->K < 1 || s->K > QC_KMAX || s->n_eq < 1 || s->n_eq > QC_EQMAX || s->n_terms < 1 || s->n_terms > QC_TERMS_MAX)
+    return false;
+  for (int t = 0; t < s->n_terms; ++t) {
+    const qc_sys_term& m = s->terms[t];
+    if (m.eq < 0 || m.eq >= s->n_eq || m.out < 0 || m.out >= s->K || m.chan < 0 || m.chan >= QC_NCH) return false;
+    if (m.mul0 < -1 || m.mul0 >= s->K || m.mul1 < -1 || m.mul1 >= s->K || !isfinite(m.coef)) return false;
+  }
+  for (int e = 0; e < s->n_eq; ++e)
+    if (!isfinite(s->w_eq[e])) return false;
+  for (int k = 0; k < s->K; ++k)
+    if (!isfinite(s->w_out[k])) return false;
+  return true;
+}
+static QcSys to_sys(const qc_step_system* s) {   // the head of the record; unused slots zeroed
+  QcSys q;
+  memset(&q, 0, sizeof(q));
+  q.K = s->K; q.n_eq = s->n_eq; q.n_terms = s->n_terms;
+  memcpy(q.terms, s->terms, sizeof(QcSysTerm) * s->n_terms);
+  for (int e = 0; e < s->n_eq; ++e) q.w_eq[e] = s->w_eq[e];
+  for (int k = 0; k < s->K; ++k) q.w_out[k] = s->w_out[k];
+  return q;
+}
+
+int qc_post_system(const float* prm, int H, int n, int n_theta, const qc_step_system* sys, const qc_pde* pde,
+                   const float* qjets, const float* target, float* qbar, float* part, int64_t part_stride, int64_t row0,
+                   int64_t B, int nch, void* stream) {
+  int rc = check_mlp(H, n, n_theta, B, nch);
+  if (rc) return rc;
+  if (!sys_ok(sys) || !prm || !pde || !qjets || !qbar || !part || row0 < 0 || (nch == 1 && !target)) return QC_ERR_ARG;
+  const QcLayout L = qc_layout(H, n, n_theta, sys->K);
+  if (part_stride < L.NP + 3) return QC_ERR_ARG;
+  rc = qc_mlp_post_system(prm, L, to_sys(sys), to_pde(pde), qjets, target, qbar, part, part_stride, row0, B, nch,
+                          (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+// a system's dataset as a source: uniform rows, target rows of n_eq / K floats
+static QcSource system_source(const qc_step_system* s) {
+  QcSource src;
+  src.kind = QC_SOURCE_ROWS;
+  src.res = {s->ds_X_res, s->ds_r, s->ds_n_res};
+  src.ic = {s->ds_X_ic, s->ds_u_ic, s->ds_n_ic};
+  src.bc = {s->ds_X_bc, s->ds_u_bc, s->ds_n_bc};
+  src.w_res = s->n_eq;
+  src.w_val = s->K;
+  return src;
+}
+
+int qc_sample_dataset_system(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
+                             int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const qc_step_system* sys,
+                             uint64_t seed, uint64_t step, void* stream) {
+  if (!sys || sys->K < 1 || sys->K > QC_KMAX || sys->n_eq < 1 || sys->n_eq > QC_EQMAX) return QC_ERR_ARG;
+  return fill_batches({X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, seed, step},
+                      system_source(sys), stream);
+}
+
 // One pipeline of the two-stream step: the value pipeline (nch = 1) or the residual pipeline (nch = 6)
 struct QcPipe {
   const float* X;
@@ -734,19 +798,25 @@ static int pipe_forward(const qc_step_desc* d, const QcPipe& q, hipStream_t st) 
 }
 
 // forward half -> post -> circuit adjoint -> [amplitude adjoint] -> pre adjoint, on one stream
-static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, const QcTarget& tg) {
+// `sys` (the system step): the K-row layout, and the system post stage on the pipeline's targets in place of post_impl
+static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, const QcTarget& tg,
+                        const qc_step_system* sys = nullptr) {
   const qc_program* p = d->prog;
   const int n = d->n, H = d->H;
   const QcTrig* trig = (const QcTrig*)d->trig_dev;
-  float* part_theta = d->part_dev + make_layout(H, n, d->n_theta).oTh;
+  float* part_theta = d->part_dev + qc_layout(H, n, d->n_theta, sys ? sys->K : 1).oTh;
   if (!q.X || !q.ajets || !q.qjets || !q.qbar || !q.abar || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
   int rc;
   if ((rc = pipe_forward(d, q, st))) return rc;
   const float* cin = q.u ? q.u : q.ajets;
   float* cout = q.u ? q.ub : q.abar;
   // abar is written only by the adjoint sweep below: its head serves as per-point cotangent scratch here
-  if ((rc = post_impl(2, q.X, d->params_dev, H, n, d->n_theta, &d->pde, q.qjets, q.abar, q.nch == 6 ? q.abar + q.B : nullptr,
-                      nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tg))) return rc;
+  if (sys) {
+    if ((rc = qc_post_system(d->params_dev, H, n, d->n_theta, sys, &d->pde, q.qjets,
+                             q.nch == 6 ? sys->target_res_dev : sys->target_val_dev, q.qbar, d->part_dev, d->part_stride,
+                             q.row0, q.B, q.nch, st))) return rc;
+  } else if ((rc = post_impl(2, q.X, d->params_dev, H, n, d->n_theta, &d->pde, q.qjets, q.abar, q.nch == 6 ? q.abar + q.B : nullptr,
+                             nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tg))) return rc;
   if ((rc = p->fam->bwd(p, trig, d->umat_dev, cin, q.qbar, cout, part_theta, d->part_stride, q.row0, q.B, q.nch, q.store, st)) ||
       (rc = after_launch())) return rc;
   if (q.u && (rc = qc_amp_backward(q.ajets, q.ub, q.abar, n, q.B, q.nch, st))) return rc;
@@ -758,14 +828,16 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
 // operator from, and in `src`, where QC_PHASE_SAMPLE takes the batches `b` from.  The dataset kinds gather rows and targets
 // (and operator rows) AHEAD of the stages, in the merged form too (the merged pre stage then runs with its own draw off,
 // so its instantiations are the analytic step's); nothing else in the step depends on the source.
+// `sys` (qc_fused_pinn_system_step, validated by its entry): K last-layer rows in the layout, the system post stage in
+// both pipelines, always the two-stream form; `tg` is then not read.
 static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches& b, const QcSource& src, int phases,
-                      void* stream) {
+                      void* stream, const qc_step_system* sys = nullptr) {
   if (!d->part_dev || !d->flat_dev || !src.holds(b)) return QC_ERR_ARG;
-  if ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem)) return QC_ERR_ARG;
+  if (!sys && ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem))) return QC_ERR_ARG;
   int rc = check_step_desc(d, false, nullptr);
   if (rc) return rc;
   const int n = d->n, H = d->H;
-  const QcLayout L = make_layout(H, n, d->n_theta);
+  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1);
   const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
   const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
   const int64_t rows = rows_res + rows_val;
@@ -774,12 +846,12 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   const QcStepLayout ws = step_layout(d->prog, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
 
   // (in the merged form below the first stage draws the points itself)
-  const bool draw_in_stage = src.kind == QC_SOURCE_DRAW && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);
+  const bool draw_in_stage = src.kind == QC_SOURCE_DRAW && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);   // (never a system's)
   if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage && (rc = fill_batches(b, src, st))) return rc;
   // register family, angle encoding, both pipelines present, final-state store available: every stage is ONE launch
   // over the value tiles and the residual tiles together (no side stream, 9 launches per step); QC_NO_MERGE=1 keeps
   // the two-stream form below
-  const bool merged = (phases & QC_PHASE_GRADS) && merged_ok(d);
+  const bool merged = !sys && (phases & QC_PHASE_GRADS) && merged_ok(d);
   if (merged) {
     for (int stage = 0; stage < QC_STAGE_COUNT; ++stage)
       if ((rc = merged_stage(d, stage, st, draw_in_stage && stage == QC_STAGE_PRE_FWD, tg))) return rc;
@@ -801,8 +873,8 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
                         ws.ub_val, d->B_val, rows_res, 1, ws.val};
     const QcPipe res = {d->X_res_dev, d->ajets_res_dev, d->qjets_res_dev, d->qbar_res_dev, d->abar_res_dev, ws.u_res,
                         ws.ub_res, d->B_res, 0, 6, ws.res};
-    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, tg.value_side()))) return rc;
-    if (d->B_res > 0 && (rc = run_pipeline(d, res, st, tg))) return rc;
+    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, tg.value_side(), sys))) return rc;
+    if (d->B_res > 0 && (rc = run_pipeline(d, res, st, tg, sys))) return rc;
     if (side) {
       hipError_t e = hipEventRecord(side->join, sv);
       if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);
@@ -864,6 +936,18 @@ int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data,
                                 const qc_step_adapt* adapt, int phases, void* stream) {
   if (!d || !data || !adapt || d->B_res <= 0) return QC_ERR_ARG;
   return step_from(d, data, coef, adapt, phases, stream);
+}
+
+int qc_fused_pinn_system_step(const qc_step_desc* d, const qc_step_system* sys, int phases, void* stream) {
+  if (!d || !sys_ok(sys) || (d->B_val > 0 && !sys->target_val_dev)) return QC_ERR_ARG;
+  const QcBatches b = {(float*)d->X_res_dev, sys->target_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev,
+                       sys->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc, d->sample_seed,
+                       d->sample_step};
+  const QcSource src = system_source(sys);
+  if ((phases & QC_PHASE_SAMPLE) && !src.ok(b)) return QC_ERR_ARG;   // ahead of everything the descriptor is asked
+  if (d->H >= 1 && d->n >= 1 && d->n_theta >= 0 && d->part_stride < qc_layout(d->H, d->n, d->n_theta, sys->K).NP + 3)
+    return QC_ERR_ARG;
+  return fused_step(d, QcTarget{}, b, src, phases, stream, sys);
 }
 
 // Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pipe_forward, then

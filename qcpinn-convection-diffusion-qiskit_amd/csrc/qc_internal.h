@@ -7,7 +7,8 @@ struct QcLayout {  // column offsets of the flat parameter / gradient vector
   int oW1, ob1, oW2, ob2, oW3, ob3, oW4, ob4, oTh, NP;
 };
 
-inline QcLayout qc_layout(int H, int n, int n_theta) {
+// K: rows of the last layer (outputs of the post network), W4[K][H] b4[K]; K = 1 is the single-output layout
+inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1) {
   QcLayout L;
   L.H = H;
   L.n = n;
@@ -18,8 +19,8 @@ inline QcLayout qc_layout(int H, int n, int n_theta) {
   L.oW3 = L.ob2 + n;
   L.ob3 = L.oW3 + H * n;
   L.oW4 = L.ob3 + H;
-  L.ob4 = L.oW4 + H;
-  L.oTh = L.ob4 + 1;
+  L.ob4 = L.oW4 + K * H;
+  L.oTh = L.ob4 + K;
   L.NP = L.oTh + n_theta;
   return L;
 }
@@ -86,6 +87,21 @@ struct QcDsSeg {
   bool serves(int64_t n_batch) const { return n_batch <= 0 || (X && tg && n >= 1 && n < ((int64_t)1 << 31)); }
 };
 
+// The operator of the system step as data (== the head of qc_step_system of the public header): K outputs of one shared
+// network, n_eq equations, each the sum of its terms  coef * q[out][chan] * (mul0 >= 0 ? u[mul0] : 1) * (mul1 >= 0 ?
+// u[mul1] : 1),  q[k][c] channel c of output k and u[k] = q[k][0]; w_eq / w_out weigh the equations in L_r and the
+// outputs in L_bc / L_ic.  A kernel argument of k_post_system: the term fields are wave-uniform run-time values.
+constexpr int QC_SYS_K = 4, QC_SYS_EQ = 4, QC_SYS_TERMS = 32;   // == QC_KMAX, QC_EQMAX, QC_TERMS_MAX
+struct QcSysTerm {
+  int eq, out, chan, mul0, mul1;
+  float coef;
+};
+struct QcSys {
+  int K, n_eq, n_terms;
+  QcSysTerm terms[QC_SYS_TERMS];
+  float w_eq[QC_SYS_EQ], w_out[QC_SYS_K];
+};
+
 // Where those batches come from: coordinates drawn in the boxes of the three analytic problems (face_pts: the boundary
 // faces, from QC_FACE_RANDOM up), rows of a resident dataset drawn uniformly, or the same with the residual row
 // drawn from the integer CDF of qc_adapt_build (cdf over cdf_rows rows, coarse table behind it).  With `table` (a
@@ -102,6 +118,9 @@ struct QcSource {
   const float* ds_coef = nullptr;
   const uint64_t *cdf = nullptr, *coarse = nullptr;
   int64_t cdf_rows = 0;
+  // target width of a system's dataset (uniform rows only): 0, one float per row; else the rows of the target tables are
+  // [w_res] / [w_val] floats, written batch-minor, and the residual table (and the batch's buffer) may be absent
+  int w_res = 0, w_val = 0;
 
   // THE validity rule, in two steps.  holds(): what a step asks of batches that are already filled (a call without
   // QC_PHASE_SAMPLE asks no more): a known boundary rule; of dataset kinds a split of the value batch, a target buffer
@@ -110,7 +129,7 @@ struct QcSource {
   bool holds(const QcBatches& b) const {
     if (face_pts < QC_FACE_RANDOM) return false;
     if (kind == QC_SOURCE_DRAW) return true;
-    if (b.n_ic < 0 || b.n_bc < 0 || (b.n_res > 0 && !b.tg_res) || (b.n_ic + b.n_bc > 0 && !b.tg_val)) return false;
+    if (b.n_ic < 0 || b.n_bc < 0 || (b.n_res > 0 && !b.tg_res && w_res == 0) || (b.n_ic + b.n_bc > 0 && !b.tg_val)) return false;
     return kind != QC_SOURCE_CDF ||
            (cdf && ((uintptr_t)cdf & 7) == 0 && cdf_rows >= 1 && cdf_rows < ((int64_t)1 << 31) && cdf_rows == res.n);
   }
@@ -121,6 +140,7 @@ struct QcSource {
     if ((b.n_res > 0 && !b.X_res) || (b.n_ic + b.n_bc > 0 && !b.X_val)) return false;
     if (kind == QC_SOURCE_DRAW) return true;
     if (table && b.n_res > 0 && (!coef_res || !ds_coef)) return false;
+    if (w_res > 0 && !res.tg) return QcDsSeg{res.X, res.X, res.n}.serves(b.n_res) && ic.serves(b.n_ic) && bc.serves(b.n_bc);
     return res.serves(b.n_res) && ic.serves(b.n_ic) && bc.serves(b.n_bc);
   }
 };
@@ -226,6 +246,10 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t,
                 const QcTarget& tg);
+// the system post stage (k_post_system): forward, terms, loss columns, cotangents and reverse of one batch in one kernel;
+// L is the K-row layout; nch = 6: tg = [n_eq][B] residual targets or null (zero); nch = 1: tg = [K][B] value targets
+int qc_mlp_post_system(const float* prm, QcLayout L, const QcSys& sys, QcPde pde, const float* qjets, const float* tg,
+                       float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t);
 int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float* w4k, const float* qjets, float* out_u,
                       const float* ubar, float* qbar, float* part, int64_t part_stride, float* partk, int64_t partk_stride,
                       int64_t row0, int64_t B, hipStream_t);

@@ -1976,3 +1976,251 @@ int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float
     if (mode == 4) launch(qc_int<4>{}); else launch(qc_int<3>{});
   });
 }
+
+// ================================================================== system post stage: K outputs, the operator as a term list
+// The post stage of qc_fused_pinn_system_step (Navier-Stokes behind one shared network, nn/pde.py:2-27, and every system
+// of that shape): ONE kernel per 64-point tile for the hidden layer, the K x NCH channels u[k][c], the residuals of the
+// n_eq equations from the term list, the loss columns, the cotangents ub[k][c] (product rule over up to three factors)
+// and the reverse pass of k_post_multi's mode 3, with the last layer's gradients in the flat row at oW4 + k H + m and
+// ob4 + k of the K-row layout.  lane = point, the four waves split the hidden units.
+// The term fields are wave-uniform run-time values: indexing the per-lane arrays u[k][c] / ub[k][c] by them would send
+// the arrays to scratch memory.  After the cross-wave sum the channels lie in LDS in lane-private columns, so wave 0
+// runs the term loop on LDS rows (s_buf[0]: u, s_buf[1]: ub) and every wave then loads ub with compile-time indices.
+// NCH = 1 (value points): u_k = W4[k] z + b4[k] against tg[k][p], weighted by segment (IC below pde.n_seg_a) and w_out[k];
+// no term list is read.  tg: [n_eq][B] (NCH = 6; null: zero) or [K][B] (NCH = 1).
+template <int N, int NCH>
+__global__ void __launch_bounds__(256) k_post_system(const float* __restrict__ prm, QcLayout L, QcSys sys, QcPde pde,
+                                                     const float* __restrict__ qjets, const float* __restrict__ tg,
+                                                     float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
+                                                     int64_t row0, int64_t B) {
+  constexpr int ROWS = NCH * (N > QC_KMAX ? N : QC_KMAX);
+  __shared__ float s_buf[QC_MS][ROWS][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t tile = blockIdx.x;
+  const int64_t p = tile * 64 + lane;
+  const bool live = p < B;
+  const int64_t pc = live ? p : B - 1;
+  const int K = sys.K;
+  float q[NCH][N];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int i = 0; i < N; ++i) q[c][i] = qjets[((int64_t)c * N + i) * B + pc];
+  const float* W3 = prm + L.oW3;
+  const float* b3 = prm + L.ob3;
+  const float* W4 = prm + L.oW4;
+  const int hq = (L.H + QC_MS - 1) / QC_MS;
+  const int m0 = wave * hq, m1 = (m0 + hq) < L.H ? (m0 + hq) : L.H;
+  auto hidden = [&](int m, float (&g)[NCH], float& z, float (&f)[NCH]) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      float sum = (c == 0) ? b3[m] : 0.f;
+#pragma unroll
+      for (int i = 0; i < N; ++i) sum = fmaf(W3[m * N + i], q[c][i], sum);
+      g[c] = sum;
+    }
+    z = qc_tanh(g[0]);
+    f[0] = z;
+    if constexpr (NCH == 6) {
+      const float d1 = 1.f - z * z, d2 = -2.f * z * d1;
+      f[1] = d1 * g[1];
+      f[2] = d1 * g[2];
+      f[3] = d1 * g[3];
+      f[4] = d2 * g[2] * g[2] + d1 * g[4];
+      f[5] = d2 * g[3] * g[3] + d1 * g[5];
+    }
+  };
+  // ---- forward: this wave's share of u[k][c], then the sum over the waves
+  {
+    float u[QC_KMAX][NCH];
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) u[k][c] = 0.f;
+    for (int m = m0; m < m1; ++m) {
+      float g[NCH], z, f[NCH];
+      hidden(m, g, z, f);
+#pragma unroll
+      for (int k = 0; k < QC_KMAX; ++k)
+        if (k < K) {
+          const float w4 = W4[k * L.H + m];
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) u[k][c] = fmaf(w4, f[c], u[k][c]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) s_buf[wave][k * NCH + c][lane] = u[k][c];
+  }
+  __syncthreads();
+  float* row = part + (row0 + tile) * part_stride;
+  float ub[QC_KMAX][NCH];
+  if constexpr (NCH == 1) {
+    // every wave forms the K values and their cotangents itself (compile-time indices); wave 0 writes the columns
+    const bool seg_a = p < pde.n_seg_a;
+    const float wv = seg_a ? pde.w_val_a : pde.w_val_b;
+    float la = 0.f, lb = 0.f;
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k) {
+      ub[k][0] = 0.f;
+      if (k < K) {
+        const float uk = ((s_buf[0][k][lane] + s_buf[1][k][lane]) + (s_buf[2][k][lane] + s_buf[3][k][lane])) + prm[L.ob4 + k];
+        const float e = live ? uk - tg[(int64_t)k * B + pc] : 0.f;
+        const float we = sys.w_out[k] * e;
+        ub[k][0] = wv * we;
+        la += seg_a ? we * e * pde.inv_n_a : 0.f;
+        lb += seg_a ? 0.f : we * e * pde.inv_n_b;
+      }
+    }
+    if (wave == 0) {
+      la = qc_wave_sum_to_lane63(la);
+      lb = qc_wave_sum_to_lane63(lb);
+      if (lane == 63) {
+        row[L.NP + 0] = 0.f;
+        row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
+        row[L.NP + 2] = la;
+      }
+    }
+  } else {
+    if (wave == 0) {
+      // u[k][c] -> s_buf[0][k * 6 + c]; zeroed cotangents -> s_buf[1] (the other waves' partial sums are consumed here)
+      for (int f = 0; f < K * NCH; ++f) {
+        float v = (s_buf[0][f][lane] + s_buf[1][f][lane]) + (s_buf[2][f][lane] + s_buf[3][f][lane]);
+        if (f % NCH == 0) v += prm[L.ob4 + f / NCH];
+        s_buf[0][f][lane] = v;
+      }
+      for (int f = 0; f < QC_KMAX * NCH; ++f) s_buf[1][f][lane] = 0.f;
+      float res[QC_SYS_EQ] = {0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < sys.n_terms; ++t) {
+        const QcSysTerm tm = sys.terms[t];
+        float v = tm.coef * s_buf[0][tm.out * NCH + tm.chan][lane];
+        if (tm.mul0 >= 0) v *= s_buf[0][tm.mul0 * NCH][lane];
+        if (tm.mul1 >= 0) v *= s_buf[0][tm.mul1 * NCH][lane];
+#pragma unroll
+        for (int e = 0; e < QC_SYS_EQ; ++e) res[e] += (tm.eq == e) ? v : 0.f;
+      }
+      float gsc[QC_SYS_EQ], ls = 0.f;
+#pragma unroll
+      for (int e = 0; e < QC_SYS_EQ; ++e) {
+        gsc[e] = 0.f;
+        if (e < sys.n_eq) {
+          const float err = live ? res[e] - (tg ? tg[(int64_t)e * B + pc] : 0.f) : 0.f;
+          const float we = sys.w_eq[e] * err;
+          gsc[e] = pde.w_res * we;
+          ls += we * err * pde.inv_n_res;
+        }
+      }
+      ls = qc_wave_sum_to_lane63(ls);
+      if (lane == 63) {
+        row[L.NP + 0] = ls;
+        row[L.NP + 1] = 0.f;
+        row[L.NP + 2] = 0.f;
+      }
+      for (int t = 0; t < sys.n_terms; ++t) {
+        const QcSysTerm tm = sys.terms[t];
+        float gv = 0.f;
+#pragma unroll
+        for (int e = 0; e < QC_SYS_EQ; ++e) gv = (tm.eq == e) ? gsc[e] : gv;
+        gv *= tm.coef;
+        const float a = s_buf[0][tm.out * NCH + tm.chan][lane];
+        const float x0 = tm.mul0 >= 0 ? s_buf[0][tm.mul0 * NCH][lane] : 1.f;
+        const float x1 = tm.mul1 >= 0 ? s_buf[0][tm.mul1 * NCH][lane] : 1.f;
+        s_buf[1][tm.out * NCH + tm.chan][lane] += gv * x0 * x1;
+        if (tm.mul0 >= 0) s_buf[1][tm.mul0 * NCH][lane] += gv * a * x1;
+        if (tm.mul1 >= 0) s_buf[1][tm.mul1 * NCH][lane] += gv * a * x0;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) ub[k][c] = k < K ? s_buf[1][k * NCH + c][lane] : 0.f;
+    __syncthreads();   // s_buf[1] is read by every wave before any wave refills its slice below
+  }
+  // ---- reverse (k_post_multi mode 3): d / d b4[k] = sum of the points' cotangents of u_k
+  if (wave == 0) {
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k)
+      if (k < K) {
+        const float sb = qc_wave_sum_to_lane63(ub[k][0]);
+        if (lane == 63) row[L.ob4 + k] = sb;
+      }
+  }
+  float qb[NCH][N];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int i = 0; i < N; ++i) qb[c][i] = 0.f;
+  for (int m = m0; m < m1; ++m) {
+    float g[NCH], z, f[NCH];
+    hidden(m, g, z, f);
+    float ubw[NCH], gk[QC_KMAX];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) ubw[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k) {
+      gk[k] = 0.f;
+      if (k < K) {
+        const float w4 = W4[k * L.H + m];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          ubw[c] = fmaf(w4, ub[k][c], ubw[c]);
+          gk[k] = fmaf(ub[k][c], f[c], gk[k]);
+        }
+      }
+    }
+    float gb[NCH], gw4;
+    post_cotangents<N, NCH>(gb, gw4, g, ubw, z, 1.f);
+    float wg[N + 1];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const float w3 = W3[m * N + i];
+      float sum = 0.f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        qb[c][i] = fmaf(w3, gb[c], qb[c][i]);
+        sum = fmaf(gb[c], q[c][i], sum);
+      }
+      wg[i] = sum;
+    }
+    wg[N] = gb[0];
+    qc_wave_sum_multi_to_lane63<N + 1>(wg);
+#pragma unroll
+    for (int k = 0; k < QC_KMAX; ++k)
+      if (k < K) gk[k] = qc_wave_sum_to_lane63(gk[k]);
+    if (lane == 63) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) row[L.oW3 + m * N + i] = wg[i];
+      row[L.ob3 + m] = wg[N];
+#pragma unroll
+      for (int k = 0; k < QC_KMAX; ++k)
+        if (k < K) row[L.oW4 + k * L.H + m] = gk[k];
+    }
+  }
+  if constexpr (NCH == 1) __syncthreads();   // the partial sums of u are read by every wave before any slice is refilled
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int i = 0; i < N; ++i) s_buf[wave][c * N + i][lane] = qb[c][i];
+  __syncthreads();
+  if (live) {
+    for (int f = wave; f < NCH * N; f += QC_MS)
+      qbar[(int64_t)f * B + p] = (s_buf[0][f][lane] + s_buf[1][f][lane]) + (s_buf[2][f][lane] + s_buf[3][f][lane]);
+  }
+}
+
+int qc_mlp_post_system(const float* prm, QcLayout L, const QcSys& sys, QcPde pde, const float* qjets, const float* tg,
+                       float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st) {
+  static_assert(QC_SYS_K == QC_KMAX, "outputs of a system");
+  if (sys.K < 1 || sys.K > QC_KMAX || L.H > 1024) return QC_ERR_UNSUPPORTED;
+  const int tiles = qc_ceil_div(B, 64);
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c) {
+      hipLaunchKernelGGL((k_post_system<n(), c()>), dim3(tiles), dim3(256), 0, st, prm, L, sys, pde, qjets, tg, qbar, part,
+                         part_stride, row0, B);
+    };
+    if (nch == 6) launch(qc_int<6>{}); else launch(qc_int<1>{});
+  });
+}

@@ -9,6 +9,7 @@
 #include "qc_philox.h"
 
 #include <tuple>
+#include <type_traits>
 
 namespace {
 
@@ -16,16 +17,26 @@ namespace {
 // its row `out` of that segment's output buffers (value rows and value targets are laid out IC first, then BC, like
 // X_val), its global index, where its point goes, the targets of its batch, and in dataset mode the resident segment it
 // copies from.  Returned by value: handed out through a reference, `ds` went through scratch memory in the CDF gathers.
-struct QcSlot {
+// SEG: the segment record, QcDsSeg (one target per row) or QcDsSegW (a row of w targets, the system step's tables).
+template <class SEG>
+struct QcSlotOf {
   int seg;
   int64_t out, gidx;
   float *X, *tg;   // X_batch + 3 * out; the batch's target buffer (indexed by out)
-  QcDsSeg ds;
+  SEG ds;
 };
-__device__ __forceinline__ QcSlot qc_slot(int64_t i, float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val,
-                                          float* tg_val, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
-                                          QcDsSeg d_res = {}, QcDsSeg d_ic = {}, QcDsSeg d_bc = {}) {
-  QcSlot s;
+using QcSlot = QcSlotOf<QcDsSeg>;
+struct QcDsSegW {
+  const float* X;   // [n][3]
+  const float* tg;  // [n][w] row-major, or null: no targets to copy
+  int64_t n;
+  int w;
+};
+template <class SEG = QcDsSeg>
+__device__ __forceinline__ QcSlotOf<SEG> qc_slot(int64_t i, float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val,
+                                                 float* tg_val, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                                                 SEG d_res = {}, SEG d_ic = {}, SEG d_bc = {}) {
+  QcSlotOf<SEG> s;
   int64_t local;
   if (i < n_res) {
     local = i;
@@ -99,13 +110,16 @@ __device__ __forceinline__ auto qc_src(P*... src) {   // pointer K of the pack, 
 enum QcRows { QC_ROWS_UNIFORM = 0, QC_ROWS_CDF_LDS, QC_ROWS_CDF_GLOBAL };
 constexpr int QC_ADAPT_LDS_MAX = 4096;   // coarse entries staged in LDS (32 KB): datasets up to 4 Mi residual rows
 
-template <QcRows ROWS, class... P>
+// SEG = QcDsSegW: the targets of a row are ds.w floats, written batch-minor (tg[k][batch]); a segment without a table
+// (the residual targets of a system may be absent: zero) copies points only.
+template <QcRows ROWS, class SEG, class... P>
 __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float* __restrict__ tg_res, int64_t n_res,
                                                 int64_t off_res, float* __restrict__ X_val, float* __restrict__ tg_val,
-                                                int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, QcDsSeg d_res,
-                                                QcDsSeg d_ic, QcDsSeg d_bc, uint64_t seed, uint64_t step,
+                                                int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, SEG d_res,
+                                                SEG d_ic, SEG d_bc, uint64_t seed, uint64_t step,
                                                 P* __restrict__... src) {
   constexpr bool CDF = ROWS != QC_ROWS_UNIFORM, LDS = ROWS == QC_ROWS_CDF_LDS, TABLE = sizeof...(P) >= 2;
+  constexpr bool WIDE = std::is_same<SEG, QcDsSegW>::value;
   float* coef_res = qc_src<0>(src...);
   const float* ds_coef = qc_src<1>(src...);
   const uint64_t *cdf = qc_src<2>(src...), *coarse = qc_src<3>(src...);
@@ -116,8 +130,8 @@ __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float
     for (int64_t b = threadIdx.x; b < nb; b += 256) sh[b] = coarse[b];
     __syncthreads();
   }
-  const QcSlot s = qc_slot((int64_t)blockIdx.x * 256 + threadIdx.x, X_res, tg_res, n_res, off_res, X_val, tg_val, n_ic,
-                           off_ic, n_bc, off_bc, d_res, d_ic, d_bc);
+  const QcSlotOf<SEG> s = qc_slot<SEG>((int64_t)blockIdx.x * 256 + threadIdx.x, X_res, tg_res, n_res, off_res, X_val, tg_val, n_ic,
+                                       off_ic, n_bc, off_bc, d_res, d_ic, d_bc);
   if (s.seg < 0) return;
   int64_t idx;
   if (CDF && s.seg == 0) {   // t = umul64hi(r64, cdf[N - 1]), r64 = word 0 << 32 | word 1 of the uniform gather's block
@@ -130,7 +144,14 @@ __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float
   s.X[0] = s.ds.X[idx * 3 + 0];
   s.X[1] = s.ds.X[idx * 3 + 1];
   s.X[2] = s.ds.X[idx * 3 + 2];
-  s.tg[s.out] = s.ds.tg[idx];
+  if constexpr (WIDE) {
+    if (s.ds.tg && s.tg) {
+      const int64_t nb_out = s.seg == 0 ? n_res : n_ic + n_bc;
+      for (int k = 0; k < s.ds.w; ++k) s.tg[(int64_t)k * nb_out + s.out] = s.ds.tg[idx * s.ds.w + k];
+    }
+  } else {
+    s.tg[s.out] = s.ds.tg[idx];
+  }
   if (TABLE && s.seg == 0 && (!CDF || coef_res != nullptr)) {
 #pragma unroll
     for (int k = 0; k < QC_COEF_N; ++k) coef_res[(int64_t)k * n_res + s.out] = ds_coef[idx * QC_COEF_N + k];
@@ -140,10 +161,10 @@ __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float
 // Implicit instantiations are emitted in order of first use, and where identical kernels lie in the object has been
 // measured (DESIGN section 6 "Batch sources"): the two uniform gathers are named here, ahead of qc_sample_launch, so the
 // order stays uniform, uniform with a table, k_sample<true>, k_sample<false>, CDF from LDS, CDF from global memory.
-constexpr auto k_gather_rows = k_gather<QC_ROWS_UNIFORM>;
-constexpr auto k_gather_rows_coef = k_gather<QC_ROWS_UNIFORM, float, const float>;
+constexpr auto k_gather_rows = k_gather<QC_ROWS_UNIFORM, QcDsSeg>;
+constexpr auto k_gather_rows_coef = k_gather<QC_ROWS_UNIFORM, QcDsSeg, float, const float>;
 template <QcRows ROWS>
-constexpr auto k_gather_cdf = k_gather<ROWS, float, const float, const uint64_t, const uint64_t>;
+constexpr auto k_gather_cdf = k_gather<ROWS, QcDsSeg, float, const float, const uint64_t, const uint64_t>;
 
 }  // namespace
 
@@ -163,6 +184,13 @@ int qc_gather_launch(const QcBatches& b, const QcSource& s, hipStream_t st) {
     hipLaunchKernelGGL(kernel, dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, b.X_res, b.tg_res, b.n_res, b.off_res, b.X_val,
                        b.tg_val, b.n_ic, b.off_ic, b.n_bc, b.off_bc, s.res, s.ic, s.bc, b.seed, b.step, src...);
   };
+  if (s.w_res > 0 || s.w_val > 0) {   // a system's dataset: rows of targets (uniform rows, no operator table)
+    const QcDsSegW r = {s.res.X, s.res.tg, s.res.n, s.w_res}, i = {s.ic.X, s.ic.tg, s.ic.n, s.w_val},
+                   c = {s.bc.X, s.bc.tg, s.bc.n, s.w_val};
+    hipLaunchKernelGGL((k_gather<QC_ROWS_UNIFORM, QcDsSegW>), dim3(qc_ceil_div(total, 256)), dim3(256), 0, st, b.X_res, b.tg_res,
+                       b.n_res, b.off_res, b.X_val, b.tg_val, b.n_ic, b.off_ic, b.n_bc, b.off_bc, r, i, c, b.seed, b.step);
+    return QC_OK;
+  }
   const bool table = s.table && b.n_res > 0;   // no residual rows: none to copy an operator row for
   float* coef_res = table ? s.coef_res : nullptr;
   const float* ds_coef = table ? s.ds_coef : nullptr;

@@ -24,7 +24,7 @@ from __future__ import annotations
 import torch
 
 from .diffusion_dataset import box
-from ..hip.lib import QC_ADAPT_FLOOR_MAX
+from ..hip.lib import QC_ADAPT_FLOOR_MAX, QC_EQMAX, QC_KMAX, QC_TERMS_MAX
 
 MAX_ROWS = 2 ** 31 - 1      # the device gather forms (32-bit word * rows) >> 32
 COEF_COLUMNS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")     # column order of a coefficient row
@@ -191,3 +191,111 @@ class TabulatedProblem:
             c = dict(coef_res=self.coef_res.to(device))
         (Xr, rr), (Xi, ui), (Xb, ub) = [(X.to(device), y.to(device)) for X, y in self.segments()]
         return TabulatedProblem(Xr, rr, Xi, ui, Xb, ub, **c)
+
+
+def _system_segment(name, X, Y, width, optional=False):
+    """(X (N, 3) float32, Y (N, width) float32 | None) of one segment of a system's dataset; N = 0 is allowed."""
+    X = torch.as_tensor(X)
+    if X.dtype != torch.float32:
+        raise ValueError(f"{name}: points and targets must be float32 tensors, got {X.dtype}")
+    if X.dim() != 2 or X.shape[1] != 3:
+        raise ValueError(f"{name}: points must have shape (N, 3) = (t, x, y) rows, got {tuple(X.shape)}")
+    if X.shape[0] > MAX_ROWS:
+        raise ValueError(f"{name}: at most {MAX_ROWS} rows per segment, got {X.shape[0]}")
+    if Y is None:
+        if not optional:
+            raise ValueError(f"{name}: targets are required")
+        return X.contiguous(), None
+    Y = torch.as_tensor(Y)
+    if Y.dtype != torch.float32:
+        raise ValueError(f"{name}: points and targets must be float32 tensors, got {X.dtype} and {Y.dtype}")
+    if Y.dim() != 2 or Y.shape[1] != width:
+        raise ValueError(f"{name}: targets must have shape (N, {width}), got {tuple(Y.shape)}")
+    if Y.shape[0] != X.shape[0]:
+        raise ValueError(f"{name}: {X.shape[0]} points but {Y.shape[0]} target rows")
+    if Y.device != X.device:
+        raise ValueError(f"{name}: points and targets must be on one device")
+    return X.contiguous(), Y.contiguous()
+
+
+def check_terms(terms, K, n_eq):
+    """The term rows (eq, out, chan, mul0, mul1, coef) of a system as a list of tuples, or ValueError naming the fault:
+    the ranges of ``qc_step_system`` (include/qcpinn_hip.h)."""
+    import math
+    terms = [tuple(t) for t in terms]
+    if not 1 <= len(terms) <= QC_TERMS_MAX:
+        raise ValueError(f"a system takes 1..{QC_TERMS_MAX} terms, got {len(terms)}")
+    out = []
+    for i, t in enumerate(terms):
+        if len(t) != 6:
+            raise ValueError(f"term {i}: expected (eq, out, chan, mul0, mul1, coef), got {t!r}")
+        eq, o, ch, m0, m1 = (int(v) for v in t[:5])
+        coef = float(t[5])
+        if not 0 <= eq < n_eq:
+            raise ValueError(f"term {i}: equation {eq} outside 0..{n_eq - 1}")
+        if not 0 <= o < K:
+            raise ValueError(f"term {i}: output {o} outside 0..{K - 1}")
+        if not 0 <= ch <= 5:
+            raise ValueError(f"term {i}: channel {ch} outside 0..5 (value, t, x, y, xx, yy)")
+        if not (-1 <= m0 < K and -1 <= m1 < K):
+            raise ValueError(f"term {i}: multipliers ({m0}, {m1}) must be -1 or an output 0..{K - 1}")
+        if not math.isfinite(coef):
+            raise ValueError(f"term {i}: coefficient {coef} is not finite")
+        out.append((eq, o, ch, m0, m1, coef))
+    return out
+
+
+class TabulatedSystem:
+    """A system of equations behind one K-output model as data: residual points with target rows ``R`` (N, n_eq) (None:
+    zero), initial and boundary points with the prescribed values ``U`` (N, K) of every output, the operator as a term
+    list (rows (eq, out, chan, mul0, mul1, coef), e.g. ``nn.pde.navier_stokes_2D_terms()``), the weights of the equations
+    in the residual loss and of the outputs in the value losses (``out_weights[k] = 0``: output k is not prescribed on
+    the boundary, e.g. the pressure)."""
+
+    def __init__(self, res, ic, bc, terms, eq_weights=None, out_weights=None):
+        import math
+        (Xi, Ui), (Xb, Ub) = ic, bc
+        if Ui is None:
+            raise ValueError("initial segment: targets are required")
+        Ui = torch.as_tensor(Ui)
+        K = int(Ui.shape[1]) if Ui.dim() == 2 else 0
+        if not 1 <= K <= QC_KMAX:
+            raise ValueError(f"initial segment: targets must have shape (N, K) with 1 <= K <= {QC_KMAX}, got {tuple(Ui.shape)}")
+        Xr, R = res
+        if R is not None:
+            R = torch.as_tensor(R)
+            n_eq = int(R.shape[1]) if R.dim() == 2 else 0
+        elif eq_weights is not None:
+            n_eq = len(eq_weights)
+        else:
+            n_eq = 1 + max(int(t[0]) for t in terms)
+        if not 1 <= n_eq <= QC_EQMAX:
+            raise ValueError(f"a system takes 1..{QC_EQMAX} equations, got {n_eq}")
+        self.K, self.n_eq = K, n_eq
+        self.X_res, self.R = _system_segment("residual segment", Xr, R, n_eq, optional=True)
+        self.X_ic, self.U_ic = _system_segment("initial segment", Xi, Ui, K)
+        self.X_bc, self.U_bc = _system_segment("boundary segment", Xb, Ub, K)
+        self.terms = check_terms(terms, K, n_eq)
+        self.eq_weights = tuple(float(w) for w in (eq_weights if eq_weights is not None else (1.0,) * n_eq))
+        self.out_weights = tuple(float(w) for w in (out_weights if out_weights is not None else (1.0,) * K))
+        if len(self.eq_weights) != n_eq or len(self.out_weights) != K:
+            raise ValueError(f"eq_weights / out_weights must hold {n_eq} / {K} entries, got {len(self.eq_weights)} / "
+                             f"{len(self.out_weights)}")
+        if not all(math.isfinite(w) for w in self.eq_weights + self.out_weights):
+            raise ValueError("eq_weights / out_weights must be finite")
+
+    def segments(self):
+        return ((self.X_res, self.R), (self.X_ic, self.U_ic), (self.X_bc, self.U_bc))
+
+    def sizes(self):
+        return tuple(int(X.shape[0]) for X, _ in self.segments())
+
+    def to(self, device):
+        """The same system with its segments on ``device`` (a system already there is returned as is)."""
+        device = torch.device(device)
+        if all(X.device == device and (Y is None or Y.device == device) for X, Y in self.segments()):
+            return self
+        mv = lambda a: None if a is None else a.to(device)
+        (Xr, R), (Xi, Ui), (Xb, Ub) = self.segments()
+        return TabulatedSystem((mv(Xr), mv(R)), (mv(Xi), mv(Ui)), (mv(Xb), mv(Ub)), self.terms, self.eq_weights,
+                               self.out_weights)

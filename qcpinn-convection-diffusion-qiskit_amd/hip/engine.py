@@ -30,14 +30,14 @@ def _need(t: torch.Tensor, device, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def param_layout(H: int, n: int, n_theta: int) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
+def param_layout(H: int, n: int, n_theta: int, K: int = 1) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
     """Offsets/shapes of the flat parameter vector = the reference's ``model.parameters()`` order
-    (nn/DVPDESolver.py:28-57: preprocessor, postprocessor, quantum_layer)."""
+    (nn/DVPDESolver.py:28-57: preprocessor, postprocessor, quantum_layer); ``K`` outputs: K rows in the last layer."""
     out, off = {}, 0
     for name, shape in (("preprocessor.0.weight", (H, 3)), ("preprocessor.0.bias", (H,)),
                         ("preprocessor.2.weight", (n, H)), ("preprocessor.2.bias", (n,)),
                         ("postprocessor.0.weight", (H, n)), ("postprocessor.0.bias", (H,)),
-                        ("postprocessor.2.weight", (1, H)), ("postprocessor.2.bias", (1,)),
+                        ("postprocessor.2.weight", (K, H)), ("postprocessor.2.bias", (K,)),
                         ("quantum_layer.params", (n_theta,))):
         out[name] = (off, shape)
         off += int(np.prod(shape))
@@ -587,3 +587,125 @@ class FusedStep:
             self.desc.sample_step += 1          # a fresh counter block per step
         name, fn, args = self._entry
         L.check(fn(*args, phases, _stream(self.eng.device)), name)
+
+
+class SystemStep:
+    """One ``qc_fused_pinn_system_step`` descriptor over fixed-size resident batches: the analogue of ``FusedStep`` for a
+    model with K outputs behind one shared network and an operator given as a term list (hip/lib.system_record).
+
+    ``flat`` is the K-row flat parameter vector (``param_layout(H, n, n_theta, K)``), trained in place.  The caller fills
+    ``X_res`` / ``X_val`` (IC points first, then BC) and the batch-minor targets ``target_res`` [n_eq, B_res] /
+    ``target_val`` [K, B_val], or hands over a resident dataset with ``set_dataset`` and lets ``QC_PHASE_SAMPLE`` gather
+    points and target rows.  ``res_targets=False``: the residual targets are zero and no buffer is kept for them."""
+
+    def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, system: "L.QcStepSystem", B_res: int, n_ic: int,
+                 n_bc: int, opt: OptimState, counts=None, loss_weights=(2.0, 4.0, 2.0), res_targets: bool = True):
+        self.lib, self.circuit, self.opt = circuit.lib, circuit, opt
+        dev, n = circuit.device, circuit.n
+        self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
+        check_network_shape(self.H, n)
+        self.K, self.n_eq = int(system.K), int(system.n_eq)
+        if not (1 <= self.K <= L.QC_KMAX and 1 <= self.n_eq <= L.QC_EQMAX):
+            raise L.QcError(f"a system has 1..{L.QC_KMAX} outputs and 1..{L.QC_EQMAX} equations, got {self.K} and {self.n_eq}")
+        self.layout = param_layout(self.H, n, self.n_theta, self.K)
+        self.NP = self.layout["__total__"][0]
+        self.theta_off = self.layout["quantum_layer.params"][0]
+        if flat.numel() != self.NP:
+            raise L.QcError(f"flat parameter vector has {flat.numel()} entries, the {self.K}-output layout needs {self.NP}")
+        if opt.m.numel() != self.NP:
+            raise L.QcError(f"optimiser state holds {opt.m.numel()} entries, the {self.K}-output layout needs {self.NP}")
+        self.flat = _need(flat, dev, "flat params")
+        self.B_res, self.n_ic, self.n_bc = B_res, n_ic, n_bc
+        B_val = n_ic + n_bc
+        f = dict(dtype=torch.float32, device=dev)
+        self.X_res = torch.zeros(max(B_res, 1), 3, **f)
+        self.X_val = torch.zeros(max(B_val, 1), 3, **f)
+        self.target_res = torch.zeros(self.n_eq, max(B_res, 1), **f) if res_targets else None
+        self.target_val = torch.zeros(self.K, max(B_val, 1), **f)
+        self.sys = system
+        self.sys.target_res_dev = self.target_res.data_ptr() if (res_targets and B_res) else None
+        self.sys.target_val_dev = self.target_val.data_ptr()
+        self._dataset = None
+        self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
+        self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
+        rows = (B_res + 63) // 64 + (B_val + 63) // 64
+        self.stride = self.NP + 3
+        self.part = torch.zeros(rows, self.stride, **f)
+        self.flat_grad = torch.zeros(self.stride, **f)
+        g_res, g_ic, g_bc = counts if counts is not None else (B_res, n_ic, n_bc)
+        g_res, g_ic, g_bc = max(g_res, 1), max(g_ic, 1), max(g_bc, 1)
+        w_r, w_bc, w_ic = (float(w) for w in loss_weights)
+        c = circuit
+        d = L.QcStepDesc()
+        d.prog, d.trig_dev, d.umat_dev = c.handle, c.trig.data_ptr(), _ptr(c.umat)
+        d.H, d.n, d.n_theta = self.H, n, self.n_theta
+        d.params_dev, d.m_dev, d.v_dev = self.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
+        d.opt_state_dev = opt.state.data_ptr()
+        d.hist_dev, d.hist_cap = (opt.hist.data_ptr() if opt.hist_cap > 0 else None), opt.hist_cap
+        d.X_res_dev, d.B_res = self.X_res.data_ptr(), B_res
+        d.X_val_dev, d.B_val = self.X_val.data_ptr(), B_val
+        (d.ajets_res_dev, d.qjets_res_dev, d.qbar_res_dev, d.abar_res_dev) = [self.ws_res[i].data_ptr() for i in range(4)]
+        (d.ajets_val_dev, d.qjets_val_dev, d.qbar_val_dev, d.abar_val_dev) = [self.ws_val[i].data_ptr() for i in range(4)]
+        d.part_dev, d.part_stride, d.part_rows_cap = self.part.data_ptr(), self.stride, rows
+        d.flat_dev = self.flat_grad.data_ptr()
+        # d loss / d err = 2 w / N per unit error; the operator coefficients and the problem id are not read
+        d.pde = L.QcPde(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 2.0 * w_r / g_res, 1.0 / g_res, 2.0 * w_ic / g_ic,
+                        2.0 * w_bc / g_bc, 1.0 / g_ic, 1.0 / g_bc, L.QC_PROBLEM_TABULATED, n_ic)
+        d.hyper = opt.hyper
+        need = int(self.lib.qc_step_workspace_bytes(c.handle, B_res, B_val))
+        self.step_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        d.circ_ws_dev, d.circ_ws_bytes = (self.step_ws.data_ptr(), need) if need else (None, 0)
+        d.n_ic = n_ic
+        d.comm = None
+        d.sample_off_res = d.sample_off_ic = d.sample_off_bc = 0
+        d.sample_seed, d.sample_step = 0, 0
+        d.sample_bc_face_points = 0
+        self.desc = d
+
+    def refresh_gates(self) -> None:
+        self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
+
+    def set_sampler(self, seed: int, off_res: int = 0, off_ic: int = 0, off_bc: int = 0) -> None:
+        """On-device gather (QC_PHASE_SAMPLE): Philox stream ``seed``; off_* = global index of this rank's first point."""
+        d = self.desc
+        d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
+        d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
+
+    def set_dataset(self, segments) -> None:
+        """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, R | None), (X_ic, U_ic), (X_bc, U_bc)) float32
+        tensors on the step's device, points [N, 3], target rows [N, n_eq] / [N, K]; None removes it."""
+        t = self.sys
+        if segments is None:
+            segments = ((None, None),) * 3
+        keep = []
+        for name, (X, Y), w in zip(("res", "ic", "bc"), segments, (self.n_eq, self.K, self.K)):
+            n = 0 if X is None else int(X.shape[0])
+            yp = None
+            if n:
+                X = _need(X, self.device, "dataset points")
+                if X.dim() != 2 or X.shape[1] != 3:
+                    raise L.QcError(f"dataset segment '{name}': points must be (N, 3)")
+                keep.append(X)
+                if Y is not None:
+                    Y = _need(Y, self.device, "dataset targets")
+                    if tuple(Y.shape) != (n, w):
+                        raise L.QcError(f"dataset segment '{name}': targets must be ({n}, {w}), got {tuple(Y.shape)}")
+                    keep.append(Y)
+                    yp = Y.data_ptr()
+                elif name != "res":
+                    raise L.QcError(f"dataset segment '{name}': value targets are required")
+                elif self.target_res is not None:
+                    raise L.QcError("a dataset without residual targets needs a step built with res_targets=False")
+            setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
+            setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], yp)
+            setattr(t, "ds_n_" + name, n)
+        self._dataset = keep        # the record holds raw pointers: keep the tensors alive
+
+    def set_comm(self, comm) -> None:
+        self.desc.comm = comm
+
+    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
+        if phases & L.QC_PHASE_SAMPLE:
+            self.desc.sample_step += 1          # a fresh counter block per step
+        L.check(self.lib.qc_fused_pinn_system_step(C.byref(self.desc), C.byref(self.sys), phases, _stream(self.device)),
+                "qc_fused_pinn_system_step")

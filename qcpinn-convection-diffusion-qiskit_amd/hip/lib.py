@@ -31,6 +31,7 @@ EXPORTS = (
     "qc_post_data", "qc_sample_dataset", "qc_fused_pinn_data_step",
     "qc_post_coef", "qc_sample_dataset_coef", "qc_fused_pinn_coef_step",
     "qc_dataset_scores", "qc_adapt_bytes", "qc_adapt_build", "qc_sample_dataset_adaptive", "qc_fused_pinn_adaptive_step",
+    "qc_post_system", "qc_sample_dataset_system", "qc_fused_pinn_system_step",
 )
 
 
@@ -39,6 +40,7 @@ QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc
 QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 (qc_step_coef)
 QC_ADAPT_BLOCK = 1024            # rows per entry of the coarse table of an adaptive-sampling buffer (qc_adapt_bytes)
 QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
+QC_KMAX, QC_EQMAX, QC_TERMS_MAX = 4, 4, 32            # outputs, equations and terms of a system (qc_step_system)
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
 QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
 
@@ -103,6 +105,40 @@ class QcStepCoef(C.Structure):
 class QcStepAdapt(C.Structure):
     """qc_step_adapt: the buffer of qc_adapt_build ({64-byte record, cdf[n_rows], coarse[ceil(n_rows / 1024)]}) and its rows."""
     _fields_ = [("adapt_dev", C.c_void_p), ("n_rows", C.c_int64)]
+
+
+class QcSysTerm(C.Structure):
+    """qc_sys_term: coef * q[out][chan] * (mul0 >= 0 ? u[mul0] : 1) * (mul1 >= 0 ? u[mul1] : 1) in equation eq."""
+    _fields_ = [("eq", C.c_int32), ("out", C.c_int32), ("chan", C.c_int32), ("mul0", C.c_int32), ("mul1", C.c_int32),
+                ("coef", C.c_float)]
+
+
+class QcStepSystem(C.Structure):
+    """qc_step_system: the operator of a K-output system as a term list, the weights of its equations and outputs, the
+    batch-minor targets of the current batches ([n_eq][B_res] or NULL, [K][B_val]) and the resident dataset with row-major
+    target tables ([N][n_eq] or NULL, [N][K], [N][K])."""
+    _fields_ = [
+        ("K", C.c_int32), ("n_eq", C.c_int32), ("n_terms", C.c_int32),
+        ("terms", QcSysTerm * QC_TERMS_MAX), ("w_eq", C.c_float * QC_EQMAX), ("w_out", C.c_float * QC_KMAX),
+        ("target_res_dev", C.c_void_p), ("target_val_dev", C.c_void_p),
+        ("ds_X_res", C.c_void_p), ("ds_r", C.c_void_p), ("ds_n_res", C.c_int64),
+        ("ds_X_ic", C.c_void_p), ("ds_u_ic", C.c_void_p), ("ds_n_ic", C.c_int64),
+        ("ds_X_bc", C.c_void_p), ("ds_u_bc", C.c_void_p), ("ds_n_bc", C.c_int64),
+    ]
+
+
+def system_record(K, n_eq, terms, w_eq, w_out) -> "QcStepSystem":
+    """A qc_step_system with its operator filled from ``terms`` = rows (eq, out, chan, mul0, mul1, coef); nothing is
+    validated here (the library refuses what is out of range)."""
+    s = QcStepSystem()
+    s.K, s.n_eq, s.n_terms = int(K), int(n_eq), len(terms)
+    for i, t in enumerate(terms[:QC_TERMS_MAX]):
+        s.terms[i] = QcSysTerm(int(t[0]), int(t[1]), int(t[2]), int(t[3]), int(t[4]), float(t[5]))
+    for e, w in enumerate(list(w_eq)[:QC_EQMAX]):
+        s.w_eq[e] = float(w)
+    for k, w in enumerate(list(w_out)[:QC_KMAX]):
+        s.w_out[k] = float(w)
+    return s
 
 
 _lib: Optional[C.CDLL] = None
@@ -175,6 +211,11 @@ def load() -> C.CDLL:
                                                C.POINTER(QcStepCoef), C.POINTER(QcStepAdapt), C.c_uint64, C.c_uint64, vp]
     lib.qc_fused_pinn_adaptive_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef),
                                                 C.POINTER(QcStepAdapt), i32, vp]
+    lib.qc_post_system.argtypes = [fp, i32, i32, i32, C.POINTER(QcStepSystem), C.POINTER(QcPde), fp, fp, fp, fp, i64, i64, i64,
+                                   i32, vp]
+    lib.qc_sample_dataset_system.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, C.POINTER(QcStepSystem), C.c_uint64,
+                                             C.c_uint64, vp]
+    lib.qc_fused_pinn_system_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepSystem), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

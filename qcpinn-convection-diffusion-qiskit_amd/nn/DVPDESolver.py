@@ -186,7 +186,8 @@ class DVPDESolver(nn.Module):
                              f"nn/pde.py): classic_network must be [3, H, K] or [2, H, K], got {self.classic_network}")
         self.input_dim = self.classic_network[0]
         # K > 1 outputs (Navier-Stokes' (u, v, p), nn/pde.py:2-27): served through jets(), one single-output
-        # evaluation of the kernels per output; the fused TRAINING step and residual() are for K = 1
+        # evaluation of the kernels per output; FusedTrainer and residual() are for K = 1, a K-output model trains on a
+        # system of equations through trainer.system_train.SystemTrainer
         self.n_out = self.classic_network[-1]
         hidden = self.classic_network[-2]
         _engine.check_network_shape(hidden, self.num_qubits)

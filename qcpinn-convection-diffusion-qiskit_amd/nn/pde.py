@@ -83,6 +83,21 @@ def navier_stokes_2D_operator(model, t, x, y, min_x=0, max_x=1):
     return [u_x + v_y, f_u, f_v]
 
 
+def navier_stokes_2D_terms(viscosity=0.00345, density=1056.0):
+    """The operator above as the term list of the fused system step (``trainer.system_train.SystemTrainer``,
+    ``qc_fused_pinn_system_step``): rows (eq, out, chan, mul0, mul1, coef) meaning
+    ``coef * q[out][chan] * u[mul0] * u[mul1]`` in equation ``eq`` (a multiplier of -1 is absent), outputs (u, v, p) =
+    0, 1, 2, channels (value, t, x, y, xx, yy) = 0..5, equations in the operator's return order [continuity, f_u, f_v]."""
+    U, V, P = 0, 1, 2
+    T, X, Y, XX, YY = 1, 2, 3, 4, 5
+    terms = [(0, U, X, -1, -1, 1.0), (0, V, Y, -1, -1, 1.0)]
+    for eq, w, p_k in ((1, U, X), (2, V, Y)):
+        terms += [(eq, w, T, -1, -1, 1.0), (eq, w, X, U, -1, 1.0), (eq, w, Y, V, -1, 1.0),
+                  (eq, P, p_k, -1, -1, 1.0 / float(density)),
+                  (eq, w, XX, -1, -1, -float(viscosity)), (eq, w, YY, -1, -1, -float(viscosity))]
+    return terms
+
+
 def _fused_second_order(model):
     """A two-input DVPDESolver: second derivatives come from the fused derivative-channel kernels."""
     return getattr(model, "second_order", None) if getattr(model, "input_dim", 0) == 2 else None

@@ -1,0 +1,254 @@
+"""Float64 references of the system step (qc_fused_pinn_system_step, qc_post_system, include/qcpinn_hip.h): a model with K
+outputs behind one shared network, the operator a term list
+
+    res_e = sum over the terms with eq == e of  coef * q[out][chan] * (mul0 >= 0 ? u[mul0] : 1) * (mul1 >= 0 ? u[mul1] : 1),
+
+q[k][c] channel c (value, t, x, y, xx, yy) of output k and u[k] = q[k][0].  ``eval_terms`` evaluates a term list on jets;
+``reference_loss_system`` composes tests/mlp_reference.py (post_jets(..., w4=, b4=)) with the circuit oracles
+(oracle/jets.py, oracle/statevector.py) as tests/tabulated_reference.py does and differentiates by torch.autograd.
+
+The seeded cases of the GPU tests live here, so that the CPU tests and tests/golden/make_system_oracle_cache.py see the
+same inputs.  The seeded system is a scaled Navier-Stokes (nu = 0.05, 1 / rho = 0.7: at the reference's 1 / rho = 1 / 1056 the
+pressure terms would not register at the tolerances) with w_eq = (1, 0.5, 2), w_out = (1, 0.5, 0), smooth non-zero
+residual targets and value targets that are no solution; the two-output case is the same system without the pressure
+and the continuity equation (a Burgers pair).
+"""
+import numpy as np
+import torch
+
+import mlp_reference as R
+from conftest import cached_oracle, pkg
+from step_reference import haar_for, step_inputs
+
+H = 50
+NU, INV_RHO = 0.05, 0.7
+W_EQ, W_OUT = (1.0, 0.5, 2.0), (1.0, 0.5, 0.0)
+LOSS_WEIGHTS = (2.0, 4.0, 2.0)         # residual, BC, IC
+NAMES = R.NAMES
+
+# id -> (ansatz, n, L, encoding, B_res, n_ic, n_bc, K); the comment names what the case reaches
+CASES = {
+    "reg_cascade4": ("cascade", 4, 1, "angle", 70, 30, 20, 3),        # register family; one value tile holds IC and BC
+    "wave_layered7": ("layered", 7, 1, "angle", 65, 1, 40, 3),        # lanes family
+    "hbm_cascade9": ("cascade", 9, 1, "angle", 65, 3, 2, 2),          # HBM family, two outputs
+    "amp_cascade4": ("cascade", 4, 1, "amplitude", 40, 10, 10, 3),    # amplitude encoding
+    "no_val": ("cascade", 4, 1, "angle", 20, 0, 0, 3),                # B_val = 0
+    "no_res": ("cascade", 4, 1, "angle", 0, 70, 75, 3),               # B_res = 0, three value tiles
+}
+CONTROLS = ("uux_to_ux", "vuy_to_uuy", "drop_px", "vyy_to_vxx", "weq_uniform", "wout_p", "roll_res")
+CONTROL_CASES = ("reg_cascade4", "wave_layered7")
+# seed of a case's weights and points (default 5).  On the layered circuit seed 5 leaves the v_yy term of f_v too light
+# for its control to clear ten tolerances in the post block (5.4 x); seeds 6 .. 13 all clear it, 7 by 33 x.
+CASE_SALT = {"wave_layered7": 7}
+
+
+def layout(H, n, n_theta, K):
+    """name -> (offset, shape) of the K-row flat vector W1 b1 W2 b2 | W3 b3 W4[K][H] b4[K] | theta, and its length."""
+    out, off = {}, 0
+    for name, shape in zip(NAMES, ((H, 3), (H,), (n, H), (n,), (H, n), (H,), (K, H), (K,), (n_theta,))):
+        out[name] = (off, shape)
+        off += int(np.prod(shape))
+    return out, off
+
+
+def unpack(flat, H, n, n_theta, K):
+    lay, NP = layout(H, n, n_theta, K)
+    flat = np.asarray(flat, dtype=np.float64)
+    assert flat.shape == (NP,)
+    return {k: torch.tensor(flat[o:o + int(np.prod(s))].reshape(s), dtype=R.F64, requires_grad=True) for k, (o, s) in lay.items()}
+
+
+def flatten(grads, H, n, n_theta, K):
+    lay, NP = layout(H, n, n_theta, K)
+    out = np.zeros(NP)
+    for k, g in grads.items():
+        if g is not None:
+            o, s = lay[k]
+            out[o:o + int(np.prod(s))] = g.detach().numpy().reshape(-1)
+    return out
+
+
+def blocks(H, n, n_theta, K):
+    lay, NP = layout(H, n, n_theta, K)
+    return {"pre": slice(0, lay["W3"][0]), "post": slice(lay["W3"][0], lay["theta"][0]), "theta": slice(lay["theta"][0], NP)}
+
+
+def eval_terms(u, terms, n_eq):
+    """u (K, 6, B) jets of the K outputs -> (n_eq, B) residuals of the term list (rows (eq, out, chan, mul0, mul1, coef))."""
+    res = [torch.zeros_like(u[0, 0]) for _ in range(n_eq)]
+    for eq, out, chan, mul0, mul1, coef in terms:
+        v = coef * u[out, chan]
+        if mul0 >= 0:
+            v = v * u[mul0, 0]
+        if mul1 >= 0:
+            v = v * u[mul1, 0]
+        res[eq] = res[eq] + v
+    return torch.stack(res)
+
+
+def reference_loss_system(flat, H, n, n_theta, theta_shape, ansatz, haar, K, terms, w_eq, w_out, X_ic, X_bc, X_res, U_ic, U_bc,
+                          R_res, loss_weights=LOSS_WEIGHTS, encoding="angle"):
+    """flat (NP_K,), three (B, 3) point sets, value targets (B, K), residual targets (B, n_eq) or None -> (grad (NP_K,),
+    parts (3,)) float64: the gradient of w_res L_r + w_bc L_bc + w_ic L_ic and (L_r, L_bc, L_ic), L_r = sum_e w_eq[e]
+    mean (res_e - r_e)^2, L_bc / L_ic = sum_k w_out[k] mean (u_k - U_k)^2."""
+    from oracle import jets as oj
+    from oracle import statevector as sv
+    P = unpack(flat, H, n, n_theta, K)
+    theta = P["theta"].reshape(theta_shape)
+    zero = torch.zeros((), dtype=R.F64)
+    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=R.F64)
+    n_eq = len(w_eq)
+    we, wo = as64(w_eq), as64(w_out)
+    l_r = zero
+    if len(X_res):
+        a = R.pre_jets(P, X_res, 6)
+        q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
+        u = R.post_jets(P, q, w4=P["W4"], b4=P["b4"])                  # (K, 6, B)
+        res = eval_terms(u, terms, n_eq)
+        if R_res is not None:
+            res = res - as64(R_res).T
+        l_r = (we * (res ** 2).mean(1)).sum()
+    out = []
+    for Xv, Uv in ((X_bc, U_bc), (X_ic, U_ic)):
+        if not len(Xv):
+            out.append(zero)
+            continue
+        av = R.pre_jets(P, Xv, 1)
+        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
+        uv = R.post_jets(P, qv, w4=P["W4"], b4=P["b4"])[:, 0]          # (K, B)
+        out.append((wo * ((uv - as64(Uv).T) ** 2).mean(1)).sum())
+    l_bc, l_ic = out
+    w_r, w_b, w_i = loss_weights
+    loss = w_r * l_r + w_b * l_bc + w_i * l_ic
+    grads = torch.autograd.grad(loss, [P[k] for k in NAMES], allow_unused=True)
+    return flatten(dict(zip(NAMES, grads)), H, n, n_theta, K), np.array([l_r.item(), l_bc.item(), l_ic.item()])
+
+
+# ---- the seeded system
+def ns_terms(nu=NU, inv_rho=INV_RHO):
+    return [tuple(t) for t in pkg("nn.pde").navier_stokes_2D_terms(viscosity=nu, density=1.0 / inv_rho)]
+
+
+def burgers_terms(nu=NU):
+    """Two outputs (u, v), two equations: the momentum equations of ns_terms without the pressure."""
+    out = []
+    for eq, out_k, chan, m0, m1, coef in ns_terms(nu):
+        if eq >= 1 and out_k != 2:
+            out.append((eq - 1, out_k, chan, m0, m1, coef))
+    return out
+
+
+def system_of(K):
+    """(terms, w_eq, w_out) of the seeded system with K outputs."""
+    if K == 3:
+        return ns_terms(), W_EQ, W_OUT
+    if K == 2:
+        return burgers_terms(), W_EQ[1:], W_OUT[:2]
+    raise ValueError(K)
+
+
+def value_targets(X, K):
+    """(N, K) float32: smooth functions that are no solution of the system."""
+    X = np.asarray(X, dtype=np.float64)
+    t, x, y = X[:, 0], X[:, 1], X[:, 2]
+    cols = [np.sin(2 * np.pi * x) * np.cos(np.pi * y) * np.exp(-0.5 * t) + 0.3,
+            0.8 * np.cos(2.0 * x - y) * np.exp(-0.3 * t) - 0.2,
+            0.5 * np.sin(x + 2.0 * y + t),
+            0.4 * np.cos(3.0 * t - x) + 0.1]
+    return np.stack(cols[:K], 1).astype(np.float32).reshape(-1, K)
+
+
+def residual_targets(X, n_eq):
+    """(N, n_eq) float32, smooth and non-zero."""
+    X = np.asarray(X, dtype=np.float64)
+    t, x, y = X[:, 0], X[:, 1], X[:, 2]
+    cols = [1.5 * np.cos(3.0 * t + x - 2.0 * y), 0.9 * np.sin(2.0 * t - x + y) + 0.4, 1.1 * np.cos(t + 2.0 * x + y) - 0.3,
+            0.7 * np.sin(3.0 * x - y)]
+    return np.stack(cols[:n_eq], 1).astype(np.float32).reshape(-1, n_eq)
+
+
+def flat_k(H, n, n_theta, B_res, n_ic, n_bc, K, salt=5):
+    """The K-row flat vector of a seeded case: step_inputs' single-output weights, with last-layer rows 1 .. K - 1 drawn
+    at the same scales; and the three point sets."""
+    flat1, X_ic, X_bc, X_res = step_inputs(H, n, n_theta, B_res, n_ic, n_bc, salt=salt)
+    lay1, _ = R.layout(H, n, n_theta)
+    layk, NPk = layout(H, n, n_theta, K)
+    g = torch.Generator().manual_seed(9000 + 13 * n + K)
+    W4 = np.concatenate([flat1[lay1["W4"][0]:lay1["W4"][0] + H][None],
+                         (torch.randn(K - 1, H, generator=g, dtype=torch.float64) / np.sqrt(H)).numpy()]).astype(np.float32)
+    b4 = np.concatenate([flat1[lay1["b4"][0]:lay1["b4"][0] + 1],
+                         (torch.randn(K - 1, generator=g, dtype=torch.float64) * 0.1).numpy()]).astype(np.float32)
+    flat = np.zeros(NPk, dtype=np.float32)
+    flat[:layk["W4"][0]] = flat1[:lay1["W4"][0]]
+    flat[layk["W4"][0]:layk["b4"][0]] = W4.reshape(-1)
+    flat[layk["b4"][0]:layk["theta"][0]] = b4
+    flat[layk["theta"][0]:] = flat1[lay1["theta"][0]:]
+    return flat, X_ic, X_bc, X_res
+
+
+def case_inputs(case):
+    """(flat, X_ic, X_bc, X_res, U_ic, U_bc, R_res) of one seeded case."""
+    ans, n, L, enc, B_res, n_ic, n_bc, K = CASES[case]
+    n_theta = L * pkg("circuits").params_per_layer(ans, n)
+    flat, X_ic, X_bc, X_res = flat_k(H, n, n_theta, B_res, n_ic, n_bc, K, salt=CASE_SALT.get(case, 5))
+    n_eq = len(system_of(K)[1])
+    return flat, X_ic, X_bc, X_res, value_targets(X_ic, K), value_targets(X_bc, K), residual_targets(X_res, n_eq)
+
+
+def control(variant, terms, w_eq, w_out, R_res):
+    """(terms, w_eq, w_out, R_res) of a negative control of the three-output system."""
+    U, V, P = 0, 1, 2
+    terms = list(terms)
+    find = lambda eq, out, chan: next(i for i, t in enumerate(terms) if t[:3] == (eq, out, chan))
+    if variant == "uux_to_ux":
+        i = find(1, U, 2)
+        terms[i] = terms[i][:3] + (-1, -1) + terms[i][5:]
+    elif variant == "vuy_to_uuy":
+        i = find(1, U, 3)
+        terms[i] = terms[i][:3] + (U, -1) + terms[i][5:]
+    elif variant == "drop_px":
+        del terms[find(1, P, 2)]
+    elif variant == "vyy_to_vxx":
+        i = find(2, V, 5)
+        terms[i] = (2, V, 4) + terms[i][3:]
+    elif variant == "weq_uniform":
+        w_eq = (1.0,) * len(w_eq)
+    elif variant == "wout_p":
+        w_out = tuple(w_out[:2]) + (1.0,)
+    elif variant == "roll_res":
+        R_res = np.roll(R_res, 1, axis=0)
+    elif variant:
+        raise ValueError(variant)
+    return terms, w_eq, w_out, R_res
+
+
+def case_reference(case, variant=""):
+    """reference_loss_system of one case through conftest.cached_oracle -> {"grad": (NP_K,), "parts": (3,)}."""
+    ans, n, L, enc, B_res, n_ic, n_bc, K = CASES[case]
+    P = int(pkg("circuits").params_per_layer(ans, n))
+    flat, X_ic, X_bc, X_res, U_ic, U_bc, R_res = case_inputs(case)
+    terms, w_eq, w_out, Rr = control(variant, *system_of(K), R_res)
+
+    def compute():
+        g, parts = reference_loss_system(flat, H, n, L * P, (L, P), ans, haar_for(n, 1), K, terms, w_eq, w_out,
+                                         *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), U_ic, U_bc, Rr,
+                                         encoding=enc)
+        return {"grad": g, "parts": parts}
+    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
+        (U_ic, U_bc, Rr, np.asarray(terms, dtype=np.float32), np.asarray(w_eq + w_out, dtype=np.float32))
+    key = f"sys_{ans}_n{n}_L{L}_{enc}_r{B_res}_i{n_ic}_b{n_bc}_K{K}" + (f"_{variant}" if variant else "")
+    return cached_oracle(key, inputs, compute)
+
+
+def oracle_jobs():
+    """(case, variant) of every committed record (tests/golden/make_system_oracle_cache.py)."""
+    return [(c, "") for c in CASES] + [(c, v) for c in CONTROL_CASES for v in CONTROLS]
+
+
+def errors(got, want_g, want_p, H, n, n_theta, K, tol_g=2e-4, tol_l=1e-4):
+    """name -> error / tolerance (< 1 passes) of the three gradient blocks and the loss parts of a flat [grad | 3] vector."""
+    NP = got.size - 3
+    out = {"parts": np.abs(got[NP:] - want_p).max() / (tol_l * max(1.0, np.abs(want_p).max()))}
+    for name, s in blocks(H, n, n_theta, K).items():
+        out[name] = np.abs(got[:NP][s] - want_g[s]).max() / (tol_g * max(1.0, np.abs(want_g[s]).max()))
+    return out
