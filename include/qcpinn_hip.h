@@ -489,6 +489,49 @@ int qc_sample_dataset_system(float* X_res_dev, float* target_res_dev, int64_t n_
  * batch, or one of 2^31 rows or more; part_stride < NP_K + 3; whatever qc_fused_pinn_data_step refuses of the descriptor. */
 int qc_fused_pinn_system_step(const qc_step_desc* desc, const qc_step_system* sys, int phases, void* stream);
 
+/* ---- inverse problems: the tabulated step with a TRAINABLE global operator.  Measurements of u are given (value points
+ * anywhere in the domain, through the IC / BC segments of qc_step_data) and coefficients of the operator are identified
+ * with the network: what the reference's generic loop would do by handing the coefficient to Adam as one more
+ * nn.Parameter.
+ *   res_p = c_u u + c_3 u^3 + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy),
+ *   c_k   = fmaf(scale[k], p[k], base[k]),   k in QC_COEF_COLS order (c_u, c_t, c_x, c_y, d_xx, d_yy, c_3).
+ * The trainable vector p[7] lives on the device in the seven flat entries behind theta,
+ *   W1 b1 W2 b2 | W3 b3 W4 b4 | theta | p[7],      NP_L = NP + 7,
+ * so the optimiser moves it with everything else and no offset of the layout at the head of this file moves.  base and
+ * scale are constants of the step.  scale[k] = 0 freezes c_k at base[k] whatever p[k] holds (its gradient entry is exactly 0).
+ * scale[k] is also the coefficient's learning-rate multiplier: Adam moves every p[k] by about lr per step, so set scale[k]
+ * to the expected magnitude of c_k (a diffusivity of 0.01 cannot be learnt in steps of 0.005).
+ * coef_hist_dev (optional, [coef_hist_cap][7]): row s - 1 - hist_base receives the seven c_k used in 1-based step s, next
+ * to hist_dev[s - 1 - hist_base], the loss of the same parameters; step and hist_base are read from the optimiser record,
+ * the store rides in the residual launch.  It is skipped when desc->opt_state_dev or the buffer is NULL, and in a step
+ * without residual points. */
+typedef struct qc_step_learn {
+  float base[QC_COEF_COLS], scale[QC_COEF_COLS];   /* finite */
+  float* coef_hist_dev; int coef_hist_cap;         /* [cap][7] or NULL/0 */
+} qc_step_learn;
+
+/* qc_post mode 2 on residual points (nch = 6) under that operator (pde->problem = QC_PROBLEM_TABULATED; pde->c_t .. d_yy
+ * are not read, w_res and inv_n_res are).  params_dev holds NP_L entries, p in its last seven.  cot_dev[6][B] receives the
+ * per-point cotangents of qc_post_coef with the uniform c_k.  Row row0 + tile of part_dev receives the columns of W3, b3,
+ * W4, b4, the seven operator columns at NP_L - 7 + k,
+ *   scale[k] * sum over the tile's points of g * (u, u_t, u_x, u_y, -u_xx, -u_yy, u^3)[k],   g = w_res (res - target),
+ * (0 where scale[k] = 0; summed in a fixed order, no atomics) and the three loss columns at NP_L .. NP_L + 2
+ * (part_stride >= NP_L + 3); nothing else.  learn->coef_hist_dev is not written.  QC_ERR_ARG: a NULL buffer, a non-finite
+ * base or scale, part_stride < NP_L + 3. */
+int qc_post_learn(const float* params_dev /*NP_L*/, int H, int n, int n_theta, const qc_pde* pde,
+                  const qc_step_learn* learn, const float* qjets_dev, const float* target_dev, float* cot_dev /*[6][B]*/,
+                  float* qbar_dev, float* part_dev, int64_t part_stride, int64_t row0, int64_t B, void* stream);
+
+/* qc_fused_pinn_data_step under that operator: desc->pde.c_t .. d_yy and data->c_u are not read.  params_dev, m_dev and
+ * v_dev hold NP_L entries, flat_dev = [grad[NP_L] | L_r, L_bc, L_ic], part_stride >= NP_L + 3.  Value tiles write zeros to
+ * the seven operator columns of their rows; the clip's global norm includes the seven entries.  Everything else (both
+ * forms, phases, sampler, circuit families, encodings, workspace, comm) is the data step's.  With B_res = 0 the step runs
+ * and the seven gradient entries are exactly 0.  QC_ERR_ARG before any launch: learn NULL; a non-finite base or scale;
+ * coef_hist_cap < 0, or a NULL buffer with a positive cap; part_stride < NP_L + 3; whatever qc_fused_pinn_data_step
+ * refuses. */
+int qc_fused_pinn_inverse_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_learn* learn,
+                               int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

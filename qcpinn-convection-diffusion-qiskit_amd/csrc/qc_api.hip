@@ -489,14 +489,15 @@ static int post_impl(int mode, const float* X, const float* prm, int H, int n, i
                      const QcTarget& tg) {
   int rc = check_mlp(H, n, n_theta, B, nch);
   if (rc) return rc;
-  const QcLayout L = make_layout(H, n, n_theta);
+  const QcLayout L = qc_layout(H, n, n_theta, 1, tg.n_op());
   const bool analytic = tg.kind == QC_TARGET_ANALYTIC;
   if (mode < 0 || mode > 4 || (!X && analytic) || !prm || !pde || !qjets) return QC_ERR_ARG;
   // the analytic targets are defined for 0..2 only; the tabulated ones by the rule of their type
   if ((mode == 2 && analytic && !problem_ok(pde->problem)) || !tg.ok(mode, nch, pde->problem)) return QC_ERR_ARG;
   if (mode >= 3 && nch != 6) return QC_ERR_ARG;          // general jets: six channels only
   if (mode >= 1 && mode <= 3 && (!qbar || !part || row0 < 0 || part_stride < L.NP + (mode == 2 ? 3 : 0))) return QC_ERR_ARG;
-  if (mode == 2 && (!out_u || (nch == 6 && !out_res && tg.kind != QC_TARGET_COEF))) return QC_ERR_ARG;  // per-point cotangent scratch
+  if (mode == 2 && (!out_u || (nch == 6 && !out_res && tg.kind != QC_TARGET_COEF && tg.kind != QC_TARGET_LEARN)))
+    return QC_ERR_ARG;  // per-point cotangent scratch
   if ((mode == 3 && !in_ubar) || (mode == 4 && !out_u)) return QC_ERR_ARG;
   rc = qc_mlp_post(mode, X, prm, L, to_pde(pde), qjets, out_u, out_res, in_ubar, in_rbar, qbar, part, part_stride,
                    row0, B, nch, (hipStream_t)stream, tg);
@@ -524,6 +525,33 @@ int qc_post_coef(const float* prm, int H, int n, int n_theta, const qc_pde* pde,
   if (!target || !coef || !cot) return QC_ERR_ARG;
   return post_impl(2, nullptr, prm, H, n, n_theta, pde, qjets, cot, nullptr, nullptr, nullptr, qbar, part, part_stride, row0, B,
                    6, stream, QcTarget::with_coef(target, target, coef));
+}
+
+// THE validity rule of a learned operator: finite base and scale, a history buffer behind a positive capacity
+static bool learn_ok(const qc_step_learn* lr) {
+  if (!lr || lr->coef_hist_cap < 0 || (lr->coef_hist_cap > 0 && !lr->coef_hist_dev)) return false;
+  for (int k = 0; k < QC_COEF_COLS; ++k)
+    if (!isfinite(lr->base[k]) || !isfinite(lr->scale[k])) return false;
+  return true;
+}
+// the kernels' record: base and scale, and the history buffer with the optimiser record that places its rows (or neither)
+static QcLearn to_learn(const qc_step_learn* lr, const void* opt_state) {
+  QcLearn q;
+  memcpy(q.base, lr->base, sizeof(q.base));
+  memcpy(q.scale, lr->scale, sizeof(q.scale));
+  const bool hist = opt_state && lr->coef_hist_dev && lr->coef_hist_cap > 0;
+  q.hist = hist ? lr->coef_hist_dev : nullptr;
+  q.hist_cap = hist ? lr->coef_hist_cap : 0;
+  q.st = hist ? (const QcOptState*)opt_state : nullptr;
+  return q;
+}
+
+int qc_post_learn(const float* prm, int H, int n, int n_theta, const qc_pde* pde, const qc_step_learn* learn,
+                  const float* qjets, const float* target, float* cot, float* qbar, float* part, int64_t part_stride,
+                  int64_t row0, int64_t B, void* stream) {
+  if (!target || !cot || !learn_ok(learn)) return QC_ERR_ARG;
+  return post_impl(2, nullptr, prm, H, n, n_theta, pde, qjets, cot, nullptr, nullptr, nullptr, qbar, part, part_stride, row0, B,
+                   6, stream, QcTarget::learned(target, target, to_learn(learn, nullptr)));
 }
 
 int qc_post_multi(int mode, const float* prm, int H, int n, int n_theta, int K, const float* w4k, const float* qjets,
@@ -675,7 +703,7 @@ static int check_step_desc(const qc_step_desc* d, bool need_umat, bool (*support
 }
 
 static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool draw, const QcTarget& tg) {
-  const QcLayout L = make_layout(d->H, d->n, d->n_theta);
+  const QcLayout L = qc_layout(d->H, d->n, d->n_theta, 1, tg.n_op());
   const int64_t rows_res = qc_ceil_div(d->B_res, 64);
   const QcTrig* trig = (const QcTrig*)d->trig_dev;
   const float* prm = d->params_dev;
@@ -837,7 +865,7 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   int rc = check_step_desc(d, false, nullptr);
   if (rc) return rc;
   const int n = d->n, H = d->H;
-  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1);
+  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1, sys ? 0 : tg.n_op());
   const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
   const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
   const int64_t rows = rows_res + rows_val;
@@ -905,12 +933,14 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   return QC_OK;
 }
 
-// the four entry points: targets, batches and source from the records each was given (the kind of step is decided here)
+// the five entry points: targets, batches and source from the records each was given (the kind of step is decided here)
+// `lr` (the inverse step, validated by its entry, never with `cf`): the trainable operator, with or without residual points
 static int step_from(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_adapt* ad, int phases,
-                     void* stream) {
+                     void* stream, const qc_step_learn* lr = nullptr) {
   if (!d) return QC_ERR_ARG;
   const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
   const QcTarget tg = !t      ? QcTarget{}
+                      : lr    ? QcTarget::learned(t->target_res_dev, t->target_val_dev, to_learn(lr, d->opt_state_dev))
                       : table ? QcTarget::with_coef(t->target_res_dev, t->target_val_dev, cf->coef_res_dev)
                               : QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u);
   return fused_step(d, tg, step_batches(d, t), make_source(t, cf, cf ? cf->coef_res_dev : nullptr, ad, d->sample_bc_face_points),
@@ -930,6 +960,12 @@ int qc_fused_pinn_coef_step(const qc_step_desc* d, const qc_step_data* data, con
                             void* stream) {
   if (!data || !coef) return QC_ERR_ARG;
   return step_from(d, data, coef, nullptr, phases, stream);
+}
+
+int qc_fused_pinn_inverse_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_learn* learn, int phases,
+                               void* stream) {
+  if (!data || !learn_ok(learn)) return QC_ERR_ARG;
+  return step_from(d, data, nullptr, nullptr, phases, stream, learn);
 }
 
 int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef,

@@ -8,7 +8,8 @@ struct QcLayout {  // column offsets of the flat parameter / gradient vector
 };
 
 // K: rows of the last layer (outputs of the post network), W4[K][H] b4[K]; K = 1 is the single-output layout
-inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1) {
+// n_op: trainable operator entries behind theta (the inverse step: QC_COEF_N), counted in NP; no offset moves
+inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1, int n_op = 0) {
   QcLayout L;
   L.H = H;
   L.n = n;
@@ -21,7 +22,7 @@ inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1) {
   L.oW4 = L.ob3 + H;
   L.ob4 = L.oW4 + K * H;
   L.oTh = L.ob4 + K;
-  L.NP = L.oTh + n_theta;
+  L.NP = L.oTh + n_theta + n_op;
   return L;
 }
 
@@ -41,23 +42,41 @@ struct QcTab {
 // batch-minor [QC_COEF_COLS][B] next to the residual targets.  == QC_COEF_COLS of the public header.
 constexpr int QC_COEF_N = 7;
 
+// The trainable global operator of the inverse step: c_k = fmaf(scale[k], p[k], base[k]) with p the QC_COEF_N flat entries
+// behind theta (params[NP_L - 7 ..]); scale[k] = 0 freezes c_k at base[k].  hist / st: tile 0 of a residual launch stores
+// the seven c_k it used in hist[(st->step - st->hist_base) * 7 + k] when that row lies in [0, hist_cap); null: no history.
+struct QcOptState;
+struct QcLearn {
+  float base[QC_COEF_N], scale[QC_COEF_N];
+  float* hist;
+  int hist_cap;
+  const QcOptState* st;
+};
+
 // Where a post stage takes its targets and its operator from: analytic (functions of X, the operator of QcPde),
-// tabulated (tab), or tabulated with a coefficient table [QC_COEF_N][B_res] for the residual points (tab.c_u is then not
-// read).  The post launchers and everything above them pass this one value; the kernels receive nothing, tab, or tab and
-// coef as their last arguments.
-enum QcTargetKind { QC_TARGET_ANALYTIC = 0, QC_TARGET_TAB, QC_TARGET_COEF };
+// tabulated (tab), tabulated with a coefficient table [QC_COEF_N][B_res] for the residual points (tab.c_u is then not
+// read), or tabulated with the trainable global operator `learn` (tab.c_u and the operator of QcPde are not read; the
+// layout then counts QC_COEF_N more entries, n_op()).  The post launchers and everything above them pass this one value;
+// the kernels receive nothing, tab, tab and coef, or tab and learn as their last arguments.
+enum QcTargetKind { QC_TARGET_ANALYTIC = 0, QC_TARGET_TAB, QC_TARGET_COEF, QC_TARGET_LEARN };
 struct QcTarget {
   QcTargetKind kind = QC_TARGET_ANALYTIC;
   QcTab tab = {nullptr, nullptr, 0.f};
   const float* coef = nullptr;
+  QcLearn learn = {};
 
   static QcTarget tabulated(const float* tg_res, const float* tg_val, float c_u) {
-    return {QC_TARGET_TAB, {tg_res, tg_val, c_u}, nullptr};
+    return {QC_TARGET_TAB, {tg_res, tg_val, c_u}, nullptr, {}};
   }
   static QcTarget with_coef(const float* tg_res, const float* tg_val, const float* coef) {
-    return {QC_TARGET_COEF, {tg_res, tg_val, 0.f}, coef};
+    return {QC_TARGET_COEF, {tg_res, tg_val, 0.f}, coef, {}};
   }
-  // the value points of a step have no operator: the same targets without the table
+  static QcTarget learned(const float* tg_res, const float* tg_val, const QcLearn& lr) {
+    return {QC_TARGET_LEARN, {tg_res, tg_val, 0.f}, nullptr, lr};
+  }
+  int n_op() const { return kind == QC_TARGET_LEARN ? QC_COEF_N : 0; }
+  // the value points of a step have no operator: the same targets without the table (a learned operator stays: the value
+  // tiles zero its gradient columns in their rows)
   QcTarget value_side() const { return kind == QC_TARGET_COEF ? tabulated(tab.tg_res, tab.tg_val, tab.c_u) : *this; }
   // THE validity rule: a coefficient table needs tabulated targets (it has them by construction), mode 2 and six
   // channels; tabulated targets need mode 2 and problem id 3

@@ -531,6 +531,62 @@ __device__ __forceinline__ void expand_ub(float (&ub)[NCH], float ub0, float gsc
   }
 }
 
+// LEARN (the inverse step): the operator is global and trainable.  The seven c_k = fmaf(scale_k, p_k, base_k) are formed once
+// per wave from the wave-uniform p = prm[NP_L - 7 ..] (L.NP counts them) and take the place of a coefficient row.
+__device__ __forceinline__ void learn_coefs(float (&cf)[QC_COEF_N], const float* __restrict__ prm, const QcLayout& L,
+                                            const float (&base)[QC_COEF_N], const float (&scale)[QC_COEF_N]) {
+  const float* __restrict__ pk = prm + (L.NP - QC_COEF_N);
+#pragma unroll
+  for (int k = 0; k < QC_COEF_N; ++k) cf[k] = fmaf(scale[k], pk[k], base[k]);
+}
+// Their gradient columns in the tile's row (wave 0): d loss / d c_k = sum over the tile's points of gsc times the term c_k
+// multiplies (dead lanes: gsc = 0), in fixed order, scaled by scale_k; exactly 0 for a frozen entry.  Tile 0 of a launch
+// with a history buffer also stores the c_k it used, in the row of the step the optimiser record is in.
+// `z`: 0, or the opaque zero of learn_late().
+__device__ __forceinline__ void learn_columns(float* __restrict__ row, const QcLayout& L, const QcLearn* lr, const int z,
+                                              const float (&scale)[QC_COEF_N], const float (&cf)[QC_COEF_N], const float gsc,
+                                              const float (&u)[6], const int lane, const bool tile0) {
+  float gv[QC_COEF_N] = {gsc * u[0], gsc * u[1], gsc * u[2], gsc * u[3], -gsc * u[4], -gsc * u[5], gsc * (u[0] * u[0] * u[0])};
+  qc_wave_sum_multi_to_lane63<QC_COEF_N>(gv);
+  if (lane == 63) {
+#pragma unroll
+    for (int k = 0; k < QC_COEF_N; ++k) row[L.NP - QC_COEF_N + k] = scale[k] == 0.f ? 0.f : scale[k] * gv[k];
+    if (tile0) {
+      float* hist = (&lr->hist)[z];
+      const QcOptState* st = (&lr->st)[z];
+      if (hist != nullptr && st != nullptr) {
+        const int hi = st->step - st->hist_base;
+        if (hi >= 0 && hi < (&lr->hist_cap)[z]) {
+#pragma unroll
+          for (int k = 0; k < QC_COEF_N; ++k) hist[(int64_t)hi * QC_COEF_N + k] = cf[k];
+        }
+      }
+    }
+  }
+}
+// The record is a kernel argument, and its fields would be fetched at the kernel's entry: eighteen more scalar registers
+// through phase A cost the fused kernels a resident wave (n = 2) or scalar spills (n = 4, 8).  Indexed with a zero the
+// compiler cannot see through, they are scalar loads where they are first needed, behind the tile's first barrier.
+__device__ __forceinline__ int learn_late() {
+  int z = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(z));
+#endif
+  return z;
+}
+__device__ __forceinline__ void learn_read(const QcLearn* lr, const int z, float (&base)[QC_COEF_N], float (&scale)[QC_COEF_N]) {
+#pragma unroll
+  for (int k = 0; k < QC_COEF_N; ++k) {
+    base[k] = lr->base[k + z];
+    scale[k] = lr->scale[k + z];
+  }
+}
+// a value tile's row: the seven columns are zero (the partial rows are scratch, and the fold sums every row)
+__device__ __forceinline__ void learn_zero_columns(float* __restrict__ row, const QcLayout& L) {
+#pragma unroll
+  for (int k = 0; k < QC_COEF_N; ++k) row[L.NP - QC_COEF_N + k] = 0.f;
+}
+
 // DATA (MODE 2 only, QC_PB_TABULATED): the point's target is tg[p] instead of the analytic function of X, and the residual
 // carries the zeroth-order term c_u u, whose cotangent on u is c_u gsc.  DATA = false is the code as it was.
 // COEF (with DATA, residual points only): the operator is the point's own row coef[k][p], k = c_u, c_t, c_x, c_y, d_xx,
@@ -538,7 +594,9 @@ __device__ __forceinline__ void expand_ub(float (&ub)[NCH], float ub0, float gsc
 // reverse pass is then per lane, and the cubic term adds a second direction, the unit cotangent of u alone (N more
 // accumulators): its weight 3 c_3 u^2 is only known after the loop.  out_u receives all six channel cotangents [6][B]
 // (the weight-gradient kernel runs in its gen mode on them); out_res is not written.
-template <int N, int NCH, int MODE, bool DATA = false, bool COEF = false>
+// LEARN (with DATA): residual points run the COEF arithmetic on the uniform c_k of `lr` and wave 0 adds their gradient
+// columns; value points only zero those columns.  OPC below: either of the two.
+template <int N, int NCH, int MODE, bool DATA = false, bool COEF = false, bool LEARN = false>
 __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                                               QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ out_res,
@@ -546,9 +604,11 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
                                               float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B,
                                               const float* __restrict__ tg = nullptr, const float c_u = 0.f,
-                                              const float* __restrict__ coef = nullptr) {
+                                              const float* __restrict__ coef = nullptr, const QcLearn* lr = nullptr) {
   static_assert(!DATA || MODE == 2, "tabulated targets: the fused mode only");
   static_assert(!COEF || (DATA && NCH == 6), "per-point operators: tabulated residual points only");
+  static_assert(!LEARN || (DATA && !COEF), "learned operators: tabulated targets, no table");
+  constexpr bool OPC = COEF || (LEARN && NCH == 6);
   // block = 4 waves on one 64-point tile; wave w owns a quarter of the hidden units
   __shared__ float s_buf[QC_MS][NCH * N][64];   // partial u jets first (NCH rows), partial qbar later
   const int lane = threadIdx.x & 63;
@@ -562,10 +622,15 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int i = 0; i < N; ++i) q[c][i] = qjets[((int64_t)c * N + i) * B + pc];
-  float cf[COEF ? QC_COEF_N : 1];
+  float cf[OPC ? QC_COEF_N : 1];
   if constexpr (COEF) {
 #pragma unroll
     for (int k = 0; k < QC_COEF_N; ++k) cf[k] = coef[(int64_t)k * B + pc];
+  }
+  float lbase[LEARN && NCH == 6 ? QC_COEF_N : 1], lscale[LEARN && NCH == 6 ? QC_COEF_N : 1];
+  if constexpr (LEARN && NCH == 6) {
+    learn_read(lr, 0, lbase, lscale);
+    learn_coefs(cf, prm, L, lbase, lscale);
   }
   const float* W3 = prm + L.oW3;
   const float* b3 = prm + L.ob3;
@@ -575,8 +640,8 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 
   float ub0 = 0.f, gsc = 0.f;  // cotangent of u, and of the residual
   float k3 = 0.f;              // COEF: 3 c_3 u^2, the weight of the second direction
-  float qbu0[COEF ? N : 1];    // COEF: reverse pass of the unit cotangent of u alone
-  if constexpr (COEF) {
+  float qbu0[OPC ? N : 1];     // COEF: reverse pass of the unit cotangent of u alone
+  if constexpr (OPC) {
 #pragma unroll
     for (int i = 0; i < N; ++i) qbu0[i] = 0.f;
   }
@@ -595,7 +660,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 #pragma unroll
     for (int c = 0; c < NCH; ++c) u[c] = 0.f;
     float ub_unit[NCH];
-    if constexpr (COEF) {
+    if constexpr (OPC) {
       ub_unit[0] = cf[0]; ub_unit[1] = cf[1]; ub_unit[2] = cf[2]; ub_unit[3] = cf[3]; ub_unit[4] = -cf[4]; ub_unit[5] = -cf[5];
     } else {
       expand_ub<NCH>(ub_unit, NCH == 6 ? (DATA ? c_u : 0.f) : 1.f, NCH == 6 ? 1.f : 0.f, pde);
@@ -629,7 +694,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 #pragma unroll
           for (int c = 0; c < NCH; ++c) qbu[c][i] = fmaf(w3, gb[c], qbu[c][i]);
         }
-        if constexpr (COEF) {   // post_cotangents of ub = (1, 0, ..): gb[0] = w4 d1 and nothing else
+        if constexpr (OPC) {   // post_cotangents of ub = (1, 0, ..): gb[0] = w4 d1 and nothing else
           const float g0 = w4 * (1.f - z * z);
 #pragma unroll
           for (int i = 0; i < N; ++i) qbu0[i] = fmaf(W3[m * N + i], g0, qbu0[i]);
@@ -652,14 +717,14 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
       return;
     }
     float res = 0.f;
-    if constexpr (COEF) {
+    if constexpr (OPC) {
       res = cf[1] * u[1] + cf[2] * u[2] + cf[3] * u[3] - (cf[4] * u[4] + cf[5] * u[5]);
       res = fmaf(fmaf(cf[6] * u[0], u[0], cf[0]), u[0], res);
       k3 = 3.f * cf[6] * u[0] * u[0];
     } else if constexpr (NCH == 6) {
       res = pde.c_t * u[1] + pde.c_x * u[2] + pde.c_y * u[3] - (pde.d_xx * u[4] + pde.d_yy * u[5]);
     }
-    if constexpr (NCH == 6 && DATA && !COEF) res = fmaf(c_u, u[0], res);
+    if constexpr (NCH == 6 && DATA && !OPC) res = fmaf(c_u, u[0], res);
     if constexpr (MODE == 0) {
       if (live && wave == 0) {
         if (out_u) out_u[p] = u[0];
@@ -679,7 +744,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
         const float target = DATA ? tgp : residual_target(pde, t, x, y);
         const float e = live ? res - target : 0.f;
         gsc = pde.w_res * e;
-        if constexpr (COEF) ub0 = (cf[0] + k3) * gsc;
+        if constexpr (OPC) ub0 = (cf[0] + k3) * gsc;
         else if constexpr (DATA) ub0 = c_u * gsc;   // reaches k_post_wg through out_u (W4 / b4 / hidden-layer gradients)
         if (wave == 0) {
           const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
@@ -688,6 +753,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
             row[L.NP + 1] = 0.f;
             row[L.NP + 2] = 0.f;
           }
+          if constexpr (LEARN) learn_columns(row, L, lr, 0, lscale, cf, gsc, u, lane, tile == 0);
         }
       } else {
         const bool seg_a = p < pde.n_seg_a;
@@ -701,10 +767,11 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
             row[L.NP + 0] = 0.f;
             row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
             row[L.NP + 2] = la;
+            if constexpr (LEARN) learn_zero_columns(row, L);
           }
         }
       }
-      if constexpr (COEF) {
+      if constexpr (OPC) {
         if (live && wave == 0) {  // the six channel cotangents, for k_post_wg in its gen mode
           out_u[p] = ub0;
           out_u[B + p] = gsc * cf[1];
@@ -729,7 +796,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
       for (int i = 0; i < N; ++i) {
-        if constexpr (COEF) s_buf[wave][c * N + i][lane] = scale * (c == 0 ? fmaf(k3, qbu0[i], qbu[c][i]) : qbu[c][i]);
+        if constexpr (OPC) s_buf[wave][c * N + i][lane] = scale * (c == 0 ? fmaf(k3, qbu0[i], qbu[c][i]) : qbu[c][i]);
         else s_buf[wave][c * N + i][lane] = scale * qbu[c][i];
       }
     __syncthreads();
@@ -787,10 +854,13 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 // template per launch shape takes them as a pack, so the analytic instantiations carry no argument for them.  QcKind
 // names the DATA / COEF flags of the bodies and picks what the bodies take out of the pack, where they take it: null /
 // zero for what the kind does not have or does not read (c_u beside a coefficient table).
+// (QcTab, QcLearn): the inverse step, the trainable global operator by value; its residual bodies take no table.
 template <class... TG>
 struct QcKind {
-  static_assert(sizeof...(TG) <= 2, "(), (QcTab) or (QcTab, const float*)");
-  static constexpr bool data = sizeof...(TG) >= 1, coef = sizeof...(TG) == 2;
+  static_assert(sizeof...(TG) <= 2, "(), (QcTab), (QcTab, const float*) or (QcTab, QcLearn)");
+  static constexpr bool data = sizeof...(TG) >= 1;
+  static constexpr bool learn = (std::is_same_v<TG, QcLearn> || ...);
+  static constexpr bool coef = sizeof...(TG) == 2 && !learn;
   static __device__ __forceinline__ const float* tg_res(const TG&... t) {
     if constexpr (data) return std::get<0>(std::tie(t...)).tg_res; else return nullptr;
   }
@@ -798,7 +868,10 @@ struct QcKind {
     if constexpr (data) return std::get<0>(std::tie(t...)).tg_val; else return nullptr;
   }
   static __device__ __forceinline__ float c_u(const TG&... t) {
-    if constexpr (data && !coef) return std::get<0>(std::tie(t...)).c_u; else return 0.f;
+    if constexpr (data && !coef && !learn) return std::get<0>(std::tie(t...)).c_u; else return 0.f;
+  }
+  static __device__ __forceinline__ const QcLearn* op(const TG&... t) {
+    if constexpr (learn) return &std::get<1>(std::tie(t...)); else return nullptr;
   }
   static __device__ __forceinline__ const float* table(const TG&... t) {
     if constexpr (coef) return std::get<1>(std::tie(t...)); else return nullptr;
@@ -815,9 +888,9 @@ __global__ void __launch_bounds__(256) k_post(const float* __restrict__ X, const
                                               float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B, TG... tg) {
   using K = QcKind<TG...>;
-  k_post_body<N, NCH, MODE, K::data, K::coef>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar, part,
-                                              part_stride, row0, B, NCH == 6 ? K::tg_res(tg...) : K::tg_val(tg...),
-                                              K::c_u(tg...), K::table(tg...));
+  k_post_body<N, NCH, MODE, K::data, K::coef, K::learn>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar,
+                                                        part, part_stride, row0, B, NCH == 6 ? K::tg_res(tg...) : K::tg_val(tg...),
+                                                        K::c_u(tg...), K::table(tg...), K::op(tg...));
 }
 
 // Weight gradients of the post network: lane = hidden unit m (owns row m of W3, b3[m], W4[m]); the
@@ -988,7 +1061,7 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
 }
 
 // fused (mode 2) post stage of a value tile: u, squared error against the analytic target, cotangent of <Z>
-template <int N, bool DATA = false>
+template <int N, bool DATA = false, bool LEARN = false>
 __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                               QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ qbar, float* __restrict__ part,
@@ -1045,6 +1118,7 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
     row[L.NP + 0] = 0.f;
     row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
     row[L.NP + 2] = la;
+    if constexpr (LEARN) learn_zero_columns(row, L);
   }
   if (live) {
     out_u[p] = ub0;
@@ -1110,7 +1184,7 @@ constexpr int qc_post_ub_a(int n) { return n == 3 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 
 constexpr bool qc_post_pf(int n) { return n <= 8; }   // prefetch of the next block
 constexpr int qc_post_ub_vb(int n) { return n <= 8 ? 2 : 1; }                 // phase B of a value tile: two reductions side by side
 
-template <int N, int TPB, bool DATA = false>
+template <int N, int TPB, bool DATA = false, bool LEARN = false>
 __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const float* __restrict__ X,
                                                         const float* __restrict__ prm, QcLayout L, QcPde pde,
                                                         const float* __restrict__ qjets, float* __restrict__ out_u,
@@ -1192,6 +1266,7 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
       row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
       row[L.NP + 2] = la;
       row[L.ob4] = sb4;
+      if constexpr (LEARN) learn_zero_columns(row, L);
     }
     if (live) out_u[p] = ub0;   // the per-point cotangent (MODE 2 contract of qc_post)
   }
@@ -1280,15 +1355,19 @@ template <int N> constexpr bool QC_POST6_PF_B = false;
 // itself, carried through expand_ub, the b4 column of the tile row and the out_u scratch.
 // COEF (with DATA): the point's own operator row coef[k][p] (see k_post_body), loaded ahead of phase A; u is known
 // before phase B, so the cubic term only changes the residual and ub0.  out_u receives the six channel cotangents [6][B].
-template <int N, bool DATA = false, bool COEF = false>
+// LEARN (with DATA): the COEF arithmetic on the uniform c_k of `lr` (learn_coefs), and seven more reductions on wave 0 for
+// their gradient columns (learn_columns).  OPC below: either of the two.
+template <int N, bool DATA = false, bool COEF = false, bool LEARN = false>
 __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                     QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                                     float* __restrict__ out_u, float* __restrict__ out_res,
                                                     float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
                                                     int64_t row0, int64_t B, float* __restrict__ s_dyn,
                                                     const float* __restrict__ tg = nullptr, const float c_u = 0.f,
-                                                    const float* __restrict__ coef = nullptr) {
+                                                    const float* __restrict__ coef = nullptr, const QcLearn* lr = nullptr) {
   static_assert(!COEF || DATA, "per-point operators: tabulated targets only");
+  static_assert(!LEARN || (DATA && !COEF), "learned operators: tabulated targets, no table");
+  constexpr bool OPC = COEF || LEARN;
   constexpr int NCH = 6;
   float* s_z = s_dyn;                                                        // [H][64]
   float (*s_u)[NCH][64] = reinterpret_cast<float (*)[NCH][64]>(s_dyn + L.H * 64);   // [QC_MS][NCH][64]
@@ -1305,7 +1384,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
 #pragma unroll
     for (int i = 0; i < N; ++i)
       q2[cp][i] = (mf2){qjets[((int64_t)(2 * cp) * N + i) * B + pc], qjets[((int64_t)(2 * cp + 1) * N + i) * B + pc]};
-  float cf[COEF ? QC_COEF_N : 1];   // seven coalesced loads, first used after phase A
+  float cf[OPC ? QC_COEF_N : 1];   // seven coalesced loads, first used after phase A
   if constexpr (COEF) {
 #pragma unroll
     for (int k = 0; k < QC_COEF_N; ++k) cf[k] = coef[(int64_t)k * B + pc];
@@ -1362,8 +1441,16 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   u[0] += prm[L.ob4];
   // ---------------- residual / error / loss sums / per-point cotangent
   float* row = part + (row0 + tile) * part_stride;
+  float lscale[LEARN ? QC_COEF_N : 1];
+  int lz = 0;
+  if constexpr (LEARN) {   // uniform: scalar loads, first needed here
+    float lbase[QC_COEF_N];
+    lz = learn_late();
+    learn_read(lr, lz, lbase, lscale);
+    learn_coefs(cf, prm, L, lbase, lscale);
+  }
   float res;
-  if constexpr (COEF) {
+  if constexpr (OPC) {
     res = cf[1] * u[1] + cf[2] * u[2] + cf[3] * u[3] - (cf[4] * u[4] + cf[5] * u[5]);
     res = fmaf(fmaf(cf[6] * u[0], u[0], cf[0]), u[0], res);
   } else {
@@ -1371,7 +1458,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   }
   float target;
   if constexpr (DATA) {
-    if constexpr (!COEF) res = fmaf(c_u, u[0], res);
+    if constexpr (!OPC) res = fmaf(c_u, u[0], res);
     target = tg[pc];
   } else {
     const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
@@ -1381,7 +1468,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   const float gsc = pde.w_res * e;
   // analytic problems: the loss sees u only through its derivatives
   float ub0 = DATA ? c_u * gsc : 0.f;
-  if constexpr (COEF) ub0 = fmaf(3.f * cf[6] * u[0], u[0], cf[0]) * gsc;
+  if constexpr (OPC) ub0 = fmaf(3.f * cf[6] * u[0], u[0], cf[0]) * gsc;
   if (wave == 0) {
     const float ls = qc_wave_sum_to_lane63(e * e * pde.inv_n_res);
     float sb4 = 0.f;      // d loss / d b4 = sum of the points' cotangents of u
@@ -1392,7 +1479,8 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
       row[L.NP + 2] = 0.f;
       row[L.ob4] = sb4;
     }
-    if constexpr (COEF) {
+    if constexpr (LEARN) learn_columns(row, L, lr, lz, lscale, cf, gsc, u, lane, tile == 0);
+    if constexpr (OPC) {
       if (live) {           // the six channel cotangents (qc_post_coef)
         out_u[p] = ub0;
         out_u[B + p] = gsc * cf[1];
@@ -1408,7 +1496,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   }
   // ---------------- phase B
   float ub[NCH];
-  if constexpr (COEF) {
+  if constexpr (OPC) {
     ub[0] = ub0; ub[1] = gsc * cf[1]; ub[2] = gsc * cf[2]; ub[3] = gsc * cf[3]; ub[4] = -cf[4] * gsc; ub[5] = -cf[5] * gsc;
   } else {
     expand_ub<NCH>(ub, ub0, gsc, pde);
@@ -1508,11 +1596,12 @@ __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X,
   extern __shared__ float s_dyn[];
   using K = QcKind<TG...>;
   if constexpr (NCH == 6)
-    k_post_fused6_body<N, K::data, K::coef>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B,
-                                            s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...));
+    k_post_fused6_body<N, K::data, K::coef, K::learn>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride,
+                                                      row0, B, s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...),
+                                                      K::op(tg...));
   else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part, part_stride,
-                                                           row0, B, s_dyn, K::tg_val(tg...));
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data, K::learn>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part,
+                                                                     part_stride, row0, B, s_dyn, K::tg_val(tg...));
 }
 
 // ================================================================== K outputs behind one shared network (Navier-Stokes)
@@ -1721,10 +1810,12 @@ __global__ void __launch_bounds__(256) k_post_both(const float* __restrict__ prm
                                                    int n_val, TG... tg) {
   using K = QcKind<TG...>;
   if ((int)blockIdx.x >= n_val)
-    k_post_body<N, 6, 2, K::data, K::coef>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr, r.qbar,
-                                           part, part_stride, r.row0, r.B, K::tg_res(tg...), K::c_u(tg...), K::table(tg...));
+    k_post_body<N, 6, 2, K::data, K::coef, K::learn>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr,
+                                                     r.qbar, part, part_stride, r.row0, r.B, K::tg_res(tg...), K::c_u(tg...),
+                                                     K::table(tg...), K::op(tg...));
   else
-    k_post_value4<N, K::data>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B, K::tg_val(tg...));
+    k_post_value4<N, K::data, K::learn>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B,
+                                        K::tg_val(tg...));
 }
 
 // fused post stage: here the residual tiles come first and the (shorter) value blocks fill the slots after them
@@ -1735,14 +1826,15 @@ __global__ void __launch_bounds__(256) k_post_fused_both(const float* __restrict
   extern __shared__ float s_dyn[];
   using K = QcKind<TG...>;
   if ((int)blockIdx.x < n_res)
-    k_post_fused6_body<N, K::data, K::coef>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride, r.row0,
-                                            r.B, s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...));
+    k_post_fused6_body<N, K::data, K::coef, K::learn>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride,
+                                                      r.row0, r.B, s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...),
+                                                      K::op(tg...));
   else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part,
-                                                           part_stride, v.row0, v.B, s_dyn, K::tg_val(tg...));
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data, K::learn>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub, v.qbar,
+                                                                     part, part_stride, v.row0, v.B, s_dyn, K::tg_val(tg...));
 }
 
-// GEN (the coefficient step): the residual tiles read their six channel cotangents from r.ub (gen mode of the body)
+// GEN (the coefficient step and the inverse step): the residual tiles read their six channel cotangents from r.ub (gen mode of the body)
 template <int N, bool GEN>
 __global__ void k_post_wg_both(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r, QcPostSeg v,
                                float* __restrict__ part, int64_t part_stride, int HB, int PS, int n_val) {
@@ -1843,11 +1935,19 @@ static inline void qc_post_mode(const int mode, F&& f) {
   f(qc_int<2>{});
 }
 
+// the learned-operator kind of both post launchers: defined at the end of this file, so that its instantiations lie behind
+// every other kernel of the code object (see qc_dispatch_seq)
+static int post_learn(const float* prm, QcLayout L, QcPde pde, const float* qjets, float* out_u, float* qbar, float* part,
+                      int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg);
+static int post_both_learn(const float* prm, QcLayout L, QcPde pde, const QcPostSeg& r, const QcPostSeg& v, float* part,
+                           int64_t part_stride, hipStream_t st, const QcTarget& tg);
+
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg) {
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   if (!tg.ok(mode, nch, pde.problem)) return QC_ERR_ARG;
+  if (tg.kind == QC_TARGET_LEARN) return post_learn(prm, L, pde, qjets, out_u, qbar, part, part_stride, row0, B, nch, st, tg);
   const int tiles = qc_ceil_div(B, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
@@ -1931,6 +2031,9 @@ int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, c
                      int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcTarget& tg) {
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   if (!tg.ok(2, 6, pde.problem)) return QC_ERR_ARG;
+  if (tg.kind == QC_TARGET_LEARN)
+    return post_both_learn(prm, L, pde, QcPostSeg{Xr, qjr, ubr, rbr, qbr, row0_r, Br}, QcPostSeg{Xv, qjv, ubv, nullptr, qbv, row0_v, Bv},
+                           part, part_stride, st, tg);
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
@@ -2222,5 +2325,61 @@ int qc_mlp_post_system(const float* prm, QcLayout L, const QcSys& sys, QcPde pde
                          part_stride, row0, B);
     };
     if (nch == 6) launch(qc_int<6>{}); else launch(qc_int<1>{});
+  });
+}
+
+// ------------------------------------------------------------------ the learned-operator kind (the inverse step)
+// qc_mlp_post (mode 2) with the trailing arguments (QcTab, QcLearn): the fused kernel, or point kernel and weight-gradient
+// kernel; the residual tiles leave their six channel cotangents in out_u, which the weight-gradient kernel reads in its
+// gen mode
+static int post_learn(const float* prm, QcLayout L, QcPde pde, const float* qjets, float* out_u, float* qbar, float* part,
+                      int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg) {
+  const int tiles = qc_ceil_div(B, 64);
+  int HB, PS, threads;
+  hidden_geometry(L.H, &HB, &PS, &threads);
+  const size_t sh = (size_t)PS * (L.n + 2) * HB * sizeof(float);
+  const bool fused = post_fused_ok(L);
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L);
+  const float* X = nullptr;      // tabulated targets: not read
+  float* out_res = nullptr;      // six cotangents in out_u: not written
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c) {
+      constexpr int N = n(), NCH = c();
+      if (fused) {
+        hipLaunchKernelGGL((k_post_fused<N, NCH, QcTab, QcLearn>), dim3(NCH == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)),
+                           dim3(256), NCH == 6 ? shr : shv, st, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0,
+                           B, tg.tab, tg.learn);
+        return;
+      }
+      hipLaunchKernelGGL((k_post<N, NCH, 2, QcTab, QcLearn>), dim3(tiles), dim3(256), 0, st, X, prm, L, pde, qjets, out_u, out_res,
+                         (const float*)nullptr, (const float*)nullptr, qbar, part, part_stride, row0, B, tg.tab, tg.learn);
+      hipLaunchKernelGGL((k_post_wg<N, NCH>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets, (const float*)out_u,
+                         (const float*)nullptr, part, part_stride, row0, B, HB, PS, NCH == 6 ? 1 : 0);
+    };
+    if (nch == 6) launch(qc_int<6>{}); else launch(qc_int<1>{});
+  });
+}
+
+// qc_mlp_post_both with the same arguments: the merged form exists for the register family only (n = 2 .. 5)
+static int post_both_learn(const float* prm, QcLayout L, QcPde pde, const QcPostSeg& r, const QcPostSeg& v, float* part,
+                           int64_t part_stride, hipStream_t st, const QcTarget& tg) {
+  const int nr = qc_ceil_div(r.B, 64), nv = qc_ceil_div(v.B, 64);
+  int HB, PS, threads;
+  hidden_geometry(L.H, &HB, &PS, &threads);
+  const size_t sh = (size_t)PS * (L.n + 2) * HB * sizeof(float);
+  const int nv4 = qc_ceil_div(nv, 4), nvf = qc_ceil_div(nv, QC_POST_VALUE_TPB);
+  const bool fused = post_fused_ok(L);
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L), shf = shr > shv ? shr : shv;
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    constexpr int N = n();
+    if (fused) {
+      hipLaunchKernelGGL((k_post_fused_both<N, QcTab, QcLearn>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,
+                         part_stride, nr, tg.tab, tg.learn);
+    } else {
+      hipLaunchKernelGGL((k_post_both<N, QcTab, QcLearn>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,
+                         nv4, tg.tab, tg.learn);
+      hipLaunchKernelGGL((k_post_wg_both<N, true>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride,
+                         HB, PS, nv);
+    }
   });
 }

@@ -82,6 +82,53 @@ def _segment(name, X, y):
     return X.contiguous(), y.contiguous()
 
 
+class LearnedOperator(torch.nn.Module):
+    """The operator of an inverse problem: one global coefficient per ``COEF_COLUMNS`` entry, some of them trainable,
+
+        c_k = scale_k * p_k + base_k        (``qc_fused_pinn_inverse_step``; formed with one fused multiply-add).
+
+    ``fixed`` maps a column to its value, ``learn`` maps a column to its initial value, ``scale`` maps a LEARNED column to
+    a positive multiplier (default 1); columns not named are fixed at 0.  ``p`` (7,) is the one Parameter and starts at
+    0, ``base`` holds the fixed and the initial values, ``scale`` is 0 for a fixed column.  Adam moves every ``p_k`` by
+    about ``lr`` per step, so ``scale_k`` is the coefficient's learning-rate multiplier: set it to the magnitude the
+    coefficient is expected to have (a diffusivity of 0.01 cannot be learnt in steps of 0.005)."""
+
+    def __init__(self, fixed=None, learn=None, scale=None):
+        super().__init__()
+        import math
+        fixed, learn, scale = dict(fixed or {}), dict(learn or {}), dict(scale or {})
+        unknown = (set(fixed) | set(learn) | set(scale)) - set(COEF_COLUMNS)
+        if unknown:
+            raise ValueError(f"unknown coefficient column(s) {sorted(unknown)}: the columns are {COEF_COLUMNS}")
+        both = set(fixed) & set(learn)
+        if both:
+            raise ValueError(f"column(s) {sorted(both)} are named as fixed and as learned")
+        stray = set(scale) - set(learn)
+        if stray:
+            raise ValueError(f"scale is for learned columns only, got {sorted(stray)}")
+        base, sc = [0.0] * len(COEF_COLUMNS), [0.0] * len(COEF_COLUMNS)
+        for k, name in enumerate(COEF_COLUMNS):
+            v = float(fixed.get(name, learn.get(name, 0.0)))
+            if not math.isfinite(v):
+                raise ValueError(f"coefficient {name}: {v} is not finite")
+            base[k] = v
+            if name in learn:
+                m = float(scale.get(name, 1.0))
+                if not (math.isfinite(m) and m > 0.0):
+                    raise ValueError(f"scale of {name}: must be a finite number > 0, got {m}")
+                sc[k] = m
+        self.p = torch.nn.Parameter(torch.zeros(len(COEF_COLUMNS), dtype=torch.float32))
+        self.register_buffer("base", torch.tensor(base, dtype=torch.float32))
+        self.register_buffer("scale", torch.tensor(sc, dtype=torch.float32))
+
+    def values(self):
+        """(7,) tensor of the effective coefficients: ``base`` where ``scale`` is 0, whatever ``p`` holds."""
+        return torch.where(self.scale == 0, self.base, torch.addcmul(self.base, self.scale, self.p.detach()))
+
+    def coefficients(self):
+        return {name: float(v) for name, v in zip(COEF_COLUMNS, self.values().cpu())}
+
+
 class AdaptiveSampling:
     """Residual-adaptive sampling of a dataset's residual rows (RAD / RAR: Wu et al. 2023, Lu et al. 2021): every ``every``
     steps, starting with the first, the residual e_j = |res_j - r_j| is evaluated on ALL residual rows under the current

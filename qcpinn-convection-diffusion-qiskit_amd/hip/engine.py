@@ -709,3 +709,123 @@ class SystemStep:
             self.desc.sample_step += 1          # a fresh counter block per step
         L.check(self.lib.qc_fused_pinn_system_step(C.byref(self.desc), C.byref(self.sys), phases, _stream(self.device)),
                 "qc_fused_pinn_system_step")
+
+
+class InverseStep:
+    """One ``qc_fused_pinn_inverse_step`` descriptor over fixed-size resident batches: the tabulated step with a trainable
+    global operator c_k = fmaf(scale_k, p_k, base_k), k in ``QC_COEF_COLS`` order.
+
+    ``flat`` holds ``NP + 7`` entries, trained in place: the single-output layout (``param_layout(H, n, n_theta)``) and
+    the seven ``p_k`` behind it; ``opt`` holds as many.  ``base`` / ``scale``: seven floats each (``scale_k = 0`` freezes
+    a coefficient).  The caller fills ``X_res`` / ``X_val`` (IC points first, then BC) and ``target_res`` / ``target_val``,
+    or hands over a resident dataset with ``set_dataset`` and lets ``QC_PHASE_SAMPLE`` gather points and targets.
+    ``coef_hist`` [hist_cap, 7] receives the coefficients each step used, beside the loss history of ``opt``."""
+
+    def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, base, scale, B_res: int, n_ic: int, n_bc: int,
+                 opt: OptimState, counts=None, loss_weights=(2.0, 4.0, 2.0)):
+        self.lib, self.circuit, self.opt = circuit.lib, circuit, opt
+        dev, n = circuit.device, circuit.n
+        self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
+        check_network_shape(self.H, n)
+        self.layout = param_layout(self.H, n, self.n_theta)
+        self.NP = self.layout["__total__"][0]
+        self.NP_L = self.NP + L.QC_COEF_COLS
+        self.theta_off = self.layout["quantum_layer.params"][0]
+        if flat.numel() != self.NP_L:
+            raise L.QcError(f"flat parameter vector has {flat.numel()} entries, the layout with the operator needs {self.NP_L}")
+        if opt.m.numel() != self.NP_L:
+            raise L.QcError(f"optimiser state holds {opt.m.numel()} entries, the layout with the operator needs {self.NP_L}")
+        self.flat = _need(flat, dev, "flat params")
+        base, scale = [float(v) for v in base], [float(v) for v in scale]
+        if len(base) != L.QC_COEF_COLS or len(scale) != L.QC_COEF_COLS:
+            raise L.QcError(f"base and scale hold {L.QC_COEF_COLS} entries each")
+        self.B_res, self.n_ic, self.n_bc = B_res, n_ic, n_bc
+        B_val = n_ic + n_bc
+        f = dict(dtype=torch.float32, device=dev)
+        self.X_res = torch.zeros(max(B_res, 1), 3, **f)
+        self.X_val = torch.zeros(max(B_val, 1), 3, **f)
+        self.target_res = torch.zeros(max(B_res, 1), **f)
+        self.target_val = torch.zeros(max(B_val, 1), **f)
+        self.data = L.QcStepData()
+        self.data.target_res_dev, self.data.target_val_dev = self.target_res.data_ptr(), self.target_val.data_ptr()
+        self.data.c_u = float("nan")                 # not read: the operator is `learn`
+        self.coef_hist = torch.zeros(max(opt.hist_cap, 1), L.QC_COEF_COLS, **f)
+        self.learn = L.QcStepLearn()
+        for k in range(L.QC_COEF_COLS):
+            self.learn.base[k], self.learn.scale[k] = base[k], scale[k]
+        self.learn.coef_hist_dev = self.coef_hist.data_ptr() if opt.hist_cap > 0 else None
+        self.learn.coef_hist_cap = opt.hist_cap
+        self._dataset = None
+        self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
+        self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
+        rows = (B_res + 63) // 64 + (B_val + 63) // 64
+        self.stride = self.NP_L + 3
+        self.part = torch.zeros(rows, self.stride, **f)
+        self.flat_grad = torch.zeros(self.stride, **f)
+        g_res, g_ic, g_bc = counts if counts is not None else (B_res, n_ic, n_bc)
+        g_res, g_ic, g_bc = max(g_res, 1), max(g_ic, 1), max(g_bc, 1)
+        w_r, w_bc, w_ic = (float(w) for w in loss_weights)
+        nan = float("nan")
+        c = circuit
+        d = L.QcStepDesc()
+        d.prog, d.trig_dev, d.umat_dev = c.handle, c.trig.data_ptr(), _ptr(c.umat)
+        d.H, d.n, d.n_theta = self.H, n, self.n_theta
+        d.params_dev, d.m_dev, d.v_dev = self.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
+        d.opt_state_dev = opt.state.data_ptr()
+        d.hist_dev, d.hist_cap = (opt.hist.data_ptr() if opt.hist_cap > 0 else None), opt.hist_cap
+        d.X_res_dev, d.B_res = self.X_res.data_ptr(), B_res
+        d.X_val_dev, d.B_val = self.X_val.data_ptr(), B_val
+        (d.ajets_res_dev, d.qjets_res_dev, d.qbar_res_dev, d.abar_res_dev) = [self.ws_res[i].data_ptr() for i in range(4)]
+        (d.ajets_val_dev, d.qjets_val_dev, d.qbar_val_dev, d.abar_val_dev) = [self.ws_val[i].data_ptr() for i in range(4)]
+        d.part_dev, d.part_stride, d.part_rows_cap = self.part.data_ptr(), self.stride, rows
+        d.flat_dev = self.flat_grad.data_ptr()
+        # d loss / d err = 2 w / N per unit error; the operator coefficients of the record are not read
+        d.pde = L.QcPde(0.0, 0.0, 0.0, nan, nan, nan, nan, nan, 2.0 * w_r / g_res, 1.0 / g_res, 2.0 * w_ic / g_ic,
+                        2.0 * w_bc / g_bc, 1.0 / g_ic, 1.0 / g_bc, L.QC_PROBLEM_TABULATED, n_ic)
+        d.hyper = opt.hyper
+        need = int(self.lib.qc_step_workspace_bytes(c.handle, B_res, B_val))
+        self.step_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        d.circ_ws_dev, d.circ_ws_bytes = (self.step_ws.data_ptr(), need) if need else (None, 0)
+        d.n_ic = n_ic
+        d.comm = None
+        d.sample_off_res = d.sample_off_ic = d.sample_off_bc = 0
+        d.sample_seed, d.sample_step = 0, 0
+        d.sample_bc_face_points = 0
+        self.desc = d
+
+    def refresh_gates(self) -> None:
+        self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
+
+    def set_sampler(self, seed: int, off_res: int = 0, off_ic: int = 0, off_bc: int = 0) -> None:
+        """On-device gather (QC_PHASE_SAMPLE): Philox stream ``seed``; off_* = global index of this rank's first point."""
+        d = self.desc
+        d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
+        d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
+
+    def set_dataset(self, segments) -> None:
+        """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on
+        the step's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it."""
+        t = self.data
+        if segments is None:
+            segments = ((None, None),) * 3
+        keep = []
+        for name, (X, y) in zip(("res", "ic", "bc"), segments):
+            n = 0 if X is None else int(X.shape[0])
+            if n:
+                X, y = _need(X, self.device, "dataset points"), _need(y.reshape(-1), self.device, "dataset targets")
+                if X.dim() != 2 or X.shape[1] != 3 or y.numel() != n:
+                    raise L.QcError(f"dataset segment '{name}': points must be (N, 3) with N targets")
+                keep += [X, y]
+            setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
+            setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], y.data_ptr() if n else None)
+            setattr(t, "ds_n_" + name, n)
+        self._dataset = keep        # the record holds raw pointers: keep the tensors alive
+
+    def set_comm(self, comm) -> None:
+        self.desc.comm = comm
+
+    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
+        if phases & L.QC_PHASE_SAMPLE:
+            self.desc.sample_step += 1          # a fresh counter block per step
+        L.check(self.lib.qc_fused_pinn_inverse_step(C.byref(self.desc), C.byref(self.data), C.byref(self.learn), phases,
+                                                    _stream(self.device)), "qc_fused_pinn_inverse_step")

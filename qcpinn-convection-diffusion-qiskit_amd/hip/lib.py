@@ -32,6 +32,7 @@ EXPORTS = (
     "qc_post_coef", "qc_sample_dataset_coef", "qc_fused_pinn_coef_step",
     "qc_dataset_scores", "qc_adapt_bytes", "qc_adapt_build", "qc_sample_dataset_adaptive", "qc_fused_pinn_adaptive_step",
     "qc_post_system", "qc_sample_dataset_system", "qc_fused_pinn_system_step",
+    "qc_post_learn", "qc_fused_pinn_inverse_step",
 )
 
 
@@ -100,6 +101,13 @@ class QcStepData(C.Structure):
 class QcStepCoef(C.Structure):
     """qc_step_coef: the [7][B_res] operator rows of the current residual batch and the dataset's [N_res][7] table."""
     _fields_ = [("coef_res_dev", C.c_void_p), ("ds_coef", C.c_void_p)]
+
+
+class QcStepLearn(C.Structure):
+    """qc_step_learn: base and scale of the trainable operator c_k = fmaf(scale_k, p_k, base_k) (QC_COEF_COLS order) and the
+    optional [cap][7] history of the c_k each step used."""
+    _fields_ = [("base", C.c_float * QC_COEF_COLS), ("scale", C.c_float * QC_COEF_COLS),
+                ("coef_hist_dev", C.c_void_p), ("coef_hist_cap", C.c_int)]
 
 
 class QcStepAdapt(C.Structure):
@@ -216,6 +224,9 @@ def load() -> C.CDLL:
     lib.qc_sample_dataset_system.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, C.POINTER(QcStepSystem), C.c_uint64,
                                              C.c_uint64, vp]
     lib.qc_fused_pinn_system_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepSystem), i32, vp]
+    lib.qc_post_learn.argtypes = [fp, i32, i32, i32, C.POINTER(QcPde), C.POINTER(QcStepLearn), fp, fp, fp, fp, fp, i64, i64,
+                                  i64, vp]
+    lib.qc_fused_pinn_inverse_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepLearn), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

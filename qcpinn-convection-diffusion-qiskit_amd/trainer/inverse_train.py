@@ -1,0 +1,224 @@
+"""Fused training of a ``DVPDESolver`` on an inverse problem (``qc_fused_pinn_inverse_step``).
+
+Measurements of ``u`` are given and coefficients of the operator
+
+    residual = c_u u + c_3 u^3 + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy)
+
+are identified together with the network.  The reference's generic torch loop would serve this by handing the coefficient
+to Adam as one more ``nn.Parameter``; an ``InverseTrainer`` keeps the coefficients on the device behind the model's
+parameters and runs the whole iteration, their gradient and their Adam update included, as one library call.  The
+observations of ``u`` go into the IC / BC segments of a ``data.tabulated.TabulatedProblem`` (value points may lie anywhere
+in the domain), the residual points and their forcing values into its residual segment, the operator into a
+``data.tabulated.LearnedOperator``.
+"""
+from __future__ import annotations
+
+import torch
+
+from ..data.tabulated import COEF_COLUMNS, LearnedOperator, TabulatedProblem, _SCALARS
+from ..hip import engine as _engine
+from ..hip import lib as _lib
+from .diffusion_train import _dist_info
+
+
+class InverseTrainer:
+    """Device-resident training state of one single-output DVPDESolver and one LearnedOperator: ONE flat buffer of
+    ``NP + 7`` entries with the model's parameters in its head (``model.parameters()`` order, re-pointed at views of it)
+    and ``operator.p`` in its tail, so ``model(X)``, ``model.residual``, ``save_state`` and ``operator.coefficients()`` see
+    the trained values with no copy; the optimiser record taken from the model's torch Adam / ReduceLROnPlateau (which
+    ``operator.p`` joins as a second param group); and the step descriptor.  ``step()`` is one training iteration without
+    host synchronisation."""
+
+    def __init__(self, model, batch_size: int, dataset: TabulatedProblem, operator: LearnedOperator, *, n_ic: int = None,
+                 n_bc: int = None, loss_weights=(2.0, 4.0, 2.0), max_norm=1.0, capacity: int = 0, sampler: str = "device"):
+        """``dataset``: the resident segments (empty segments serve ``load_batches`` only); its scalar coefficients stay at
+        their defaults and it has no ``coef_res``: the operator is ``operator``.  ``batch_size`` residual, ``n_ic`` /
+        ``n_bc`` (default ``batch_size // 3``) value points per step; ``loss_weights`` = (residual, BC, IC); ``max_norm``
+        None: no clipping; ``capacity``: length of the loss and coefficient histories; ``sampler`` = "device" (the
+        library's gather) or "torch" (``torch.randint`` rows and a copy)."""
+        if not isinstance(dataset, TabulatedProblem):
+            raise ValueError("InverseTrainer needs dataset= a TabulatedProblem (residual and observation segments)")
+        if not isinstance(operator, LearnedOperator):
+            raise ValueError("InverseTrainer needs operator= a LearnedOperator")
+        if dataset.coef_res is not None:
+            raise ValueError("the dataset carries a per-point coefficient table (coef_res): an inverse problem takes its "
+                             "coefficients from operator= (LearnedOperator(fixed=..., learn=...)), one global value each")
+        defaults = tuple(float(_SCALARS[k]) for k in ("c_t", "c_x", "c_y", "d_xx", "d_yy"))
+        if tuple(dataset.coeffs) != defaults or dataset.c_u != float(_SCALARS["c_u"]):
+            raise ValueError("the dataset's scalar coefficients are not read by an inverse problem: leave them at their "
+                             "defaults and give them to operator= (LearnedOperator(fixed=..., learn=...))")
+        if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
+            raise ValueError("InverseTrainer needs classic_network = [3, H, 1]")
+        if sampler not in ("device", "torch"):
+            raise ValueError("sampler must be 'device' or 'torch'")
+        world, _ = _dist_info()
+        if world > 1:
+            raise ValueError("InverseTrainer is single-process: world_size > 1 is not supported")
+        n3 = batch_size // 3
+        self.B_res = int(batch_size)
+        self.n_ic = n3 if n_ic is None else int(n_ic)
+        self.n_bc = n3 if n_bc is None else int(n_bc)
+        if min(self.B_res, self.n_ic, self.n_bc) < 0 or self.B_res + self.n_ic + self.n_bc == 0:
+            raise ValueError("batch sizes must be non-negative and not all zero")
+        dev = model._resolve_device(model.device)
+        if dev is None or dev.type != "cuda":
+            raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
+        self.model, self.operator, self.device, self.sampler = model, operator, dev, sampler
+        self.dataset = dataset.to(dev)
+        self.max_norm = max_norm
+        self.loss_weights = tuple(float(w) for w in loss_weights)
+        self._pack()
+        self.circuit = model.quantum_layer._circuit_for(dev)
+        self.optimizer, self.scheduler = model.optimizer, model.scheduler
+        self.attach(model, operator)
+        self.opt = self._make_opt_state(int(capacity))
+        self.fs = _engine.InverseStep(self.circuit, model.hidden_width, self.flat, operator.base.tolist(),
+                                      operator.scale.tolist(), self.B_res, self.n_ic, self.n_bc, self.opt,
+                                      loss_weights=self.loss_weights)
+        ds = self.dataset
+        self._sampled = all(n_rows > 0 or n_batch == 0
+                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
+        if self._sampled:
+            self.fs.set_dataset(ds.segments())
+        self.fs.refresh_gates()
+        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        self._explicit = False
+        model._sync_fused_to_torch = self.sync_to_torch
+
+    @staticmethod
+    def attach(model, operator):
+        """``operator.p`` joins ``model.optimizer`` as a second param group with the hyper-parameters of the first, if it is
+        not there yet (the constructor calls this; call it on a fresh model before loading a saved optimiser state)."""
+        opt = model.optimizer
+        if not any(p is operator.p for g in opt.param_groups for p in g["params"]):
+            g0 = opt.param_groups[0]
+            opt.add_param_group({"params": [operator.p], **{k: v for k, v in g0.items() if k != "params"}})
+            sch = model.scheduler
+            sch.min_lrs = list(sch.min_lrs) + [sch.min_lrs[0]] * (len(opt.param_groups) - len(sch.min_lrs))
+
+    def _params(self):
+        return list(self.model.parameters()) + [self.operator.p]
+
+    def _pack(self):
+        """One flat buffer [model parameters | operator.p]; the model's own flat buffer becomes its head (a view), the way
+        ``model._pack`` builds it, and ``operator.p`` (base, scale) move to the device with p a view of the tail."""
+        model, op, dev = self.model, self.operator, self.device
+        if not model._packed_ok() or model._flat.device != dev:
+            model._pack(dev)
+        NP = model._flat.numel()
+        big = getattr(model, "_inverse_flat", None)
+        if not (big is not None and big.device == dev and big.numel() == NP + len(COEF_COLUMNS)
+                and model._flat.data_ptr() == big.data_ptr() and op.p.data_ptr() == big.data_ptr() + 4 * NP):
+            big = torch.cat([model._flat.detach(), op.p.detach().to(device=dev, dtype=torch.float32)])
+            off = 0
+            for p, k, pad in model._slots():
+                p.data = big[off:off + k].view(p.shape)
+                off += k
+            model._flat = big[:NP]
+            model._engines = {}
+            model._inverse_flat = big
+            op.p.data = big[NP:]
+            op.base.data = op.base.to(dev)
+            op.scale.data = op.scale.to(dev)
+        self.flat = model._inverse_flat
+        self.NP = NP
+
+    # -- optimiser state: continue from the torch optimiser / scheduler objects of the model (FusedTrainer's rule)
+    def _make_opt_state(self, capacity):
+        opt, sch = self.optimizer, self.scheduler
+        g = opt.param_groups[0]
+        st = _engine.OptimState(self.flat.numel(), float(g["lr"]), self.device, hist_cap=capacity, betas=tuple(g["betas"]),
+                                eps=float(g["eps"]), max_norm=self.max_norm, factor=float(sch.factor),
+                                patience=int(sch.patience), threshold=float(sch.threshold), min_lr=float(sch.min_lrs[0]),
+                                sched_eps=float(sch.eps), loss_weights=self.loss_weights)
+        steps, off = 0, 0
+        for p in self._params():
+            s = opt.state.get(p, None)
+            k = p.numel()
+            if s:
+                st.m[off:off + k] = s["exp_avg"].reshape(-1).to(self.device)
+                st.v[off:off + k] = s["exp_avg_sq"].reshape(-1).to(self.device)
+                steps = int(s["step"])
+            off += k
+        st.write(best=float(sch.best), num_bad=int(sch.num_bad_epochs), step=steps, hist_base=steps)
+        return st
+
+    def sync_to_torch(self):
+        """Mirror the device optimiser record into model.optimizer / model.scheduler (``save_state`` calls this)."""
+        rec = self.opt.read()
+        off = 0
+        for p in self._params():
+            k = p.numel()
+            self.optimizer.state[p] = {"step": torch.tensor(float(rec["step"])),
+                                       "exp_avg": self.opt.m[off:off + k].view(p.shape),
+                                       "exp_avg_sq": self.opt.v[off:off + k].view(p.shape)}
+            off += k
+        for g in self.optimizer.param_groups:
+            g["lr"] = rec["lr"]
+        sch = self.scheduler
+        sch.best, sch.num_bad_epochs = rec["best"], rec["num_bad_epochs"]
+        sch.last_epoch = rec["step"]
+        sch._last_lr = [rec["lr"]] * len(self.optimizer.param_groups)
+
+    # -- batches
+    def sample(self):
+        """Rows of the dataset, drawn with replacement.  With the device sampler this only arms the next ``step()``."""
+        if not self._sampled:
+            raise ValueError("the dataset has an empty segment behind a non-empty batch: use load_batches(...)")
+        self._explicit = False
+        if self.sampler == "device":
+            return
+        self._explicit = True
+        fs, dev = self.fs, self.device
+        (Xr, r), (Xi, ui), (Xb, ub) = self.dataset.segments()
+        for X, y, n, dX, dy, o in ((Xi, ui, self.n_ic, fs.X_val, fs.target_val, 0),
+                                   (Xb, ub, self.n_bc, fs.X_val, fs.target_val, self.n_ic),
+                                   (Xr, r, self.B_res, fs.X_res, fs.target_res, 0)):
+            if n:
+                idx = torch.randint(0, X.shape[0], (n,), device=dev)
+                dX[o:o + n] = X[idx]
+                dy[o:o + n] = y[idx]
+
+    def load_batches(self, X_ic, X_bc, X_res, targets):
+        """Use given batches: ``targets`` = (u_ic (n_ic,), u_bc (n_bc,), r_res (B_res,))."""
+        u_ic, u_bc, r = targets
+        fs, dev = self.fs, self.device
+        if (X_ic.shape[0], X_bc.shape[0], X_res.shape[0]) != (self.n_ic, self.n_bc, self.B_res):
+            raise ValueError(f"batches must hold ({self.n_ic}, {self.n_bc}, {self.B_res}) points")
+        as32 = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev)
+        for y, n, name in ((u_ic, self.n_ic, "u_ic"), (u_bc, self.n_bc, "u_bc"), (r, self.B_res, "r_res")):
+            if n and torch.as_tensor(y).numel() != n:
+                raise ValueError(f"{name} must hold {n} values: one per point")
+        self._explicit = True
+        if self.n_ic:
+            fs.X_val[: self.n_ic] = as32(X_ic)
+            fs.target_val[: self.n_ic] = as32(u_ic).reshape(-1)
+        if self.n_bc:
+            fs.X_val[self.n_ic: self.n_ic + self.n_bc] = as32(X_bc)
+            fs.target_val[self.n_ic: self.n_ic + self.n_bc] = as32(u_bc).reshape(-1)
+        if self.B_res:
+            fs.X_res[: self.B_res] = as32(X_res)
+            fs.target_res[: self.B_res] = as32(r).reshape(-1)
+
+    def step(self):
+        draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
+        self.fs.run(draw | _lib.QC_PHASE_GRADS | _lib.QC_PHASE_UPDATE)
+
+    def loss_history(self, steps=None):
+        return self.opt.loss_history(steps)
+
+    def losses(self):
+        rec = self.opt.read()
+        return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
+
+    def coefficient_history(self, steps=None):
+        """(steps, 7) tensor: row i holds the coefficients (``COEF_COLUMNS`` order) the i-th step of THIS history buffer
+        used, next to ``loss_history()[i]`` (default: all steps taken so far)."""
+        if steps is None:
+            rec = self.opt.read()
+            steps = rec["step"] - rec["hist_base"]
+        return self.fs.coef_hist[: max(0, min(int(steps), self.opt.hist_cap))].cpu()
+
+    def coefficients(self):
+        """The current effective coefficients as a dict over ``COEF_COLUMNS``."""
+        return self.operator.coefficients()
