@@ -216,6 +216,87 @@ int qc_adam_step(float* flat_dev, int NP, float* params_dev, float* m_dev, float
                  const qc_opt_hyper* hp, float* hist_dev, int hist_cap, const qc_program* prog, int theta_off,
                  void* trig_dev, void* stream);
 
+/* ---- L-BFGS on the device: the second training phase (Adam first, then L-BFGS on a fixed batch; the "Adam / L-BFGS"
+ * update of the reference's design note hybrid_testing/hybrid_qpinn.md).  qc_lbfgs_step is the counterpart of qc_adam_step:
+ * it reads flat_dev = [grad[NP] | L_r, L_bc, L_ic] evaluated at the CURRENT params_dev (what a step call with QC_PHASE_GRADS
+ * leaves, for every kind of step: NP is whatever that step's flat vector counts), advances a state machine that lives
+ * entirely in ws_dev, and writes the NEXT point to evaluate into params_dev; the trig table and the diagonal-run tables are
+ * refreshed from the new theta as qc_adam_step does.  One single-block launch; nothing is read back by the host; flat_dev is
+ * not written.  Fixed summation order: two runs of the same sequence are bit-identical.
+ *
+ * Workspace, 4-byte words, qc_lbfgs_workspace_bytes = 4 (32 + 3 NP + 2 m NP + m + 4 m^2), m = history:
+ *   words 0..31, the record (128 bytes):
+ *     int   0 phase            0: the next call is a first evaluation; 1: a trial point is pending
+ *     int   1 n_eval           calls so far (never reset by qc_lbfgs_restart)
+ *     int   2 n_iter           accepted points so far, first evaluations included
+ *     int   3 n_pairs          kept curvature pairs, <= m
+ *     int   4 head             ring slot the next kept pair is written to; the pairs, oldest first, sit in slots
+ *                              (head - n_pairs + k) mod m, k = 0 .. n_pairs - 1
+ *     int   5 ls_trials        rejected trials of the running line search
+ *     int   6 n_rejected   7 n_skipped_pairs   8 n_resets   9 stalled
+ *     int  10 sd_failed        the running search is the steepest-descent restart behind an exhausted search
+ *     int  11 NP  12 history  13 accepted (of the last call: 0 / 1)   14, 15 zero
+ *     float 16 t               step of the pending trial: params = x_k + t d (FIXED: the step the next pair is formed with)
+ *     float 17 f0  18 gtd0     loss at x_k and g_k . d
+ *     float 19 gamma           y.s / y.y of the newest kept pair (1 before the first)
+ *     float 20 f  21..23 L_r, L_bc, L_ic of the last call
+ *     float 24 t_led           the step that led from x_k to the pending point (0: the pending point is x_k)
+ *     25..31 zero
+ *   x_k[NP], g_k[NP], d[NP]    the last accepted point, its gradient, the search direction
+ *   S[m][NP], Y[m][NP]         the pairs s = t d, y = g - g_k by ring slot;  rho[m] = 1 / (y.s)
+ *   SY[m][m][2], YY[m][m][2]   Gram entries s_i . y_j and y_i . y_j by ring slot, each a (high, low) float pair whose sum in
+ *                              double is the entry: only the new pair's row and column are computed per call, together
+ *                              with S.g and Y.g, in ONE batched reduction; the two-loop recursion then runs on these
+ *                              scalars and d is one combination of [S, Y, g].  Scalars, recursion and combination are
+ *                              double; every stored vector is fp32.
+ *
+ * The rule.  f = w_res L_r + w_bc L_bc + w_ic L_ic; g = grad; no gradient clipping.  tfirst(v) = lr min(1, 1 / |v|_1).
+ *   push(s, y): keep the pair iff y.s > curv_eps (the oldest drops when m are kept) and then gamma = y.s / y.y; else count
+ *     it in n_skipped_pairs (ARMIJO) and keep gamma.
+ *   dir(g): d = -H g by the two-loop recursion over the kept pairs with H0 = gamma I (newest to oldest a_i = rho_i s_i.q,
+ *     q -= a_i y_i; r = gamma q; oldest to newest b_i = rho_i y_i.r, r += (a_i - b_i) s_i; d = -r).
+ *   First evaluation (after qc_lbfgs_init or qc_lbfgs_restart): x_k = params, g_k = g, f0 = f, d = -g, gtd0 = -g.g,
+ *     t = tfirst(g), params = x_k + t d, phase = 1, ls_trials = 0.  History row (f, 0, 1).
+ *   QC_LBFGS_FIXED, every later call: push(t d, g - g_k); x_k = params, g_k = g, f0 = f; d = dir(g); t = lr; gtd0 = g.d;
+ *     params += t d unless g.d >= 0, when params stays (t_led = 0; t, d, g_k are still replaced).  This is
+ *     torch.optim.LBFGS(lr, max_iter=1, history_size=m, tolerance_grad=0, tolerance_change=0, line_search_fn=None) called
+ *     once per evaluation.
+ *   QC_LBFGS_ARMIJO, a later call, not stalled: the trial is ACCEPTED iff f and every gradient entry are finite and
+ *     f <= f0 + c1 t gtd0.
+ *     accepted: push(t d, g - g_k); x_k = params, g_k = g, f0 = f, ls_trials = 0, sd_failed = 0.  With no kept pair:
+ *       d = -g, t = tfirst(g), gtd0 = -g.g.  Else d = dir(g), gtd0 = g.d, t = lr; if not gtd0 < 0: all pairs are dropped,
+ *       n_resets += 1, and d, t, gtd0 are those of the no-pair case.  params = x_k + t d.
+ *     rejected (n_rejected += 1), ls_trials + 1 < max_ls: ls_trials += 1; t_q = -gtd0 t^2 / (2 (f - f0 - gtd0 t));
+ *       t <- min(max(t_q, shrink_lo t), shrink_hi t), and t <- shrink_hi t when f or t_q is not finite;
+ *       params = x_k + t d.
+ *     rejected, ls_trials + 1 >= max_ls (the search is exhausted): if sd_failed is set and no pair is kept: stalled = 1,
+ *       params = x_k.  Else n_resets += 1, all pairs dropped, sd_failed = 1, ls_trials = 0, d = -g_k, t = tfirst(g_k),
+ *       gtd0 = -g_k.g_k, params = x_k + t d  (x_k, g_k, f0 stay).
+ *     stalled: params = x_k on every call; only n_eval, f and the loss parts change.
+ *   So an accepted iteration costs one evaluation, and every rejected trial one more.
+ *   History: hist_dev[e] = (f, t_led before the call, accepted 0 / 1) for the 0-based evaluation e = n_eval < hist_cap.
+ * qc_lbfgs_restart makes the next call a first evaluation at the current params (a new batch); keep_history = 0 also drops
+ * the pairs and sets gamma = 1.  Both clear stalled, sd_failed and ls_trials.
+ * QC_ERR_ARG, without a GPU: a NULL or misaligned buffer (hist_dev may be NULL), history outside 1..QC_LBFGS_MAX_HISTORY,
+ * NP < 1, an unknown line_search, max_ls < 1, lr, c1, shrink_lo, shrink_hi or curv_eps not finite or not positive,
+ * shrink_lo > shrink_hi, shrink_hi >= 1, a non-finite weight; prog with trig_dev NULL or theta_off + n_params > NP.
+ * qc_lbfgs_workspace_bytes returns 0 for a refused shape.  NP + 3 <= 3072 keeps a call's vectors in registers; larger NP
+ * strides over them. */
+#define QC_LBFGS_MAX_HISTORY 32
+#define QC_LBFGS_FIXED  0   /* torch.optim.LBFGS(line_search_fn=None): every trial is accepted */
+#define QC_LBFGS_ARMIJO 1   /* backtracking with safeguarded quadratic interpolation */
+typedef struct qc_lbfgs_hyper {
+  int history, line_search, max_ls;
+  float lr, c1, shrink_lo, shrink_hi, curv_eps;   /* defaults 1, 1e-4, 0.1, 0.5, 1e-10 */
+  float w_res, w_bc, w_ic;
+} qc_lbfgs_hyper;
+size_t qc_lbfgs_workspace_bytes(int NP, int history);
+int qc_lbfgs_init(void* ws_dev, int NP, int history, void* stream);
+int qc_lbfgs_restart(void* ws_dev, int keep_history, void* stream);
+int qc_lbfgs_step(float* flat_dev, int NP, float* params_dev, void* ws_dev, const qc_lbfgs_hyper* hp,
+                  float* hist_dev /*[hist_cap][3]*/, int hist_cap,
+                  const qc_program* prog, int theta_off, void* trig_dev, void* stream);
+
 /* ---- the three uniform batches of a step (trainer/diffusion_train.py:9-20,34-36: IC t=0 face, BC1 x=0
  * face, residual in [0,1]^3; data/diffusion_dataset.py:12-19) drawn on device with Philox4x32-10 keyed by
  * (seed, step, batch) and indexed by the GLOBAL point index off_* + i: ranks of a data-parallel run fill

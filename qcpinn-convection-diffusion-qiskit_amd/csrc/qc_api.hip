@@ -586,6 +586,42 @@ int qc_adam_step(float* flat, int NP, float* prm, float* m, float* v, void* stat
   return after_launch();
 }
 
+// ---- L-BFGS (qc_lbfgs.hip)
+static_assert(sizeof(QcLbfgsHyper) == sizeof(qc_lbfgs_hyper), "qc_lbfgs_hyper layout");
+static bool lbfgs_shape_ok(int NP, int history) { return NP >= 1 && history >= 1 && history <= QC_LBFGS_MAX_HISTORY; }
+static bool pos_finite(float v) { return isfinite(v) && v > 0.f; }
+
+size_t qc_lbfgs_workspace_bytes(int NP, int history) {
+  return lbfgs_shape_ok(NP, history) ? sizeof(float) * qc_lbfgs_words(NP, history) : 0;
+}
+
+int qc_lbfgs_init(void* ws, int NP, int history, void* stream) {
+  if (!ws || ((uintptr_t)ws & 3) || !lbfgs_shape_ok(NP, history)) return QC_ERR_ARG;
+  qc_lbfgs_init_launch(ws, NP, history, (hipStream_t)stream);
+  return after_launch();
+}
+
+int qc_lbfgs_restart(void* ws, int keep_history, void* stream) {
+  if (!ws || ((uintptr_t)ws & 3)) return QC_ERR_ARG;
+  qc_lbfgs_restart_launch(ws, keep_history != 0, (hipStream_t)stream);
+  return after_launch();
+}
+
+int qc_lbfgs_step(float* flat, int NP, float* prm, void* ws, const qc_lbfgs_hyper* hp, float* hist, int hist_cap,
+                  const qc_program* prog, int theta_off, void* trig, void* stream) {
+  if (!flat || !prm || !ws || ((uintptr_t)ws & 3) || !hp || !lbfgs_shape_ok(NP, hp->history)) return QC_ERR_ARG;
+  if (hp->line_search != QC_LBFGS_FIXED && hp->line_search != QC_LBFGS_ARMIJO) return QC_ERR_ARG;
+  if (hp->max_ls < 1 || !pos_finite(hp->lr) || !pos_finite(hp->c1) || !pos_finite(hp->shrink_lo) || !pos_finite(hp->shrink_hi) ||
+      !pos_finite(hp->curv_eps) || hp->shrink_lo > hp->shrink_hi || hp->shrink_hi >= 1.f)
+    return QC_ERR_ARG;
+  if (!isfinite(hp->w_res) || !isfinite(hp->w_bc) || !isfinite(hp->w_ic) || hist_cap < 0) return QC_ERR_ARG;
+  if (prog && (!trig || theta_off < 0 || theta_off + prog->n_params > NP)) return QC_ERR_ARG;
+  QcLbfgsHyper h;
+  memcpy(&h, hp, sizeof(h));
+  qc_lbfgs_step_launch(flat, NP, prm, ws, h, hist, hist_cap, prog, theta_off, (QcTrig*)trig, (hipStream_t)stream);
+  return after_launch();
+}
+
 // The one place that fills batches: the source's rule, the launch its kind selects, the launch status
 static int fill_batches(const QcBatches& b, const QcSource& s, void* stream) {
   if (!s.ok(b)) return QC_ERR_ARG;

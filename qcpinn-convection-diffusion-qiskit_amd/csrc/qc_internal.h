@@ -207,6 +207,30 @@ struct QcOptHyper {  // == qc_opt_hyper of the public header
   float w_res, w_bc, w_ic;  // loss = w_res*L_r + w_bc*L_bc + w_ic*L_ic   (2, 4, 2)
 };
 
+// The head of the L-BFGS workspace (qc_lbfgs.hip; == the 128-byte record documented at qc_lbfgs_step in the public header)
+constexpr int QC_LBFGS_REC_WORDS = 32;
+struct QcLbfgsRec {
+  int phase;            // 0: the next call is a first evaluation; 1: a trial point is pending
+  int n_eval, n_iter;   // calls so far; accepted points so far (first evaluations included)
+  int n_pairs, head;    // kept pairs; the ring slot the next pair goes to
+  int ls_trials;        // rejected trials of the running line search
+  int n_rejected, n_skipped_pairs, n_resets, stalled;
+  int sd_failed;        // the running search is the steepest-descent restart behind an exhausted one
+  int NP, history, accepted;
+  int pad0[2];
+  float t, f0, gtd0, gamma;   // step of the pending trial; loss and g.d at x_k; y.s / y.y of the newest kept pair
+  float f, loss_parts[3];     // of the last call
+  float t_led;                // the step that led from x_k to the pending point (0: the point is x_k itself)
+  float pad1[7];
+};
+static_assert(sizeof(QcLbfgsRec) == 4 * QC_LBFGS_REC_WORDS, "L-BFGS record");
+
+struct QcLbfgsHyper {  // == qc_lbfgs_hyper of the public header
+  int history, line_search, max_ls;
+  float lr, c1, shrink_lo, shrink_hi, curv_eps;
+  float w_res, w_bc, w_ic;
+};
+
 // ---- circuit families: one record per kernel family, chosen once per program (qc_program_create)
 // Scratch and kept final states of one pipeline.  HBM family: `p`/`bytes` is the scratch, `keep` keeps every tile
 // resident from the forward pass to the adjoint pass of the same batch.  Register and wave families: `p` is the store
@@ -280,6 +304,12 @@ int qc_opt_adam_fold(const float* part, int64_t stride, int RS, float* flat, int
 int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState* state, QcOptHyper hp,
                 float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t);
 int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hipStream_t);
+// qc_lbfgs.hip: floats of a workspace; zero it and write its record; make the next call a first evaluation; one call
+size_t qc_lbfgs_words(int NP, int m);
+int qc_lbfgs_init_launch(void* ws, int NP, int m, hipStream_t);
+int qc_lbfgs_restart_launch(void* ws, int keep, hipStream_t);
+int qc_lbfgs_step_launch(const float* flat, int NP, float* prm, void* ws, QcLbfgsHyper hp, float* hist, int hist_cap,
+                         const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t);
 // qc_sample.hip: fill the batches `b` from a source that QcSource::ok passed: the coordinate draw, or the dataset kinds
 int qc_sample_launch(const QcBatches& b, int64_t bc_face_points, hipStream_t);
 int qc_gather_launch(const QcBatches& b, const QcSource& s, hipStream_t);

@@ -411,6 +411,62 @@ class OptimState:
         return self.hist[: max(0, min(steps, self.hist_cap))].cpu().tolist()
 
 
+LBFGS_LINE_SEARCH = {"fixed": L.QC_LBFGS_FIXED, None: L.QC_LBFGS_FIXED, "armijo": L.QC_LBFGS_ARMIJO}
+
+
+class LbfgsState:
+    """Device-resident L-BFGS state of ``qc_lbfgs_step``: the workspace (128-byte record, x_k, g_k, d, the curvature pairs
+    and their Gram entries), the hyper-parameters and the [capacity][3] history (f, t that led to the point, accepted).
+    ``advance`` enqueues one call; ``read`` and ``history`` are host reads."""
+
+    _INTS = ("phase", "n_eval", "n_iter", "n_pairs", "head", "ls_trials", "n_rejected", "n_skipped_pairs", "n_resets",
+             "stalled", "sd_failed", "NP", "history", "accepted")
+    _FLOATS = ("t", "f0", "gtd0", "gamma", "f", "loss_res", "loss_bc", "loss_ic", "t_led")
+
+    def __init__(self, NP: int, device, history: int = 10, line_search="armijo", lr=1.0, c1=1e-4, max_ls=10,
+                 shrink_lo=0.1, shrink_hi=0.5, curv_eps=1e-10, loss_weights=(2.0, 4.0, 2.0), capacity: int = 0):
+        if line_search not in LBFGS_LINE_SEARCH:
+            raise ValueError(f"line_search must be 'armijo', 'fixed' or None, got {line_search!r}")
+        self.lib = L.load()
+        self.NP, self.m, self.device, self.hist_cap = int(NP), int(history), device, int(capacity)
+        need = int(self.lib.qc_lbfgs_workspace_bytes(self.NP, self.m))
+        if need == 0:
+            raise ValueError(f"L-BFGS needs NP >= 1 and 1 <= history <= {L.QC_LBFGS_MAX_HISTORY}, got NP={NP}, history={history}")
+        self.hyper = L.QcLbfgsHyper(self.m, LBFGS_LINE_SEARCH[line_search], int(max_ls), lr, c1, shrink_lo, shrink_hi, curv_eps,
+                                    *loss_weights)
+        self.ws = torch.empty(need // 4, dtype=torch.float32, device=device)
+        self.hist = torch.zeros(max(self.hist_cap, 1), 3, dtype=torch.float32, device=device)
+        L.check(self.lib.qc_lbfgs_init(self.ws.data_ptr(), self.NP, self.m, _stream(device)), "qc_lbfgs_init")
+
+    def restart(self, keep_history: bool = False) -> None:
+        """The next call is a first evaluation at the current parameters (a new batch)."""
+        L.check(self.lib.qc_lbfgs_restart(self.ws.data_ptr(), int(bool(keep_history)), _stream(self.device)), "qc_lbfgs_restart")
+
+    def advance(self, flat: torch.Tensor, params: torch.Tensor, circuit: Optional["Circuit"] = None, theta_off: int = 0) -> None:
+        """One ``qc_lbfgs_step``: ``flat`` = [grad[NP] | L_r, L_bc, L_ic] at ``params``; ``params`` receives the next point."""
+        prog, trig = (circuit.handle, circuit.trig.data_ptr()) if circuit is not None else (None, None)
+        L.check(self.lib.qc_lbfgs_step(flat.data_ptr(), self.NP, params.data_ptr(), self.ws.data_ptr(), C.byref(self.hyper),
+                                       self.hist.data_ptr() if self.hist_cap > 0 else None, self.hist_cap, prog, theta_off,
+                                       trig, _stream(self.device)), "qc_lbfgs_step")
+
+    def read(self) -> dict:
+        raw = self.ws[:L.QC_LBFGS_REC_WORDS].cpu().numpy()
+        ints = raw.view(np.int32)
+        out = {k: int(ints[i]) for i, k in enumerate(self._INTS)}
+        out.update({k: float(raw[16 + i]) for i, k in enumerate(self._FLOATS)})
+        return out
+
+    def x_k(self) -> torch.Tensor:
+        """The last accepted point (a view of the workspace)."""
+        return self.ws[L.QC_LBFGS_REC_WORDS:L.QC_LBFGS_REC_WORDS + self.NP]
+
+    def history(self, n: Optional[int] = None) -> np.ndarray:
+        """Rows (f, t, accepted) of the first ``n`` evaluations (default: all so far) that fit the buffer."""
+        if n is None:
+            n = self.read()["n_eval"]
+        return self.hist[: max(0, min(n, self.hist_cap))].cpu().numpy()
+
+
 class FusedStep:
     """One ``qc_fused_pinn_residual_step`` descriptor over fixed-size resident batches.  The caller
     fills ``X_res`` / ``X_val`` (IC points first, then BC points) and calls ``run``.

@@ -33,6 +33,7 @@ EXPORTS = (
     "qc_dataset_scores", "qc_adapt_bytes", "qc_adapt_build", "qc_sample_dataset_adaptive", "qc_fused_pinn_adaptive_step",
     "qc_post_system", "qc_sample_dataset_system", "qc_fused_pinn_system_step",
     "qc_post_learn", "qc_fused_pinn_inverse_step",
+    "qc_lbfgs_workspace_bytes", "qc_lbfgs_init", "qc_lbfgs_restart", "qc_lbfgs_step",
 )
 
 
@@ -44,6 +45,9 @@ QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
 QC_KMAX, QC_EQMAX, QC_TERMS_MAX = 4, 4, 32            # outputs, equations and terms of a system (qc_step_system)
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
 QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
+QC_LBFGS_MAX_HISTORY = 32                            # most curvature pairs of an L-BFGS workspace (qc_lbfgs_init)
+QC_LBFGS_FIXED, QC_LBFGS_ARMIJO = 0, 1               # qc_lbfgs_hyper.line_search
+QC_LBFGS_REC_WORDS = 32                              # 4-byte words of the record at the head of an L-BFGS workspace
 
 
 class QcError(RuntimeError):
@@ -63,6 +67,13 @@ class QcOptHyper(C.Structure):
                 ("sched_factor", C.c_float), ("sched_threshold", C.c_float), ("sched_min_lr", C.c_float),
                 ("sched_eps", C.c_float), ("sched_patience", C.c_int), ("w_res", C.c_float),
                 ("w_bc", C.c_float), ("w_ic", C.c_float)]
+
+
+class QcLbfgsHyper(C.Structure):
+    """qc_lbfgs_hyper: history size, line search and its constants, and the loss weights of f."""
+    _fields_ = [("history", C.c_int), ("line_search", C.c_int), ("max_ls", C.c_int),
+                ("lr", C.c_float), ("c1", C.c_float), ("shrink_lo", C.c_float), ("shrink_hi", C.c_float),
+                ("curv_eps", C.c_float), ("w_res", C.c_float), ("w_bc", C.c_float), ("w_ic", C.c_float)]
 
 
 class QcStepDesc(C.Structure):
@@ -227,6 +238,11 @@ def load() -> C.CDLL:
     lib.qc_post_learn.argtypes = [fp, i32, i32, i32, C.POINTER(QcPde), C.POINTER(QcStepLearn), fp, fp, fp, fp, fp, i64, i64,
                                   i64, vp]
     lib.qc_fused_pinn_inverse_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepLearn), i32, vp]
+    lib.qc_lbfgs_workspace_bytes.restype = C.c_size_t
+    lib.qc_lbfgs_workspace_bytes.argtypes = [i32, i32]
+    lib.qc_lbfgs_init.argtypes = [vp, i32, i32, vp]
+    lib.qc_lbfgs_restart.argtypes = [vp, i32, vp]
+    lib.qc_lbfgs_step.argtypes = [fp, i32, fp, vp, C.POINTER(QcLbfgsHyper), fp, i32, vp, i32, vp, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]
@@ -234,7 +250,7 @@ def load() -> C.CDLL:
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qc_error_string", "qc_trig_bytes", "qc_circuit_workspace_bytes", "qc_circuit_workspace_bytes_batch",
-                        "qc_step_workspace_bytes", "qc_adapt_bytes"):
+                        "qc_step_workspace_bytes", "qc_adapt_bytes", "qc_lbfgs_workspace_bytes"):
             fn.restype = i32
     _lib = lib
     return lib

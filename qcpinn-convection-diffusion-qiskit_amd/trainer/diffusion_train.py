@@ -394,7 +394,9 @@ def _check_adaptive(adaptive, dataset, batch_size, sampler="device"):
         raise ValueError("adaptive= draws on the device: it cannot be combined with sampler='torch'")
 
 
-def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None):
+def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None, lbfgs=None):
+    if lbfgs is not None and adaptive is not None:
+        raise ValueError("lbfgs= needs a fixed objective: it cannot be combined with adaptive= sampling")
     steps = model.epochs + 1
     tr = FusedTrainer(model, batch_size, capacity=steps, dataset=dataset, adaptive=adaptive)
     t0 = time.time()
@@ -422,6 +424,16 @@ def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None):
                 model.save_state()
     hist = tr.opt.loss_history(steps)
     model.loss_history.extend(hist[done:])
+    if lbfgs is not None:
+        # the second phase: L-BFGS evaluations on the batches of the last Adam step (explicit batches) or on a fresh draw;
+        # the model is left at the last accepted point and the accepted losses continue the history
+        from .lbfgs_train import run_phase
+        lb = tr.lbfgs = run_phase(tr, lbfgs)
+        model.loss_history.extend(lb.accepted_losses())
+        rec = lb.state()
+        model.logger.print("L-BFGS: %d evaluations, %d accepted, %d rejected trials, %d resets%s | Loss: %.2e"
+                           % (rec["n_eval"], rec["n_iter"], rec["n_rejected"], rec["n_resets"],
+                              ", stalled" if rec["stalled"] else "", rec["f0"]))
     tr.sync_to_torch()
     total = time.time() - t0
     model.total_training_time += total
@@ -545,15 +557,21 @@ def _train_generic(model, batch_size, dataset=None, adaptive=None):
 
 
 def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None,
-          adaptive=None):
+          adaptive=None, lbfgs=None):
     """``batches`` (keyword-only, not in the reference): a per-iteration list of
     ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests; with a dataset each entry carries a
     fourth element, the targets ``(u_ic, u_bc, r_res)``.  ``dataset`` (keyword-only): a ``TabulatedProblem`` whose targets
     and operator replace the analytic problem (module docstring).  ``adaptive`` (keyword-only): an ``AdaptiveSampling``
-    for the residual rows of ``dataset`` (module docstring)."""
+    for the residual rows of ``dataset`` (module docstring).  ``lbfgs`` (keyword-only): a ``trainer.lbfgs_train.LbfgsPhase``,
+    that many L-BFGS evaluations on the device behind the Adam epochs (``DVPDESolver`` models only); its accepted losses
+    continue ``model.loss_history`` and the model ends at the last accepted point."""
+    if lbfgs is not None and not (hasattr(lbfgs, "evals") and hasattr(lbfgs, "options")):
+        raise ValueError("lbfgs= must be a trainer.lbfgs_train.LbfgsPhase")
     if hasattr(model, "_engine_for") and hasattr(model, "quantum_layer"):
-        _train_fused(model, batch_size, batches, dataset, adaptive)
+        _train_fused(model, batch_size, batches, dataset, adaptive, lbfgs)
     else:
+        if lbfgs is not None:
+            raise ValueError("lbfgs= runs on the device: it is only supported for DVPDESolver models")
         if batches is not None:
             raise ValueError("explicit batches are only supported for DVPDESolver models")
         _train_generic(model, batch_size, dataset, adaptive)
