@@ -613,6 +613,55 @@ int qc_post_learn(const float* params_dev /*NP_L*/, int H, int n, int n_theta, c
 int qc_fused_pinn_inverse_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_learn* learn,
                                int phases, void* stream);
 
+/* ---- learned loss weights (uncertainty balancing): the tabulated step with one trainable log-variance per loss term,
+ * in the order of the loss columns and of qc_opt_hyper's weights: residual, BC, IC.  The step minimises
+ *   F = sum_k ( w_k e_k L_k + s_k ),   s_k = scale[k] * p[k],   e_k = expf(-s_k) (fp32, the precise exponential),
+ *   w_k = hyper.w_res, w_bc, w_ic,
+ * over the network and over p[3], which lives on the device in the three flat entries behind theta,
+ *   W1 b1 W2 b2 | W3 b3 W4 b4 | theta | p[3],      NP_B = NP + 3.
+ * Network entries: the gradient is sum_k w_k e_k grad L_k: every point's cotangent is scaled by the e of its class (e_res
+ * on residual points, e_ic on value points below pde.n_seg_a, e_bc on the others).  Entry NP + k: scale[k] * (1 - w_k e_k
+ * L_k), formed in the optimiser launch from the reduced loss columns (after the all-reduce under a communicator); every
+ * tile row holds 0 in these three columns, so after a GRADS-only call the three entries of flat_dev are exactly 0, and
+ * UPDATE leaves their values visible there next to the clipped network gradient.  The clip's norm and factor cover the first NP
+ * entries only (last_norm is that norm); the three entries are not scaled.  The step's Adam moves all NP_B entries.
+ * scale[k] = 0 freezes term k (gradient exactly 0; p[k], m, v bit-unchanged from a zero start); scale[k] is also the
+ * learning-rate multiplier of s_k.  The plateau scheduler, hist_dev and last_loss see F, which may be negative; loss_parts
+ * stay the raw L_r, L_bc, L_ic.  weight_hist_dev (optional, [weight_hist_cap][3]): row s - 1 - hist_base receives the
+ * effective weights w_k e_k used in 1-based step s; the store rides in the optimiser launch, which reads p before moving it. */
+#define QC_BAL_TERMS 3
+typedef struct qc_step_balance {
+  float scale[QC_BAL_TERMS];                   /* finite */
+  float* weight_hist_dev; int weight_hist_cap; /* [cap][3] or NULL/0 */
+} qc_step_balance;
+
+/* qc_post_data under those weights: params_dev holds NP_B entries, p in its last three; nch = 6 scales the cotangents by
+ * pde->w_res * e_res, nch = 1 by pde->w_val_a * e_ic (points below pde->n_seg_a) or pde->w_val_b * e_bc.  The tile rows
+ * receive what qc_post_data writes, the loss columns (unweighted) at NP_B .. NP_B + 2 (part_stride >= NP_B + 3) and 0 in
+ * columns NP_B - 3 .. NP_B - 1.  bal->weight_hist_dev is not written.  QC_ERR_ARG: bal NULL or not valid (below), and
+ * whatever qc_post_data refuses. */
+int qc_post_balance(const float* params_dev /*NP_B*/, int H, int n, int n_theta, const qc_pde* pde,
+                    const qc_step_balance* bal, const float* qjets_dev, const float* target_dev, float c_u, float* out_u,
+                    float* out_res, float* qbar_dev, float* part_dev, int64_t part_stride, int64_t row0, int64_t B, int nch,
+                    void* stream);
+
+/* qc_adam_step for flat_dev = [grad[NP_B] | L_r, L_bc, L_ic] under those weights: the three entries in front of the loss
+ * columns are formed here (whatever flat_dev holds there) and written back, F goes to the scheduler, hist_dev and
+ * last_loss, and the weight row is stored.  One launch (NP_B + 3 <= 3072: the single-round-trip kernel), nothing is read
+ * back.  QC_ERR_ARG: bal NULL; a non-finite scale; weight_hist_cap < 0, or a NULL buffer with a positive cap; NP_B < 4;
+ * theta_off + prog->n_params > NP_B - 3; whatever qc_adam_step refuses. */
+int qc_balance_adam_step(float* flat_dev, int NP_B, float* params_dev, float* m_dev, float* v_dev, void* opt_state_dev,
+                         const qc_opt_hyper* hp, const qc_step_balance* bal, float* hist_dev, int hist_cap,
+                         const qc_program* prog, int theta_off, void* trig_dev, void* stream);
+
+/* qc_fused_pinn_data_step under those weights: params_dev, m_dev and v_dev hold NP_B entries, flat_dev = [grad[NP_B] | L_r,
+ * L_bc, L_ic], part_stride >= NP_B + 3.  Everything else (both forms, phases, sampler, circuit families, encodings,
+ * workspace, comm) is the data step's, and a GRADS | UPDATE call has its launch count.  QC_ERR_ARG before any launch: bal
+ * NULL; a non-finite scale; weight_hist_cap < 0, or a NULL buffer with a positive cap; part_stride < NP_B + 3; whatever
+ * qc_fused_pinn_data_step refuses. */
+int qc_fused_pinn_balanced_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_balance* bal,
+                                int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

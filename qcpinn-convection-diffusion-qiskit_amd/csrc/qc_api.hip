@@ -554,6 +554,31 @@ int qc_post_learn(const float* prm, int H, int n, int n_theta, const qc_pde* pde
                    6, stream, QcTarget::learned(target, target, to_learn(learn, nullptr)));
 }
 
+// THE validity rule of a balancer: finite scales, a history buffer behind a positive capacity
+static bool bal_ok(const qc_step_balance* b) {
+  if (!b || b->weight_hist_cap < 0 || (b->weight_hist_cap > 0 && !b->weight_hist_dev)) return false;
+  for (int k = 0; k < QC_BAL_TERMS; ++k)
+    if (!isfinite(b->scale[k])) return false;
+  return true;
+}
+// the kernels' record (the post stage reads the scales only; the history is the optimiser launch's)
+static QcBal to_bal(const qc_step_balance* b) {
+  QcBal q;
+  memcpy(q.scale, b->scale, sizeof(q.scale));
+  const bool hist = b->weight_hist_dev && b->weight_hist_cap > 0;
+  q.hist = hist ? b->weight_hist_dev : nullptr;
+  q.hist_cap = hist ? b->weight_hist_cap : 0;
+  return q;
+}
+
+int qc_post_balance(const float* prm, int H, int n, int n_theta, const qc_pde* pde, const qc_step_balance* bal,
+                    const float* qjets, const float* target, float c_u, float* out_u, float* out_res, float* qbar, float* part,
+                    int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream) {
+  if (!target || !bal_ok(bal)) return QC_ERR_ARG;
+  return post_impl(2, nullptr, prm, H, n, n_theta, pde, qjets, out_u, out_res, nullptr, nullptr, qbar, part, part_stride,
+                   row0, B, nch, stream, QcTarget::balanced(target, target, c_u, to_bal(bal)));
+}
+
 int qc_post_multi(int mode, const float* prm, int H, int n, int n_theta, int K, const float* w4k, const float* qjets,
                   float* out_u, const float* in_ubar, float* qbar, float* part, int64_t part_stride, float* partk,
                   int64_t partk_stride, int64_t row0, int64_t B, void* stream) {
@@ -575,15 +600,32 @@ int qc_reduce_rows(const float* part, int64_t rows, int64_t stride, int ncols, f
   return after_launch();
 }
 
-int qc_adam_step(float* flat, int NP, float* prm, float* m, float* v, void* state, const qc_opt_hyper* hp,
-                 float* hist, int hist_cap, const qc_program* prog, int theta_off, void* trig, void* stream) {
-  if (!flat || NP <= 0 || !prm || !m || !v || !state || !hp) return QC_ERR_ARG;
-  if (prog && (!trig || theta_off < 0 || theta_off + prog->n_params > NP)) return QC_ERR_ARG;
+// qc_adam_step, and with `bal` (validated by the caller) qc_balance_adam_step: the last QC_BAL_TERMS of the NP entries are
+// the balancer's, at least one entry is the network's, and theta lies in front of them
+static int adam_step_impl(float* flat, int NP, float* prm, float* m, float* v, void* state, const qc_opt_hyper* hp,
+                          float* hist, int hist_cap, const qc_program* prog, int theta_off, void* trig, void* stream,
+                          const QcBal* bal) {
+  const int n_own = bal ? QC_BAL_TERMS : 0;
+  if (!flat || NP <= n_own || !prm || !m || !v || !state || !hp) return QC_ERR_ARG;
+  if (prog && (!trig || theta_off < 0 || theta_off + prog->n_params > NP - n_own)) return QC_ERR_ARG;
   QcOptHyper h;
   memcpy(&h, hp, sizeof(h));
   qc_opt_adam(flat, NP, prm, m, v, (QcOptState*)state, h, hist, hist_cap, prog, theta_off, (QcTrig*)trig,
-              (hipStream_t)stream);
+              (hipStream_t)stream, bal);
   return after_launch();
+}
+
+int qc_adam_step(float* flat, int NP, float* prm, float* m, float* v, void* state, const qc_opt_hyper* hp,
+                 float* hist, int hist_cap, const qc_program* prog, int theta_off, void* trig, void* stream) {
+  return adam_step_impl(flat, NP, prm, m, v, state, hp, hist, hist_cap, prog, theta_off, trig, stream, nullptr);
+}
+
+int qc_balance_adam_step(float* flat, int NP_B, float* prm, float* m, float* v, void* state, const qc_opt_hyper* hp,
+                         const qc_step_balance* bal, float* hist, int hist_cap, const qc_program* prog, int theta_off,
+                         void* trig, void* stream) {
+  if (!bal_ok(bal)) return QC_ERR_ARG;
+  const QcBal q = to_bal(bal);
+  return adam_step_impl(flat, NP_B, prm, m, v, state, hp, hist, hist_cap, prog, theta_off, trig, stream, &q);
 }
 
 // ---- L-BFGS (qc_lbfgs.hip)
@@ -945,6 +987,8 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
       if (e != hipSuccess) return hip_fail(e);
     }
   }
+  // the balanced step: the optimiser launch forms the balancer's three gradient entries from the reduced loss columns
+  const QcBal* bal = !sys && tg.kind == QC_TARGET_BAL ? &tg.bal : nullptr;
   if (phases & QC_PHASE_GRADS) {
     // the step owns its partial-row matrix, so the reduction folds it in place (two levels, fixed order);
     // with the update phase in the same call the second level rides in the optimiser launch
@@ -954,7 +998,8 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
       QcOptHyper h;
       memcpy(&h, &d->hyper, sizeof(h));
       qc_opt_adam_fold(d->part_dev, d->part_stride, RS, d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev,
-                       (QcOptState*)d->opt_state_dev, h, d->hist_dev, d->hist_cap, d->prog, L.oTh, (QcTrig*)d->trig_dev, st);
+                       (QcOptState*)d->opt_state_dev, h, d->hist_dev, d->hist_cap, d->prog, L.oTh, (QcTrig*)d->trig_dev, st,
+                       bal);
       return after_launch();
     }
     if ((rc = qc_reduce_rows(d->part_dev, RS, d->part_stride, L.NP + 3, d->flat_dev, st))) return rc;
@@ -963,20 +1008,22 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   }
   if (phases & QC_PHASE_UPDATE) {
     if (!d->m_dev || !d->v_dev || !d->opt_state_dev) return QC_ERR_ARG;
-    if ((rc = qc_adam_step(d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev, d->opt_state_dev, &d->hyper,
-                           d->hist_dev, d->hist_cap, d->prog, L.oTh, d->trig_dev, st))) return rc;
+    if ((rc = adam_step_impl(d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev, d->opt_state_dev, &d->hyper,
+                             d->hist_dev, d->hist_cap, d->prog, L.oTh, d->trig_dev, st, bal))) return rc;
   }
   return QC_OK;
 }
 
-// the five entry points: targets, batches and source from the records each was given (the kind of step is decided here)
+// the six entry points: targets, batches and source from the records each was given (the kind of step is decided here)
 // `lr` (the inverse step, validated by its entry, never with `cf`): the trainable operator, with or without residual points
+// `bl` (the balanced step, validated by its entry, alone): the tabulated step under balanced loss weights
 static int step_from(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_adapt* ad, int phases,
-                     void* stream, const qc_step_learn* lr = nullptr) {
+                     void* stream, const qc_step_learn* lr = nullptr, const qc_step_balance* bl = nullptr) {
   if (!d) return QC_ERR_ARG;
   const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
   const QcTarget tg = !t      ? QcTarget{}
                       : lr    ? QcTarget::learned(t->target_res_dev, t->target_val_dev, to_learn(lr, d->opt_state_dev))
+                      : bl    ? QcTarget::balanced(t->target_res_dev, t->target_val_dev, t->c_u, to_bal(bl))
                       : table ? QcTarget::with_coef(t->target_res_dev, t->target_val_dev, cf->coef_res_dev)
                               : QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u);
   return fused_step(d, tg, step_batches(d, t), make_source(t, cf, cf ? cf->coef_res_dev : nullptr, ad, d->sample_bc_face_points),
@@ -1002,6 +1049,12 @@ int qc_fused_pinn_inverse_step(const qc_step_desc* d, const qc_step_data* data, 
                                void* stream) {
   if (!data || !learn_ok(learn)) return QC_ERR_ARG;
   return step_from(d, data, nullptr, nullptr, phases, stream, learn);
+}
+
+int qc_fused_pinn_balanced_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_balance* bal, int phases,
+                                void* stream) {
+  if (!data || !bal_ok(bal)) return QC_ERR_ARG;
+  return step_from(d, data, nullptr, nullptr, phases, stream, nullptr, bal);
 }
 
 int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef,

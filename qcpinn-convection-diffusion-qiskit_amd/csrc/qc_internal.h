@@ -8,7 +8,7 @@ struct QcLayout {  // column offsets of the flat parameter / gradient vector
 };
 
 // K: rows of the last layer (outputs of the post network), W4[K][H] b4[K]; K = 1 is the single-output layout
-// n_op: trainable operator entries behind theta (the inverse step: QC_COEF_N), counted in NP; no offset moves
+// n_op: trainable entries behind theta (the inverse step: QC_COEF_N; the balanced step: QC_BAL_N), counted in NP; no offset moves
 inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1, int n_op = 0) {
   QcLayout L;
   L.H = H;
@@ -53,30 +53,49 @@ struct QcLearn {
   const QcOptState* st;
 };
 
+// Uncertainty balancing of the three loss terms (the balanced step): F = sum_k (w_k e_k L_k + s_k), s_k = scale[k] p[k],
+// e_k = exp(-s_k), with p the QC_BAL_N flat entries behind theta (params[NP_B - 3 ..]) in the order of the loss columns:
+// residual, BC, IC.  scale[k] = 0 freezes term k (e_k = 1, gradient entry exactly 0).  hist (the optimiser launch only):
+// row step - 1 - hist_base of [hist_cap][3] receives the effective weights w_k e_k the step used; null: no history.
+constexpr int QC_BAL_N = 3;   // == QC_BAL_TERMS of the public header
+struct QcBal {
+  float scale[QC_BAL_N];
+  float* hist;
+  int hist_cap;
+};
+// THE factor e_k, for the post stage (cotangent scales) and the optimiser launch (gradient entries, F, weight history)
+// alike: the precise exponential, so both see the same bits
+__device__ __forceinline__ float qc_bal_factor(const float scale, const float p) { return expf(-(scale * p)); }
+
 // Where a post stage takes its targets and its operator from: analytic (functions of X, the operator of QcPde),
 // tabulated (tab), tabulated with a coefficient table [QC_COEF_N][B_res] for the residual points (tab.c_u is then not
 // read), or tabulated with the trainable global operator `learn` (tab.c_u and the operator of QcPde are not read; the
-// layout then counts QC_COEF_N more entries, n_op()).  The post launchers and everything above them pass this one value;
-// the kernels receive nothing, tab, tab and coef, or tab and learn as their last arguments.
-enum QcTargetKind { QC_TARGET_ANALYTIC = 0, QC_TARGET_TAB, QC_TARGET_COEF, QC_TARGET_LEARN };
+// layout then counts QC_COEF_N more entries, n_op()), or tabulated with balanced loss weights `bal` (the tabulated kind's
+// arithmetic on cotangent scales taken from params; QC_BAL_N more entries).  The post launchers and everything above them
+// pass this one value; the kernels receive nothing, tab, tab and coef, tab and learn, or tab and bal as their last arguments.
+enum QcTargetKind { QC_TARGET_ANALYTIC = 0, QC_TARGET_TAB, QC_TARGET_COEF, QC_TARGET_LEARN, QC_TARGET_BAL };
 struct QcTarget {
   QcTargetKind kind = QC_TARGET_ANALYTIC;
   QcTab tab = {nullptr, nullptr, 0.f};
   const float* coef = nullptr;
   QcLearn learn = {};
+  QcBal bal = {};
 
   static QcTarget tabulated(const float* tg_res, const float* tg_val, float c_u) {
-    return {QC_TARGET_TAB, {tg_res, tg_val, c_u}, nullptr, {}};
+    return {QC_TARGET_TAB, {tg_res, tg_val, c_u}, nullptr, {}, {}};
   }
   static QcTarget with_coef(const float* tg_res, const float* tg_val, const float* coef) {
-    return {QC_TARGET_COEF, {tg_res, tg_val, 0.f}, coef, {}};
+    return {QC_TARGET_COEF, {tg_res, tg_val, 0.f}, coef, {}, {}};
   }
   static QcTarget learned(const float* tg_res, const float* tg_val, const QcLearn& lr) {
-    return {QC_TARGET_LEARN, {tg_res, tg_val, 0.f}, nullptr, lr};
+    return {QC_TARGET_LEARN, {tg_res, tg_val, 0.f}, nullptr, lr, {}};
   }
-  int n_op() const { return kind == QC_TARGET_LEARN ? QC_COEF_N : 0; }
-  // the value points of a step have no operator: the same targets without the table (a learned operator stays: the value
-  // tiles zero its gradient columns in their rows)
+  static QcTarget balanced(const float* tg_res, const float* tg_val, float c_u, const QcBal& bl) {
+    return {QC_TARGET_BAL, {tg_res, tg_val, c_u}, nullptr, {}, bl};
+  }
+  int n_op() const { return kind == QC_TARGET_LEARN ? QC_COEF_N : (kind == QC_TARGET_BAL ? QC_BAL_N : 0); }
+  // the value points of a step have no operator: the same targets without the table (a learned operator and balanced
+  // weights stay: the value tiles zero those columns in their rows)
   QcTarget value_side() const { return kind == QC_TARGET_COEF ? tabulated(tab.tg_res, tab.tg_val, tab.c_u) : *this; }
   // THE validity rule: a coefficient table needs tabulated targets (it has them by construction), mode 2 and six
   // channels; tabulated targets need mode 2 and problem id 3
@@ -298,11 +317,14 @@ int qc_mlp_post_multi(int mode, const float* prm, QcLayout L, int K, const float
                       int64_t row0, int64_t B, hipStream_t);
 int qc_opt_reduce_rows(const float* part, int64_t rows, int64_t stride, int ncols, float* out, hipStream_t);
 int qc_opt_fold_rows(float* part, int64_t rows, int64_t stride, int ncols, hipStream_t);
+// `bal` (both optimiser launchers; the balanced step): NP counts its QC_BAL_N entries, whose gradients are formed in the
+// launch from the loss columns; null: the plain update
 int qc_opt_adam_fold(const float* part, int64_t stride, int RS, float* flat, int NP, float* prm, float* m, float* v,
                      QcOptState* state, QcOptHyper hp, float* hist, int hist_cap, const qc_program* pg, int theta_off,
-                     QcTrig* trig, hipStream_t);
+                     QcTrig* trig, hipStream_t, const QcBal* bal = nullptr);
 int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState* state, QcOptHyper hp,
-                float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t);
+                float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t,
+                const QcBal* bal = nullptr);
 int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hipStream_t);
 // qc_lbfgs.hip: floats of a workspace; zero it and write its record; make the next call a first evaluation; one call
 size_t qc_lbfgs_words(int NP, int m);

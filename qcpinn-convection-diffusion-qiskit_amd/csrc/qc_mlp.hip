@@ -587,6 +587,31 @@ __device__ __forceinline__ void learn_zero_columns(float* __restrict__ row, cons
   for (int k = 0; k < QC_COEF_N; ++k) row[L.NP - QC_COEF_N + k] = 0.f;
 }
 
+// BAL (the balanced step, with DATA): the cotangent scale of a tile's class is pde.w_* e_k, e_k = qc_bal_factor(scale_k, p_k)
+// with p = prm[NP_B - 3 ..] (order residual, BC, IC; L.NP counts them; segment a = IC, b = BC).  p and scale are
+// wave-uniform, read like the learned operator's p[7]; the product is formed once per wave, where the error is first needed,
+// and handed back to a scalar register, so the per-point code is the tabulated kind's with a different scalar.  A residual
+// tile needs one factor, a value tile two.
+template <int NCH>
+__device__ __forceinline__ void bal_weights(QcPde& pde, const float* __restrict__ prm, const QcLayout& L, const QcBal* bl) {
+  const float* __restrict__ pk = prm + (L.NP - QC_BAL_N);
+  auto uniform = [](const float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+  };
+  if constexpr (NCH == 6) {
+    pde.w_res = uniform(pde.w_res * qc_bal_factor(bl->scale[0], pk[0]));
+  } else {
+    pde.w_val_b = uniform(pde.w_val_b * qc_bal_factor(bl->scale[1], pk[1]));
+    pde.w_val_a = uniform(pde.w_val_a * qc_bal_factor(bl->scale[2], pk[2]));
+  }
+}
+// every tile's row: the three columns are zero (their gradient is a function of the reduced loss columns and is formed in
+// the optimiser launch; the partial rows are scratch, and the fold sums every row)
+__device__ __forceinline__ void bal_zero_columns(float* __restrict__ row, const QcLayout& L) {
+#pragma unroll
+  for (int k = 0; k < QC_BAL_N; ++k) row[L.NP - QC_BAL_N + k] = 0.f;
+}
+
 // DATA (MODE 2 only, QC_PB_TABULATED): the point's target is tg[p] instead of the analytic function of X, and the residual
 // carries the zeroth-order term c_u u, whose cotangent on u is c_u gsc.  DATA = false is the code as it was.
 // COEF (with DATA, residual points only): the operator is the point's own row coef[k][p], k = c_u, c_t, c_x, c_y, d_xx,
@@ -596,7 +621,8 @@ __device__ __forceinline__ void learn_zero_columns(float* __restrict__ row, cons
 // (the weight-gradient kernel runs in its gen mode on them); out_res is not written.
 // LEARN (with DATA): residual points run the COEF arithmetic on the uniform c_k of `lr` and wave 0 adds their gradient
 // columns; value points only zero those columns.  OPC below: either of the two.
-template <int N, int NCH, int MODE, bool DATA = false, bool COEF = false, bool LEARN = false>
+// BAL (with DATA): see bal_weights; every tile zeroes the three columns of its row.
+template <int N, int NCH, int MODE, bool DATA = false, bool COEF = false, bool LEARN = false, bool BAL = false>
 __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
                                               QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ out_res,
@@ -604,10 +630,12 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
                                               float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B,
                                               const float* __restrict__ tg = nullptr, const float c_u = 0.f,
-                                              const float* __restrict__ coef = nullptr, const QcLearn* lr = nullptr) {
+                                              const float* __restrict__ coef = nullptr, const QcLearn* lr = nullptr,
+                                              const QcBal* bl = nullptr) {
   static_assert(!DATA || MODE == 2, "tabulated targets: the fused mode only");
   static_assert(!COEF || (DATA && NCH == 6), "per-point operators: tabulated residual points only");
   static_assert(!LEARN || (DATA && !COEF), "learned operators: tabulated targets, no table");
+  static_assert(!BAL || (DATA && !COEF && !LEARN), "balanced weights: the tabulated kind's operator");
   constexpr bool OPC = COEF || (LEARN && NCH == 6);
   // block = 4 waves on one 64-point tile; wave w owns a quarter of the hidden units
   __shared__ float s_buf[QC_MS][NCH * N][64];   // partial u jets first (NCH rows), partial qbar later
@@ -740,6 +768,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
         t = X[pc * 3 + 0]; x = X[pc * 3 + 1]; y = X[pc * 3 + 2];
       }
       float* row = part + (row0 + tile) * part_stride;
+      if constexpr (BAL) bal_weights<NCH>(pde, prm, L, bl);
       if constexpr (NCH == 6) {
         const float target = DATA ? tgp : residual_target(pde, t, x, y);
         const float e = live ? res - target : 0.f;
@@ -752,6 +781,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
             row[L.NP + 0] = ls;
             row[L.NP + 1] = 0.f;
             row[L.NP + 2] = 0.f;
+            if constexpr (BAL) bal_zero_columns(row, L);
           }
           if constexpr (LEARN) learn_columns(row, L, lr, 0, lscale, cf, gsc, u, lane, tile == 0);
         }
@@ -768,6 +798,7 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
             row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
             row[L.NP + 2] = la;
             if constexpr (LEARN) learn_zero_columns(row, L);
+            if constexpr (BAL) bal_zero_columns(row, L);
           }
         }
       }
@@ -855,12 +886,14 @@ __device__ __forceinline__ void k_post_body(const int64_t bid, const float* __re
 // names the DATA / COEF flags of the bodies and picks what the bodies take out of the pack, where they take it: null /
 // zero for what the kind does not have or does not read (c_u beside a coefficient table).
 // (QcTab, QcLearn): the inverse step, the trainable global operator by value; its residual bodies take no table.
+// (QcTab, QcBal): the balanced step, the tabulated kind (c_u is read) with the balancer's record by value.
 template <class... TG>
 struct QcKind {
-  static_assert(sizeof...(TG) <= 2, "(), (QcTab), (QcTab, const float*) or (QcTab, QcLearn)");
+  static_assert(sizeof...(TG) <= 2, "(), (QcTab), (QcTab, const float*), (QcTab, QcLearn) or (QcTab, QcBal)");
   static constexpr bool data = sizeof...(TG) >= 1;
   static constexpr bool learn = (std::is_same_v<TG, QcLearn> || ...);
-  static constexpr bool coef = sizeof...(TG) == 2 && !learn;
+  static constexpr bool bal = (std::is_same_v<TG, QcBal> || ...);
+  static constexpr bool coef = sizeof...(TG) == 2 && !learn && !bal;
   static __device__ __forceinline__ const float* tg_res(const TG&... t) {
     if constexpr (data) return std::get<0>(std::tie(t...)).tg_res; else return nullptr;
   }
@@ -872,6 +905,9 @@ struct QcKind {
   }
   static __device__ __forceinline__ const QcLearn* op(const TG&... t) {
     if constexpr (learn) return &std::get<1>(std::tie(t...)); else return nullptr;
+  }
+  static __device__ __forceinline__ const QcBal* weights(const TG&... t) {
+    if constexpr (bal) return &std::get<1>(std::tie(t...)); else return nullptr;
   }
   static __device__ __forceinline__ const float* table(const TG&... t) {
     if constexpr (coef) return std::get<1>(std::tie(t...)); else return nullptr;
@@ -888,9 +924,10 @@ __global__ void __launch_bounds__(256) k_post(const float* __restrict__ X, const
                                               float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B, TG... tg) {
   using K = QcKind<TG...>;
-  k_post_body<N, NCH, MODE, K::data, K::coef, K::learn>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar, qbar,
-                                                        part, part_stride, row0, B, NCH == 6 ? K::tg_res(tg...) : K::tg_val(tg...),
-                                                        K::c_u(tg...), K::table(tg...), K::op(tg...));
+  k_post_body<N, NCH, MODE, K::data, K::coef, K::learn, K::bal>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, in_ubar, in_rbar,
+                                                                qbar, part, part_stride, row0, B,
+                                                                NCH == 6 ? K::tg_res(tg...) : K::tg_val(tg...), K::c_u(tg...),
+                                                                K::table(tg...), K::op(tg...), K::weights(tg...));
 }
 
 // Weight gradients of the post network: lane = hidden unit m (owns row m of W3, b3[m], W4[m]); the
@@ -1061,12 +1098,12 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
 }
 
 // fused (mode 2) post stage of a value tile: u, squared error against the analytic target, cotangent of <Z>
-template <int N, bool DATA = false, bool LEARN = false>
+template <int N, bool DATA = false, bool LEARN = false, bool BAL = false>
 __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                               QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                               float* __restrict__ out_u, float* __restrict__ qbar, float* __restrict__ part,
                                               int64_t part_stride, int64_t row0, int64_t B,
-                                              const float* __restrict__ tg = nullptr) {
+                                              const float* __restrict__ tg = nullptr, const QcBal* bl = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t tile = bid * 4 + wave;
@@ -1109,6 +1146,7 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
     const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
     target = value_target(pde, seg_a, t, x, y);
   }
+  if constexpr (BAL) bal_weights<1>(pde, prm, L, bl);
   const float e = live ? u - target : 0.f;
   const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
   const float la = qc_wave_sum_to_lane63(seg_a ? e * e * pde.inv_n_a : 0.f);
@@ -1119,6 +1157,7 @@ __device__ __forceinline__ void k_post_value4(const int64_t bid, const float* __
     row[L.NP + 1] = lb;  // column order: residual, BC, IC; segment a = IC, b = BC
     row[L.NP + 2] = la;
     if constexpr (LEARN) learn_zero_columns(row, L);
+    if constexpr (BAL) bal_zero_columns(row, L);
   }
   if (live) {
     out_u[p] = ub0;
@@ -1184,13 +1223,14 @@ constexpr int qc_post_ub_a(int n) { return n == 3 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 
 constexpr bool qc_post_pf(int n) { return n <= 8; }   // prefetch of the next block
 constexpr int qc_post_ub_vb(int n) { return n <= 8 ? 2 : 1; }                 // phase B of a value tile: two reductions side by side
 
-template <int N, int TPB, bool DATA = false, bool LEARN = false>
+template <int N, int TPB, bool DATA = false, bool LEARN = false, bool BAL = false>
 __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const float* __restrict__ X,
                                                         const float* __restrict__ prm, QcLayout L, QcPde pde,
                                                         const float* __restrict__ qjets, float* __restrict__ out_u,
                                                         float* __restrict__ qbar, float* __restrict__ part,
                                                         int64_t part_stride, int64_t row0, int64_t B,
-                                                        float* __restrict__ s_v, const float* __restrict__ tg = nullptr) {
+                                                        float* __restrict__ s_v, const float* __restrict__ tg = nullptr,
+                                                        const QcBal* bl = nullptr) {
   constexpr int WPT = QC_MS / TPB, QPW = QC_MS / WPT;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1254,6 +1294,7 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
     const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
     target = value_target(pde, seg_a, t, x, y);
   }
+  if constexpr (BAL) bal_weights<1>(pde, prm, L, bl);
   const float e = live ? u - target : 0.f;
   const float ub0 = (seg_a ? pde.w_val_a : pde.w_val_b) * e;
   if (wt == 0 && tile_ok) {
@@ -1267,6 +1308,7 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
       row[L.NP + 2] = la;
       row[L.ob4] = sb4;
       if constexpr (LEARN) learn_zero_columns(row, L);
+      if constexpr (BAL) bal_zero_columns(row, L);
     }
     if (live) out_u[p] = ub0;   // the per-point cotangent (MODE 2 contract of qc_post)
   }
@@ -1357,16 +1399,19 @@ template <int N> constexpr bool QC_POST6_PF_B = false;
 // before phase B, so the cubic term only changes the residual and ub0.  out_u receives the six channel cotangents [6][B].
 // LEARN (with DATA): the COEF arithmetic on the uniform c_k of `lr` (learn_coefs), and seven more reductions on wave 0 for
 // their gradient columns (learn_columns).  OPC below: either of the two.
-template <int N, bool DATA = false, bool COEF = false, bool LEARN = false>
+// BAL (with DATA): see bal_weights; the tile zeroes the three columns of its row.
+template <int N, bool DATA = false, bool COEF = false, bool LEARN = false, bool BAL = false>
 __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
                                                     QcLayout L, QcPde pde, const float* __restrict__ qjets,
                                                     float* __restrict__ out_u, float* __restrict__ out_res,
                                                     float* __restrict__ qbar, float* __restrict__ part, int64_t part_stride,
                                                     int64_t row0, int64_t B, float* __restrict__ s_dyn,
                                                     const float* __restrict__ tg = nullptr, const float c_u = 0.f,
-                                                    const float* __restrict__ coef = nullptr, const QcLearn* lr = nullptr) {
+                                                    const float* __restrict__ coef = nullptr, const QcLearn* lr = nullptr,
+                                                    const QcBal* bl = nullptr) {
   static_assert(!COEF || DATA, "per-point operators: tabulated targets only");
   static_assert(!LEARN || (DATA && !COEF), "learned operators: tabulated targets, no table");
+  static_assert(!BAL || (DATA && !COEF && !LEARN), "balanced weights: the tabulated kind's operator");
   constexpr bool OPC = COEF || LEARN;
   constexpr int NCH = 6;
   float* s_z = s_dyn;                                                        // [H][64]
@@ -1464,6 +1509,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
     const float t = X[pc * 3 + 0], x = X[pc * 3 + 1], y = X[pc * 3 + 2];
     target = residual_target(pde, t, x, y);
   }
+  if constexpr (BAL) bal_weights<6>(pde, prm, L, bl);
   const float e = live ? res - target : 0.f;
   const float gsc = pde.w_res * e;
   // analytic problems: the loss sees u only through its derivatives
@@ -1478,6 +1524,7 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
       row[L.NP + 1] = 0.f;
       row[L.NP + 2] = 0.f;
       row[L.ob4] = sb4;
+      if constexpr (BAL) bal_zero_columns(row, L);
     }
     if constexpr (LEARN) learn_columns(row, L, lr, lz, lscale, cf, gsc, u, lane, tile == 0);
     if constexpr (OPC) {
@@ -1596,12 +1643,13 @@ __global__ void __launch_bounds__(256) k_post_fused(const float* __restrict__ X,
   extern __shared__ float s_dyn[];
   using K = QcKind<TG...>;
   if constexpr (NCH == 6)
-    k_post_fused6_body<N, K::data, K::coef, K::learn>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride,
-                                                      row0, B, s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...),
-                                                      K::op(tg...));
+    k_post_fused6_body<N, K::data, K::coef, K::learn, K::bal>(blockIdx.x, X, prm, L, pde, qjets, out_u, out_res, qbar, part,
+                                                              part_stride, row0, B, s_dyn, K::tg_res(tg...), K::c_u(tg...),
+                                                              K::table(tg...), K::op(tg...), K::weights(tg...));
   else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data, K::learn>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part,
-                                                                     part_stride, row0, B, s_dyn, K::tg_val(tg...));
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data, K::learn, K::bal>(blockIdx.x, X, prm, L, pde, qjets, out_u, qbar, part,
+                                                                             part_stride, row0, B, s_dyn, K::tg_val(tg...),
+                                                                             K::weights(tg...));
 }
 
 // ================================================================== K outputs behind one shared network (Navier-Stokes)
@@ -1810,12 +1858,12 @@ __global__ void __launch_bounds__(256) k_post_both(const float* __restrict__ prm
                                                    int n_val, TG... tg) {
   using K = QcKind<TG...>;
   if ((int)blockIdx.x >= n_val)
-    k_post_body<N, 6, 2, K::data, K::coef, K::learn>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, nullptr, nullptr,
-                                                     r.qbar, part, part_stride, r.row0, r.B, K::tg_res(tg...), K::c_u(tg...),
-                                                     K::table(tg...), K::op(tg...));
+    k_post_body<N, 6, 2, K::data, K::coef, K::learn, K::bal>(blockIdx.x - n_val, r.X, prm, L, pde, r.qjets, r.ub, r.rb, nullptr,
+                                                             nullptr, r.qbar, part, part_stride, r.row0, r.B, K::tg_res(tg...),
+                                                             K::c_u(tg...), K::table(tg...), K::op(tg...), K::weights(tg...));
   else
-    k_post_value4<N, K::data, K::learn>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0, v.B,
-                                        K::tg_val(tg...));
+    k_post_value4<N, K::data, K::learn, K::bal>(blockIdx.x, v.X, prm, L, pde, v.qjets, v.ub, v.qbar, part, part_stride, v.row0,
+                                                v.B, K::tg_val(tg...), K::weights(tg...));
 }
 
 // fused post stage: here the residual tiles come first and the (shorter) value blocks fill the slots after them
@@ -1826,12 +1874,13 @@ __global__ void __launch_bounds__(256) k_post_fused_both(const float* __restrict
   extern __shared__ float s_dyn[];
   using K = QcKind<TG...>;
   if ((int)blockIdx.x < n_res)
-    k_post_fused6_body<N, K::data, K::coef, K::learn>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part, part_stride,
-                                                      r.row0, r.B, s_dyn, K::tg_res(tg...), K::c_u(tg...), K::table(tg...),
-                                                      K::op(tg...));
+    k_post_fused6_body<N, K::data, K::coef, K::learn, K::bal>(blockIdx.x, r.X, prm, L, pde, r.qjets, r.ub, r.rb, r.qbar, part,
+                                                              part_stride, r.row0, r.B, s_dyn, K::tg_res(tg...), K::c_u(tg...),
+                                                              K::table(tg...), K::op(tg...), K::weights(tg...));
   else
-    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data, K::learn>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub, v.qbar,
-                                                                     part, part_stride, v.row0, v.B, s_dyn, K::tg_val(tg...));
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB, K::data, K::learn, K::bal>(blockIdx.x - n_res, v.X, prm, L, pde, v.qjets, v.ub,
+                                                                             v.qbar, part, part_stride, v.row0, v.B, s_dyn,
+                                                                             K::tg_val(tg...), K::weights(tg...));
 }
 
 // GEN (the coefficient step and the inverse step): the residual tiles read their six channel cotangents from r.ub (gen mode of the body)
@@ -1941,6 +1990,11 @@ static int post_learn(const float* prm, QcLayout L, QcPde pde, const float* qjet
                       int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg);
 static int post_both_learn(const float* prm, QcLayout L, QcPde pde, const QcPostSeg& r, const QcPostSeg& v, float* part,
                            int64_t part_stride, hipStream_t st, const QcTarget& tg);
+// the balanced kind of both, behind those
+static int post_bal(const float* prm, QcLayout L, QcPde pde, const float* qjets, float* out_u, float* out_res, float* qbar,
+                    float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg);
+static int post_both_bal(const float* prm, QcLayout L, QcPde pde, const QcPostSeg& r, const QcPostSeg& v, float* part,
+                         int64_t part_stride, hipStream_t st, const QcTarget& tg);
 
 int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pde, const float* qjets,
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
@@ -1948,6 +2002,7 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
   if (L.H > 1024) return QC_ERR_UNSUPPORTED;
   if (!tg.ok(mode, nch, pde.problem)) return QC_ERR_ARG;
   if (tg.kind == QC_TARGET_LEARN) return post_learn(prm, L, pde, qjets, out_u, qbar, part, part_stride, row0, B, nch, st, tg);
+  if (tg.kind == QC_TARGET_BAL) return post_bal(prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0, B, nch, st, tg);
   const int tiles = qc_ceil_div(B, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
@@ -2034,6 +2089,9 @@ int qc_mlp_post_both(const float* prm, QcLayout L, QcPde pde, const float* Xr, c
   if (tg.kind == QC_TARGET_LEARN)
     return post_both_learn(prm, L, pde, QcPostSeg{Xr, qjr, ubr, rbr, qbr, row0_r, Br}, QcPostSeg{Xv, qjv, ubv, nullptr, qbv, row0_v, Bv},
                            part, part_stride, st, tg);
+  if (tg.kind == QC_TARGET_BAL)
+    return post_both_bal(prm, L, pde, QcPostSeg{Xr, qjr, ubr, rbr, qbr, row0_r, Br}, QcPostSeg{Xv, qjv, ubv, nullptr, qbv, row0_v, Bv},
+                         part, part_stride, st, tg);
   const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
   int HB, PS, threads;
   hidden_geometry(L.H, &HB, &PS, &threads);
@@ -2379,6 +2437,60 @@ static int post_both_learn(const float* prm, QcLayout L, QcPde pde, const QcPost
       hipLaunchKernelGGL((k_post_both<N, QcTab, QcLearn>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,
                          nv4, tg.tab, tg.learn);
       hipLaunchKernelGGL((k_post_wg_both<N, true>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride,
+                         HB, PS, nv);
+    }
+  });
+}
+
+// ------------------------------------------------------------------ the balanced kind (the balanced step)
+// qc_mlp_post (mode 2) with the trailing arguments (QcTab, QcBal): the tabulated kind's launches (per-point cotangents in
+// out_u / out_res, the weight-gradient kernel in its plain mode)
+static int post_bal(const float* prm, QcLayout L, QcPde pde, const float* qjets, float* out_u, float* out_res, float* qbar,
+                    float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st, const QcTarget& tg) {
+  const int tiles = qc_ceil_div(B, 64);
+  int HB, PS, threads;
+  hidden_geometry(L.H, &HB, &PS, &threads);
+  const size_t sh = (size_t)PS * (L.n + 2) * HB * sizeof(float);
+  const bool fused = post_fused_ok(L);
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L);
+  const float* X = nullptr;      // tabulated targets: not read
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c) {
+      constexpr int N = n(), NCH = c();
+      if (fused) {
+        hipLaunchKernelGGL((k_post_fused<N, NCH, QcTab, QcBal>), dim3(NCH == 6 ? tiles : qc_ceil_div(tiles, QC_POST_VALUE_TPB)),
+                           dim3(256), NCH == 6 ? shr : shv, st, X, prm, L, pde, qjets, out_u, out_res, qbar, part, part_stride, row0,
+                           B, tg.tab, tg.bal);
+        return;
+      }
+      hipLaunchKernelGGL((k_post<N, NCH, 2, QcTab, QcBal>), dim3(tiles), dim3(256), 0, st, X, prm, L, pde, qjets, out_u, out_res,
+                         (const float*)nullptr, (const float*)nullptr, qbar, part, part_stride, row0, B, tg.tab, tg.bal);
+      hipLaunchKernelGGL((k_post_wg<N, NCH>), dim3(tiles), dim3(threads), sh, st, prm, L, pde, qjets, (const float*)out_u,
+                         (NCH == 6 ? (const float*)out_res : nullptr), part, part_stride, row0, B, HB, PS, 0);
+    };
+    if (nch == 6) launch(qc_int<6>{}); else launch(qc_int<1>{});
+  });
+}
+
+// qc_mlp_post_both with the same arguments: the merged form exists for the register family only (n = 2 .. 5)
+static int post_both_bal(const float* prm, QcLayout L, QcPde pde, const QcPostSeg& r, const QcPostSeg& v, float* part,
+                         int64_t part_stride, hipStream_t st, const QcTarget& tg) {
+  const int nr = qc_ceil_div(r.B, 64), nv = qc_ceil_div(v.B, 64);
+  int HB, PS, threads;
+  hidden_geometry(L.H, &HB, &PS, &threads);
+  const size_t sh = (size_t)PS * (L.n + 2) * HB * sizeof(float);
+  const int nv4 = qc_ceil_div(nv, 4), nvf = qc_ceil_div(nv, QC_POST_VALUE_TPB);
+  const bool fused = post_fused_ok(L);
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L), shf = shr > shv ? shr : shv;
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    constexpr int N = n();
+    if (fused) {
+      hipLaunchKernelGGL((k_post_fused_both<N, QcTab, QcBal>), dim3(nr + nvf), dim3(256), shf, st, prm, L, pde, r, v, part,
+                         part_stride, nr, tg.tab, tg.bal);
+    } else {
+      hipLaunchKernelGGL((k_post_both<N, QcTab, QcBal>), dim3(nr + nv4), dim3(256), 0, st, prm, L, pde, r, v, part, part_stride,
+                         nv4, tg.tab, tg.bal);
+      hipLaunchKernelGGL((k_post_wg_both<N, false>), dim3(nr + nv), dim3(threads), sh, st, prm, L, pde, r, v, part, part_stride,
                          HB, PS, nv);
     }
   });

@@ -76,9 +76,28 @@ struct QcAdamArgs {
   QcDiagRuns runs;
 };
 
-__device__ __forceinline__ void adam_block(const QcAdamArgs& a, float* s_red) {
+// The balancer's share of an optimiser launch (BAL below), on the thread that owns entry NP_B - 3 + k, from the entry's
+// value p BEFORE the update and the reduced loss column Lk: the effective weight w_k e_k (stored to row `hi` of the weight
+// history), the term w_k e_k L_k + s_k of F (to s_term[k], read by thread 0 behind the next barrier), and the gradient
+// entry scale_k (1 - w_k e_k L_k), exactly 0 for a frozen term.
+__device__ __forceinline__ float bal_entry(const int k, const float p, const float Lk, const QcOptHyper& hp, const QcBal& bl,
+                                           const int hi, float* s_term) {
+  const float sc = k == 0 ? bl.scale[0] : (k == 1 ? bl.scale[1] : bl.scale[2]);
+  const float w = (k == 0 ? hp.w_res : (k == 1 ? hp.w_bc : hp.w_ic)) * qc_bal_factor(sc, p);
+  if (bl.hist != nullptr && hi >= 0 && hi < bl.hist_cap) bl.hist[(int64_t)hi * QC_BAL_N + k] = w;
+  s_term[k] = fmaf(w, Lk, sc * p);
+  return sc == 0.f ? 0.f : sc * (1.f - w * Lk);
+}
+
+// BAL (the balanced step): the last QC_BAL_N of the NP entries are the balancer's.  Their gradients are formed here
+// (bal_entry) whatever flat holds in their slots, they stay out of the clip's norm and are not scaled by its factor, and
+// the scheduler, the history and last_loss see F; loss_parts stay the raw columns.
+template <bool BAL = false>
+__device__ __forceinline__ void adam_block(const QcAdamArgs& a, float* s_red, const QcBal* bl = nullptr,
+                                           float* s_term = nullptr) {
   float* __restrict__ flat = a.flat;
   const int NP = a.NP;
+  const int NPn = BAL ? NP - QC_BAL_N : NP;   // the clipped (network) entries
   float *__restrict__ prm = a.prm, *__restrict__ m = a.m, *__restrict__ v = a.v;
   QcOptState* __restrict__ st = a.st;
   const QcOptHyper& hp = a.hp;
@@ -87,7 +106,7 @@ __device__ __forceinline__ void adam_block(const QcAdamArgs& a, float* s_red) {
   const QcGate* __restrict__ prog = a.prog;
   QcTrig* __restrict__ trig = a.trig;
   float ss = 0.f;
-  for (int i = threadIdx.x; i < NP; i += blockDim.x) ss += flat[i] * flat[i];
+  for (int i = threadIdx.x; i < NPn; i += blockDim.x) ss += flat[i] * flat[i];
   const float norm = sqrtf(block_sum_1024(ss, s_red));
   float coef = hp.max_norm / (norm + 1e-6f);           // torch.nn.utils.clip_grad_norm_
   coef = coef > 1.f ? 1.f : coef;
@@ -99,7 +118,9 @@ __device__ __forceinline__ void adam_block(const QcAdamArgs& a, float* s_red) {
   const float bc2s = (float)sqrt(1.0 - qc_ipow(hp.beta2, step));
   const float step_size = (float)((double)lr / bc1);
   for (int i = threadIdx.x; i < NP; i += blockDim.x) {
-    const float g = flat[i] * coef;
+    float g = flat[i] * coef;
+    if constexpr (BAL)
+      if (i >= NPn) g = bal_entry(i - NPn, prm[i], flat[NP + i - NPn], hp, *bl, step - 1 - st->hist_base, s_term);
     flat[i] = g;                                       // leave the clipped gradient visible
     const float mi = m[i] + (1.f - b1) * (g - m[i]);       // exp_avg.lerp_(grad, 1 - beta1)
     const float vi = b2 * v[i] + (1.f - b2) * g * g;
@@ -124,7 +145,8 @@ __device__ __forceinline__ void adam_block(const QcAdamArgs& a, float* s_red) {
   }
   if (threadIdx.x == 0) {
     const float lr_ = flat[NP], lb = flat[NP + 1], li = flat[NP + 2];
-    const float loss = hp.w_res * lr_ + hp.w_bc * lb + hp.w_ic * li;
+    float loss = hp.w_res * lr_ + hp.w_bc * lb + hp.w_ic * li;
+    if constexpr (BAL) loss = (s_term[0] + s_term[1]) + s_term[2];
     // ReduceLROnPlateau.step(loss), mode "min", threshold_mode "rel", cooldown 0
     float best = st->best;
     int bad = st->num_bad;
@@ -207,13 +229,21 @@ __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restri
 // memory latencies, so the loads are issued together up front and the new theta reaches the trig table
 // through LDS instead of a store -> load of global memory.  Arithmetic identical to adam_block.
 // FOLD: flat[c] = part[0][c] + ... + part[RS-1][c] (second reduction level, fixed order) is formed here.
+// BL = (QcBal): BAL as in adam_block; the owner of a balancer entry holds its value in a register and finds the loss
+// columns in LDS.  (A trailing pack, as the post kernels take their target kinds: the plain instantiations carry no
+// argument for it and keep their code.)
 constexpr int QC_ADAM_K = 3;
-template <bool FOLD>
-__global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* __restrict__ part, int64_t stride, int RS) {
+template <bool FOLD, class... BL>
+__global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* __restrict__ part, int64_t stride, int RS,
+                                                    BL... bl) {
+  static_assert(sizeof...(BL) == 0 || (sizeof...(BL) == 1 && (std::is_same_v<BL, QcBal> && ...)), "() or (QcBal)");
+  constexpr bool BAL = sizeof...(BL) == 1;
   __shared__ float s_red[16];
-  __shared__ float s_loss[3];
+  __shared__ float s_loss[BAL ? 3 + QC_BAL_N : 3];   // BAL: the terms of F behind the loss columns
+  [[maybe_unused]] float* s_term = s_loss + 3;
   extern __shared__ float s_theta[];   // [n_theta], then (cos, sin)[n_gates][2]
   const int NP = a.NP, tid = threadIdx.x;
+  const int NPn = BAL ? NP - QC_BAL_N : NP;   // the clipped (network) entries
   const QcOptHyper& hp = a.hp;
   const int step = a.st->step + 1;
   const float lr = a.st->lr;
@@ -250,8 +280,8 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
 #pragma unroll
   for (int k = 0; k < QC_ADAM_K; ++k) {
     const int i = tid + k * 1024;
-    if (i < NP) ss += g[k] * g[k];
-    else if (i < NP + 3) s_loss[i - NP] = g[k];
+    if (i < NPn) ss += g[k] * g[k];
+    else if ((!BAL || i >= NP) && i < NP + 3) s_loss[i - NP] = g[k];
   }
   const float norm = sqrtf(block_sum_1024(ss, s_red));   // (its barriers also publish s_loss)
   float coef = hp.max_norm / (norm + 1e-6f);
@@ -260,13 +290,15 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
   const double bc1 = 1.0 - qc_ipow(hp.beta1, step);
   const float bc2s = (float)sqrt(1.0 - qc_ipow(hp.beta2, step));
   const float step_size = (float)((double)lr / bc1);
-  const int n_theta = NP - a.theta_off;
+  const int n_theta = NPn - a.theta_off;
   float* s_cs = s_theta + (a.prog != nullptr ? n_theta : 0);
 #pragma unroll
   for (int k = 0; k < QC_ADAM_K; ++k) {
     const int i = tid + k * 1024;
     if (i < NP) {
-      const float gc = g[k] * coef;
+      float gc = g[k] * coef;
+      if constexpr (BAL)
+        if (i >= NPn) gc = bal_entry(i - NPn, pi[k], s_loss[i - NPn], hp, bl..., step - 1 - hist_base, s_term);
       const float mn = mi[k] + (1.f - b1) * (gc - mi[k]);
       const float vn = b2 * vi[k] + (1.f - b2) * gc * gc;
       const float denom = sqrtf(vn) / bc2s + hp.eps;
@@ -275,7 +307,7 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
       a.m[i] = mn;
       a.v[i] = vn;
       a.prm[i] = pn;
-      if (a.prog != nullptr && i >= a.theta_off) s_theta[i - a.theta_off] = pn;
+      if (a.prog != nullptr && i >= a.theta_off && (!BAL || i < NPn)) s_theta[i - a.theta_off] = pn;
     } else if (FOLD && i < NP + 3) {
       a.flat[i] = g[k];
     }
@@ -301,7 +333,8 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
   }
   if (tid == 0) {
     const float lr_ = s_loss[0], lb = s_loss[1], li = s_loss[2];
-    const float loss = hp.w_res * lr_ + hp.w_bc * lb + hp.w_ic * li;
+    float loss = hp.w_res * lr_ + hp.w_bc * lb + hp.w_ic * li;
+    if constexpr (BAL) loss = (s_term[0] + s_term[1]) + s_term[2];
     float new_lr = lr;
     if (loss < best * (1.f - hp.sched_threshold)) {
       best = loss;
@@ -369,10 +402,18 @@ static QcAdamArgs adam_args(float* flat, int NP, float* prm, float* m, float* v,
 
 static bool adam_fast_ok(int NP) { return NP + 3 <= QC_ADAM_K * 1024; }
 
+// the balanced launches of both entry points below: defined at the end of this file, so that their kernels lie behind
+// every other kernel of the code object
+static void adam_bal_launch(const QcAdamArgs& a, bool fold, const float* part, int64_t stride, int RS, size_t lds,
+                            const QcBal& bal, hipStream_t st);
+
 int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState* state, QcOptHyper hp,
-                float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t st) {
+                float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t st,
+                const QcBal* bal) {
   const QcAdamArgs a = adam_args(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig);
-  if (adam_fast_ok(NP))
+  if (bal)
+    adam_bal_launch(a, false, nullptr, 0, 0, sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0), *bal, st);
+  else if (adam_fast_ok(NP))
     hipLaunchKernelGGL((k_adam_fast<false>), dim3(1), dim3(1024), sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0), st, a,
                        (const float*)nullptr, (int64_t)0, 0);
   else
@@ -390,18 +431,41 @@ int qc_opt_fold_rows(float* part, int64_t rows, int64_t stride, int ncols, hipSt
 // Second level + optimiser update (flat = [grad | 3 loss parts] is written as well).
 int qc_opt_adam_fold(const float* part, int64_t stride, int RS, float* flat, int NP, float* prm, float* m, float* v,
                      QcOptState* state, QcOptHyper hp, float* hist, int hist_cap, const qc_program* pg, int theta_off,
-                     QcTrig* trig, hipStream_t st) {
+                     QcTrig* trig, hipStream_t st, const QcBal* bal) {
   if (adam_fast_ok(NP)) {
-    hipLaunchKernelGGL((k_adam_fast<true>), dim3(1), dim3(1024), sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0), st,
-                       adam_args(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig), part, stride, RS);
+    const size_t lds = sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0);
+    const QcAdamArgs a = adam_args(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig);
+    if (bal) adam_bal_launch(a, true, part, stride, RS, lds, *bal, st);
+    else hipLaunchKernelGGL((k_adam_fast<true>), dim3(1), dim3(1024), lds, st, a, part, stride, RS);
     return QC_OK;
   }
   qc_opt_reduce_rows(part, RS, stride, NP + 3, flat, st);
-  return qc_opt_adam(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig, st);
+  return qc_opt_adam(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig, st, bal);
 }
 
 int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hipStream_t st) {
   hipLaunchKernelGGL(k_prep_trig, dim3(1), dim3(256), 0, st, pg->d_gates, pg->n_gates, pg->n_qubits, theta, trig,
                      qc_diag_runs_of(pg));
   return QC_OK;
+}
+
+// ------------------------------------------------------------------ the balanced update (the balanced step)
+// adam_block with BAL set (the fast sizes: k_adam_fast<FOLD, QcBal>): one launch, nothing read back.  a.NP counts the
+// balancer's three entries.
+namespace {
+
+__global__ void __launch_bounds__(1024) k_adam_bal(QcAdamArgs a, QcBal bal) {
+  __shared__ float s_red[16];
+  __shared__ float s_term[QC_BAL_N];
+  adam_block<true>(a, s_red, &bal, s_term);
+}
+
+}  // namespace
+
+// fold: the second reduction level rides in the launch (fast sizes only: the caller reduces first otherwise)
+static void adam_bal_launch(const QcAdamArgs& a, bool fold, const float* part, int64_t stride, int RS, size_t lds,
+                            const QcBal& bal, hipStream_t st) {
+  if (!adam_fast_ok(a.NP)) hipLaunchKernelGGL(k_adam_bal, dim3(1), dim3(1024), 0, st, a, bal);
+  else if (fold) hipLaunchKernelGGL((k_adam_fast<true, QcBal>), dim3(1), dim3(1024), lds, st, a, part, stride, RS, bal);
+  else hipLaunchKernelGGL((k_adam_fast<false, QcBal>), dim3(1), dim3(1024), lds, st, a, (const float*)nullptr, (int64_t)0, 0, bal);
 }

@@ -777,6 +777,8 @@ class InverseStep:
     or hands over a resident dataset with ``set_dataset`` and lets ``QC_PHASE_SAMPLE`` gather points and targets.
     ``coef_hist`` [hist_cap, 7] receives the coefficients each step used, beside the loss history of ``opt``."""
 
+    N_OWN = L.QC_COEF_COLS      # trainable entries behind theta (``BalancedStep``: its three)
+
     def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, base, scale, B_res: int, n_ic: int, n_bc: int,
                  opt: OptimState, counts=None, loss_weights=(2.0, 4.0, 2.0)):
         self.lib, self.circuit, self.opt = circuit.lib, circuit, opt
@@ -785,7 +787,7 @@ class InverseStep:
         check_network_shape(self.H, n)
         self.layout = param_layout(self.H, n, self.n_theta)
         self.NP = self.layout["__total__"][0]
-        self.NP_L = self.NP + L.QC_COEF_COLS
+        self.NP_L = self.NP + self.N_OWN
         self.theta_off = self.layout["quantum_layer.params"][0]
         if flat.numel() != self.NP_L:
             raise L.QcError(f"flat parameter vector has {flat.numel()} entries, the layout with the operator needs {self.NP_L}")
@@ -885,3 +887,41 @@ class InverseStep:
             self.desc.sample_step += 1          # a fresh counter block per step
         L.check(self.lib.qc_fused_pinn_inverse_step(C.byref(self.desc), C.byref(self.data), C.byref(self.learn), phases,
                                                     _stream(self.device)), "qc_fused_pinn_inverse_step")
+
+
+class BalancedStep(InverseStep):
+    """One ``qc_fused_pinn_balanced_step`` descriptor over fixed-size resident batches: the tabulated step under learned
+    loss weights (uncertainty balancing), F = sum_k (w_k exp(-s_k) L_k + s_k) with s_k = scale_k p_k, k = residual, BC, IC.
+
+    ``flat`` holds ``NP + 3`` entries, trained in place: the single-output layout and the three ``p_k`` behind it; ``opt``
+    holds as many.  ``scale``: three floats (``scale_k = 0`` freezes a term at weight w_k).  ``coeffs`` = (c_t, c_x, c_y,
+    d_xx, d_yy) and ``c_u``: the operator of the tabulated residual.  Batches, dataset, sampler and communicator are
+    ``InverseStep``'s.  ``weight_hist`` [hist_cap, 3] receives the effective weights w_k exp(-s_k) each step used, beside
+    the history of F in ``opt``."""
+
+    N_OWN = L.QC_BAL_TERMS
+
+    def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, scale, B_res: int, n_ic: int, n_bc: int,
+                 opt: OptimState, coeffs, c_u: float = 0.0, counts=None, loss_weights=(2.0, 4.0, 2.0)):
+        scale = [float(v) for v in scale]
+        if len(scale) != L.QC_BAL_TERMS:
+            raise L.QcError(f"scale holds {L.QC_BAL_TERMS} entries: residual, BC, IC")
+        zeros = [0.0] * L.QC_COEF_COLS
+        super().__init__(circuit, hidden, flat, zeros, zeros, B_res, n_ic, n_bc, opt, counts=counts, loss_weights=loss_weights)
+        del self.learn, self.coef_hist      # no operator record: the operator is the tabulated step's
+        self.NP_B = self.NP_L
+        self.data.c_u = float(c_u)
+        d = self.desc
+        d.pde.c_t, d.pde.c_x, d.pde.c_y, d.pde.d_xx, d.pde.d_yy = (float(c) for c in coeffs)
+        self.weight_hist = torch.zeros(max(opt.hist_cap, 1), L.QC_BAL_TERMS, dtype=torch.float32, device=self.device)
+        self.bal = L.QcStepBalance()
+        for k in range(L.QC_BAL_TERMS):
+            self.bal.scale[k] = scale[k]
+        self.bal.weight_hist_dev = self.weight_hist.data_ptr() if opt.hist_cap > 0 else None
+        self.bal.weight_hist_cap = opt.hist_cap
+
+    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
+        if phases & L.QC_PHASE_SAMPLE:
+            self.desc.sample_step += 1          # a fresh counter block per step
+        L.check(self.lib.qc_fused_pinn_balanced_step(C.byref(self.desc), C.byref(self.data), C.byref(self.bal), phases,
+                                                     _stream(self.device)), "qc_fused_pinn_balanced_step")

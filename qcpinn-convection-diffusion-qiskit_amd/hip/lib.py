@@ -34,13 +34,15 @@ EXPORTS = (
     "qc_post_system", "qc_sample_dataset_system", "qc_fused_pinn_system_step",
     "qc_post_learn", "qc_fused_pinn_inverse_step",
     "qc_lbfgs_workspace_bytes", "qc_lbfgs_init", "qc_lbfgs_restart", "qc_lbfgs_step",
+    "qc_post_balance", "qc_balance_adam_step", "qc_fused_pinn_balanced_step",
 )
 
 
 QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_PULSE = 0, 1, 2      # qc_pde.problem
 QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc_fused_pinn_data_step only
 QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 (qc_step_coef)
-QC_ADAPT_BLOCK = 1024            # rows per entry of the coarse table of an adaptive-sampling buffer (qc_adapt_bytes)
+QC_BAL_TERMS = 3                # loss terms of a balancer: residual, BC, IC (qc_step_balance)
+QC_ADAPT_BLOCK = 1024           # rows per entry of the coarse table of an adaptive-sampling buffer (qc_adapt_bytes)
 QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
 QC_KMAX, QC_EQMAX, QC_TERMS_MAX = 4, 4, 32            # outputs, equations and terms of a system (qc_step_system)
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
@@ -119,6 +121,12 @@ class QcStepLearn(C.Structure):
     optional [cap][7] history of the c_k each step used."""
     _fields_ = [("base", C.c_float * QC_COEF_COLS), ("scale", C.c_float * QC_COEF_COLS),
                 ("coef_hist_dev", C.c_void_p), ("coef_hist_cap", C.c_int)]
+
+
+class QcStepBalance(C.Structure):
+    """qc_step_balance: scale of the three log-variances s_k = scale_k p_k (order residual, BC, IC) and the optional
+    [cap][3] history of the effective weights w_k exp(-s_k) each step used."""
+    _fields_ = [("scale", C.c_float * QC_BAL_TERMS), ("weight_hist_dev", C.c_void_p), ("weight_hist_cap", C.c_int)]
 
 
 class QcStepAdapt(C.Structure):
@@ -243,6 +251,11 @@ def load() -> C.CDLL:
     lib.qc_lbfgs_init.argtypes = [vp, i32, i32, vp]
     lib.qc_lbfgs_restart.argtypes = [vp, i32, vp]
     lib.qc_lbfgs_step.argtypes = [fp, i32, fp, vp, C.POINTER(QcLbfgsHyper), fp, i32, vp, i32, vp, vp]
+    lib.qc_post_balance.argtypes = [fp, i32, i32, i32, C.POINTER(QcPde), C.POINTER(QcStepBalance), fp, fp, C.c_float, fp, fp,
+                                    fp, fp, i64, i64, i64, i32, vp]
+    lib.qc_balance_adam_step.argtypes = [fp, i32, fp, fp, fp, vp, C.POINTER(QcOptHyper), C.POINTER(QcStepBalance), fp, i32, vp,
+                                         i32, vp, vp]
+    lib.qc_fused_pinn_balanced_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepBalance), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

@@ -1,0 +1,197 @@
+"""Fused training of a ``DVPDESolver`` under learned loss weights (``qc_fused_pinn_balanced_step``).
+
+The tabulated step minimises ``w_res L_r + w_bc L_bc + w_ic L_ic`` with weights fixed for the run.  Here the three terms
+are balanced by one trainable log-variance each (``nn.loss_balance.AdaptiveMultiLoss``, the interface of the reference's
+hybrid script):
+
+    F = sum_k ( w_k exp(-s_k) L_k + s_k ),      s_k = scale_k p_k,      k = residual, BC, IC.
+
+The weights of a step depend on the losses of the step before, so setting them from the host would cost a synchronisation
+per step; a ``BalancedTrainer`` keeps the three ``p_k`` on the device behind the model's parameters and runs the whole
+iteration, their gradient and their Adam update included, as one library call.  As in the reference, the gradient clip
+covers the model's parameters only.  The reference's script uses AdamW; this step keeps the model's Adam.
+"""
+from __future__ import annotations
+
+import time
+
+import torch
+
+from ..data.tabulated import TabulatedProblem
+from ..hip import engine as _engine
+from ..hip import lib as _lib
+from ..nn.loss_balance import TERMS, AdaptiveMultiLoss
+from .diffusion_train import _dist_info, _log_line
+from .inverse_train import InverseTrainer
+
+
+def check_balance(model, dataset, balancer, adaptive=None, lbfgs=None):
+    """The argument errors of ``balance=``: one ``ValueError`` per fault, none of which needs a GPU."""
+    if not isinstance(balancer, AdaptiveMultiLoss):
+        raise ValueError("balance= must be an nn.loss_balance.AdaptiveMultiLoss")
+    if sorted(balancer.names) != sorted(TERMS):
+        raise ValueError(f"the balancer's names must be exactly the three loss terms {TERMS}, got {tuple(balancer.names)}")
+    if not isinstance(dataset, TabulatedProblem):
+        raise ValueError("balance= needs dataset= a TabulatedProblem: the analytic problems can be tabulated first")
+    if dataset.coef_res is not None:
+        raise ValueError("balance= does not take a per-point coefficient table (dataset.coef_res)")
+    if adaptive is not None:
+        raise ValueError("balance= cannot be combined with adaptive= sampling")
+    if lbfgs is not None:
+        raise ValueError("balance= cannot be combined with an lbfgs= phase")
+    world, _ = _dist_info()
+    if world > 1:
+        raise ValueError("balance= is single-process: world_size > 1 is not supported")
+    if not (hasattr(model, "_engine_for") and hasattr(model, "quantum_layer")):
+        raise ValueError("balance= runs in the fused step: it is only supported for DVPDESolver models")
+    if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
+        raise ValueError("balance= needs classic_network = [3, H, 1]")
+
+
+class BalancedTrainer(InverseTrainer):
+    """Device-resident training state of one single-output DVPDESolver and one AdaptiveMultiLoss: ONE flat buffer of
+    ``NP + 3`` entries with the model's parameters in its head (``model.parameters()`` order, re-pointed at views of it)
+    and the three ``log_vars`` in its tail, in the order residual, BC, IC, so ``model(X)``, ``save_state`` and
+    ``balancer.weights()`` see the trained values with no copy; the optimiser record taken from the model's torch Adam /
+    ReduceLROnPlateau (which the balancer joins as a second param group); and the step descriptor.  ``step()`` is one
+    training iteration without host synchronisation.  Batches, sampling and the optimiser record are ``InverseTrainer``'s."""
+
+    def __init__(self, model, batch_size: int, dataset: TabulatedProblem, balancer: AdaptiveMultiLoss, *, n_ic: int = None,
+                 n_bc: int = None, loss_weights=(2.0, 4.0, 2.0), max_norm=1.0, capacity: int = 0, sampler: str = "device"):
+        """``dataset``: the resident segments and the operator (``coeffs``, ``c_u``) of the tabulated step; ``batch_size``
+        residual, ``n_ic`` / ``n_bc`` (default ``batch_size // 3``) value points per step; ``loss_weights`` = the base
+        weights w_k (residual, BC, IC); ``capacity``: length of the histories of F and of the effective weights."""
+        check_balance(model, dataset, balancer)
+        if sampler not in ("device", "torch"):
+            raise ValueError("sampler must be 'device' or 'torch'")
+        n3 = batch_size // 3
+        self.B_res = int(batch_size)
+        self.n_ic = n3 if n_ic is None else int(n_ic)
+        self.n_bc = n3 if n_bc is None else int(n_bc)
+        if min(self.B_res, self.n_ic, self.n_bc) < 0 or self.B_res + self.n_ic + self.n_bc == 0:
+            raise ValueError("batch sizes must be non-negative and not all zero")
+        dev = model._resolve_device(model.device)
+        if dev is None or dev.type != "cuda":
+            raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
+        self.model, self.balancer, self.device, self.sampler = model, balancer, dev, sampler
+        self.dataset = dataset.to(dev)
+        self.max_norm = max_norm
+        self.loss_weights = tuple(float(w) for w in loss_weights)
+        self._pack()
+        self.circuit = model.quantum_layer._circuit_for(dev)
+        self.optimizer, self.scheduler = model.optimizer, model.scheduler
+        self.attach(model, balancer)
+        self.opt = self._make_opt_state(int(capacity))
+        ds = self.dataset
+        scale = balancer.scale.tolist()
+        scale = [scale[balancer.names.index(name)] for name in TERMS]      # the step's order, whatever the balancer's
+        self.fs = _engine.BalancedStep(self.circuit, model.hidden_width, self.flat, scale, self.B_res, self.n_ic, self.n_bc,
+                                       self.opt, ds.coeffs, ds.c_u, loss_weights=self.loss_weights)
+        self._sampled = all(n_rows > 0 or n_batch == 0
+                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
+        if self._sampled:
+            self.fs.set_dataset(ds.segments())
+        self.fs.refresh_gates()
+        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        self._explicit = False
+        model._sync_fused_to_torch = self.sync_to_torch
+
+    @staticmethod
+    def _own(balancer):
+        return [balancer.log_vars[name] for name in TERMS]
+
+    @staticmethod
+    def attach(model, balancer):
+        """The three ``log_vars`` join ``model.optimizer`` as a second param group with the hyper-parameters of the first,
+        if they are not there yet (the constructor calls this; call it on a fresh model before loading a saved optimiser
+        state)."""
+        opt = model.optimizer
+        own = BalancedTrainer._own(balancer)
+        if not any(p is own[0] for g in opt.param_groups for p in g["params"]):
+            g0 = opt.param_groups[0]
+            opt.add_param_group({"params": own, **{k: v for k, v in g0.items() if k != "params"}})
+            sch = model.scheduler
+            sch.min_lrs = list(sch.min_lrs) + [sch.min_lrs[0]] * (len(opt.param_groups) - len(sch.min_lrs))
+
+    def _params(self):
+        return list(self.model.parameters()) + self._own(self.balancer)
+
+    def _pack(self):
+        """One flat buffer [model parameters | p_res, p_bc, p_ic]; the model's own flat buffer becomes its head (a view),
+        the way ``model._pack`` builds it, and the three ``log_vars`` become views of the tail."""
+        model, bal, dev = self.model, self.balancer, self.device
+        if not model._packed_ok() or model._flat.device != dev:
+            model._pack(dev)
+        NP = model._flat.numel()
+        own = self._own(bal)
+        big = getattr(model, "_balanced_flat", None)
+        if not (big is not None and big.device == dev and big.numel() == NP + len(TERMS)
+                and model._flat.data_ptr() == big.data_ptr()
+                and all(p.data_ptr() == big.data_ptr() + 4 * (NP + k) for k, p in enumerate(own))):
+            tail = torch.cat([p.detach().reshape(1).to(device=dev, dtype=torch.float32) for p in own])
+            big = torch.cat([model._flat.detach(), tail])
+            off = 0
+            for p, k, pad in model._slots():
+                p.data = big[off:off + k].view(p.shape)
+                off += k
+            model._flat = big[:NP]
+            model._engines = {}
+            model._balanced_flat = big
+            for k, p in enumerate(own):
+                p.data = big[NP + k:NP + k + 1]
+            bal.scale.data = bal.scale.to(dev)
+        self.flat = model._balanced_flat
+        self.NP = NP
+
+    def weight_history(self, steps=None):
+        """(steps, 3) tensor: row i holds the effective weights w_k exp(-s_k) (residual, BC, IC) the i-th step of THIS
+        history buffer used, next to ``loss_history()[i]`` (default: all steps taken so far)."""
+        if steps is None:
+            rec = self.opt.read()
+            steps = rec["step"] - rec["hist_base"]
+        return self.fs.weight_hist[: max(0, min(int(steps), self.opt.hist_cap))].cpu()
+
+    def weights(self):
+        """The current effective weights w_k exp(-s_k) as a dict over the three terms."""
+        e = self.balancer.weights()
+        return {name: w * e[name] for name, w in zip(TERMS, self.loss_weights)}
+
+    def coefficient_history(self, steps=None):
+        raise AttributeError("a BalancedTrainer trains no operator: see weight_history() and weights()")
+
+    coefficients = coefficient_history
+
+
+def train_balanced(model, batch_size, batches, dataset, balancer):
+    """The loop of ``trainer.diffusion_train.train`` over a ``BalancedTrainer``: the logged loss is F."""
+    steps = model.epochs + 1
+    tr = BalancedTrainer(model, batch_size, dataset, balancer, capacity=steps)
+    t0 = time.time()
+    model.logger.print(f"Starting training for {model.epochs} epochs with learned loss weights...")
+    model.logger.print(f"Batch size: {batch_size}")
+    pe = model.args["print_every"]
+    done = 0
+    for it in range(steps):
+        if batches is None:
+            tr.sample()
+        else:
+            tr.load_batches(*batches[it][:3], targets=batches[it][3])
+        tr.step()
+        if it % pe == 0 or it == 0:
+            parts, lr = tr.losses()
+            el = time.time() - t0
+            _log_line(model, it, parts, lr, el / (it + 1), el)
+            w = tr.weights()
+            model.logger.print("  loss weights: " + ", ".join(f"{k} {v:.3e}" for k, v in w.items()))
+            if it > 0 and it % pe == 0:
+                hist = tr.loss_history(it + 1)
+                model.loss_history.extend(hist[done:])
+                done = len(hist)
+                model.save_state()
+    hist = tr.loss_history(steps)
+    model.loss_history.extend(hist[done:])
+    tr.sync_to_torch()
+    total = time.time() - t0
+    model.total_training_time += total
+    model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
+    return tr

@@ -30,6 +30,10 @@ dataset's residual rows with probability proportional to |res|^power / mean + fl
 re-evaluated on all rows every ``every`` steps: on the device for a ``DVPDESolver`` (``qc_dataset_scores``,
 ``qc_adapt_build``, ``qc_fused_pinn_adaptive_step``: still one call per iteration, no host read), with torch ops and
 ``torch.searchsorted`` on the same integer weights for any other model.
+
+``balance=`` (keyword-only, an ``nn.loss_balance.AdaptiveMultiLoss``, with ``dataset=``) learns the three loss weights on
+the device (``qc_fused_pinn_balanced_step``, ``trainer.balanced_train``): ``DVPDESolver`` models only, not together with
+``adaptive=`` or ``lbfgs=``.
 """
 from __future__ import annotations
 
@@ -557,14 +561,22 @@ def _train_generic(model, batch_size, dataset=None, adaptive=None):
 
 
 def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None,
-          adaptive=None, lbfgs=None):
+          adaptive=None, lbfgs=None, balance=None):
     """``batches`` (keyword-only, not in the reference): a per-iteration list of
     ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests; with a dataset each entry carries a
     fourth element, the targets ``(u_ic, u_bc, r_res)``.  ``dataset`` (keyword-only): a ``TabulatedProblem`` whose targets
     and operator replace the analytic problem (module docstring).  ``adaptive`` (keyword-only): an ``AdaptiveSampling``
     for the residual rows of ``dataset`` (module docstring).  ``lbfgs`` (keyword-only): a ``trainer.lbfgs_train.LbfgsPhase``,
     that many L-BFGS evaluations on the device behind the Adam epochs (``DVPDESolver`` models only); its accepted losses
-    continue ``model.loss_history`` and the model ends at the last accepted point."""
+    continue ``model.loss_history`` and the model ends at the last accepted point.  ``balance`` (keyword-only): an
+    ``nn.loss_balance.AdaptiveMultiLoss`` over ("residual", "bc", "ic"); the three loss weights are then learned on the
+    device (``trainer.balanced_train``; needs ``dataset``, ``DVPDESolver`` models only, not with ``adaptive`` or
+    ``lbfgs``), and the logged loss is the balanced objective.  ``update_lam`` stays unused."""
+    if balance is not None:
+        from .balanced_train import check_balance, train_balanced
+        check_balance(model, dataset, balance, adaptive, lbfgs)
+        train_balanced(model, batch_size, batches, dataset, balance)
+        return
     if lbfgs is not None and not (hasattr(lbfgs, "evals") and hasattr(lbfgs, "options")):
         raise ValueError("lbfgs= must be a trainer.lbfgs_train.LbfgsPhase")
     if hasattr(model, "_engine_for") and hasattr(model, "quantum_layer"):
