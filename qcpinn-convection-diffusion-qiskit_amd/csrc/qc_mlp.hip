@@ -337,6 +337,72 @@ __global__ void __launch_bounds__(256) k_pre_fwd(const float* __restrict__ X, co
 }
 
 // ================================================================== pre network, reverse pass
+// ------------------------------------------------------------------ tile staging and group sums of these kernels
+// Staging: a wave fetches whole 64-point rows of the tile, wave w the rows w, w + nw, ... of the block's nw waves, so a
+// row's address is wave-uniform (scalar base) and the lane is the point.  The requests of one chunk of rows, together
+// with everything else the block reads from memory (its X values, a thread's weights), are written ahead of the first
+// LDS store: ONE memory round trip where a loop of run-time stride made one per row.  A chunk serves every block of
+// 192 threads or more; a chunk loop takes the rest of a narrower block's rows.  Lanes at or past cnt read the tile's
+// last live point (never memory past the batch) and stage 0.
+// Two things the compiler does otherwise: it folds the lane's offset into the row address first and
+// then holds one 64-bit vector address per row (sixteen registers a chunk), and it sinks a request into the branch that
+// stores its value, where the request waits alone.  So the row address passes through an empty asm as one scalar pair
+// (the load's scalar-base form), and qc_pin, placed behind the last request, keeps every request in front of it.
+__device__ __forceinline__ float qc_row_load(const float* __restrict__ row, const unsigned lane_off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  using G = const __attribute__((address_space(1))) char*;   // (the asm hides that the address is global memory)
+  G b = (G)row;
+  asm("" : "+s"(b));
+  return *(const __attribute__((address_space(1))) float*)(b + (size_t)(lane_off * 4u));
+#else
+  return row[lane_off];
+#endif
+}
+__device__ __forceinline__ void qc_pin(float& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(v));
+#endif
+}
+template <int A, int B2>
+__device__ __forceinline__ void qc_pin(float (&v)[A][B2]) {
+#pragma unroll
+  for (int a = 0; a < A; ++a)
+#pragma unroll
+    for (int b = 0; b < B2; ++b) qc_pin(v[a][b]);
+}
+template <int A>
+__device__ __forceinline__ void qc_pin(float (&v)[A]) {
+#pragma unroll
+  for (int a = 0; a < A; ++a) qc_pin(v[a]);
+}
+
+// The sums over the PS point groups of hidden unit m's K accumulators (s_acc = [PS][K][HB]), ascending in the group like
+// the plain loop.  The reads of GC groups (about forty registers) are all requested before the first add; a group past PS
+// reads the last one and adds +0.f instead: a sum that starts at +0.f is never -0.f, so the bits are the plain loop's.
+template <int K>
+__device__ __forceinline__ void qc_group_sums(const float* s_acc, const int PS, const int HB, const int m, float (&tot)[K]) {
+  constexpr int GC = K >= 40 ? 1 : 40 / K;
+#pragma unroll
+  for (int k = 0; k < K; ++k) tot[k] = 0.f;
+  for (int g0 = 0; g0 < PS; g0 += GC) {
+    float v[GC][K];
+#pragma unroll
+    for (int j = 0; j < GC; ++j) {
+      const int gc = (g0 + j) < PS ? (g0 + j) : PS - 1;
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[j][k] = s_acc[((size_t)gc * K + k) * HB + m];
+    }
+#pragma unroll
+    for (int j = 0; j < GC; ++j)
+#pragma unroll
+      for (int k = 0; k < K; ++k) tot[k] += (g0 + j) < PS ? v[j][k] : 0.f;
+  }
+}
+
+// For n <= 8.  Above (the circuit is then nine tenths of a step and more) these kernels sit at register limits the batch
+// would cross (a wave per SIMD at n = 9, 12, 15, 16, scratch at n = 14 .. 16): they keep the plain loops.
+constexpr bool qc_stage_batched(const int n) { return n <= 8; }
+
 // lane = hidden unit (each lane owns one row of W1 / column of W2, so weight gradients need no
 // cross-lane reduction).  The block's 64-point tile is staged in LDS and split over PS groups of HB
 // threads (16 points each, read as LDS broadcasts); the groups' accumulators meet in LDS.
@@ -352,41 +418,130 @@ __device__ __forceinline__ void k_pre_bwd_body(const int64_t bid, const float* _
   extern __shared__ float s_acc[];  // [PS][4 + N][HB]
   const int64_t base = (int64_t)bid * 64;
   const int cnt = (int)((B - base) < 64 ? (B - base) : 64);
-  for (int i = threadIdx.x; i < 64 * 3; i += blockDim.x) {
-    const int pp = i / 3, k = i % 3;
-    sX[k][pp] = pp < cnt ? X[(base + pp) * 3 + k] : 0.f;
-  }
-  if constexpr (MAP == 0) {
-    for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
-      const int f = i >> 6, pp = i & 63;      // f = c * N + i
-      const int c = f / N, w = f % N;
-      const float v = pp < cnt ? abar[(int64_t)f * B + base + pp] : 0.f;
-      if (c & 1) sA2[(c >> 1) * N + w][pp].y = v;
-      else sA2[(c >> 1) * N + w][pp].x = v;
+  int grp, m;   // group and hidden unit of the thread; threads past HB * PS (block rounded up to waves) idle
+  float w0, w1, w2, bb, w2c[N];
+  constexpr bool BATCH = qc_stage_batched(N);
+  if constexpr (BATCH) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const bool live = lane < cnt;
+    const unsigned pc = live ? lane : cnt - 1;
+    // MAP = 0: a staged row is a row of sA2 (a wire's channel pair: two loads, one 64-bit store; NCH = 1: one and .x).
+    // MAP = 1: a staged row is a wire, all its channels of abar and of the angle jets aj: the angle cotangents are pulled
+    // back through a = pi tanh(v) on load (angle_map_bwd); the rest of the pass is the MAP = 0 pass on the cotangents of v.
+    constexpr int NR = MAP == 0 ? NP2 * N : N;                      // rows to stage
+    constexpr int NV = MAP == 0 ? (NCH == 6 ? 2 : 1) : 2 * NCH;     // loads per row
+    constexpr int CH = NV == 12 ? 1 : 8 / NV;                       // rows per chunk: 8 loads (12 for a six-channel wire)
+    auto request = [&](const int r0, float (&v)[CH][NV]) {
+#pragma unroll
+      for (int j = 0; j < CH; ++j) {
+        const int r = r0 + j * nw, rc = r < NR ? r : 0;
+        if constexpr (MAP == 0) {
+          const int cp = rc / N, w = rc % N;
+#pragma unroll
+          for (int q = 0; q < NV; ++q) v[j][q] = qc_row_load(abar + ((int64_t)((2 * cp + q) * N + w) * B + base), pc);
+        } else {
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            const int64_t o = (int64_t)(c * N + rc) * B + base;
+            v[j][c] = qc_row_load(abar + o, pc);
+            v[j][NCH + c] = qc_row_load(aj + o, pc);
+          }
+        }
+      }
+    };
+    auto put = [&](const int r0, const float (&v)[CH][NV]) {
+#pragma unroll
+      for (int j = 0; j < CH; ++j) {
+        const int r = r0 + j * nw;
+        if (r < NR) {
+          if constexpr (MAP == 0) {
+            if constexpr (NCH == 6) sA2[r][lane] = (mf2){live ? v[j][0] : 0.f, live ? v[j][1] : 0.f};
+            else sA2[r][lane].x = live ? v[j][0] : 0.f;
+          } else {
+            float ab[NCH], a[NCH], vb[NCH];
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+              ab[c] = live ? v[j][c] : 0.f;
+              a[c] = live ? v[j][NCH + c] : 0.f;
+            }
+            angle_map_bwd<NCH>(ab, a, vb);
+            if constexpr (NCH == 6) {
+#pragma unroll
+              for (int cp = 0; cp < 3; ++cp) sA2[cp * N + r][lane] = (mf2){vb[2 * cp], vb[2 * cp + 1]};
+            } else {
+              sA2[r][lane].x = vb[0];
+            }
+          }
+        }
+      }
+    };
+    // the requests: the wave's first chunk of cotangent rows, its row of the tile's 192 X values, the thread's weights
+    float stg[CH][NV];
+    request(wave, stg);
+    const int xi = (wave < 3 ? wave : 0) * 64 + lane;
+    float xv = qc_row_load(X + base * 3, xi < 3 * cnt ? xi : 3 * cnt - 1);
+    grp = threadIdx.x / HB, m = threadIdx.x % HB;
+    const int mc = m < L.H ? m : L.H - 1;      // (a thread without a hidden unit reads the last one's)
+    w0 = prm[L.oW1 + 3 * mc], w1 = prm[L.oW1 + 3 * mc + 1], w2 = prm[L.oW1 + 3 * mc + 2];
+    bb = prm[L.ob1 + mc];
+#pragma unroll
+    for (int i = 0; i < N; ++i) w2c[i] = prm[L.oW2 + i * L.H + mc];
+    // one wait, then the LDS stores
+    qc_pin(stg);
+    qc_pin(xv);
+    qc_pin(w0);
+    qc_pin(w1);
+    qc_pin(w2);
+    qc_pin(bb);
+    qc_pin(w2c);
+    if (wave < 3) sX[xi % 3][xi / 3] = xi < 3 * cnt ? xv : 0.f;
+    put(wave, stg);
+    // blocks of fewer than three waves, or of fewer waves than a chunk covers: the rows left
+    for (int r = wave + nw; r < 3; r += nw) {
+      const int i = r * 64 + lane;
+      sX[i % 3][i / 3] = i < 3 * cnt ? X[base * 3 + i] : 0.f;
+    }
+    for (int r0 = wave + CH * nw; r0 < NR; r0 += CH * nw) {
+      request(r0, stg);
+      qc_pin(stg);
+      put(r0, stg);
     }
   } else {
-    // angle cotangents pulled back through a = pi tanh(v) on load (angle_map_bwd), from the angle jets aj of the same
-    // points; the rest of the pass is the MAP = 0 pass on the cotangents of v
-    for (int i = threadIdx.x; i < N * 64; i += blockDim.x) {
-      const int w = i >> 6, pp = i & 63;
-      float ab[NCH], a[NCH], vb[NCH];
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int64_t o = (int64_t)(c * N + w) * B + base + pp;
-        ab[c] = pp < cnt ? abar[o] : 0.f;
-        a[c] = pp < cnt ? aj[o] : 0.f;
+    for (int i = threadIdx.x; i < 64 * 3; i += blockDim.x) {
+      const int pp = i / 3, k = i % 3;
+      sX[k][pp] = pp < cnt ? X[(base + pp) * 3 + k] : 0.f;
+    }
+    if constexpr (MAP == 0) {
+      for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
+        const int f = i >> 6, pp = i & 63;      // f = c * N + i
+        const int c = f / N, w = f % N;
+        const float v = pp < cnt ? abar[(int64_t)f * B + base + pp] : 0.f;
+        if (c & 1) sA2[(c >> 1) * N + w][pp].y = v;
+        else sA2[(c >> 1) * N + w][pp].x = v;
       }
-      angle_map_bwd<NCH>(ab, a, vb);
+    } else {
+      for (int i = threadIdx.x; i < N * 64; i += blockDim.x) {
+        const int w = i >> 6, pp = i & 63;
+        float ab[NCH], a[NCH], vb[NCH];
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        if (c & 1) sA2[(c >> 1) * N + w][pp].y = vb[c];
-        else sA2[(c >> 1) * N + w][pp].x = vb[c];
+        for (int c = 0; c < NCH; ++c) {
+          const int64_t o = (int64_t)(c * N + w) * B + base + pp;
+          ab[c] = pp < cnt ? abar[o] : 0.f;
+          a[c] = pp < cnt ? aj[o] : 0.f;
+        }
+        angle_map_bwd<NCH>(ab, a, vb);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          if (c & 1) sA2[(c >> 1) * N + w][pp].y = vb[c];
+          else sA2[(c >> 1) * N + w][pp].x = vb[c];
+        }
       }
     }
   }
   __syncthreads();
 
-  const int grp = threadIdx.x / HB, m = threadIdx.x % HB;   // threads past HB * PS (block rounded up to waves) idle
+  if constexpr (!BATCH) grp = threadIdx.x / HB, m = threadIdx.x % HB;
   const int per = (64 + PS - 1) / PS;
   const int p0 = grp * per, p1 = (p0 + per) < cnt ? (p0 + per) : cnt;
   float gW1[3] = {0.f, 0.f, 0.f}, gb1 = 0.f;
@@ -394,11 +549,12 @@ __device__ __forceinline__ void k_pre_bwd_body(const int64_t bid, const float* _
 #pragma unroll
   for (int i = 0; i < N; ++i) gW2p[i] = (mf2){0.f, 0.f};
   if (grp < PS && m < L.H) {
-    const float w0 = prm[L.oW1 + 3 * m], w1 = prm[L.oW1 + 3 * m + 1], w2 = prm[L.oW1 + 3 * m + 2];
-    const float bb = prm[L.ob1 + m];
-    float w2c[N];
+    if constexpr (!BATCH) {
+      w0 = prm[L.oW1 + 3 * m], w1 = prm[L.oW1 + 3 * m + 1], w2 = prm[L.oW1 + 3 * m + 2];
+      bb = prm[L.ob1 + m];
 #pragma unroll
-    for (int i = 0; i < N; ++i) w2c[i] = prm[L.oW2 + i * L.H + m];
+      for (int i = 0; i < N; ++i) w2c[i] = prm[L.oW2 + i * L.H + m];
+    }
     for (int pp = p0; pp < p1; ++pp) {
       const float t = sX[0][pp], x = sX[1][pp], y = sX[2][pp];
       const float h = fmaf(w0, t, fmaf(w1, x, fmaf(w2, y, bb)));
@@ -458,11 +614,15 @@ __device__ __forceinline__ void k_pre_bwd_body(const int64_t bid, const float* _
   float* row = part + (row0 + bid) * part_stride;
   if (grp == 0 && m < L.H) {
     float tot[4 + N];
+    if constexpr (BATCH) {
+      qc_group_sums<4 + N>(s_acc, PS, HB, m, tot);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4 + N; ++k) {
-      float sum = 0.f;
-      for (int g2 = 0; g2 < PS; ++g2) sum += s_acc[((size_t)g2 * (4 + N) + k) * HB + m];
-      tot[k] = sum;
+      for (int k = 0; k < 4 + N; ++k) {
+        float sum = 0.f;
+        for (int g2 = 0; g2 < PS; ++g2) sum += s_acc[((size_t)g2 * (4 + N) + k) * HB + m];
+        tot[k] = sum;
+      }
     }
     row[L.oW1 + 3 * m] = tot[0];
     row[L.oW1 + 3 * m + 1] = tot[1];
@@ -943,34 +1103,119 @@ __device__ __forceinline__ void k_post_wg_body(const int64_t bid, const float* _
   extern __shared__ float s_acc[];  // [PS][N + 2][HB]
   const int64_t base = (int64_t)bid * 64;
   const int cnt = (int)((B - base) < 64 ? (B - base) : 64);
-  for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
-    const int f = i >> 6, pp = i & 63;
-    sQ[f][pp] = pp < cnt ? qjets[(int64_t)f * B + base + pp] : 0.f;
-  }
-  if (NCH == 6 && gen) {
-    for (int i = threadIdx.x; i < 6 * 64; i += blockDim.x) {
-      const int k = i >> 6, pp = i & 63;
-      sU[k][pp] = pp < cnt ? ubar[(int64_t)k * B + base + pp] : 0.f;
+  int grp, m;   // group and hidden unit of the thread; threads past HB * PS (block rounded up to waves) idle
+  float w3[N], b3m, w4;
+  constexpr bool BATCH = qc_stage_batched(N);
+  if constexpr (BATCH) {
+    // staged by whole rows, the first chunk's requests and the thread's weights ahead of the first LDS store (see
+    // qc_row_load): eight rows of <Z> jets and two cotangent rows per wave
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const bool live = lane < cnt;
+    const unsigned pc = live ? lane : cnt - 1;
+    constexpr int NRQ = NCH * N, CHQ = 8, CHU = 2;
+    const int NRU = (NCH == 6 && gen) ? 6 : 2;   // gen: one row per channel of ubar; else (ubar, rbar), either may be absent
+    auto request_q = [&](const int r0, float (&v)[CHQ]) {
+#pragma unroll
+      for (int j = 0; j < CHQ; ++j) {
+        const int r = r0 + j * nw, rc = r < NRQ ? r : 0;
+        v[j] = qc_row_load(qjets + ((int64_t)rc * B + base), pc);
+      }
+    };
+    auto put_q = [&](const int r0, const float (&v)[CHQ]) {
+#pragma unroll
+      for (int j = 0; j < CHQ; ++j) {
+        const int r = r0 + j * nw;
+        if (r < NRQ) sQ[r][lane] = live ? v[j] : 0.f;
+      }
+    };
+    auto source_u = [&](const int r) -> const float* {   // nullptr: the row stages zeros
+      if (r >= NRU) return nullptr;
+      if (NCH == 6 && gen) return ubar + ((int64_t)r * B + base);
+      const float* src = r == 0 ? ubar : rbar;
+      return src != nullptr ? src + base : nullptr;
+    };
+    auto request_u = [&](const int r0, float (&v)[CHU]) {
+#pragma unroll
+      for (int j = 0; j < CHU; ++j) {
+        const float* src = source_u(r0 + j * nw);
+        v[j] = qc_row_load(src != nullptr ? src : qjets + base, pc);
+      }
+    };
+    auto put_u = [&](const int r0, const float (&v)[CHU]) {
+#pragma unroll
+      for (int j = 0; j < CHU; ++j) {
+        const int r = r0 + j * nw;
+        if (r < NRU) sU[r][lane] = (live && source_u(r) != nullptr) ? v[j] : 0.f;
+      }
+    };
+    // (ubar, rbar) of a six-channel tile keep their loop, one trip of half the block at 128 threads or more: with these two
+    // rows in the batch the merged kernel of n = 4 holds 71 vector registers against 63 and loses its eighth wave
+    const bool batch_u = NCH == 1 || gen;
+    float stq[CHQ], stu[CHU];
+    request_q(wave, stq);
+    if (batch_u) request_u(wave, stu);
+    grp = threadIdx.x / HB, m = threadIdx.x % HB;
+    const int mc = m < L.H ? m : L.H - 1;      // (a thread without a hidden unit reads the last one's)
+#pragma unroll
+    for (int i = 0; i < N; ++i) w3[i] = prm[L.oW3 + mc * N + i];
+    b3m = prm[L.ob3 + mc], w4 = prm[L.oW4 + mc];
+    qc_pin(stq);
+    if (batch_u) qc_pin(stu);
+    qc_pin(w3);
+    qc_pin(b3m);
+    qc_pin(w4);
+    put_q(wave, stq);
+    if (batch_u) put_u(wave, stu);
+    for (int r0 = wave + CHQ * nw; r0 < NRQ; r0 += CHQ * nw) {
+      request_q(r0, stq);
+      qc_pin(stq);
+      put_q(r0, stq);
+    }
+    if (batch_u) {
+      for (int r0 = wave + CHU * nw; r0 < NRU; r0 += CHU * nw) {
+        request_u(r0, stu);
+        qc_pin(stu);
+        put_u(r0, stu);
+      }
+    } else {
+      for (int i = threadIdx.x; i < 128; i += blockDim.x) {
+        const int k = i >> 6, pp = i & 63;
+        const float* src = k == 0 ? ubar : rbar;
+        sU[k][pp] = (pp < cnt && src != nullptr) ? src[base + pp] : 0.f;
+      }
     }
   } else {
-    for (int i = threadIdx.x; i < 128; i += blockDim.x) {
-      const int k = i >> 6, pp = i & 63;
-      const float* src = k == 0 ? ubar : rbar;
-      sU[k][pp] = (pp < cnt && src != nullptr) ? src[base + pp] : 0.f;
+    for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
+      const int f = i >> 6, pp = i & 63;
+      sQ[f][pp] = pp < cnt ? qjets[(int64_t)f * B + base + pp] : 0.f;
+    }
+    if (NCH == 6 && gen) {
+      for (int i = threadIdx.x; i < 6 * 64; i += blockDim.x) {
+        const int k = i >> 6, pp = i & 63;
+        sU[k][pp] = pp < cnt ? ubar[(int64_t)k * B + base + pp] : 0.f;
+      }
+    } else {
+      for (int i = threadIdx.x; i < 128; i += blockDim.x) {
+        const int k = i >> 6, pp = i & 63;
+        const float* src = k == 0 ? ubar : rbar;
+        sU[k][pp] = (pp < cnt && src != nullptr) ? src[base + pp] : 0.f;
+      }
     }
   }
   __syncthreads();
-  const int grp = threadIdx.x / HB, m = threadIdx.x % HB;   // threads past HB * PS (block rounded up to waves) idle
+  if constexpr (!BATCH) grp = threadIdx.x / HB, m = threadIdx.x % HB;
   const int per = (64 + PS - 1) / PS;
   const int p0 = grp * per, p1 = (p0 + per) < cnt ? (p0 + per) : cnt;
   float gW3[N], gb3 = 0.f, gW4 = 0.f;
 #pragma unroll
   for (int i = 0; i < N; ++i) gW3[i] = 0.f;
   if (grp < PS && m < L.H) {
-    float w3[N];
+    if constexpr (!BATCH) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) w3[i] = prm[L.oW3 + m * N + i];
-    const float b3m = prm[L.ob3 + m], w4 = prm[L.oW4 + m];
+      for (int i = 0; i < N; ++i) w3[i] = prm[L.oW3 + m * N + i];
+      b3m = prm[L.ob3 + m], w4 = prm[L.oW4 + m];
+    }
     for (int pp = p0; pp < p1; ++pp) {
       float g[NCH];
 #pragma unroll
@@ -1012,11 +1257,15 @@ __device__ __forceinline__ void k_post_wg_body(const int64_t bid, const float* _
   float* row = part + (row0 + bid) * part_stride;
   if (grp == 0 && m < L.H) {
     float tot[N + 2];
+    if constexpr (BATCH) {
+      qc_group_sums<N + 2>(s_acc, PS, HB, m, tot);
+    } else {
 #pragma unroll
-    for (int k = 0; k < N + 2; ++k) {
-      float sum = 0.f;
-      for (int g2 = 0; g2 < PS; ++g2) sum += s_acc[((size_t)g2 * (N + 2) + k) * HB + m];
-      tot[k] = sum;
+      for (int k = 0; k < N + 2; ++k) {
+        float sum = 0.f;
+        for (int g2 = 0; g2 < PS; ++g2) sum += s_acc[((size_t)g2 * (N + 2) + k) * HB + m];
+        tot[k] = sum;
+      }
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) row[L.oW3 + m * N + i] = tot[i];
