@@ -662,6 +662,74 @@ int qc_balance_adam_step(float* flat_dev, int NP_B, float* params_dev, float* m_
 int qc_fused_pinn_balanced_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_balance* bal,
                                 int phases, void* stream);
 
+/* ---- causal training (Wang, Sankaran, Perdikaris 2022): the tabulated step on a time-dependent problem, with the
+ * residual of a late time slab held back until the earlier slabs are fitted.  The residual rows of the dataset are sorted
+ * by t and cut into M = n_slabs slabs of equal width in t; slab_lo_dev[M + 1] (int64, device) holds the first row of each
+ * slab and the row count behind the last.  Every 64-point tile of the residual batch holds points of ONE slab: the tile of
+ * global point index g is tau = g / 64 and its slab is tau mod M.  With L_i the mean squared residual of the batch's
+ * points of slab i, the step minimises
+ *   w_res L_r^c + w_bc L_bc + w_ic L_ic,   L_r^c = (1/M) sum_i W_i L_i,   W_i = exp(-eps sum_{k<i} L_k),   W_0 = 1,
+ * the W_i taken as constants when differentiating.  Nothing in the stages changes: each writes one partial row per tile
+ * and the reverse pass is linear in the per-point cotangent, so the causal gradient is the ordinary partial rows summed
+ * with one scalar per residual row, known when the row fold runs.  A single-block launch ahead of the fold forms the L_i
+ * from the L_r column of the residual rows (L_i = M * the sum of the column over the rows of slab i; lane l of the wave
+ * that owns the slab adds the slab's rows l, l + 64, ... in ascending order in double, the 64 lane sums are added by a
+ * butterfly over lane distances 32, 16, .. 1; the cumulative sums run over the slabs in ascending order, in double; W_i is
+ * the double exponential rounded to fp32), and the fold scales residual row r by W[(r + off_res / 64) mod M] as it loads
+ * it, value rows by nothing, in the summation order of the plain fold.  The folded L_r column is L_r^c, which the
+ * unchanged optimiser launch weighs with w_res; loss_parts[0] and the history see it.  eps = 0 gives W = 1 exactly and
+ * the data step bit for bit.
+ * state_dev: the record of 4 + 2 M 4-byte words {float eps; int32 n_raised; int32 n_steps; int32 hist_base; float W[M];
+ * float L[M]}, seeded by the init call below.  Every causal fold reads eps, writes the W and L it used, stores the row
+ * [eps, W[M], L[M]] to row n_steps - hist_base of hist_dev ([hist_cap][1 + 2 M], optional) when that row lies in the buffer,
+ * adds 1 to n_steps and anneals eps for the NEXT fold: if W[M - 1] (the smallest weight, as L >= 0) exceeds delta (compared
+ * in fp32) and eps < eps_max then eps = min(eps * eps_growth, eps_max) (formed in double, stored in fp32) and n_raised
+ * grows by 1. */
+#define QC_CAUSAL_MAX_SLABS 64
+#define QC_CAUSAL_STATE_WORDS(M) (4 + 2 * (M))
+typedef struct qc_step_causal {
+  int32_t n_slabs;                              /* M: 2 .. QC_CAUSAL_MAX_SLABS */
+  float eps0, eps_growth, eps_max, delta;       /* eps0 >= 0 (read by the init call only); the others finite and > 0 */
+  const int64_t* slab_lo_dev;                   /* [M + 1] row offsets of the slabs (QC_PHASE_SAMPLE and the gather only) */
+  void* state_dev;                              /* the record above, 4-byte aligned */
+  float* hist_dev; int32_t hist_cap;            /* [cap][1 + 2 M] or NULL/0 */
+} qc_step_causal;
+
+/* Seeds the record: eps = eps0, n_raised = n_steps = hist_base = 0, W = 1, L = 0.  QC_ERR_ARG: a NULL or misaligned
+ * state_dev, causal NULL or not valid (as the causal step refuses it). */
+int qc_causal_init(void* state_dev, const qc_step_causal* causal, void* stream);
+
+/* qc_sample_dataset with the residual rows stratified by slab: a residual point with global index g takes row
+ *   slab_lo[s] + ((word 0 * (slab_lo[s + 1] - slab_lo[s])) >> 32),   s = (g / 64) mod n_slabs,
+ * word 0 of the block qc_sample_dataset draws for it; IC and BC points draw as there, so the value batches are bit-identical.
+ * QC_ERR_ARG without a GPU: n_res not a multiple of 64 * n_slabs, off_res not a multiple of 64, n_slabs outside
+ * 2..QC_CAUSAL_MAX_SLABS, slab_lo_dev NULL, whatever qc_sample_dataset refuses.  An empty slab is NOT refused on the
+ * device: its points take the row at the slab's offset, and every row index is clamped into the residual segment, so a
+ * wrong table cannot read outside it (data.tabulated.CausalWeighting raises on an empty slab). */
+int qc_sample_dataset_slabs(float* X_res_dev, float* target_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev,
+                            float* target_val_dev, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                            const qc_step_data* data, int n_slabs, const int64_t* slab_lo_dev, uint64_t seed, uint64_t step,
+                            void* stream);
+
+/* The causal reduction of a partial-row matrix on its own: weights from column ncols - 3 of rows [0, rows_res), the
+ * weighted first level in place (part_dev is overwritten like the step's own matrix), the second level into
+ * flat_dev[ncols]; the tile offset is 0.  Two runs on equal inputs and records are bit-identical.  QC_ERR_ARG: a NULL
+ * buffer, ncols < 3, stride < ncols, rows outside [1, 2^31), rows_res outside [1, rows] or not a multiple of n_slabs,
+ * causal NULL or not valid. */
+int qc_causal_fold(float* part_dev, int64_t rows, int64_t rows_res, int64_t stride, int ncols, const qc_step_causal* causal,
+                   float* flat_dev, void* stream);
+
+/* qc_fused_pinn_data_step under causal weights: QC_PHASE_SAMPLE gathers with the slab rule above, and the causal fold
+ * stands in place of the plain row fold; every other launch, both forms (merged and two-stream) and all three circuit
+ * families are the data step's (in each family row r of the residual pipeline holds exactly points [64 r, 64 r + 64)).  A
+ * GRADS | UPDATE call has one launch more than the data step's.  Refused before any launch: desc->comm set:
+ * QC_ERR_UNSUPPORTED (the slab losses would need a reduction of their own); QC_ERR_ARG: causal NULL, n_slabs out of range,
+ * a NULL or misaligned state_dev, a non-finite or non-positive eps_growth, eps_max or delta, a negative or non-finite
+ * eps0, hist_cap < 0 or a NULL hist_dev with a positive cap, B_res not a positive multiple of 64 * n_slabs, sample_off_res
+ * not a multiple of 64, QC_PHASE_SAMPLE with slab_lo_dev NULL, whatever qc_fused_pinn_data_step refuses. */
+int qc_fused_pinn_causal_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_causal* causal, int phases,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -936,8 +936,9 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
 // so its instantiations are the analytic step's); nothing else in the step depends on the source.
 // `sys` (qc_fused_pinn_system_step, validated by its entry): K last-layer rows in the layout, the system post stage in
 // both pipelines, always the two-stream form; `tg` is then not read.
+// `cz` (qc_fused_pinn_causal_step, validated by its entry): the causal fold in place of the plain row fold.
 static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches& b, const QcSource& src, int phases,
-                      void* stream, const qc_step_system* sys = nullptr) {
+                      void* stream, const qc_step_system* sys = nullptr, const QcCausal* cz = nullptr) {
   if (!d->part_dev || !d->flat_dev || !src.holds(b)) return QC_ERR_ARG;
   if (!sys && ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem))) return QC_ERR_ARG;
   int rc = check_step_desc(d, false, nullptr);
@@ -992,7 +993,8 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   if (phases & QC_PHASE_GRADS) {
     // the step owns its partial-row matrix, so the reduction folds it in place (two levels, fixed order);
     // with the update phase in the same call the second level rides in the optimiser launch
-    const int RS = qc_opt_fold_rows(d->part_dev, rows, d->part_stride, L.NP + 3, st);
+    const int RS = cz ? qc_opt_causal_fold(d->part_dev, rows, rows_res, d->part_stride, L.NP + 3, *cz, st)
+                      : qc_opt_fold_rows(d->part_dev, rows, d->part_stride, L.NP + 3, st);
     if ((phases & QC_PHASE_UPDATE) && !d->comm) {
       if (!d->m_dev || !d->v_dev || !d->opt_state_dev) return QC_ERR_ARG;
       QcOptHyper h;
@@ -1073,6 +1075,73 @@ int qc_fused_pinn_system_step(const qc_step_desc* d, const qc_step_system* sys, 
   if (d->H >= 1 && d->n >= 1 && d->n_theta >= 0 && d->part_stride < qc_layout(d->H, d->n, d->n_theta, sys->K).NP + 3)
     return QC_ERR_ARG;
   return fused_step(d, QcTarget{}, b, src, phases, stream, sys);
+}
+
+// ---- causal weighting of the residual slabs
+static_assert(QC_CAUSAL_SLABS == QC_CAUSAL_MAX_SLABS && QC_CAUSAL_STATE_WORDS(1) == QC_CAUSAL_HEAD + 2, "causal record");
+// THE validity rule of a causal record: slab count in range, an aligned state record, eps0 >= 0, growth, eps_max and delta
+// finite and positive, a history buffer behind a positive capacity
+static bool causal_ok(const qc_step_causal* c) {
+  if (!c || c->n_slabs < 2 || c->n_slabs > QC_CAUSAL_MAX_SLABS || !c->state_dev || ((uintptr_t)c->state_dev & 3)) return false;
+  if (!isfinite(c->eps0) || c->eps0 < 0.f || !pos_finite(c->eps_growth) || !pos_finite(c->eps_max) || !pos_finite(c->delta)) return false;
+  return c->hist_cap >= 0 && (c->hist_cap == 0 || c->hist_dev);
+}
+static QcCausal to_causal(const qc_step_causal* c, int64_t tile_off) {
+  QcCausal q;
+  q.M = c->n_slabs;
+  q.tile_off = (int)(tile_off % c->n_slabs);
+  q.growth = c->eps_growth; q.eps_max = c->eps_max; q.delta = c->delta;
+  q.rec = (float*)c->state_dev;
+  const bool hist = c->hist_dev && c->hist_cap > 0;
+  q.hist = hist ? c->hist_dev : nullptr;
+  q.hist_cap = hist ? c->hist_cap : 0;
+  return q;
+}
+
+int qc_causal_init(void* state_dev, const qc_step_causal* causal, void* stream) {
+  if (!state_dev || ((uintptr_t)state_dev & 3) || !causal) return QC_ERR_ARG;
+  qc_step_causal c = *causal;   // the rule asks for a record: the one being seeded serves
+  c.state_dev = state_dev;
+  if (!causal_ok(&c)) return QC_ERR_ARG;
+  qc_opt_causal_init((float*)state_dev, causal->n_slabs, causal->eps0, (hipStream_t)stream);
+  return after_launch();
+}
+
+int qc_sample_dataset_slabs(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
+                            int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, const qc_step_data* t, int n_slabs,
+                            const int64_t* slab_lo, uint64_t seed, uint64_t step, void* stream) {
+  if (!t) return QC_ERR_ARG;
+  QcSource s = make_source(t, nullptr, nullptr, nullptr);
+  s.kind = QC_SOURCE_SLABS;
+  s.slab_lo = slab_lo;
+  s.n_slabs = n_slabs;
+  return fill_batches({X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, seed, step}, s, stream);
+}
+
+int qc_causal_fold(float* part, int64_t rows, int64_t rows_res, int64_t stride, int ncols, const qc_step_causal* causal,
+                   float* flat, void* stream) {
+  if (!part || !flat || ncols < 3 || stride < ncols || rows < 1 || rows >= ((int64_t)1 << 31) || !causal_ok(causal)) return QC_ERR_ARG;
+  if (rows_res < 1 || rows_res > rows || rows_res % causal->n_slabs != 0) return QC_ERR_ARG;
+  const int RS = qc_opt_causal_fold(part, rows, rows_res, stride, ncols, to_causal(causal, 0), (hipStream_t)stream);
+  int rc = after_launch();
+  if (rc) return rc;
+  return qc_reduce_rows(part, RS, stride, ncols, flat, stream);
+}
+
+int qc_fused_pinn_causal_step(const qc_step_desc* d, const qc_step_data* t, const qc_step_causal* causal, int phases,
+                              void* stream) {
+  if (!d || !t || !causal_ok(causal)) return QC_ERR_ARG;
+  if (d->comm) return QC_ERR_UNSUPPORTED;   // the slab losses of the ranks would need a reduction of their own
+  if (d->B_res <= 0 || d->B_res % (64 * (int64_t)causal->n_slabs) != 0 || d->sample_off_res < 0 || d->sample_off_res % 64 != 0)
+    return QC_ERR_ARG;
+  if (d->part_rows_cap >= ((int64_t)1 << 31)) return QC_ERR_ARG;
+  QcSource s = make_source(t, nullptr, nullptr, nullptr, d->sample_bc_face_points);
+  s.kind = QC_SOURCE_SLABS;
+  s.slab_lo = causal->slab_lo_dev;
+  s.n_slabs = causal->n_slabs;
+  const QcCausal cz = to_causal(causal, d->sample_off_res / 64);
+  return fused_step(d, QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u), step_batches(d, t), s, phases, stream,
+                    nullptr, &cz);
 }
 
 // Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pipe_forward, then

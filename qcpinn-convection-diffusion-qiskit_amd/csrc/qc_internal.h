@@ -145,7 +145,10 @@ struct QcSys {
 // drawn from the integer CDF of qc_adapt_build (cdf over cdf_rows rows, coarse table behind it).  With `table` (a
 // qc_step_coef was given) a residual point also copies its operator row, ds_coef[idx][QC_COEF_N] -> coef_res.  The
 // sampler's launchers and everything above them pass this one value; qc_sample.hip maps it to a kernel.
-enum QcSourceKind { QC_SOURCE_DRAW = 0, QC_SOURCE_ROWS, QC_SOURCE_CDF };
+// QC_SOURCE_SLABS (the causal step): uniform rows with the residual row drawn inside the time slab of the point's tile, slab
+// (g / 64) mod n_slabs of the table slab_lo[n_slabs + 1] of row offsets (the residual segment sorted by t).
+enum QcSourceKind { QC_SOURCE_DRAW = 0, QC_SOURCE_ROWS, QC_SOURCE_CDF, QC_SOURCE_SLABS };
+constexpr int QC_CAUSAL_SLABS = 64;      // == QC_CAUSAL_MAX_SLABS of the public header
 constexpr int64_t QC_FACE_RANDOM = -1;   // == QC_BC_RANDOM_FACE of the public header: the smallest face_pts
 struct QcSource {
   QcSourceKind kind = QC_SOURCE_DRAW;
@@ -159,6 +162,8 @@ struct QcSource {
   // target width of a system's dataset (uniform rows only): 0, one float per row; else the rows of the target tables are
   // [w_res] / [w_val] floats, written batch-minor, and the residual table (and the batch's buffer) may be absent
   int w_res = 0, w_val = 0;
+  const int64_t* slab_lo = nullptr;   // QC_SOURCE_SLABS
+  int n_slabs = 0;
 
   // THE validity rule, in two steps.  holds(): what a step asks of batches that are already filled (a call without
   // QC_PHASE_SAMPLE asks no more): a known boundary rule; of dataset kinds a split of the value batch, a target buffer
@@ -178,6 +183,10 @@ struct QcSource {
     if ((b.n_res > 0 && !b.X_res) || (b.n_ic + b.n_bc > 0 && !b.X_val)) return false;
     if (kind == QC_SOURCE_DRAW) return true;
     if (table && b.n_res > 0 && (!coef_res || !ds_coef)) return false;
+    // slabs: a table, a slab count in range, whole tiles of one slab each and as many tiles of every slab
+    if (kind == QC_SOURCE_SLABS && (!slab_lo || n_slabs < 2 || n_slabs > QC_CAUSAL_SLABS || table || w_res > 0 || w_val > 0 ||
+                                    b.n_res % (64 * (int64_t)n_slabs) != 0 || b.off_res % 64 != 0))
+      return false;
     if (w_res > 0 && !res.tg) return QcDsSeg{res.X, res.X, res.n}.serves(b.n_res) && ic.serves(b.n_ic) && bc.serves(b.n_bc);
     return res.serves(b.n_res) && ic.serves(b.n_ic) && bc.serves(b.n_bc);
   }
@@ -326,6 +335,19 @@ int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState*
                 float* hist, int hist_cap, const qc_program* pg, int theta_off, QcTrig* trig, hipStream_t,
                 const QcBal* bal = nullptr);
 int qc_opt_prep_trig(const qc_program* pg, const float* theta, QcTrig* trig, hipStream_t);
+// Causal weighting (the causal step).  rec: the device record {float eps; int n_raised, n_steps, hist_base; float W[M], L[M]}
+// (== the layout documented at qc_step_causal in the public header); tile_off: the global tile index of row 0, mod M.
+constexpr int QC_CAUSAL_HEAD = 4;
+struct QcCausal {
+  int M, tile_off;
+  float growth, eps_max, delta;
+  float* rec;
+  float* hist;
+  int hist_cap;
+};
+int qc_opt_causal_init(float* rec, int M, float eps0, hipStream_t);
+// weights from column ncols - 3 of rows [0, rows_res), then qc_opt_fold_rows with residual row r scaled by its slab's weight
+int qc_opt_causal_fold(float* part, int64_t rows, int64_t rows_res, int64_t stride, int ncols, const QcCausal& cz, hipStream_t);
 // qc_lbfgs.hip: floats of a workspace; zero it and write its record; make the next call a first evaluation; one call
 size_t qc_lbfgs_words(int NP, int m);
 int qc_lbfgs_init_launch(void* ws, int NP, int m, hipStream_t);

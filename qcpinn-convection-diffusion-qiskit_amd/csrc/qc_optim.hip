@@ -185,9 +185,22 @@ __global__ void __launch_bounds__(1024) k_adam(QcAdamArgs a) {
 // rs + 2 RS, ... of column block cb into row rs (only that block ever touches row rs of those columns).
 // The RS = gridDim.y surviving rows are added, in order, by k_adam_fold (same call) or k_reduce_rows.
 // 1 700 rows become ~7 dependent loads per wave on 384 blocks instead of ~27 on 12.
+// CW = (QcCausalRows) (the causal step): residual row r < rows_res is scaled by the weight of its slab, W[(r + tile_off) mod M],
+// as it is loaded; value rows are not scaled; the order of the sums is the plain fold's.  (A trailing pack, as k_adam_fast
+// takes its balancer: the plain instantiation carries no argument for it and keeps its code.)
+struct QcCausalRows {
+  const float* W;   // [M], written by k_causal_weights ahead of this launch
+  int rows_res, M, tile_off;
+};
+__device__ __forceinline__ float qc_causal_w(const int64_t r, const QcCausalRows& c) {
+  return r < c.rows_res ? c.W[(uint32_t)((int)r + c.tile_off) % (uint32_t)c.M] : 1.f;
+}
 constexpr int QC_RED_WAVES = 8;
+template <class... CW>
 __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restrict__ part, int64_t rows, int64_t stride,
-                                                                 int ncols) {
+                                                                 int ncols, CW... cw) {
+  static_assert(sizeof...(CW) == 0 || (sizeof...(CW) == 1 && (std::is_same_v<CW, QcCausalRows> && ...)), "() or (QcCausalRows)");
+  constexpr bool CAUSAL = sizeof...(CW) == 1;
   __shared__ float s[QC_RED_WAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = blockIdx.x * 64 + lane;
@@ -203,6 +216,7 @@ __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restri
     for (int k = 0; k < 8; ++k) {
       const int64_t r = r0 + k * hop;
       v[k] = r < rows ? part[r * stride + col] : 0.f;
+      if constexpr (CAUSAL) v[k] *= qc_causal_w(r, cw...);
     }
 #pragma unroll
     for (int k = 0; k < 8; k += 2) {
@@ -210,8 +224,13 @@ __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restri
       a1 += v[k + 1];
     }
     for (int64_t r = r0 + 8 * hop; r < rows; r += 2 * hop) {
-      a0 += part[r * stride + col];
-      if (r + hop < rows) a1 += part[(r + hop) * stride + col];
+      if constexpr (CAUSAL) {
+        a0 += part[r * stride + col] * qc_causal_w(r, cw...);
+        if (r + hop < rows) a1 += part[(r + hop) * stride + col] * qc_causal_w(r + hop, cw...);
+      } else {
+        a0 += part[r * stride + col];
+        if (r + hop < rows) a1 += part[(r + hop) * stride + col];
+      }
     }
   }
   s[wave][lane] = a0 + a1;
@@ -223,6 +242,9 @@ __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restri
     part[(int64_t)rs * stride + col] = t;
   }
 }
+// implicit instantiations are emitted in order of first use: the plain fold is named here so that it keeps its place in the
+// code object, ahead of the optimiser kernels
+constexpr auto k_fold_rows_plain = k_fold_rows<>;
 
 // The optimiser update with everything it reads fetched in ONE round trip (state record, gradient or the
 // RS folded rows of it, moments, parameters), for NP + 3 <= 3 * 1024: a single-block kernel is a chain of
@@ -424,7 +446,7 @@ int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState*
 // In-place first level over the step's own partial-row matrix; returns the number of surviving rows.
 int qc_opt_fold_rows(float* part, int64_t rows, int64_t stride, int ncols, hipStream_t st) {
   const int RS = (int)(rows < 32 ? rows : 32);
-  hipLaunchKernelGGL(k_fold_rows, dim3(qc_ceil_div(ncols, 64), RS), dim3(64 * QC_RED_WAVES), 0, st, part, rows, stride, ncols);
+  hipLaunchKernelGGL(k_fold_rows_plain, dim3(qc_ceil_div(ncols, 64), RS), dim3(64 * QC_RED_WAVES), 0, st, part, rows, stride, ncols);
   return RS;
 }
 
@@ -468,4 +490,81 @@ static void adam_bal_launch(const QcAdamArgs& a, bool fold, const float* part, i
   if (!adam_fast_ok(a.NP)) hipLaunchKernelGGL(k_adam_bal, dim3(1), dim3(1024), 0, st, a, bal);
   else if (fold) hipLaunchKernelGGL((k_adam_fast<true, QcBal>), dim3(1), dim3(1024), lds, st, a, part, stride, RS, bal);
   else hipLaunchKernelGGL((k_adam_fast<false, QcBal>), dim3(1), dim3(1024), lds, st, a, (const float*)nullptr, (int64_t)0, 0, bal);
+}
+
+// ------------------------------------------------------------------ causal weighting of the residual rows (the causal step)
+// One launch ahead of the weighted fold, kept apart from it: every fold block would otherwise redo the M slab sums.
+namespace {
+
+// One block.  Slab i owns the residual rows r with (r + tile_off) mod M = i.  Wave i mod 16 sums its L_r entries: lane l
+// adds the slab's rows l, l + 64, ... (ascending) in double, then the 64 lane sums meet in a butterfly over lane distances
+// 32, 16, .. 1 (every lane ends with the same bits); L_i = M * that sum.  Thread i < M then adds L_0 .. L_{i-1} in ascending
+// order (double) and forms W_i = exp(-eps * sum) in double, rounded to float.  Thread M - 1 holds the smallest weight and
+// anneals eps for the next launch.  Everything of the record that is read is read ahead of the barrier, written behind it.
+__global__ void __launch_bounds__(1024) k_causal_weights(const float* __restrict__ part, int64_t stride, int col, int rows_res,
+                                                         QcCausal c) {
+  __shared__ double s_L[QC_CAUSAL_SLABS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, M = c.M;
+  int* irec = reinterpret_cast<int*>(c.rec);
+  const double eps = (double)c.rec[0];
+  const int n_raised = irec[1], n_steps = irec[2], hist_base = irec[3];
+  for (int s = wave; s < M; s += 16) {
+    const int first = (s - c.tile_off + M) % M;   // tile_off in [0, M)
+    double acc = 0.0;
+    for (int r = first + lane * M; r < rows_res; r += 64 * M) acc += (double)part[(int64_t)r * stride + col];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) s_L[s] = acc * (double)M;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < M) {
+    const int i = threadIdx.x;
+    double cum = 0.0;
+    for (int k = 0; k < i; ++k) cum += s_L[k];
+    const float W = (float)exp(-eps * cum);
+    const float Li = (float)s_L[i];
+    c.rec[QC_CAUSAL_HEAD + i] = W;
+    c.rec[QC_CAUSAL_HEAD + M + i] = Li;
+    const int hi = n_steps - hist_base;
+    float* row = (c.hist != nullptr && hi >= 0 && hi < c.hist_cap) ? c.hist + (int64_t)hi * (1 + 2 * M) : nullptr;
+    if (row != nullptr) {
+      row[1 + i] = W;
+      row[1 + M + i] = Li;
+    }
+    if (i == M - 1) {
+      if (row != nullptr) row[0] = (float)eps;
+      irec[2] = n_steps + 1;
+      if (W > c.delta && (float)eps < c.eps_max) {
+        c.rec[0] = (float)fmin(eps * (double)c.growth, (double)c.eps_max);
+        irec[1] = n_raised + 1;
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(2 * QC_CAUSAL_SLABS) k_causal_init(float* __restrict__ rec, int M, float eps0) {
+  const int i = threadIdx.x;
+  if (i < 2 * M) rec[QC_CAUSAL_HEAD + i] = i < M ? 1.f : 0.f;
+  if (i == 0) {
+    int* irec = reinterpret_cast<int*>(rec);
+    rec[0] = eps0;
+    irec[1] = irec[2] = irec[3] = 0;
+  }
+}
+
+}  // namespace
+
+int qc_opt_causal_init(float* rec, int M, float eps0, hipStream_t st) {
+  hipLaunchKernelGGL(k_causal_init, dim3(1), dim3(2 * QC_CAUSAL_SLABS), 0, st, rec, M, eps0);
+  return QC_OK;
+}
+
+// In-place first level like qc_opt_fold_rows, under the weights of this call; returns the number of surviving rows.
+int qc_opt_causal_fold(float* part, int64_t rows, int64_t rows_res, int64_t stride, int ncols, const QcCausal& cz, hipStream_t st) {
+  hipLaunchKernelGGL(k_causal_weights, dim3(1), dim3(1024), 0, st, (const float*)part, stride, ncols - 3, (int)rows_res, cz);
+  const int RS = (int)(rows < 32 ? rows : 32);
+  const QcCausalRows cw = {cz.rec + QC_CAUSAL_HEAD, (int)rows_res, cz.M, cz.tile_off};
+  hipLaunchKernelGGL((k_fold_rows<QcCausalRows>), dim3(qc_ceil_div(ncols, 64), RS), dim3(64 * QC_RED_WAVES), 0, st, part, rows,
+                     stride, ncols, cw);
+  return RS;
 }

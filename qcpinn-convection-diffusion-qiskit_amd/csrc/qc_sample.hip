@@ -32,6 +32,12 @@ struct QcDsSegW {
   int64_t n;
   int w;
 };
+struct QcDsSegSlab {   // the slab rule's segment record: the residual one carries the slab count
+  const float* X;   // [n][3]
+  const float* tg;  // [n]
+  int64_t n;
+  int n_slabs;
+};
 template <class SEG = QcDsSeg>
 __device__ __forceinline__ QcSlotOf<SEG> qc_slot(int64_t i, float* X_res, float* tg_res, int64_t n_res, int64_t off_res, float* X_val,
                                                  float* tg_val, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
@@ -107,7 +113,11 @@ __device__ __forceinline__ auto qc_src(P*... src) {   // pointer K of the pack, 
   if constexpr (K < sizeof...(P)) return std::get<K>(std::tie(src...));
   else return nullptr;
 }
-enum QcRows { QC_ROWS_UNIFORM = 0, QC_ROWS_CDF_LDS, QC_ROWS_CDF_GLOBAL };
+// The slab rule (the causal step; SEG = QcDsSegSlab, `src` = (slab_lo)): a residual point with global index g draws inside
+// slab (g / 64) mod n_slabs of the residual segment, rows [slab_lo[s], slab_lo[s + 1]), with the word the uniform gather
+// draws for it; IC and BC points draw as before.  An empty slab gives the row at its offset, and the index is clamped into
+// the segment, so no table reads outside it.
+enum QcRows { QC_ROWS_UNIFORM = 0, QC_ROWS_CDF_LDS, QC_ROWS_CDF_GLOBAL, QC_ROWS_SLABS };
 constexpr int QC_ADAPT_LDS_MAX = 4096;   // coarse entries staged in LDS (32 KB): datasets up to 4 Mi residual rows
 
 // SEG = QcDsSegW: the targets of a row are ds.w floats, written batch-minor (tg[k][batch]); a segment without a table
@@ -118,10 +128,19 @@ __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float
                                                 int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, SEG d_res,
                                                 SEG d_ic, SEG d_bc, uint64_t seed, uint64_t step,
                                                 P* __restrict__... src) {
-  constexpr bool CDF = ROWS != QC_ROWS_UNIFORM, LDS = ROWS == QC_ROWS_CDF_LDS, TABLE = sizeof...(P) >= 2;
+  constexpr bool SLABS = ROWS == QC_ROWS_SLABS;
+  constexpr bool CDF = ROWS == QC_ROWS_CDF_LDS || ROWS == QC_ROWS_CDF_GLOBAL, LDS = ROWS == QC_ROWS_CDF_LDS;
+  constexpr bool TABLE = !SLABS && sizeof...(P) >= 2;
   constexpr bool WIDE = std::is_same<SEG, QcDsSegW>::value;
-  float* coef_res = qc_src<0>(src...);
-  const float* ds_coef = qc_src<1>(src...);
+  float* coef_res = nullptr;
+  const float* ds_coef = nullptr;
+  [[maybe_unused]] const int64_t* slab_lo = nullptr;
+  if constexpr (SLABS) {
+    slab_lo = qc_src<0>(src...);
+  } else {
+    coef_res = qc_src<0>(src...);
+    ds_coef = qc_src<1>(src...);
+  }
   const uint64_t *cdf = qc_src<2>(src...), *coarse = qc_src<3>(src...);
   __shared__ uint64_t sh[LDS ? QC_ADAPT_LDS_MAX : 1];
   const int64_t N = d_res.n;
@@ -138,6 +157,13 @@ __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float
     const U4 ctr = {(uint32_t)s.gidx, (uint32_t)(s.gidx >> 32), (uint32_t)step, (uint32_t)(step >> 32)};
     const U4 r = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
     idx = qc_cdf_search(__umul64hi(((uint64_t)r.x << 32) | r.y, cdf[N - 1]), cdf, LDS ? sh : coarse, N, nb);
+  } else if (SLABS && s.seg == 0) {
+    if constexpr (SLABS) {
+      const int sl = (int)((uint64_t)(s.gidx >> 6) % (uint32_t)s.ds.n_slabs);
+      const int64_t lo = slab_lo[sl], w = slab_lo[sl + 1] - lo;
+      idx = lo + (w > 0 ? qc_draw_index(0, s.gidx, w, seed, step) : 0);
+      idx = idx < 0 ? 0 : (idx < N ? idx : N - 1);
+    }
   } else {
     idx = qc_draw_index(s.seg, s.gidx, s.ds.n, seed, step);   // < ds.n: the product's high word
   }
@@ -160,7 +186,7 @@ __global__ void __launch_bounds__(256) k_gather(float* __restrict__ X_res, float
 
 // Implicit instantiations are emitted in order of first use, and where identical kernels lie in the object has been
 // measured (DESIGN section 6 "Batch sources"): the two uniform gathers are named here, ahead of qc_sample_launch, so the
-// order stays uniform, uniform with a table, k_sample<true>, k_sample<false>, CDF from LDS, CDF from global memory.
+// order stays uniform, uniform with a table, k_sample<true>, k_sample<false>, CDF from LDS, CDF from global memory, the slab rule.
 constexpr auto k_gather_rows = k_gather<QC_ROWS_UNIFORM, QcDsSeg>;
 constexpr auto k_gather_rows_coef = k_gather<QC_ROWS_UNIFORM, QcDsSeg, float, const float>;
 template <QcRows ROWS>
@@ -194,14 +220,20 @@ int qc_gather_launch(const QcBatches& b, const QcSource& s, hipStream_t st) {
   const bool table = s.table && b.n_res > 0;   // no residual rows: none to copy an operator row for
   float* coef_res = table ? s.coef_res : nullptr;
   const float* ds_coef = table ? s.ds_coef : nullptr;
-  if (s.kind != QC_SOURCE_CDF) {
+  if (s.kind == QC_SOURCE_ROWS) {
     if (table) launch(k_gather_rows_coef, coef_res, ds_coef);   // rows, targets and operator rows in one launch
     else launch(k_gather_rows);
-  } else if ((s.res.n + QC_ADAPT_ROWS - 1) / QC_ADAPT_ROWS <= QC_ADAPT_LDS_MAX) {
+  } else if (s.kind == QC_SOURCE_CDF && (s.res.n + QC_ADAPT_ROWS - 1) / QC_ADAPT_ROWS <= QC_ADAPT_LDS_MAX) {
     // measured faster than the search from global memory alone
     launch(k_gather_cdf<QC_ROWS_CDF_LDS>, coef_res, ds_coef, s.cdf, s.coarse);
-  } else {
+  } else if (s.kind == QC_SOURCE_CDF) {
     launch(k_gather_cdf<QC_ROWS_CDF_GLOBAL>, coef_res, ds_coef, s.cdf, s.coarse);
+  } else {
+    // the slab rule, first used here so that its kernel lies behind every other gather of the object
+    const QcDsSegSlab r = {s.res.X, s.res.tg, s.res.n, s.n_slabs}, i = {s.ic.X, s.ic.tg, s.ic.n, 0}, c = {s.bc.X, s.bc.tg, s.bc.n, 0};
+    hipLaunchKernelGGL((k_gather<QC_ROWS_SLABS, QcDsSegSlab, const int64_t>), dim3(qc_ceil_div(total, 256)), dim3(256), 0, st,
+                       b.X_res, b.tg_res, b.n_res, b.off_res, b.X_val, b.tg_val, b.n_ic, b.off_ic, b.n_bc, b.off_bc, r, i, c, b.seed,
+                       b.step, s.slab_lo);
   }
   return QC_OK;
 }

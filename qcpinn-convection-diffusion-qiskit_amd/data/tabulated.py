@@ -24,7 +24,7 @@ from __future__ import annotations
 import torch
 
 from .diffusion_dataset import box
-from ..hip.lib import QC_ADAPT_FLOOR_MAX, QC_EQMAX, QC_KMAX, QC_TERMS_MAX
+from ..hip.lib import QC_ADAPT_FLOOR_MAX, QC_CAUSAL_MAX_SLABS, QC_EQMAX, QC_KMAX, QC_TERMS_MAX
 
 MAX_ROWS = 2 ** 31 - 1      # the device gather forms (32-bit word * rows) >> 32
 COEF_COLUMNS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")     # column order of a coefficient row
@@ -153,6 +153,71 @@ class AdaptiveSampling:
 
     def __repr__(self):
         return f"AdaptiveSampling(power={self.power}, floor={self.floor}, every={self.every})"
+
+
+class CausalWeighting:
+    """Causal training of a time-dependent problem (Wang, Sankaran, Perdikaris 2022): the residual points are cut into
+    ``n_slabs`` time slabs of equal width and the residual loss becomes
+
+        L_r^c = (1/M) sum_i W_i L_i,      W_i = exp(-eps sum_{k<i} L_k),      W_0 = 1,
+
+    L_i the mean squared residual of the batch's points in slab i, the weights constants when differentiating: a late
+    slab counts only once the earlier ones are fitted (``qc_fused_pinn_causal_step``).  ``eps`` is the starting value;
+    after every step whose smallest weight W_{M-1} exceeds ``delta`` it is multiplied by ``growth`` up to ``eps_max``.
+    ``t_range`` = (t_lo, t_hi) of the slabs (default: the smallest and largest t of the residual points)."""
+
+    def __init__(self, n_slabs: int, eps: float = 1.0, growth: float = 10.0, eps_max: float = 100.0, delta: float = 0.99,
+                 t_range=None):
+        import math
+        if isinstance(n_slabs, bool) or not isinstance(n_slabs, int) or not 2 <= n_slabs <= QC_CAUSAL_MAX_SLABS:
+            raise ValueError(f"causal weighting: n_slabs must be an integer in 2..{QC_CAUSAL_MAX_SLABS}, got {n_slabs!r}")
+        eps, growth, eps_max, delta = float(eps), float(growth), float(eps_max), float(delta)
+        if not (math.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"causal weighting: eps must be a finite number >= 0, got {eps!r}")
+        for name, v in (("growth", growth), ("eps_max", eps_max), ("delta", delta)):
+            if not (math.isfinite(v) and v > 0.0):
+                raise ValueError(f"causal weighting: {name} must be a finite number > 0, got {v!r}")
+        if t_range is not None:
+            t_range = (float(t_range[0]), float(t_range[1]))
+            if not (math.isfinite(t_range[0]) and math.isfinite(t_range[1]) and t_range[0] < t_range[1]):
+                raise ValueError(f"causal weighting: t_range must be finite with t_lo < t_hi, got {t_range!r}")
+        self.n_slabs, self.eps, self.growth, self.eps_max, self.delta, self.t_range = n_slabs, eps, growth, eps_max, delta, t_range
+
+    def __repr__(self):
+        return (f"CausalWeighting(n_slabs={self.n_slabs}, eps={self.eps}, growth={self.growth}, eps_max={self.eps_max}, "
+                f"delta={self.delta}, t_range={self.t_range})")
+
+    def edges(self, t):
+        """The M + 1 float64 slab edges over ``t_range`` (default: the range of ``t``)."""
+        lo, hi = self.t_range if self.t_range is not None else (float(t.min()), float(t.max()))
+        if not lo < hi:
+            raise ValueError("causal weighting: the residual points span no time interval")
+        return torch.linspace(lo, hi, self.n_slabs + 1, dtype=torch.float64)
+
+    def stratify(self, dataset):
+        """(sorted, slab_lo): a copy of ``dataset`` whose residual segment is sorted by t (a stable sort: rows of equal t
+        keep their order) and the (M + 1,) int64 offsets of the slabs in it.  Slab i holds the rows with edge_i <= t <
+        edge_{i+1}; rows below the first edge join slab 0, rows at or above the last edge join slab M - 1.  ValueError on
+        an empty slab, on an empty residual segment and on a coefficient table."""
+        if dataset.coef_res is not None:
+            raise ValueError("causal weighting does not take a per-point coefficient table (dataset.coef_res)")
+        if dataset.X_res.shape[0] == 0:
+            raise ValueError("causal weighting needs residual points: the dataset's residual segment is empty")
+        t = dataset.X_res[:, 0].detach().cpu().double()
+        order = torch.sort(t, stable=True).indices
+        ts = t[order]
+        edges = self.edges(ts)
+        lo = torch.searchsorted(ts, edges[1:-1].contiguous(), right=False)      # first row with t >= inner edge
+        slab_lo = torch.cat([torch.zeros(1, dtype=torch.int64), lo.to(torch.int64),
+                             torch.tensor([ts.numel()], dtype=torch.int64)])
+        empty = (slab_lo[1:] - slab_lo[:-1] <= 0).nonzero().reshape(-1).tolist()
+        if empty:
+            raise ValueError(f"causal weighting: slab(s) {empty} of {self.n_slabs} hold no residual point")
+        order = order.to(dataset.X_res.device)
+        c = dict(zip(("c_t", "c_x", "c_y", "d_xx", "d_yy"), dataset.coeffs), c_u=dataset.c_u)
+        out = TabulatedProblem(dataset.X_res[order].clone(), dataset.r[order].clone(), dataset.X_ic, dataset.u_ic,
+                               dataset.X_bc, dataset.u_bc, **c)
+        return out, slab_lo
 
 
 def adaptive_cdf(score, power: int, floor: float):

@@ -925,3 +925,67 @@ class BalancedStep(InverseStep):
             self.desc.sample_step += 1          # a fresh counter block per step
         L.check(self.lib.qc_fused_pinn_balanced_step(C.byref(self.desc), C.byref(self.data), C.byref(self.bal), phases,
                                                      _stream(self.device)), "qc_fused_pinn_balanced_step")
+
+
+class CausalStep(FusedStep):
+    """One ``qc_fused_pinn_causal_step`` descriptor over fixed-size resident batches: the tabulated step (the engine's
+    problem must be ``QC_PROBLEM_TABULATED``, without coefficient mode) with the residual of time slab i weighted by
+    W_i = exp(-eps sum_{k<i} L_k).  ``B_res`` must be a multiple of ``64 * n_slabs``: tile r of the residual batch holds
+    points of slab r mod n_slabs, drawn from the dataset's residual segment sorted by t (``set_dataset`` with the sorted
+    segments, then ``set_slabs`` with the (M + 1,) int64 offsets of ``data.tabulated.CausalWeighting.stratify``).  Explicit
+    batches must be laid out the same way.  ``state`` is the device record {eps, n_raised, n_steps, hist_base, W[M], L[M]};
+    ``causal_hist`` [capacity, 1 + 2 M] receives (eps, W, L) of every step."""
+
+    def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, n_slabs: int, eps: float,
+                 growth: float, eps_max: float, delta: float, capacity: int = 0, counts=None):
+        M = int(n_slabs)
+        if not 2 <= M <= L.QC_CAUSAL_MAX_SLABS:
+            raise L.QcError(f"n_slabs must lie in 2..{L.QC_CAUSAL_MAX_SLABS}, got {M}")
+        if B_res <= 0 or B_res % (64 * M):
+            raise L.QcError(f"the causal step needs B_res a positive multiple of 64 * n_slabs = {64 * M}, got {B_res}")
+        if eng.problem != L.QC_PROBLEM_TABULATED or eng.coef_mode:
+            raise L.QcError("the causal step is the tabulated step without a coefficient table")
+        dev = eng.device
+        self.n_slabs, self.causal_cap = M, int(capacity)
+        self.state = torch.zeros(L.QC_CAUSAL_HEAD + 2 * M, dtype=torch.float32, device=dev)
+        self.causal_hist = torch.zeros(max(self.causal_cap, 1), 1 + 2 * M, dtype=torch.float32, device=dev)
+        self.slab_lo = None
+        self.causal = L.QcStepCausal(M, float(eps), float(growth), float(eps_max), float(delta), None, self.state.data_ptr(),
+                                     self.causal_hist.data_ptr() if self.causal_cap > 0 else None, self.causal_cap)
+        super().__init__(eng, B_res, n_ic, n_bc, opt, counts)
+        L.check(eng.lib.qc_causal_init(self.state.data_ptr(), C.byref(self.causal), _stream(dev)), "qc_causal_init")
+
+    def set_slabs(self, slab_lo) -> None:
+        """The (M + 1,) int64 row offsets of the slabs in the dataset's (sorted) residual segment; None removes them."""
+        if slab_lo is None:
+            self.slab_lo, self.causal.slab_lo_dev = None, None
+            return
+        t = torch.as_tensor(slab_lo, dtype=torch.int64).reshape(-1).to(self.eng.device).contiguous()
+        if t.numel() != self.n_slabs + 1:
+            raise L.QcError(f"slab_lo holds n_slabs + 1 = {self.n_slabs + 1} offsets, got {t.numel()}")
+        self.slab_lo, self.causal.slab_lo_dev = t, t.data_ptr()
+
+    def set_adaptive(self, power: int = 1, floor: float = 1.0) -> None:
+        raise L.QcError("the causal step draws its residual rows by slab: adaptive sampling is not supported")
+
+    def _bind(self) -> None:
+        name = "qc_fused_pinn_causal_step"
+        self._entry = name, getattr(self.eng.lib, name), (C.byref(self.desc), C.byref(self.data), C.byref(self.causal))
+
+    def set_hist_base(self, n_steps: int, hist_base: int) -> None:
+        """Rewrites the two counters of the record (a new history buffer starts at step ``hist_base``)."""
+        self.state[2:4] = torch.tensor([n_steps, hist_base], dtype=torch.int32).view(torch.float32).to(self.state.device)
+
+    def read_state(self) -> dict:
+        """The record as a dict (a host read): eps of the NEXT step, the counters, W and L of the last step."""
+        raw = self.state.cpu().numpy()
+        ints, M = raw.view(np.int32), self.n_slabs
+        return {"eps": float(raw[0]), "n_raised": int(ints[1]), "n_steps": int(ints[2]), "hist_base": int(ints[3]),
+                "W": raw[L.QC_CAUSAL_HEAD:L.QC_CAUSAL_HEAD + M].copy(), "L": raw[L.QC_CAUSAL_HEAD + M:L.QC_CAUSAL_HEAD + 2 * M].copy()}
+
+    def history(self, steps: Optional[int] = None) -> np.ndarray:
+        """Rows (eps, W[M], L[M]) of the first ``steps`` steps of the history buffer (default: all taken so far)."""
+        if steps is None:
+            rec = self.read_state()
+            steps = rec["n_steps"] - rec["hist_base"]
+        return self.causal_hist[: max(0, min(int(steps), self.causal_cap))].cpu().numpy()

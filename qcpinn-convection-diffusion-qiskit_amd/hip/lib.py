@@ -35,6 +35,7 @@ EXPORTS = (
     "qc_post_learn", "qc_fused_pinn_inverse_step",
     "qc_lbfgs_workspace_bytes", "qc_lbfgs_init", "qc_lbfgs_restart", "qc_lbfgs_step",
     "qc_post_balance", "qc_balance_adam_step", "qc_fused_pinn_balanced_step",
+    "qc_causal_init", "qc_sample_dataset_slabs", "qc_causal_fold", "qc_fused_pinn_causal_step",
 )
 
 
@@ -42,6 +43,8 @@ QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_
 QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc_fused_pinn_data_step only
 QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 (qc_step_coef)
 QC_BAL_TERMS = 3                # loss terms of a balancer: residual, BC, IC (qc_step_balance)
+QC_CAUSAL_MAX_SLABS = 64        # most time slabs of a causal record (qc_step_causal)
+QC_CAUSAL_HEAD = 4              # words {eps, n_raised, n_steps, hist_base} ahead of W[M], L[M] in a causal record
 QC_ADAPT_BLOCK = 1024           # rows per entry of the coarse table of an adaptive-sampling buffer (qc_adapt_bytes)
 QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
 QC_KMAX, QC_EQMAX, QC_TERMS_MAX = 4, 4, 32            # outputs, equations and terms of a system (qc_step_system)
@@ -127,6 +130,15 @@ class QcStepBalance(C.Structure):
     """qc_step_balance: scale of the three log-variances s_k = scale_k p_k (order residual, BC, IC) and the optional
     [cap][3] history of the effective weights w_k exp(-s_k) each step used."""
     _fields_ = [("scale", C.c_float * QC_BAL_TERMS), ("weight_hist_dev", C.c_void_p), ("weight_hist_cap", C.c_int)]
+
+
+class QcStepCausal(C.Structure):
+    """qc_step_causal: slab count, the annealing of eps (start, growth, cap, threshold on the smallest weight), the
+    [M + 1] int64 slab offsets of the sorted residual segment, the device record {eps, n_raised, n_steps, hist_base, W[M],
+    L[M]} and the optional [cap][1 + 2 M] history of (eps, W, L) per step."""
+    _fields_ = [("n_slabs", C.c_int32), ("eps0", C.c_float), ("eps_growth", C.c_float), ("eps_max", C.c_float),
+                ("delta", C.c_float), ("slab_lo_dev", C.c_void_p), ("state_dev", C.c_void_p), ("hist_dev", C.c_void_p),
+                ("hist_cap", C.c_int32)]
 
 
 class QcStepAdapt(C.Structure):
@@ -256,6 +268,11 @@ def load() -> C.CDLL:
     lib.qc_balance_adam_step.argtypes = [fp, i32, fp, fp, fp, vp, C.POINTER(QcOptHyper), C.POINTER(QcStepBalance), fp, i32, vp,
                                          i32, vp, vp]
     lib.qc_fused_pinn_balanced_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepBalance), i32, vp]
+    lib.qc_causal_init.argtypes = [vp, C.POINTER(QcStepCausal), vp]
+    lib.qc_sample_dataset_slabs.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, C.POINTER(QcStepData), i32, vp,
+                                            C.c_uint64, C.c_uint64, vp]
+    lib.qc_causal_fold.argtypes = [fp, i64, i64, i64, i32, C.POINTER(QcStepCausal), fp, vp]
+    lib.qc_fused_pinn_causal_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCausal), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

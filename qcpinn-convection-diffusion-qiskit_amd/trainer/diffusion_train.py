@@ -34,6 +34,10 @@ re-evaluated on all rows every ``every`` steps: on the device for a ``DVPDESolve
 ``balance=`` (keyword-only, an ``nn.loss_balance.AdaptiveMultiLoss``, with ``dataset=``) learns the three loss weights on
 the device (``qc_fused_pinn_balanced_step``, ``trainer.balanced_train``): ``DVPDESolver`` models only, not together with
 ``adaptive=`` or ``lbfgs=``.
+
+``causal=`` (keyword-only, a ``data.tabulated.CausalWeighting``, with ``dataset=``) weighs the residual of every time slab
+by how well the earlier slabs are fitted, on the device (``qc_fused_pinn_causal_step``, ``trainer.causal_train``):
+``DVPDESolver`` models only, not together with ``adaptive=``, ``lbfgs=`` or ``balance=``.
 """
 from __future__ import annotations
 
@@ -159,7 +163,7 @@ class FusedTrainer:
         self.n_bc = shard_count(nb, self.world, self.rank)
         self.bc_start = shard_slice(nb, self.world, self.rank).start
         self.opt = self._make_opt_state(capacity)
-        self.fs = self.eng.fused(self.B_res, self.n_ic, self.n_bc, self.opt, self.global_counts)
+        self.fs = self._make_step()
         if self.tabulated:
             (self.eng.problem, self.eng.c_u), self.eng.coeffs = before, None
         self.eng.coef_mode = False
@@ -193,6 +197,10 @@ class FusedTrainer:
         if self.world > 1 and os.environ.get("QC_DP_COLLECTIVE", "torch") == "rccl":
             self._comm = self._make_comm()
             self.fs.set_comm(self._comm)
+
+    def _make_step(self):
+        """The step descriptor over this trainer's batch sizes (the engine holds what the constructor configured)."""
+        return self.eng.fused(self.B_res, self.n_ic, self.n_bc, self.opt, self.global_counts)
 
     def _make_comm(self):
         """One library-owned RCCL communicator over the ranks of the default process group (the 128-byte id travels
@@ -561,7 +569,7 @@ def _train_generic(model, batch_size, dataset=None, adaptive=None):
 
 
 def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None,
-          adaptive=None, lbfgs=None, balance=None):
+          adaptive=None, lbfgs=None, balance=None, causal=None):
     """``batches`` (keyword-only, not in the reference): a per-iteration list of
     ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests; with a dataset each entry carries a
     fourth element, the targets ``(u_ic, u_bc, r_res)``.  ``dataset`` (keyword-only): a ``TabulatedProblem`` whose targets
@@ -571,7 +579,16 @@ def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *
     continue ``model.loss_history`` and the model ends at the last accepted point.  ``balance`` (keyword-only): an
     ``nn.loss_balance.AdaptiveMultiLoss`` over ("residual", "bc", "ic"); the three loss weights are then learned on the
     device (``trainer.balanced_train``; needs ``dataset``, ``DVPDESolver`` models only, not with ``adaptive`` or
-    ``lbfgs``), and the logged loss is the balanced objective.  ``update_lam`` stays unused."""
+    ``lbfgs``), and the logged loss is the balanced objective.  ``causal`` (keyword-only): a
+    ``data.tabulated.CausalWeighting``; the residual of a late time slab is then held back on the device until the earlier
+    slabs are fitted (``trainer.causal_train``; needs ``dataset`` and a batch size that is a multiple of 64 * n_slabs,
+    ``DVPDESolver`` models only, not with ``adaptive``, ``lbfgs`` or ``balance``); ``model.causal_history`` receives the
+    rows (eps, W, L) of the steps.  ``update_lam`` stays unused."""
+    if causal is not None:
+        from .causal_train import check_causal, train_causal
+        check_causal(model, dataset, causal, batch_size, adaptive, lbfgs, balance)
+        train_causal(model, batch_size, batches, dataset, causal)
+        return
     if balance is not None:
         from .balanced_train import check_balance, train_balanced
         check_balance(model, dataset, balance, adaptive, lbfgs)
