@@ -192,6 +192,16 @@ class Circuit:
         return self._amp_bwd(a, abar, nch) if self.amplitude else abar
 
 
+def _pde_record(operator, loss_weights, counts, problem: int, n_seg_a: int) -> "L.QcPde":
+    """A ``QcPde``: ``operator`` = its eight floats (D, vx, vy, c_t, c_x, c_y, d_xx, d_yy) as the caller states them, and the
+    loss scales of ``loss_weights`` = (residual, BC, IC) over ``counts`` = (residual, IC, BC) points: d loss / d err =
+    2 w / N per unit error, 1 / N for the logged means.  Value segment a is the IC points (the first ``n_seg_a``)."""
+    w_r, w_bc, w_ic = (float(w) for w in loss_weights)
+    n_res, n_ic, n_bc = counts
+    return L.QcPde(*operator, 2.0 * w_r / n_res, 1.0 / n_res, 2.0 * w_ic / n_ic, 2.0 * w_bc / n_bc, 1.0 / n_ic, 1.0 / n_bc,
+                   problem, n_seg_a)
+
+
 class SolverEngine:
     """Kernel pipelines of DVPDESolver on one GPU: value forward, residual forward, their reverse
     passes (autograd path), and the fused training step."""
@@ -228,9 +238,7 @@ class SolverEngine:
         st, sx, sy = self.sigma
         co = self.coeffs if self.coeffs is not None else (1.0 / st, self.vx / sx, self.vy / sy, self.D / (sx * sx),
                                                           self.D / (sy * sy))
-        w_r, w_bc, w_ic = self.loss_weights
-        return L.QcPde(self.D, self.vx, self.vy, co[0], co[1], co[2], co[3], co[4], 2.0 * w_r / n_res, 1.0 / n_res,
-                       2.0 * w_ic / n_ic, 2.0 * w_bc / n_bc, 1.0 / n_ic, 1.0 / n_bc, self.problem, n_seg_a)
+        return _pde_record((self.D, self.vx, self.vy, *co), self.loss_weights, (n_res, n_ic, n_bc), self.problem, n_seg_a)
 
     def refresh_gates(self) -> None:
         self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
@@ -467,54 +475,48 @@ class LbfgsState:
         return self.hist[: max(0, min(n, self.hist_cap))].cpu().numpy()
 
 
-class FusedStep:
-    """One ``qc_fused_pinn_residual_step`` descriptor over fixed-size resident batches.  The caller
-    fills ``X_res`` / ``X_val`` (IC points first, then BC points) and calls ``run``.
+class _Step:
+    """What every fused step shares: the resident batches ``X_res`` / ``X_val`` (IC points first, then BC) and the stage
+    scratch over fixed batch sizes, the per-tile gradient rows ``part`` and their fold ``flat_grad`` ([gradient | L_r, L_bc,
+    L_ic], ``stride`` entries), the step workspace, the one ``QcStepDesc`` over them, and the entry point bound once.
 
-    When the engine's problem is ``QC_PROBLEM_TABULATED`` the step is ``qc_fused_pinn_data_step``: the caller also fills
-    ``target_res`` / ``target_val`` (same order as the points), or hands over a resident dataset with ``set_dataset`` and
-    lets ``QC_PHASE_SAMPLE`` gather points and targets from it.  In the engine's coefficient mode (``coef_mode``, tabulated
-    only) the step is ``qc_fused_pinn_coef_step``: ``coef_res`` [7][B_res] holds the operator rows of the residual batch
-    (c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 per point), filled by the caller or gathered from the dataset's table."""
+    ``flat`` holds the ``param_layout(H, n, n_theta, K)`` entries and the class's ``N_OWN`` trainable entries behind them,
+    trained in place; ``what`` names that layout in the size errors (None: the caller has checked)."""
 
-    def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, counts=None):
-        self.eng, self.opt = eng, opt
-        dev, n = eng.device, eng.n
+    N_OWN = 0       # trainable entries behind theta (the operator's seven, a balancer's three)
+
+    def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, opt: OptimState, pde: "L.QcPde", B_res: int,
+                 n_ic: int, n_bc: int, K: int = 1, what: Optional[str] = None):
+        self.lib, self.circuit, self.opt = circuit.lib, circuit, opt
+        dev, n = circuit.device, circuit.n
+        self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
+        check_network_shape(self.H, n)
+        self.layout = param_layout(self.H, n, self.n_theta, K)
+        self.NP = self.layout["__total__"][0]
+        self.theta_off = self.layout["quantum_layer.params"][0]
+        NP_total = self.NP + self.N_OWN
+        if what is not None and flat.numel() != NP_total:
+            raise L.QcError(f"flat parameter vector has {flat.numel()} entries, {what} needs {NP_total}")
+        if what is not None and opt.m.numel() != NP_total:
+            raise L.QcError(f"optimiser state holds {opt.m.numel()} entries, {what} needs {NP_total}")
+        self.flat = _need(flat, dev, "flat params")
         self.B_res, self.n_ic, self.n_bc = B_res, n_ic, n_bc
         B_val = n_ic + n_bc
         f = dict(dtype=torch.float32, device=dev)
         self.X_res = torch.zeros(max(B_res, 1), 3, **f)
         self.X_val = torch.zeros(max(B_val, 1), 3, **f)
-        # targets of the current batches and the (optional) resident dataset of the tabulated step
-        self.tabulated = eng.problem == L.QC_PROBLEM_TABULATED
-        self.target_res = torch.zeros(max(B_res, 1), **f)
-        self.target_val = torch.zeros(max(B_val, 1), **f)
-        self.data = L.QcStepData()
-        self.data.target_res_dev, self.data.target_val_dev = self.target_res.data_ptr(), self.target_val.data_ptr()
-        self.data.c_u = eng.c_u
-        self._dataset = None
-        self.coef_mode = bool(eng.coef_mode)
-        if self.coef_mode and not self.tabulated:
-            raise L.QcError("per-point operator rows need the tabulated step (problem = QC_PROBLEM_TABULATED)")
-        if self.coef_mode:
-            self.coef_res = torch.zeros(L.QC_COEF_COLS, max(B_res, 1), **f)
-            self.coef = L.QcStepCoef()
-            self.coef.coef_res_dev, self.coef.ds_coef = (self.coef_res.data_ptr() if B_res else None), None
-        self.scores = self.adapt_buf = None
-        self.adapt = None       # QcStepAdapt once set_adaptive armed residual-adaptive sampling
         self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
         self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
         rows = (B_res + 63) // 64 + (B_val + 63) // 64
-        self.stride = eng.NP + 3
+        self.stride = NP_total + 3
         self.part = torch.zeros(rows, self.stride, **f)
         self.flat_grad = torch.zeros(self.stride, **f)
-        # global point counts (differ from the local ones under data parallelism)
-        g_res, g_ic, g_bc = counts if counts is not None else (B_res, n_ic, n_bc)
-        c = eng.circuit
+        self._dataset = None
+        c = circuit
         d = L.QcStepDesc()
         d.prog, d.trig_dev, d.umat_dev = c.handle, c.trig.data_ptr(), _ptr(c.umat)
-        d.H, d.n, d.n_theta = eng.H, n, eng.n_theta
-        d.params_dev, d.m_dev, d.v_dev = eng.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
+        d.H, d.n, d.n_theta = self.H, n, self.n_theta
+        d.params_dev, d.m_dev, d.v_dev = self.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
         d.opt_state_dev = opt.state.data_ptr()
         d.hist_dev, d.hist_cap = (opt.hist.data_ptr() if opt.hist_cap > 0 else None), opt.hist_cap
         d.X_res_dev, d.B_res = self.X_res.data_ptr(), B_res
@@ -523,9 +525,9 @@ class FusedStep:
         (d.ajets_val_dev, d.qjets_val_dev, d.qbar_val_dev, d.abar_val_dev) = [self.ws_val[i].data_ptr() for i in range(4)]
         d.part_dev, d.part_stride, d.part_rows_cap = self.part.data_ptr(), self.stride, rows
         d.flat_dev = self.flat_grad.data_ptr()
-        d.pde = eng._pde(max(g_res, 1), max(g_ic, 1), max(g_bc, 1), n_ic)
+        d.pde = pde
         d.hyper = opt.hyper
-        need = int(eng.lib.qc_step_workspace_bytes(c.handle, B_res, B_val))
+        need = int(self.lib.qc_step_workspace_bytes(c.handle, B_res, B_val))
         self.step_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
         d.circ_ws_dev, d.circ_ws_bytes = (self.step_ws.data_ptr(), need) if need else (None, 0)
         d.n_ic = n_ic
@@ -534,7 +536,38 @@ class FusedStep:
         d.sample_seed, d.sample_step = 0, 0
         d.sample_bc_face_points = 0
         self.desc = d
-        self._bind()
+
+    @staticmethod
+    def _counts(counts, B_res: int, n_ic: int, n_bc: int):
+        """The GLOBAL (residual, IC, BC) point counts the losses are means over (they differ from the local ones under
+        data parallelism), at least 1 each."""
+        return tuple(max(c, 1) for c in (counts if counts is not None else (B_res, n_ic, n_bc)))
+
+    def _scalar_targets(self, c_u: float) -> None:
+        """``target_res`` / ``target_val``, one value per point of the current batches, and the ``QcStepData`` over them
+        (the tabulated step and the steps built on it)."""
+        f = dict(dtype=torch.float32, device=self.device)
+        self.target_res = torch.zeros(max(self.B_res, 1), **f)
+        self.target_val = torch.zeros(max(self.n_ic + self.n_bc, 1), **f)
+        self.data = L.QcStepData()
+        self.data.target_res_dev, self.data.target_val_dev = self.target_res.data_ptr(), self.target_val.data_ptr()
+        self.data.c_u = c_u
+
+    def _own_hist(self, cols: int):
+        """([max(hist_cap, 1), cols] history of the class's own entries beside the loss history of ``opt``, its address
+        for the record or None without a history, hist_cap)."""
+        cap = self.opt.hist_cap
+        hist = torch.zeros(max(cap, 1), cols, dtype=torch.float32, device=self.device)
+        return hist, (hist.data_ptr() if cap > 0 else None), cap
+
+    def _bind_entry(self, name: str, *records) -> None:
+        """The export ``run`` calls and its arguments ahead of ``phases``: ``desc`` and the side records (None: a null
+        pointer).  Bound once, so that no ``run`` builds a ``byref``; the records are edited in place afterwards."""
+        args = (C.byref(self.desc), *(None if r is None else C.byref(r) for r in records))
+        self._entry = name, getattr(self.lib, name), args
+
+    def refresh_gates(self) -> None:
+        self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
 
     def set_sampler(self, seed: int, off_res: int = 0, off_ic: int = 0, off_bc: int = 0,
                     bc_face_points: int = 0) -> None:
@@ -546,38 +579,101 @@ class FusedStep:
         d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
         d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
 
-    def set_dataset(self, segments, coef=None) -> None:
-        """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on
-        the engine's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it.
-        ``coef``: the (N_res, 7) float32 operator table beside the residual segment (coefficient mode only, where a
-        non-empty residual segment needs it)."""
-        t = self.data
-        if coef is not None and not self.coef_mode:
-            raise L.QcError("a coefficient table needs a step in coefficient mode")
+    def _bind_dataset(self, rec, segments, widths=None, res_optional: bool = False) -> None:
+        """Points ``rec`` (a ``QcStepData`` or ``QcStepSystem``: the same ``ds_*`` fields) at the resident dataset
+        QC_PHASE_SAMPLE gathers from, ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on the step's device, or at
+        nothing (None).  ``widths`` None: [N, 3] points and [N] targets per segment; else (N, widths[i]) target rows, which
+        the residual segment may go without when ``res_optional``.  An empty segment serves an empty batch only."""
         if segments is None:
             segments = ((None, None),) * 3
         keep = []
-        for name, (X, y) in zip(("res", "ic", "bc"), segments):
+        for i, (name, (X, Y)) in enumerate(zip(("res", "ic", "bc"), segments)):
             n = 0 if X is None else int(X.shape[0])
-            if n:
-                X, y = _need(X, self.eng.device, "dataset points"), _need(y.reshape(-1), self.eng.device, "dataset targets")
-                if X.dim() != 2 or X.shape[1] != 3 or y.numel() != n:
+            if n and widths is None:
+                X, Y = _need(X, self.device, "dataset points"), _need(Y.reshape(-1), self.device, "dataset targets")
+                if X.dim() != 2 or X.shape[1] != 3 or Y.numel() != n:
                     raise L.QcError(f"dataset segment '{name}': points must be (N, 3) with N targets")
-                keep += [X, y]
-            setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
-            setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], y.data_ptr() if n else None)
-            setattr(t, "ds_n_" + name, n)
+            elif n:
+                X = _need(X, self.device, "dataset points")
+                if X.dim() != 2 or X.shape[1] != 3:
+                    raise L.QcError(f"dataset segment '{name}': points must be (N, 3)")
+                if Y is not None:
+                    Y = _need(Y, self.device, "dataset targets")
+                    if tuple(Y.shape) != (n, widths[i]):
+                        raise L.QcError(f"dataset segment '{name}': targets must be ({n}, {widths[i]}), got {tuple(Y.shape)}")
+                elif name != "res":
+                    raise L.QcError(f"dataset segment '{name}': value targets are required")
+                elif not res_optional:
+                    raise L.QcError("a dataset without residual targets needs a step built with res_targets=False")
+            if n:
+                keep += [t for t in (X, Y) if t is not None]
+            setattr(rec, "ds_X_" + name, X.data_ptr() if n else None)
+            setattr(rec, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name],
+                    Y.data_ptr() if n and Y is not None else None)
+            setattr(rec, "ds_n_" + name, n)
+        self._dataset = keep        # the record holds raw pointers: keep the tensors alive
+
+    def set_dataset(self, segments) -> None:
+        """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on
+        the step's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it."""
+        self._bind_dataset(self.data, segments)
+
+    def set_comm(self, comm) -> None:
+        """A communicator of ``qc_comm_create`` (or None): GRADS | UPDATE in one call then all-reduces the flat
+        [gradient | 3 loss sums] vector across the ranks inside the library (RCCL, same stream)."""
+        self.desc.comm = comm
+
+    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
+        if phases & L.QC_PHASE_SAMPLE:
+            self.desc.sample_step += 1          # a fresh counter block per step
+        name, fn, args = self._entry
+        L.check(fn(*args, phases, _stream(self.device)), name)
+
+
+class FusedStep(_Step):
+    """One ``qc_fused_pinn_residual_step`` descriptor over fixed-size resident batches.  The caller
+    fills ``X_res`` / ``X_val`` (IC points first, then BC points) and calls ``run``.
+
+    When the engine's problem is ``QC_PROBLEM_TABULATED`` the step is ``qc_fused_pinn_data_step``: the caller also fills
+    ``target_res`` / ``target_val`` (same order as the points), or hands over a resident dataset with ``set_dataset`` and
+    lets ``QC_PHASE_SAMPLE`` gather points and targets from it.  In the engine's coefficient mode (``coef_mode``, tabulated
+    only) the step is ``qc_fused_pinn_coef_step``: ``coef_res`` [7][B_res] holds the operator rows of the residual batch
+    (c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 per point), filled by the caller or gathered from the dataset's table."""
+
+    def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, counts=None):
+        self.eng = eng
+        self.tabulated = eng.problem == L.QC_PROBLEM_TABULATED
+        self.coef_mode = bool(eng.coef_mode)
+        if self.coef_mode and not self.tabulated:
+            raise L.QcError("per-point operator rows need the tabulated step (problem = QC_PROBLEM_TABULATED)")
+        super().__init__(eng.circuit, eng.H, eng.flat, opt, eng._pde(*self._counts(counts, B_res, n_ic, n_bc), n_ic),
+                         B_res, n_ic, n_bc)
+        # targets of the current batches and the (optional) resident dataset of the tabulated step
+        self._scalar_targets(eng.c_u)
         if self.coef_mode:
-            n_res = int(t.ds_n_res)
+            self.coef_res = torch.zeros(L.QC_COEF_COLS, max(B_res, 1), dtype=torch.float32, device=self.device)
+            self.coef = L.QcStepCoef()
+            self.coef.coef_res_dev, self.coef.ds_coef = (self.coef_res.data_ptr() if B_res else None), None
+        self.scores = self.adapt_buf = None
+        self.adapt = None       # QcStepAdapt once set_adaptive armed residual-adaptive sampling
+        self._bind()
+
+    def set_dataset(self, segments, coef=None) -> None:
+        """``_Step.set_dataset``, and ``coef``: the (N_res, 7) float32 operator table beside the residual segment
+        (coefficient mode only, where a non-empty residual segment needs it)."""
+        if coef is not None and not self.coef_mode:
+            raise L.QcError("a coefficient table needs a step in coefficient mode")
+        self._bind_dataset(self.data, segments)
+        if self.coef_mode:
+            n_res = int(self.data.ds_n_res)
             if coef is not None and n_res:
-                coef = _need(coef, self.eng.device, "dataset coefficient table")
+                coef = _need(coef, self.device, "dataset coefficient table")
                 if coef.dim() != 2 or tuple(coef.shape) != (n_res, L.QC_COEF_COLS):
                     raise L.QcError(f"dataset coefficient table must be ({n_res}, {L.QC_COEF_COLS}), got {tuple(coef.shape)}")
-                keep.append(coef)
+                self._dataset.append(coef)
                 self.coef.ds_coef = coef.data_ptr()
             else:
                 self.coef.ds_coef = None
-        self._dataset = keep        # the descriptor holds raw pointers: keep the tensors alive
         if self.adapt is not None:      # a CDF belongs to the rows it was built for: a uniform one over the new rows
             self.set_adaptive(self.adapt_power, self.adapt_floor)
 
@@ -589,11 +685,10 @@ class FusedStep:
         n_rows = int(self.data.ds_n_res)
         if not self.tabulated or n_rows < 1 or self.B_res < 1:
             raise L.QcError("adaptive sampling needs a tabulated step with residual points and a dataset with residual rows")
-        dev = self.eng.device
         self.adapt_power, self.adapt_floor = int(power), float(floor)
-        self.scores = torch.zeros(n_rows, dtype=torch.float32, device=dev)
-        need = int(self.eng.lib.qc_adapt_bytes(n_rows))
-        self.adapt_buf = torch.zeros((need + 7) // 8, dtype=torch.int64, device=dev)        # 8-byte aligned
+        self.scores = torch.zeros(n_rows, dtype=torch.float32, device=self.device)
+        need = int(self.lib.qc_adapt_bytes(n_rows))
+        self.adapt_buf = torch.zeros((need + 7) // 8, dtype=torch.int64, device=self.device)        # 8-byte aligned
         self.adapt = L.QcStepAdapt(self.adapt_buf.data_ptr(), n_rows)
         self._bind()
         self._build_cdf()       # zero scores: uniform weights
@@ -604,14 +699,14 @@ class FusedStep:
         self._bind()
 
     def _build_cdf(self) -> None:
-        L.check(self.eng.lib.qc_adapt_build(self.scores.data_ptr(), self.adapt.n_rows, self.adapt_power, self.adapt_floor,
-                                            self.adapt_buf.data_ptr(), _stream(self.eng.device)), "qc_adapt_build")
+        L.check(self.lib.qc_adapt_build(self.scores.data_ptr(), self.adapt.n_rows, self.adapt_power, self.adapt_floor,
+                                        self.adapt_buf.data_ptr(), _stream(self.device)), "qc_adapt_build")
 
     def rescore(self) -> None:
         """Enqueue, on the step's stream, the scores |res - r| of every residual row of the dataset under the current
         parameters and the CDF built from them.  No host read; the step's residual scratch is used between steps."""
-        L.check(self.eng.lib.qc_dataset_scores(C.byref(self.desc), C.byref(self.data), C.byref(self.coef) if self.coef_mode else None,
-                                               0, self.adapt.n_rows, self.scores.data_ptr(), _stream(self.eng.device)),
+        L.check(self.lib.qc_dataset_scores(C.byref(self.desc), C.byref(self.data), C.byref(self.coef) if self.coef_mode else None,
+                                           0, self.adapt.n_rows, self.scores.data_ptr(), _stream(self.device)),
                 "qc_dataset_scores")
         self._build_cdf()
 
@@ -621,31 +716,21 @@ class FusedStep:
         return {"total": int(raw[0]), "q_sum": int(raw[1]), "add": int(raw[2]), "max_p": float(raw[3:4].view(np.float32)[0]),
                 "shift": int(raw[3:4].view(np.int32)[1])}
 
-    def set_comm(self, comm) -> None:
-        """A communicator of ``qc_comm_create`` (or None): GRADS | UPDATE in one call then all-reduces the flat
-        [gradient | 3 loss sums] vector across the ranks inside the library (RCCL, same stream)."""
-        self.desc.comm = comm
-
     def _bind(self) -> None:
         """THE place that maps what the step was given (an armed CDF, coefficient mode, a tabulated problem, none of them)
-        to one of the four exports and its arguments ahead of ``phases``; re-run when adaptive sampling is (dis)armed."""
-        data, coef = C.byref(self.data), C.byref(self.coef) if self.coef_mode else None
+        to one of the four exports and its arguments; re-run when adaptive sampling is (dis)armed."""
+        coef = self.coef if self.coef_mode else None
         if self.adapt is not None:
-            name, args = "qc_fused_pinn_adaptive_step", (data, coef, C.byref(self.adapt))
+            self._bind_entry("qc_fused_pinn_adaptive_step", self.data, coef, self.adapt)
         elif self.coef_mode:
-            name, args = "qc_fused_pinn_coef_step", (data, coef)
+            self._bind_entry("qc_fused_pinn_coef_step", self.data, coef)
+        elif self.tabulated:
+            self._bind_entry("qc_fused_pinn_data_step", self.data)
         else:
-            name, args = ("qc_fused_pinn_data_step", (data,)) if self.tabulated else ("qc_fused_pinn_residual_step", ())
-        self._entry = name, getattr(self.eng.lib, name), (C.byref(self.desc), *args)
-
-    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
-        if phases & L.QC_PHASE_SAMPLE:
-            self.desc.sample_step += 1          # a fresh counter block per step
-        name, fn, args = self._entry
-        L.check(fn(*args, phases, _stream(self.eng.device)), name)
+            self._bind_entry("qc_fused_pinn_residual_step")
 
 
-class SystemStep:
+class SystemStep(_Step):
     """One ``qc_fused_pinn_system_step`` descriptor over fixed-size resident batches: the analogue of ``FusedStep`` for a
     model with K outputs behind one shared network and an operator given as a term list (hip/lib.system_record).
 
@@ -656,118 +741,27 @@ class SystemStep:
 
     def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, system: "L.QcStepSystem", B_res: int, n_ic: int,
                  n_bc: int, opt: OptimState, counts=None, loss_weights=(2.0, 4.0, 2.0), res_targets: bool = True):
-        self.lib, self.circuit, self.opt = circuit.lib, circuit, opt
-        dev, n = circuit.device, circuit.n
-        self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
-        check_network_shape(self.H, n)
         self.K, self.n_eq = int(system.K), int(system.n_eq)
         if not (1 <= self.K <= L.QC_KMAX and 1 <= self.n_eq <= L.QC_EQMAX):
             raise L.QcError(f"a system has 1..{L.QC_KMAX} outputs and 1..{L.QC_EQMAX} equations, got {self.K} and {self.n_eq}")
-        self.layout = param_layout(self.H, n, self.n_theta, self.K)
-        self.NP = self.layout["__total__"][0]
-        self.theta_off = self.layout["quantum_layer.params"][0]
-        if flat.numel() != self.NP:
-            raise L.QcError(f"flat parameter vector has {flat.numel()} entries, the {self.K}-output layout needs {self.NP}")
-        if opt.m.numel() != self.NP:
-            raise L.QcError(f"optimiser state holds {opt.m.numel()} entries, the {self.K}-output layout needs {self.NP}")
-        self.flat = _need(flat, dev, "flat params")
-        self.B_res, self.n_ic, self.n_bc = B_res, n_ic, n_bc
-        B_val = n_ic + n_bc
-        f = dict(dtype=torch.float32, device=dev)
-        self.X_res = torch.zeros(max(B_res, 1), 3, **f)
-        self.X_val = torch.zeros(max(B_val, 1), 3, **f)
+        # the operator coefficients and the problem id of the record are not read
+        pde = _pde_record((0.0,) * 8, loss_weights, self._counts(counts, B_res, n_ic, n_bc), L.QC_PROBLEM_TABULATED, n_ic)
+        super().__init__(circuit, hidden, flat, opt, pde, B_res, n_ic, n_bc, K=self.K, what=f"the {self.K}-output layout")
+        f = dict(dtype=torch.float32, device=self.device)
         self.target_res = torch.zeros(self.n_eq, max(B_res, 1), **f) if res_targets else None
-        self.target_val = torch.zeros(self.K, max(B_val, 1), **f)
+        self.target_val = torch.zeros(self.K, max(n_ic + n_bc, 1), **f)
         self.sys = system
         self.sys.target_res_dev = self.target_res.data_ptr() if (res_targets and B_res) else None
         self.sys.target_val_dev = self.target_val.data_ptr()
-        self._dataset = None
-        self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
-        self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
-        rows = (B_res + 63) // 64 + (B_val + 63) // 64
-        self.stride = self.NP + 3
-        self.part = torch.zeros(rows, self.stride, **f)
-        self.flat_grad = torch.zeros(self.stride, **f)
-        g_res, g_ic, g_bc = counts if counts is not None else (B_res, n_ic, n_bc)
-        g_res, g_ic, g_bc = max(g_res, 1), max(g_ic, 1), max(g_bc, 1)
-        w_r, w_bc, w_ic = (float(w) for w in loss_weights)
-        c = circuit
-        d = L.QcStepDesc()
-        d.prog, d.trig_dev, d.umat_dev = c.handle, c.trig.data_ptr(), _ptr(c.umat)
-        d.H, d.n, d.n_theta = self.H, n, self.n_theta
-        d.params_dev, d.m_dev, d.v_dev = self.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
-        d.opt_state_dev = opt.state.data_ptr()
-        d.hist_dev, d.hist_cap = (opt.hist.data_ptr() if opt.hist_cap > 0 else None), opt.hist_cap
-        d.X_res_dev, d.B_res = self.X_res.data_ptr(), B_res
-        d.X_val_dev, d.B_val = self.X_val.data_ptr(), B_val
-        (d.ajets_res_dev, d.qjets_res_dev, d.qbar_res_dev, d.abar_res_dev) = [self.ws_res[i].data_ptr() for i in range(4)]
-        (d.ajets_val_dev, d.qjets_val_dev, d.qbar_val_dev, d.abar_val_dev) = [self.ws_val[i].data_ptr() for i in range(4)]
-        d.part_dev, d.part_stride, d.part_rows_cap = self.part.data_ptr(), self.stride, rows
-        d.flat_dev = self.flat_grad.data_ptr()
-        # d loss / d err = 2 w / N per unit error; the operator coefficients and the problem id are not read
-        d.pde = L.QcPde(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 2.0 * w_r / g_res, 1.0 / g_res, 2.0 * w_ic / g_ic,
-                        2.0 * w_bc / g_bc, 1.0 / g_ic, 1.0 / g_bc, L.QC_PROBLEM_TABULATED, n_ic)
-        d.hyper = opt.hyper
-        need = int(self.lib.qc_step_workspace_bytes(c.handle, B_res, B_val))
-        self.step_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        d.circ_ws_dev, d.circ_ws_bytes = (self.step_ws.data_ptr(), need) if need else (None, 0)
-        d.n_ic = n_ic
-        d.comm = None
-        d.sample_off_res = d.sample_off_ic = d.sample_off_bc = 0
-        d.sample_seed, d.sample_step = 0, 0
-        d.sample_bc_face_points = 0
-        self.desc = d
-
-    def refresh_gates(self) -> None:
-        self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
-
-    def set_sampler(self, seed: int, off_res: int = 0, off_ic: int = 0, off_bc: int = 0) -> None:
-        """On-device gather (QC_PHASE_SAMPLE): Philox stream ``seed``; off_* = global index of this rank's first point."""
-        d = self.desc
-        d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
-        d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
+        self._bind_entry("qc_fused_pinn_system_step", self.sys)
 
     def set_dataset(self, segments) -> None:
         """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, R | None), (X_ic, U_ic), (X_bc, U_bc)) float32
         tensors on the step's device, points [N, 3], target rows [N, n_eq] / [N, K]; None removes it."""
-        t = self.sys
-        if segments is None:
-            segments = ((None, None),) * 3
-        keep = []
-        for name, (X, Y), w in zip(("res", "ic", "bc"), segments, (self.n_eq, self.K, self.K)):
-            n = 0 if X is None else int(X.shape[0])
-            yp = None
-            if n:
-                X = _need(X, self.device, "dataset points")
-                if X.dim() != 2 or X.shape[1] != 3:
-                    raise L.QcError(f"dataset segment '{name}': points must be (N, 3)")
-                keep.append(X)
-                if Y is not None:
-                    Y = _need(Y, self.device, "dataset targets")
-                    if tuple(Y.shape) != (n, w):
-                        raise L.QcError(f"dataset segment '{name}': targets must be ({n}, {w}), got {tuple(Y.shape)}")
-                    keep.append(Y)
-                    yp = Y.data_ptr()
-                elif name != "res":
-                    raise L.QcError(f"dataset segment '{name}': value targets are required")
-                elif self.target_res is not None:
-                    raise L.QcError("a dataset without residual targets needs a step built with res_targets=False")
-            setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
-            setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], yp)
-            setattr(t, "ds_n_" + name, n)
-        self._dataset = keep        # the record holds raw pointers: keep the tensors alive
-
-    def set_comm(self, comm) -> None:
-        self.desc.comm = comm
-
-    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
-        if phases & L.QC_PHASE_SAMPLE:
-            self.desc.sample_step += 1          # a fresh counter block per step
-        L.check(self.lib.qc_fused_pinn_system_step(C.byref(self.desc), C.byref(self.sys), phases, _stream(self.device)),
-                "qc_fused_pinn_system_step")
+        self._bind_dataset(self.sys, segments, (self.n_eq, self.K, self.K), res_optional=self.target_res is None)
 
 
-class InverseStep:
+class InverseStep(_Step):
     """One ``qc_fused_pinn_inverse_step`` descriptor over fixed-size resident batches: the tabulated step with a trainable
     global operator c_k = fmaf(scale_k, p_k, base_k), k in ``QC_COEF_COLS`` order.
 
@@ -777,127 +771,36 @@ class InverseStep:
     or hands over a resident dataset with ``set_dataset`` and lets ``QC_PHASE_SAMPLE`` gather points and targets.
     ``coef_hist`` [hist_cap, 7] receives the coefficients each step used, beside the loss history of ``opt``."""
 
-    N_OWN = L.QC_COEF_COLS      # trainable entries behind theta (``BalancedStep``: its three)
+    N_OWN = L.QC_COEF_COLS
 
     def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, base, scale, B_res: int, n_ic: int, n_bc: int,
                  opt: OptimState, counts=None, loss_weights=(2.0, 4.0, 2.0)):
-        self.lib, self.circuit, self.opt = circuit.lib, circuit, opt
-        dev, n = circuit.device, circuit.n
-        self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
-        check_network_shape(self.H, n)
-        self.layout = param_layout(self.H, n, self.n_theta)
-        self.NP = self.layout["__total__"][0]
+        # the operator is `learn`: the record's own coefficients and data.c_u are poisoned, nothing may read them
+        nan = float("nan")
+        pde = _pde_record((0.0, 0.0, 0.0, nan, nan, nan, nan, nan), loss_weights, self._counts(counts, B_res, n_ic, n_bc),
+                          L.QC_PROBLEM_TABULATED, n_ic)
+        super().__init__(circuit, hidden, flat, opt, pde, B_res, n_ic, n_bc, what="the layout with the operator")
         self.NP_L = self.NP + self.N_OWN
-        self.theta_off = self.layout["quantum_layer.params"][0]
-        if flat.numel() != self.NP_L:
-            raise L.QcError(f"flat parameter vector has {flat.numel()} entries, the layout with the operator needs {self.NP_L}")
-        if opt.m.numel() != self.NP_L:
-            raise L.QcError(f"optimiser state holds {opt.m.numel()} entries, the layout with the operator needs {self.NP_L}")
-        self.flat = _need(flat, dev, "flat params")
         base, scale = [float(v) for v in base], [float(v) for v in scale]
         if len(base) != L.QC_COEF_COLS or len(scale) != L.QC_COEF_COLS:
             raise L.QcError(f"base and scale hold {L.QC_COEF_COLS} entries each")
-        self.B_res, self.n_ic, self.n_bc = B_res, n_ic, n_bc
-        B_val = n_ic + n_bc
-        f = dict(dtype=torch.float32, device=dev)
-        self.X_res = torch.zeros(max(B_res, 1), 3, **f)
-        self.X_val = torch.zeros(max(B_val, 1), 3, **f)
-        self.target_res = torch.zeros(max(B_res, 1), **f)
-        self.target_val = torch.zeros(max(B_val, 1), **f)
-        self.data = L.QcStepData()
-        self.data.target_res_dev, self.data.target_val_dev = self.target_res.data_ptr(), self.target_val.data_ptr()
-        self.data.c_u = float("nan")                 # not read: the operator is `learn`
-        self.coef_hist = torch.zeros(max(opt.hist_cap, 1), L.QC_COEF_COLS, **f)
+        self._scalar_targets(nan)
         self.learn = L.QcStepLearn()
         for k in range(L.QC_COEF_COLS):
             self.learn.base[k], self.learn.scale[k] = base[k], scale[k]
-        self.learn.coef_hist_dev = self.coef_hist.data_ptr() if opt.hist_cap > 0 else None
-        self.learn.coef_hist_cap = opt.hist_cap
-        self._dataset = None
-        self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
-        self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
-        rows = (B_res + 63) // 64 + (B_val + 63) // 64
-        self.stride = self.NP_L + 3
-        self.part = torch.zeros(rows, self.stride, **f)
-        self.flat_grad = torch.zeros(self.stride, **f)
-        g_res, g_ic, g_bc = counts if counts is not None else (B_res, n_ic, n_bc)
-        g_res, g_ic, g_bc = max(g_res, 1), max(g_ic, 1), max(g_bc, 1)
-        w_r, w_bc, w_ic = (float(w) for w in loss_weights)
-        nan = float("nan")
-        c = circuit
-        d = L.QcStepDesc()
-        d.prog, d.trig_dev, d.umat_dev = c.handle, c.trig.data_ptr(), _ptr(c.umat)
-        d.H, d.n, d.n_theta = self.H, n, self.n_theta
-        d.params_dev, d.m_dev, d.v_dev = self.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
-        d.opt_state_dev = opt.state.data_ptr()
-        d.hist_dev, d.hist_cap = (opt.hist.data_ptr() if opt.hist_cap > 0 else None), opt.hist_cap
-        d.X_res_dev, d.B_res = self.X_res.data_ptr(), B_res
-        d.X_val_dev, d.B_val = self.X_val.data_ptr(), B_val
-        (d.ajets_res_dev, d.qjets_res_dev, d.qbar_res_dev, d.abar_res_dev) = [self.ws_res[i].data_ptr() for i in range(4)]
-        (d.ajets_val_dev, d.qjets_val_dev, d.qbar_val_dev, d.abar_val_dev) = [self.ws_val[i].data_ptr() for i in range(4)]
-        d.part_dev, d.part_stride, d.part_rows_cap = self.part.data_ptr(), self.stride, rows
-        d.flat_dev = self.flat_grad.data_ptr()
-        # d loss / d err = 2 w / N per unit error; the operator coefficients of the record are not read
-        d.pde = L.QcPde(0.0, 0.0, 0.0, nan, nan, nan, nan, nan, 2.0 * w_r / g_res, 1.0 / g_res, 2.0 * w_ic / g_ic,
-                        2.0 * w_bc / g_bc, 1.0 / g_ic, 1.0 / g_bc, L.QC_PROBLEM_TABULATED, n_ic)
-        d.hyper = opt.hyper
-        need = int(self.lib.qc_step_workspace_bytes(c.handle, B_res, B_val))
-        self.step_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        d.circ_ws_dev, d.circ_ws_bytes = (self.step_ws.data_ptr(), need) if need else (None, 0)
-        d.n_ic = n_ic
-        d.comm = None
-        d.sample_off_res = d.sample_off_ic = d.sample_off_bc = 0
-        d.sample_seed, d.sample_step = 0, 0
-        d.sample_bc_face_points = 0
-        self.desc = d
-
-    def refresh_gates(self) -> None:
-        self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
-
-    def set_sampler(self, seed: int, off_res: int = 0, off_ic: int = 0, off_bc: int = 0) -> None:
-        """On-device gather (QC_PHASE_SAMPLE): Philox stream ``seed``; off_* = global index of this rank's first point."""
-        d = self.desc
-        d.sample_seed = seed & 0xFFFFFFFFFFFFFFFF
-        d.sample_off_res, d.sample_off_ic, d.sample_off_bc = off_res, off_ic, off_bc
-
-    def set_dataset(self, segments) -> None:
-        """The resident dataset QC_PHASE_SAMPLE gathers from: ((X_res, r), (X_ic, u_ic), (X_bc, u_bc)) float32 tensors on
-        the step's device, [N, 3] and [N] per segment (an empty segment serves an empty batch only); None removes it."""
-        t = self.data
-        if segments is None:
-            segments = ((None, None),) * 3
-        keep = []
-        for name, (X, y) in zip(("res", "ic", "bc"), segments):
-            n = 0 if X is None else int(X.shape[0])
-            if n:
-                X, y = _need(X, self.device, "dataset points"), _need(y.reshape(-1), self.device, "dataset targets")
-                if X.dim() != 2 or X.shape[1] != 3 or y.numel() != n:
-                    raise L.QcError(f"dataset segment '{name}': points must be (N, 3) with N targets")
-                keep += [X, y]
-            setattr(t, "ds_X_" + name, X.data_ptr() if n else None)
-            setattr(t, {"res": "ds_r", "ic": "ds_u_ic", "bc": "ds_u_bc"}[name], y.data_ptr() if n else None)
-            setattr(t, "ds_n_" + name, n)
-        self._dataset = keep        # the record holds raw pointers: keep the tensors alive
-
-    def set_comm(self, comm) -> None:
-        self.desc.comm = comm
-
-    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
-        if phases & L.QC_PHASE_SAMPLE:
-            self.desc.sample_step += 1          # a fresh counter block per step
-        L.check(self.lib.qc_fused_pinn_inverse_step(C.byref(self.desc), C.byref(self.data), C.byref(self.learn), phases,
-                                                    _stream(self.device)), "qc_fused_pinn_inverse_step")
+        self.coef_hist, self.learn.coef_hist_dev, self.learn.coef_hist_cap = self._own_hist(L.QC_COEF_COLS)
+        self._bind_entry("qc_fused_pinn_inverse_step", self.data, self.learn)
 
 
-class BalancedStep(InverseStep):
+class BalancedStep(_Step):
     """One ``qc_fused_pinn_balanced_step`` descriptor over fixed-size resident batches: the tabulated step under learned
     loss weights (uncertainty balancing), F = sum_k (w_k exp(-s_k) L_k + s_k) with s_k = scale_k p_k, k = residual, BC, IC.
 
     ``flat`` holds ``NP + 3`` entries, trained in place: the single-output layout and the three ``p_k`` behind it; ``opt``
     holds as many.  ``scale``: three floats (``scale_k = 0`` freezes a term at weight w_k).  ``coeffs`` = (c_t, c_x, c_y,
-    d_xx, d_yy) and ``c_u``: the operator of the tabulated residual.  Batches, dataset, sampler and communicator are
-    ``InverseStep``'s.  ``weight_hist`` [hist_cap, 3] receives the effective weights w_k exp(-s_k) each step used, beside
-    the history of F in ``opt``."""
+    d_xx, d_yy) and ``c_u``: the operator of the tabulated residual.  Batches, targets and dataset as in ``InverseStep``.
+    ``weight_hist`` [hist_cap, 3] receives the effective weights w_k exp(-s_k) each step used, beside the history of F in
+    ``opt``."""
 
     N_OWN = L.QC_BAL_TERMS
 
@@ -906,25 +809,16 @@ class BalancedStep(InverseStep):
         scale = [float(v) for v in scale]
         if len(scale) != L.QC_BAL_TERMS:
             raise L.QcError(f"scale holds {L.QC_BAL_TERMS} entries: residual, BC, IC")
-        zeros = [0.0] * L.QC_COEF_COLS
-        super().__init__(circuit, hidden, flat, zeros, zeros, B_res, n_ic, n_bc, opt, counts=counts, loss_weights=loss_weights)
-        del self.learn, self.coef_hist      # no operator record: the operator is the tabulated step's
-        self.NP_B = self.NP_L
-        self.data.c_u = float(c_u)
-        d = self.desc
-        d.pde.c_t, d.pde.c_x, d.pde.c_y, d.pde.d_xx, d.pde.d_yy = (float(c) for c in coeffs)
-        self.weight_hist = torch.zeros(max(opt.hist_cap, 1), L.QC_BAL_TERMS, dtype=torch.float32, device=self.device)
+        pde = _pde_record((0.0, 0.0, 0.0, *(float(c) for c in coeffs)), loss_weights,
+                          self._counts(counts, B_res, n_ic, n_bc), L.QC_PROBLEM_TABULATED, n_ic)
+        super().__init__(circuit, hidden, flat, opt, pde, B_res, n_ic, n_bc, what="the layout with the operator")
+        self.NP_L = self.NP_B = self.NP + self.N_OWN
+        self._scalar_targets(float(c_u))
         self.bal = L.QcStepBalance()
         for k in range(L.QC_BAL_TERMS):
             self.bal.scale[k] = scale[k]
-        self.bal.weight_hist_dev = self.weight_hist.data_ptr() if opt.hist_cap > 0 else None
-        self.bal.weight_hist_cap = opt.hist_cap
-
-    def run(self, phases: int = L.QC_PHASE_GRADS | L.QC_PHASE_UPDATE) -> None:
-        if phases & L.QC_PHASE_SAMPLE:
-            self.desc.sample_step += 1          # a fresh counter block per step
-        L.check(self.lib.qc_fused_pinn_balanced_step(C.byref(self.desc), C.byref(self.data), C.byref(self.bal), phases,
-                                                     _stream(self.device)), "qc_fused_pinn_balanced_step")
+        self.weight_hist, self.bal.weight_hist_dev, self.bal.weight_hist_cap = self._own_hist(L.QC_BAL_TERMS)
+        self._bind_entry("qc_fused_pinn_balanced_step", self.data, self.bal)
 
 
 class CausalStep(FusedStep):
@@ -969,8 +863,7 @@ class CausalStep(FusedStep):
         raise L.QcError("the causal step draws its residual rows by slab: adaptive sampling is not supported")
 
     def _bind(self) -> None:
-        name = "qc_fused_pinn_causal_step"
-        self._entry = name, getattr(self.eng.lib, name), (C.byref(self.desc), C.byref(self.data), C.byref(self.causal))
+        self._bind_entry("qc_fused_pinn_causal_step", self.data, self.causal)
 
     def set_hist_base(self, n_steps: int, hist_base: int) -> None:
         """Rewrites the two counters of the record (a new history buffer starts at step ``hist_base``)."""

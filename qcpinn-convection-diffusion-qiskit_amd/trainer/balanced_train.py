@@ -15,11 +15,8 @@ from __future__ import annotations
 
 import time
 
-import torch
-
 from ..data.tabulated import TabulatedProblem
 from ..hip import engine as _engine
-from ..hip import lib as _lib
 from ..nn.loss_balance import TERMS, AdaptiveMultiLoss
 from .diffusion_train import _dist_info, _log_line
 from .inverse_train import InverseTrainer
@@ -61,87 +58,24 @@ class BalancedTrainer(InverseTrainer):
         """``dataset``: the resident segments and the operator (``coeffs``, ``c_u``) of the tabulated step; ``batch_size``
         residual, ``n_ic`` / ``n_bc`` (default ``batch_size // 3``) value points per step; ``loss_weights`` = the base
         weights w_k (residual, BC, IC); ``capacity``: length of the histories of F and of the effective weights."""
-        check_balance(model, dataset, balancer)
-        if sampler not in ("device", "torch"):
-            raise ValueError("sampler must be 'device' or 'torch'")
-        n3 = batch_size // 3
-        self.B_res = int(batch_size)
-        self.n_ic = n3 if n_ic is None else int(n_ic)
-        self.n_bc = n3 if n_bc is None else int(n_bc)
-        if min(self.B_res, self.n_ic, self.n_bc) < 0 or self.B_res + self.n_ic + self.n_bc == 0:
-            raise ValueError("batch sizes must be non-negative and not all zero")
-        dev = model._resolve_device(model.device)
-        if dev is None or dev.type != "cuda":
-            raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
-        self.model, self.balancer, self.device, self.sampler = model, balancer, dev, sampler
-        self.dataset = dataset.to(dev)
-        self.max_norm = max_norm
-        self.loss_weights = tuple(float(w) for w in loss_weights)
-        self._pack()
-        self.circuit = model.quantum_layer._circuit_for(dev)
-        self.optimizer, self.scheduler = model.optimizer, model.scheduler
-        self.attach(model, balancer)
-        self.opt = self._make_opt_state(int(capacity))
-        ds = self.dataset
-        scale = balancer.scale.tolist()
-        scale = [scale[balancer.names.index(name)] for name in TERMS]      # the step's order, whatever the balancer's
-        self.fs = _engine.BalancedStep(self.circuit, model.hidden_width, self.flat, scale, self.B_res, self.n_ic, self.n_bc,
-                                       self.opt, ds.coeffs, ds.c_u, loss_weights=self.loss_weights)
-        self._sampled = all(n_rows > 0 or n_batch == 0
-                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
-        if self._sampled:
-            self.fs.set_dataset(ds.segments())
-        self.fs.refresh_gates()
-        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
-        self._explicit = False
-        model._sync_fused_to_torch = self.sync_to_torch
+        super().__init__(model, batch_size, dataset, balancer, n_ic=n_ic, n_bc=n_bc, loss_weights=loss_weights,
+                         max_norm=max_norm, capacity=capacity, sampler=sampler)
+
+    FLAT_ATTR = "_balanced_flat"
+    _check = staticmethod(check_balance)
+    balancer = property(lambda self: self.operator)
 
     @staticmethod
     def _own(balancer):
+        """The three ``log_vars`` in the step's order (residual, BC, IC), whatever the balancer's."""
         return [balancer.log_vars[name] for name in TERMS]
 
-    @staticmethod
-    def attach(model, balancer):
-        """The three ``log_vars`` join ``model.optimizer`` as a second param group with the hyper-parameters of the first,
-        if they are not there yet (the constructor calls this; call it on a fresh model before loading a saved optimiser
-        state)."""
-        opt = model.optimizer
-        own = BalancedTrainer._own(balancer)
-        if not any(p is own[0] for g in opt.param_groups for p in g["params"]):
-            g0 = opt.param_groups[0]
-            opt.add_param_group({"params": own, **{k: v for k, v in g0.items() if k != "params"}})
-            sch = model.scheduler
-            sch.min_lrs = list(sch.min_lrs) + [sch.min_lrs[0]] * (len(opt.param_groups) - len(sch.min_lrs))
-
-    def _params(self):
-        return list(self.model.parameters()) + self._own(self.balancer)
-
-    def _pack(self):
-        """One flat buffer [model parameters | p_res, p_bc, p_ic]; the model's own flat buffer becomes its head (a view),
-        the way ``model._pack`` builds it, and the three ``log_vars`` become views of the tail."""
-        model, bal, dev = self.model, self.balancer, self.device
-        if not model._packed_ok() or model._flat.device != dev:
-            model._pack(dev)
-        NP = model._flat.numel()
-        own = self._own(bal)
-        big = getattr(model, "_balanced_flat", None)
-        if not (big is not None and big.device == dev and big.numel() == NP + len(TERMS)
-                and model._flat.data_ptr() == big.data_ptr()
-                and all(p.data_ptr() == big.data_ptr() + 4 * (NP + k) for k, p in enumerate(own))):
-            tail = torch.cat([p.detach().reshape(1).to(device=dev, dtype=torch.float32) for p in own])
-            big = torch.cat([model._flat.detach(), tail])
-            off = 0
-            for p, k, pad in model._slots():
-                p.data = big[off:off + k].view(p.shape)
-                off += k
-            model._flat = big[:NP]
-            model._engines = {}
-            model._balanced_flat = big
-            for k, p in enumerate(own):
-                p.data = big[NP + k:NP + k + 1]
-            bal.scale.data = bal.scale.to(dev)
-        self.flat = model._balanced_flat
-        self.NP = NP
+    def _make_step(self):
+        ds, bal = self.dataset, self.balancer
+        scale = bal.scale.tolist()
+        scale = [scale[bal.names.index(name)] for name in TERMS]      # the step's order, whatever the balancer's
+        return _engine.BalancedStep(self.circuit, self.model.hidden_width, self.flat, scale, self.B_res, self.n_ic, self.n_bc,
+                                    self.opt, ds.coeffs, ds.c_u, loss_weights=self.loss_weights)
 
     def weight_history(self, steps=None):
         """(steps, 3) tensor: row i holds the effective weights w_k exp(-s_k) (residual, BC, IC) the i-th step of THIS

@@ -84,6 +84,84 @@ def _log_line(model, it, parts, lr, step_time, total_elapsed):
            step_time, total_elapsed, step_time * remaining))
 
 
+# --------------------------------------------------------------------------------------------- shared by the trainers
+def opt_state_from_torch(params, optimizer, scheduler, device, capacity, max_norm, loss_weights):
+    """The device optimiser state over ``params`` (in the flat vector's order), continued from the torch Adam /
+    ReduceLROnPlateau objects: hyper-parameters of the first param group, the moments of every parameter that has them."""
+    params = list(params)
+    g = optimizer.param_groups[0]
+    st = _engine.OptimState(sum(p.numel() for p in params), float(g["lr"]), device, hist_cap=capacity,
+                            betas=tuple(g["betas"]), eps=float(g["eps"]), max_norm=max_norm,
+                            factor=float(scheduler.factor), patience=int(scheduler.patience),
+                            threshold=float(scheduler.threshold), min_lr=float(scheduler.min_lrs[0]),
+                            sched_eps=float(scheduler.eps), loss_weights=loss_weights)
+    steps, off = 0, 0
+    for p in params:
+        s = optimizer.state.get(p, None)
+        k = p.numel()
+        if s:
+            st.m[off:off + k] = s["exp_avg"].reshape(-1).to(device)
+            st.v[off:off + k] = s["exp_avg_sq"].reshape(-1).to(device)
+            steps = int(s["step"])
+        off += k
+    # a model trained before continues its Adam step count; the loss history of THIS run starts at index 0
+    st.write(best=float(scheduler.best), num_bad=int(scheduler.num_bad_epochs), step=steps, hist_base=steps)
+    return st
+
+
+def sync_opt_state_to_torch(opt, params, optimizer, scheduler):
+    """Mirror the device optimiser record ``opt`` into the torch optimiser / scheduler (``save_state`` calls this through
+    the trainers' ``sync_to_torch``): the moments become views of the device state."""
+    rec = opt.read()
+    off = 0
+    for p in params:
+        k = p.numel()
+        optimizer.state[p] = {"step": torch.tensor(float(rec["step"])),
+                              "exp_avg": opt.m[off:off + k].view(p.shape),
+                              "exp_avg_sq": opt.v[off:off + k].view(p.shape)}
+        off += k
+    for g in optimizer.param_groups:
+        g["lr"] = rec["lr"]
+    scheduler.best, scheduler.num_bad_epochs = rec["best"], rec["num_bad_epochs"]
+    scheduler.last_epoch = rec["step"]
+    scheduler._last_lr = [rec["lr"]] * len(optimizer.param_groups)
+
+
+def batch_prologue(model, batch_size, n_ic, n_bc, sampler):
+    """(B_res, n_ic, n_bc, device) of a single-process dataset trainer: ``n_ic`` / ``n_bc`` default to ``batch_size // 3``;
+    raises for an unknown sampler, negative or all-zero batch sizes, and a model that is not on a GPU."""
+    if sampler not in ("device", "torch"):
+        raise ValueError("sampler must be 'device' or 'torch'")
+    n3 = batch_size // 3
+    B_res, n_ic, n_bc = int(batch_size), (n3 if n_ic is None else int(n_ic)), (n3 if n_bc is None else int(n_bc))
+    if min(B_res, n_ic, n_bc) < 0 or B_res + n_ic + n_bc == 0:
+        raise ValueError("batch sizes must be non-negative and not all zero")
+    dev = model._resolve_device(model.device)
+    if dev is None or dev.type != "cuda":
+        raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
+    return B_res, n_ic, n_bc, dev
+
+
+def gather_rows(fs, segments, counts, batch_minor=False, coef=None):
+    """The "torch" sampler over a resident dataset: ``torch.randint`` rows of ``segments`` = ((X_res, r), (X_ic, u_ic),
+    (X_bc, u_bc)), drawn IC -> BC -> residual like the reference's batches, copied into the batches and targets of the step
+    ``fs``.  ``counts`` = (B_res, n_ic, n_bc); ``batch_minor``: target rows [N, w] go into [w, B] targets (absent rows:
+    none copied); ``coef``: the (N_res, 7) operator table whose drawn rows go into ``fs.coef_res``."""
+    (Xr, Yr), (Xi, Yi), (Xb, Yb) = segments
+    B_res, n_ic, n_bc = counts
+    for X, Y, n, dX, dY, o in ((Xi, Yi, n_ic, fs.X_val, fs.target_val, 0), (Xb, Yb, n_bc, fs.X_val, fs.target_val, n_ic),
+                               (Xr, Yr, B_res, fs.X_res, fs.target_res, 0)):
+        if n:
+            idx = torch.randint(0, X.shape[0], (n,), device=dX.device)
+            dX[o:o + n] = X[idx]
+            if batch_minor and Y is not None:
+                dY[:, o:o + n] = Y[idx].t()
+            elif Y is not None:
+                dY[o:o + n] = Y[idx]
+            if coef is not None and dX is fs.X_res:
+                fs.coef_res[:, :n] = coef[idx].t()
+
+
 # ---------------------------------------------------------------------------------------------
 class FusedTrainer:
     """Device-resident training state of one DVPDESolver: sampler boxes, optimiser record,
@@ -232,48 +310,14 @@ class FusedTrainer:
     def __del__(self):
         self.close()
 
-    # -- optimiser state: continue from the torch optimiser / scheduler objects of the model
     def _make_opt_state(self, capacity):
-        model = self.model
-        opt, sch = self.optimizer, self.scheduler
-        g = opt.param_groups[0]
-        st = _engine.OptimState(self.eng.NP, float(g["lr"]), self.device, hist_cap=capacity,
-                                betas=tuple(g["betas"]), eps=float(g["eps"]), max_norm=self.max_norm,
-                                factor=float(sch.factor), patience=int(sch.patience),
-                                threshold=float(sch.threshold), min_lr=float(sch.min_lrs[0]),
-                                sched_eps=float(sch.eps), loss_weights=self.eng.loss_weights)
-        steps, off = 0, 0
-        for p in model.parameters():
-            s = opt.state.get(p, None)
-            k = p.numel()
-            if s:
-                st.m[off:off + k] = s["exp_avg"].reshape(-1).to(self.device)
-                st.v[off:off + k] = s["exp_avg_sq"].reshape(-1).to(self.device)
-                steps = int(s["step"])
-            off += k
-        # a model trained before continues its Adam step count; the loss history of THIS run starts at index 0
-        st.write(best=float(sch.best), num_bad=int(sch.num_bad_epochs), step=steps, hist_base=steps)
-        return st
+        return opt_state_from_torch(self.model.parameters(), self.optimizer, self.scheduler, self.device, capacity,
+                                    self.max_norm, self.eng.loss_weights)
 
     def sync_to_torch(self):
         """Mirror the device optimiser record into model.optimizer / model.scheduler so that
         ``save_state`` writes a checkpoint interchangeable with the reference's."""
-        model, rec = self.model, self.opt.read()
-        off = 0
-        for p in model.parameters():
-            k = p.numel()
-            self.optimizer.state[p] = {
-                "step": torch.tensor(float(rec["step"])),
-                "exp_avg": self.opt.m[off:off + k].view(p.shape),
-                "exp_avg_sq": self.opt.v[off:off + k].view(p.shape),
-            }
-            off += k
-        for g in self.optimizer.param_groups:
-            g["lr"] = rec["lr"]
-        sch = self.scheduler
-        sch.best, sch.num_bad_epochs = rec["best"], rec["num_bad_epochs"]
-        sch.last_epoch = rec["step"]
-        sch._last_lr = [rec["lr"]]
+        sync_opt_state_to_torch(self.opt, self.model.parameters(), self.optimizer, self.scheduler)
 
     # -- batches
     def sample(self):
@@ -287,16 +331,7 @@ class FusedTrainer:
         self._explicit = True
         fs, dev = self.fs, self.device
         if self.dataset is not None:     # torch.randint minibatches, IC -> BC -> residual like the draws below
-            (Xr, rr), (Xi, ui), (Xb, ub) = self.dataset.segments()
-            for X, y, n, dX, dy, o in ((Xi, ui, self.n_ic, fs.X_val, fs.target_val, 0),
-                                       (Xb, ub, self.n_bc, fs.X_val, fs.target_val, self.n_ic),
-                                       (Xr, rr, self.B_res, fs.X_res, fs.target_res, 0)):
-                if n:
-                    idx = torch.randint(0, X.shape[0], (n,), device=dev)
-                    dX[o:o + n] = X[idx]
-                    dy[o:o + n] = y[idx]
-                    if self.coef_mode and X is Xr:
-                        fs.coef_res[:, :n] = self.dataset.coef_res[idx].t()
+            gather_rows(fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), coef=self.dataset.coef_res)
             return
         if self.n_ic:
             fs.X_val[: self.n_ic] = self.lo["ics"] + self.span["ics"] * torch.rand(self.n_ic, 3, device=dev)

@@ -15,10 +15,34 @@ from __future__ import annotations
 
 import torch
 
-from ..data.tabulated import COEF_COLUMNS, LearnedOperator, TabulatedProblem, _SCALARS
+from ..data.tabulated import LearnedOperator, TabulatedProblem, _SCALARS
 from ..hip import engine as _engine
 from ..hip import lib as _lib
-from .diffusion_train import _dist_info
+from .diffusion_train import _dist_info, batch_prologue, gather_rows, opt_state_from_torch, sync_opt_state_to_torch
+
+
+def pack_with_tail(model, tail, attr, dev):
+    """One flat float32 buffer [model parameters | the tensors of ``tail``] on ``dev``, cached on the model as ``attr``: the
+    model's own flat buffer becomes its head (a view), the way ``model._pack`` builds it, and the Parameters of ``tail``
+    become views of what follows, in order.  Returns the buffer; rebuilt only when one of the views no longer holds."""
+    if not model._packed_ok() or model._flat.device != dev:
+        model._pack(dev)             # one flat buffer in model.parameters() order, parameters re-pointed at views
+    NP = model._flat.numel()
+    offs = [NP + sum(p.numel() for p in tail[:k]) for k in range(len(tail) + 1)]
+    big = getattr(model, attr, None)
+    if not (big is not None and big.device == dev and big.numel() == offs[-1] and model._flat.data_ptr() == big.data_ptr()
+            and all(p.data_ptr() == big.data_ptr() + 4 * o for p, o in zip(tail, offs))):
+        big = torch.cat([model._flat.detach()] + [p.detach().reshape(-1).to(device=dev, dtype=torch.float32) for p in tail])
+        off = 0
+        for p, k, pad in model._slots():
+            p.data = big[off:off + k].view(p.shape)
+            off += k
+        model._flat = big[:NP]
+        model._engines = {}
+        setattr(model, attr, big)
+        for p, o in zip(tail, offs):
+            p.data = big[o:o + p.numel()].view(p.shape)
+    return big
 
 
 class InverseTrainer:
@@ -36,6 +60,33 @@ class InverseTrainer:
         ``n_bc`` (default ``batch_size // 3``) value points per step; ``loss_weights`` = (residual, BC, IC); ``max_norm``
         None: no clipping; ``capacity``: length of the loss and coefficient histories; ``sampler`` = "device" (the
         library's gather) or "torch" (``torch.randint`` rows and a copy)."""
+        self._check(model, dataset, operator)
+        self.B_res, self.n_ic, self.n_bc, dev = batch_prologue(model, batch_size, n_ic, n_bc, sampler)
+        self.model, self.operator, self.device, self.sampler = model, operator, dev, sampler
+        self.dataset = dataset.to(dev)
+        self.max_norm = max_norm
+        self.loss_weights = tuple(float(w) for w in loss_weights)
+        self._pack()
+        self.circuit = model.quantum_layer._circuit_for(dev)
+        self.optimizer, self.scheduler = model.optimizer, model.scheduler
+        self.attach(model, operator)
+        self.opt = self._make_opt_state(int(capacity))
+        self.fs = self._make_step()
+        ds = self.dataset
+        self._sampled = all(n_rows > 0 or n_batch == 0
+                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
+        if self._sampled:
+            self.fs.set_dataset(ds.segments())
+        self.fs.refresh_gates()
+        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        self._explicit = False
+        model._sync_fused_to_torch = self.sync_to_torch
+
+    FLAT_ATTR = "_inverse_flat"     # where the model keeps the flat buffer [model parameters | own entries]
+
+    @staticmethod
+    def _check(model, dataset, operator):
+        """The argument errors that need no GPU."""
         if not isinstance(dataset, TabulatedProblem):
             raise ValueError("InverseTrainer needs dataset= a TabulatedProblem (residual and observation segments)")
         if not isinstance(operator, LearnedOperator):
@@ -49,116 +100,50 @@ class InverseTrainer:
                              "defaults and give them to operator= (LearnedOperator(fixed=..., learn=...))")
         if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
             raise ValueError("InverseTrainer needs classic_network = [3, H, 1]")
-        if sampler not in ("device", "torch"):
-            raise ValueError("sampler must be 'device' or 'torch'")
         world, _ = _dist_info()
         if world > 1:
             raise ValueError("InverseTrainer is single-process: world_size > 1 is not supported")
-        n3 = batch_size // 3
-        self.B_res = int(batch_size)
-        self.n_ic = n3 if n_ic is None else int(n_ic)
-        self.n_bc = n3 if n_bc is None else int(n_bc)
-        if min(self.B_res, self.n_ic, self.n_bc) < 0 or self.B_res + self.n_ic + self.n_bc == 0:
-            raise ValueError("batch sizes must be non-negative and not all zero")
-        dev = model._resolve_device(model.device)
-        if dev is None or dev.type != "cuda":
-            raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
-        self.model, self.operator, self.device, self.sampler = model, operator, dev, sampler
-        self.dataset = dataset.to(dev)
-        self.max_norm = max_norm
-        self.loss_weights = tuple(float(w) for w in loss_weights)
-        self._pack()
-        self.circuit = model.quantum_layer._circuit_for(dev)
-        self.optimizer, self.scheduler = model.optimizer, model.scheduler
-        self.attach(model, operator)
-        self.opt = self._make_opt_state(int(capacity))
-        self.fs = _engine.InverseStep(self.circuit, model.hidden_width, self.flat, operator.base.tolist(),
-                                      operator.scale.tolist(), self.B_res, self.n_ic, self.n_bc, self.opt,
-                                      loss_weights=self.loss_weights)
-        ds = self.dataset
-        self._sampled = all(n_rows > 0 or n_batch == 0
-                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
-        if self._sampled:
-            self.fs.set_dataset(ds.segments())
-        self.fs.refresh_gates()
-        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
-        self._explicit = False
-        model._sync_fused_to_torch = self.sync_to_torch
 
     @staticmethod
-    def attach(model, operator):
-        """``operator.p`` joins ``model.optimizer`` as a second param group with the hyper-parameters of the first, if it is
-        not there yet (the constructor calls this; call it on a fresh model before loading a saved optimiser state)."""
-        opt = model.optimizer
-        if not any(p is operator.p for g in opt.param_groups for p in g["params"]):
+    def _own(operator):
+        """The trainable tensors behind the model's parameters, in the flat buffer's order."""
+        return [operator.p]
+
+    def _make_step(self):
+        op = self.operator
+        return _engine.InverseStep(self.circuit, self.model.hidden_width, self.flat, op.base.tolist(), op.scale.tolist(),
+                                   self.B_res, self.n_ic, self.n_bc, self.opt, loss_weights=self.loss_weights)
+
+    @classmethod
+    def attach(cls, model, operator):
+        """The own entries (``operator.p``; a balancer's ``log_vars``) join ``model.optimizer`` as a second param group with
+        the hyper-parameters of the first, if they are not there yet (the constructor calls this; call it on a fresh model
+        before loading a saved optimiser state)."""
+        opt, own = model.optimizer, cls._own(operator)
+        if not any(p is own[0] for g in opt.param_groups for p in g["params"]):
             g0 = opt.param_groups[0]
-            opt.add_param_group({"params": [operator.p], **{k: v for k, v in g0.items() if k != "params"}})
+            opt.add_param_group({"params": own, **{k: v for k, v in g0.items() if k != "params"}})
             sch = model.scheduler
             sch.min_lrs = list(sch.min_lrs) + [sch.min_lrs[0]] * (len(opt.param_groups) - len(sch.min_lrs))
 
     def _params(self):
-        return list(self.model.parameters()) + [self.operator.p]
+        return list(self.model.parameters()) + self._own(self.operator)
 
     def _pack(self):
-        """One flat buffer [model parameters | operator.p]; the model's own flat buffer becomes its head (a view), the way
-        ``model._pack`` builds it, and ``operator.p`` (base, scale) move to the device with p a view of the tail."""
-        model, op, dev = self.model, self.operator, self.device
-        if not model._packed_ok() or model._flat.device != dev:
-            model._pack(dev)
-        NP = model._flat.numel()
-        big = getattr(model, "_inverse_flat", None)
-        if not (big is not None and big.device == dev and big.numel() == NP + len(COEF_COLUMNS)
-                and model._flat.data_ptr() == big.data_ptr() and op.p.data_ptr() == big.data_ptr() + 4 * NP):
-            big = torch.cat([model._flat.detach(), op.p.detach().to(device=dev, dtype=torch.float32)])
-            off = 0
-            for p, k, pad in model._slots():
-                p.data = big[off:off + k].view(p.shape)
-                off += k
-            model._flat = big[:NP]
-            model._engines = {}
-            model._inverse_flat = big
-            op.p.data = big[NP:]
-            op.base.data = op.base.to(dev)
-            op.scale.data = op.scale.to(dev)
-        self.flat = model._inverse_flat
-        self.NP = NP
+        """One flat buffer [model parameters | own entries]: ``self.flat``, with ``self.NP`` model parameters in its head."""
+        self.flat = pack_with_tail(self.model, self._own(self.operator), self.FLAT_ATTR, self.device)
+        self.NP = self.model._flat.numel()
+        for b in self.operator.buffers():       # base / scale follow to the device
+            b.data = b.to(self.device)
 
     # -- optimiser state: continue from the torch optimiser / scheduler objects of the model (FusedTrainer's rule)
     def _make_opt_state(self, capacity):
-        opt, sch = self.optimizer, self.scheduler
-        g = opt.param_groups[0]
-        st = _engine.OptimState(self.flat.numel(), float(g["lr"]), self.device, hist_cap=capacity, betas=tuple(g["betas"]),
-                                eps=float(g["eps"]), max_norm=self.max_norm, factor=float(sch.factor),
-                                patience=int(sch.patience), threshold=float(sch.threshold), min_lr=float(sch.min_lrs[0]),
-                                sched_eps=float(sch.eps), loss_weights=self.loss_weights)
-        steps, off = 0, 0
-        for p in self._params():
-            s = opt.state.get(p, None)
-            k = p.numel()
-            if s:
-                st.m[off:off + k] = s["exp_avg"].reshape(-1).to(self.device)
-                st.v[off:off + k] = s["exp_avg_sq"].reshape(-1).to(self.device)
-                steps = int(s["step"])
-            off += k
-        st.write(best=float(sch.best), num_bad=int(sch.num_bad_epochs), step=steps, hist_base=steps)
-        return st
+        return opt_state_from_torch(self._params(), self.optimizer, self.scheduler, self.device, capacity, self.max_norm,
+                                    self.loss_weights)
 
     def sync_to_torch(self):
         """Mirror the device optimiser record into model.optimizer / model.scheduler (``save_state`` calls this)."""
-        rec = self.opt.read()
-        off = 0
-        for p in self._params():
-            k = p.numel()
-            self.optimizer.state[p] = {"step": torch.tensor(float(rec["step"])),
-                                       "exp_avg": self.opt.m[off:off + k].view(p.shape),
-                                       "exp_avg_sq": self.opt.v[off:off + k].view(p.shape)}
-            off += k
-        for g in self.optimizer.param_groups:
-            g["lr"] = rec["lr"]
-        sch = self.scheduler
-        sch.best, sch.num_bad_epochs = rec["best"], rec["num_bad_epochs"]
-        sch.last_epoch = rec["step"]
-        sch._last_lr = [rec["lr"]] * len(self.optimizer.param_groups)
+        sync_opt_state_to_torch(self.opt, self._params(), self.optimizer, self.scheduler)
 
     # -- batches
     def sample(self):
@@ -169,15 +154,7 @@ class InverseTrainer:
         if self.sampler == "device":
             return
         self._explicit = True
-        fs, dev = self.fs, self.device
-        (Xr, r), (Xi, ui), (Xb, ub) = self.dataset.segments()
-        for X, y, n, dX, dy, o in ((Xi, ui, self.n_ic, fs.X_val, fs.target_val, 0),
-                                   (Xb, ub, self.n_bc, fs.X_val, fs.target_val, self.n_ic),
-                                   (Xr, r, self.B_res, fs.X_res, fs.target_res, 0)):
-            if n:
-                idx = torch.randint(0, X.shape[0], (n,), device=dev)
-                dX[o:o + n] = X[idx]
-                dy[o:o + n] = y[idx]
+        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc))
 
     def load_batches(self, X_ic, X_bc, X_res, targets):
         """Use given batches: ``targets`` = (u_ic (n_ic,), u_bc (n_bc,), r_res (B_res,))."""

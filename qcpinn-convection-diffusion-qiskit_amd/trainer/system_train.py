@@ -15,7 +15,7 @@ import torch
 from ..data.tabulated import TabulatedSystem
 from ..hip import engine as _engine
 from ..hip import lib as _lib
-from .diffusion_train import _dist_info
+from .diffusion_train import _dist_info, batch_prologue, gather_rows, opt_state_from_torch, sync_opt_state_to_torch
 
 
 class SystemTrainer:
@@ -38,20 +38,10 @@ class SystemTrainer:
         K = int(getattr(model, "n_out", 1))
         if K != dataset.K:
             raise ValueError(f"the model has {K} outputs but the dataset prescribes {dataset.K}")
-        if sampler not in ("device", "torch"):
-            raise ValueError("sampler must be 'device' or 'torch'")
         world, _ = _dist_info()
         if world > 1:
             raise ValueError("SystemTrainer is single-process: world_size > 1 is not supported")
-        n3 = batch_size // 3
-        self.B_res = int(batch_size)
-        self.n_ic = n3 if n_ic is None else int(n_ic)
-        self.n_bc = n3 if n_bc is None else int(n_bc)
-        if min(self.B_res, self.n_ic, self.n_bc) < 0 or self.B_res + self.n_ic + self.n_bc == 0:
-            raise ValueError("batch sizes must be non-negative and not all zero")
-        dev = model._resolve_device(model.device)
-        if dev is None or dev.type != "cuda":
-            raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
+        self.B_res, self.n_ic, self.n_bc, dev = batch_prologue(model, batch_size, n_ic, n_bc, sampler)
         self.model, self.device, self.K, self.sampler = model, dev, K, sampler
         self.dataset = dataset.to(dev)
         self.max_norm = max_norm
@@ -79,40 +69,12 @@ class SystemTrainer:
 
     # -- optimiser state: continue from the torch optimiser / scheduler objects of the model (FusedTrainer's rule)
     def _make_opt_state(self, capacity):
-        opt, sch = self.optimizer, self.scheduler
-        g = opt.param_groups[0]
-        st = _engine.OptimState(self.NP, float(g["lr"]), self.device, hist_cap=capacity, betas=tuple(g["betas"]),
-                                eps=float(g["eps"]), max_norm=self.max_norm, factor=float(sch.factor),
-                                patience=int(sch.patience), threshold=float(sch.threshold), min_lr=float(sch.min_lrs[0]),
-                                sched_eps=float(sch.eps), loss_weights=self.loss_weights)
-        steps, off = 0, 0
-        for p in self.model.parameters():
-            s = opt.state.get(p, None)
-            k = p.numel()
-            if s:
-                st.m[off:off + k] = s["exp_avg"].reshape(-1).to(self.device)
-                st.v[off:off + k] = s["exp_avg_sq"].reshape(-1).to(self.device)
-                steps = int(s["step"])
-            off += k
-        st.write(best=float(sch.best), num_bad=int(sch.num_bad_epochs), step=steps, hist_base=steps)
-        return st
+        return opt_state_from_torch(self.model.parameters(), self.optimizer, self.scheduler, self.device, capacity,
+                                    self.max_norm, self.loss_weights)
 
     def sync_to_torch(self):
         """Mirror the device optimiser record into model.optimizer / model.scheduler (``save_state`` calls this)."""
-        rec = self.opt.read()
-        off = 0
-        for p in self.model.parameters():
-            k = p.numel()
-            self.optimizer.state[p] = {"step": torch.tensor(float(rec["step"])),
-                                       "exp_avg": self.opt.m[off:off + k].view(p.shape),
-                                       "exp_avg_sq": self.opt.v[off:off + k].view(p.shape)}
-            off += k
-        for g in self.optimizer.param_groups:
-            g["lr"] = rec["lr"]
-        sch = self.scheduler
-        sch.best, sch.num_bad_epochs = rec["best"], rec["num_bad_epochs"]
-        sch.last_epoch = rec["step"]
-        sch._last_lr = [rec["lr"]]
+        sync_opt_state_to_torch(self.opt, self.model.parameters(), self.optimizer, self.scheduler)
 
     # -- batches
     def sample(self):
@@ -123,16 +85,7 @@ class SystemTrainer:
         if self.sampler == "device":
             return
         self._explicit = True
-        fs, dev = self.fs, self.device
-        (Xr, R), (Xi, Ui), (Xb, Ub) = self.dataset.segments()
-        for X, Y, n, dX, dY, o in ((Xi, Ui, self.n_ic, fs.X_val, fs.target_val, 0),
-                                   (Xb, Ub, self.n_bc, fs.X_val, fs.target_val, self.n_ic),
-                                   (Xr, R, self.B_res, fs.X_res, fs.target_res, 0)):
-            if n:
-                idx = torch.randint(0, X.shape[0], (n,), device=dev)
-                dX[o:o + n] = X[idx]
-                if Y is not None:
-                    dY[:, o:o + n] = Y[idx].t()
+        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), batch_minor=True)
 
     def load_batches(self, X_ic, X_bc, X_res, targets):
         """Use given batches: ``targets`` = (U_ic (n_ic, K), U_bc (n_bc, K), R_res (B_res, n_eq) | None)."""
