@@ -730,6 +730,69 @@ int qc_causal_fold(float* part_dev, int64_t rows, int64_t rows_res, int64_t stri
 int qc_fused_pinn_causal_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_causal* causal, int phases,
                               void* stream);
 
+/* ---- gradient-norm loss weights (Wang, Teng, Perdikaris 2021, "learning-rate annealing", Algorithm 1): the analytic, the
+ * tabulated or the coefficient step with the two data terms weighted from this step's own per-class gradients,
+ *   hat_k = max_j |G_res[j]| / mean_j |G_k[j]|,   lam_k <- (1 - alpha) lam_k + alpha hat_k,   k in {BC, IC},
+ * and the descent direction G_res + lam_bc G_bc + lam_ic G_ic.  G_c is the gradient of class c as the rows carry it, the
+ * loss weight and the mean included (G_k = w_k grad L_k): with unit loss weights the rule is the paper's.
+ * Nothing in the stages changes.  Every stage writes one partial row per 64-point tile, the residual tiles rows
+ * [0, rows_res), value tile k row rows_res + k, and the value batch holds its IC points first: with n_ic a multiple of 64
+ * (or one value class empty) every row belongs to ONE class.  The class fold reduces the rows of each class in place to
+ * at most 32 (block (cb, rs, c) folds rows lo_c + rs, lo_c + rs + RS_c, .. into row lo_c + rs, RS_c = min(n_c, 32), in the
+ * summation order of the plain fold on the class's rows alone).  A single-block launch then forms G_c[j], the left-to-right
+ * sum of the class's surviving rows, for all NP + 3 columns, and, when n_steps % every == 0,
+ *   m_r = max_{j<NP} |G_res[j]|,   a_k = (1/NP) sum_{j<NP} |G_k[j]|   (sums in double, fixed order),
+ *   lam_k = min(lam_max, (1 - alpha) lam_k + alpha m_r / a_k)          (formed in double, stored in fp32);
+ * lam_k keeps its value when class k is empty, when a_k = 0 and when m_r or a_k is not finite (hat_k is then recorded as
+ * 0).  It writes flat[j] = fmaf(lam_ic, G_ic[j], fmaf(lam_bc, G_bc[j], G_res[j])) for j < NP with the weights AFTER this
+ * update, and flat[NP..NP+2] = L_r, L_bc, L_ic, the unscaled column sums (G_res + G_ic) + G_bc.  The unchanged optimiser
+ * launch follows on flat: it clips the combined gradient, and its record, the loss history and the plateau scheduler see
+ * w_res L_r + w_bc L_bc + w_ic L_ic as in every other step, comparable from step to step while lam moves.
+ * state_dev: the record of QC_GRADNORM_STATE_WORDS 4-byte words
+ *   {float lam_bc, lam_ic; int32 n_steps, hist_base, n_updates; float m_r, a_bc, a_ic, hat_bc, hat_ic; 6 words of 0},
+ * seeded by the init call below: lam of the NEXT step, the counters, and the statistics of the last update.  Every call
+ * stores the row {lam_bc, lam_ic, m_r, a_bc, a_ic, wl, updated} (QC_GRADNORM_HIST_COLS floats) to row n_steps - hist_base
+ * of hist_dev ([hist_cap][QC_GRADNORM_HIST_COLS], optional) when that row lies in the buffer: the weights the step used,
+ * the statistics of the record (this step's when updated = 1, else those of the last update),
+ * wl = w_res L_r + lam_bc w_bc L_bc + lam_ic w_ic L_ic, and 1 or 0; then n_steps grows by 1. */
+#define QC_GRADNORM_STATE_WORDS 16
+#define QC_GRADNORM_HIST_COLS 7
+typedef struct qc_step_gradnorm {
+  float alpha;                         /* in [0, 1]; 0 keeps the weights */
+  float lam_max;                       /* finite and > 0 */
+  int32_t every;                       /* >= 1: the weights move on the steps with n_steps % every == 0 */
+  float lam0_bc, lam0_ic;              /* finite and > 0 (read by the init call only) */
+  float* state_dev;                    /* the record above, 4-byte aligned */
+  float* hist_dev; int32_t hist_cap;   /* [cap][QC_GRADNORM_HIST_COLS] or NULL/0 */
+} qc_step_gradnorm;
+
+/* Seeds the record: lam = lam0, every counter and statistic 0.  QC_ERR_ARG: a NULL or misaligned state_dev, gn NULL or not
+ * valid (as the gradient-norm step refuses it). */
+int qc_gradnorm_init(float* state_dev, const qc_step_gradnorm* gn, void* stream);
+
+/* The two launches above on any row matrix: rows [0, rows_res) are the residual class, the next rows_ic rows the IC class,
+ * the remaining rows - rows_res - rows_ic the BC class; the first level is in place (part_dev is overwritten like the
+ * step's own matrix, rows outside the classes' survivors and columns >= ncols are not written), flat_dev[ncols] receives
+ * the combination (the last three columns are the loss columns, wl is formed with unit loss weights) and class_dev
+ * ([3][ncols]: G_res, G_ic, G_bc; or NULL) the class sums.  Two runs on equal inputs and records are bit-identical.
+ * QC_ERR_ARG: a NULL part_dev or flat_dev, ncols < 4, stride < ncols, rows outside [1, 2^31), rows_res or rows_ic negative
+ * or rows_res + rows_ic > rows, gn NULL or not valid. */
+int qc_gradnorm_fold(float* part_dev, int64_t rows, int64_t rows_res, int64_t rows_ic, int64_t stride, int ncols,
+                     const qc_step_gradnorm* gn, float* flat_dev, float* class_dev, void* stream);
+
+/* The fused step under gradient-norm weights.  data NULL: the analytic step (the problems and the draw of the residual
+ * step); data alone: the tabulated step; data and coef: the coefficient step.  All three circuit families, both encodings
+ * and both forms (merged and two-stream) are the underlying step's.  QC_PHASE_GRADS: the stages, the class fold and the
+ * combination; the weights move here and flat_dev then holds the combined gradient and the loss columns.
+ * QC_PHASE_UPDATE: the plain optimiser launch on flat_dev.  A GRADS | UPDATE call has two launches more than the
+ * tabulated step's.  Refused before any launch: desc->comm set: QC_ERR_UNSUPPORTED (the class gradients of the ranks
+ * would need a reduction of 3 (NP + 3) entries ahead of the ratio); QC_ERR_ARG: gn NULL, a NULL or misaligned state_dev,
+ * alpha outside [0, 1], every < 1, a non-finite or non-positive lam_max, lam0_bc or lam0_ic, hist_cap < 0 or a NULL
+ * hist_dev with a positive cap, n_ic not a multiple of 64 while both n_ic and B_val - n_ic are positive (a value tile
+ * would mix the classes), coef without data, whatever the underlying step refuses. */
+int qc_fused_pinn_gradnorm_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef,
+                                const qc_step_gradnorm* gn, int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

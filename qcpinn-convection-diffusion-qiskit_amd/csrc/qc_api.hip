@@ -937,8 +937,11 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
 // `sys` (qc_fused_pinn_system_step, validated by its entry): K last-layer rows in the layout, the system post stage in
 // both pipelines, always the two-stream form; `tg` is then not read.
 // `cz` (qc_fused_pinn_causal_step, validated by its entry): the causal fold in place of the plain row fold.
+// `gn` (qc_fused_pinn_gradnorm_step, validated by its entry, never with a communicator): the class fold and the
+// combination in place of both reduction levels; the optimiser launch then takes flat_dev.
 static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches& b, const QcSource& src, int phases,
-                      void* stream, const qc_step_system* sys = nullptr, const QcCausal* cz = nullptr) {
+                      void* stream, const qc_step_system* sys = nullptr, const QcCausal* cz = nullptr,
+                      const QcGradnorm* gn = nullptr) {
   if (!d->part_dev || !d->flat_dev || !src.holds(b)) return QC_ERR_ARG;
   if (!sys && ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem))) return QC_ERR_ARG;
   int rc = check_step_desc(d, false, nullptr);
@@ -990,7 +993,12 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   }
   // the balanced step: the optimiser launch forms the balancer's three gradient entries from the reduced loss columns
   const QcBal* bal = !sys && tg.kind == QC_TARGET_BAL ? &tg.bal : nullptr;
-  if (phases & QC_PHASE_GRADS) {
+  if ((phases & QC_PHASE_GRADS) && gn) {
+    // value tile k wrote row rows_res + k in every stage and the IC points come first: the IC class ends on a tile boundary
+    const int64_t rows_ic = b.n_bc > 0 ? b.n_ic / 64 : rows_val;
+    qc_opt_gradnorm_fold(d->part_dev, rows_res, rows_ic, rows_val - rows_ic, d->part_stride, L.NP + 3, *gn, d->flat_dev, nullptr, st);
+    if ((rc = after_launch())) return rc;
+  } else if (phases & QC_PHASE_GRADS) {
     // the step owns its partial-row matrix, so the reduction folds it in place (two levels, fixed order);
     // with the update phase in the same call the second level rides in the optimiser launch
     const int RS = cz ? qc_opt_causal_fold(d->part_dev, rows, rows_res, d->part_stride, L.NP + 3, *cz, st)
@@ -1019,8 +1027,10 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
 // the six entry points: targets, batches and source from the records each was given (the kind of step is decided here)
 // `lr` (the inverse step, validated by its entry, never with `cf`): the trainable operator, with or without residual points
 // `bl` (the balanced step, validated by its entry, alone): the tabulated step under balanced loss weights
+// `gn` (the gradient-norm step, validated by its entry, never with `ad`, `lr` or `bl`): gradient-norm loss weights
 static int step_from(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_adapt* ad, int phases,
-                     void* stream, const qc_step_learn* lr = nullptr, const qc_step_balance* bl = nullptr) {
+                     void* stream, const qc_step_learn* lr = nullptr, const qc_step_balance* bl = nullptr,
+                     const QcGradnorm* gn = nullptr) {
   if (!d) return QC_ERR_ARG;
   const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
   const QcTarget tg = !t      ? QcTarget{}
@@ -1029,7 +1039,7 @@ static int step_from(const qc_step_desc* d, const qc_step_data* t, const qc_step
                       : table ? QcTarget::with_coef(t->target_res_dev, t->target_val_dev, cf->coef_res_dev)
                               : QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u);
   return fused_step(d, tg, step_batches(d, t), make_source(t, cf, cf ? cf->coef_res_dev : nullptr, ad, d->sample_bc_face_points),
-                    phases, stream);
+                    phases, stream, nullptr, nullptr, gn);
 }
 
 int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream) {
@@ -1142,6 +1152,56 @@ int qc_fused_pinn_causal_step(const qc_step_desc* d, const qc_step_data* t, cons
   const QcCausal cz = to_causal(causal, d->sample_off_res / 64);
   return fused_step(d, QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u), step_batches(d, t), s, phases, stream,
                     nullptr, &cz);
+}
+
+// ---- gradient-norm loss weights
+static_assert(QC_GRADNORM_WORDS == QC_GRADNORM_STATE_WORDS && QC_GRADNORM_COLS == QC_GRADNORM_HIST_COLS, "gradient-norm record");
+// THE validity rule of a gradient-norm record: an aligned state record, alpha in [0, 1], every >= 1, lam_max and the two
+// starting weights finite and positive, a history buffer behind a positive capacity
+static bool gradnorm_ok(const qc_step_gradnorm* g) {
+  if (!g || !g->state_dev || ((uintptr_t)g->state_dev & 3)) return false;
+  if (!(g->alpha >= 0.f && g->alpha <= 1.f) || g->every < 1) return false;
+  if (!pos_finite(g->lam_max) || !pos_finite(g->lam0_bc) || !pos_finite(g->lam0_ic)) return false;
+  return g->hist_cap >= 0 && (g->hist_cap == 0 || g->hist_dev);
+}
+static QcGradnorm to_gradnorm(const qc_step_gradnorm* g, float w_res, float w_bc, float w_ic) {
+  QcGradnorm q;
+  q.alpha = g->alpha; q.lam_max = g->lam_max; q.every = g->every;
+  q.w[0] = w_res; q.w[1] = w_bc; q.w[2] = w_ic;
+  q.rec = g->state_dev;
+  const bool hist = g->hist_dev && g->hist_cap > 0;
+  q.hist = hist ? g->hist_dev : nullptr;
+  q.hist_cap = hist ? g->hist_cap : 0;
+  return q;
+}
+
+int qc_gradnorm_init(float* state_dev, const qc_step_gradnorm* gn, void* stream) {
+  if (!state_dev || ((uintptr_t)state_dev & 3) || !gn) return QC_ERR_ARG;
+  qc_step_gradnorm g = *gn;   // the rule asks for a record: the one being seeded serves
+  g.state_dev = state_dev;
+  if (!gradnorm_ok(&g)) return QC_ERR_ARG;
+  qc_opt_gradnorm_init(state_dev, gn->lam0_bc, gn->lam0_ic, (hipStream_t)stream);
+  return after_launch();
+}
+
+int qc_gradnorm_fold(float* part, int64_t rows, int64_t rows_res, int64_t rows_ic, int64_t stride, int ncols,
+                     const qc_step_gradnorm* gn, float* flat, float* class_out, void* stream) {
+  if (!part || !flat || ncols < 4 || stride < ncols || rows < 1 || rows >= ((int64_t)1 << 31) || !gradnorm_ok(gn)) return QC_ERR_ARG;
+  if (rows_res < 0 || rows_ic < 0 || rows_res > rows || rows_ic > rows - rows_res) return QC_ERR_ARG;
+  qc_opt_gradnorm_fold(part, rows_res, rows_ic, rows - rows_res - rows_ic, stride, ncols, to_gradnorm(gn, 1.f, 1.f, 1.f), flat,
+                       class_out, (hipStream_t)stream);
+  return after_launch();
+}
+
+int qc_fused_pinn_gradnorm_step(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_gradnorm* gn,
+                                int phases, void* stream) {
+  if (!d || !gradnorm_ok(gn) || (cf && !t)) return QC_ERR_ARG;
+  if (d->comm) return QC_ERR_UNSUPPORTED;   // the class gradients of the ranks would need a reduction ahead of the ratio
+  if (d->n_ic < 0 || d->B_val < d->n_ic) return QC_ERR_ARG;
+  if (d->n_ic > 0 && d->B_val > d->n_ic && d->n_ic % 64 != 0) return QC_ERR_ARG;   // a value tile would mix IC and BC points
+  if (d->part_rows_cap >= ((int64_t)1 << 31)) return QC_ERR_ARG;
+  const QcGradnorm q = to_gradnorm(gn, d->hyper.w_res, d->hyper.w_bc, d->hyper.w_ic);
+  return step_from(d, t, cf, nullptr, phases, stream, nullptr, nullptr, &q);
 }
 
 // Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pipe_forward, then

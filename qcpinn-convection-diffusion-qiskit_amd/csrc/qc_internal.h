@@ -348,6 +348,25 @@ struct QcCausal {
 int qc_opt_causal_init(float* rec, int M, float eps0, hipStream_t);
 // weights from column ncols - 3 of rows [0, rows_res), then qc_opt_fold_rows with residual row r scaled by its slab's weight
 int qc_opt_causal_fold(float* part, int64_t rows, int64_t rows_res, int64_t stride, int ncols, const QcCausal& cz, hipStream_t);
+// Gradient-norm loss weights (the gradient-norm step).  rec: the device record of QC_GRADNORM_WORDS 4-byte words {float
+// lam_bc, lam_ic; int n_steps, hist_base, n_updates; float m_r, a_bc, a_ic, hat_bc, hat_ic; 0 ..} (== the layout
+// documented at qc_step_gradnorm in the public header); w: the loss weights of the lambda-weighted loss in the history row.
+constexpr int QC_GRADNORM_WORDS = 16, QC_GRADNORM_COLS = 7;
+struct QcGradnorm {
+  float alpha, lam_max;
+  int every;
+  float w[3];   // residual, BC, IC
+  float* rec;
+  float* hist;
+  int hist_cap;
+};
+int qc_opt_gradnorm_init(float* rec, float lam_bc, float lam_ic, hipStream_t);
+// The three row classes of a partial-row matrix: residual rows [0, n_res), IC rows behind them, BC rows behind those.  The
+// class fold (in place, every class like qc_opt_fold_rows on its own rows), then the single-block launch that forms the
+// class sums, moves the weights and writes flat[ncols] = [G_res + lam_bc G_bc + lam_ic G_ic | L_r, L_bc, L_ic];
+// class_out: [3][ncols] (G_res, G_ic, G_bc) or null.
+int qc_opt_gradnorm_fold(float* part, int64_t n_res, int64_t n_ic, int64_t n_bc, int64_t stride, int ncols, const QcGradnorm& gn,
+                         float* flat, float* class_out, hipStream_t);
 // qc_lbfgs.hip: floats of a workspace; zero it and write its record; make the next call a first evaluation; one call
 size_t qc_lbfgs_words(int NP, int m);
 int qc_lbfgs_init_launch(void* ws, int NP, int m, hipStream_t);

@@ -195,16 +195,36 @@ struct QcCausalRows {
 __device__ __forceinline__ float qc_causal_w(const int64_t r, const QcCausalRows& c) {
   return r < c.rows_res ? c.W[(uint32_t)((int)r + c.tile_off) % (uint32_t)c.M] : 1.f;
 }
+// CW = (QcClassRows) (the gradient-norm step): three folds in one launch, the class in blockIdx.z.  Class c owns rows
+// [lo_c, lo_c + n_c); block (cb, rs, c) folds rows lo_c + rs, lo_c + rs + RS_c, ... into row lo_c + rs, RS_c = min(n_c, 32),
+// exactly as the plain fold would fold the class's rows alone; blocks with rs >= RS_c (an empty class: all of them) return.
+struct QcClassRows {
+  int lo_ic, lo_bc;          // first row of the IC and of the BC class (the residual class starts at row 0)
+  int n_res, n_ic, n_bc;
+};
 constexpr int QC_RED_WAVES = 8;
 template <class... CW>
 __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restrict__ part, int64_t rows, int64_t stride,
                                                                  int ncols, CW... cw) {
-  static_assert(sizeof...(CW) == 0 || (sizeof...(CW) == 1 && (std::is_same_v<CW, QcCausalRows> && ...)), "() or (QcCausalRows)");
-  constexpr bool CAUSAL = sizeof...(CW) == 1;
+  static_assert(sizeof...(CW) == 0 ||
+                    (sizeof...(CW) == 1 && ((std::is_same_v<CW, QcCausalRows> || std::is_same_v<CW, QcClassRows>) && ...)),
+                "(), (QcCausalRows) or (QcClassRows)");
+  constexpr bool CAUSAL = (std::is_same_v<CW, QcCausalRows> || ...);
+  constexpr bool CLASSES = (std::is_same_v<CW, QcClassRows> || ...);
   __shared__ float s[QC_RED_WAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = blockIdx.x * 64 + lane;
-  const int RS = gridDim.y, rs = blockIdx.y;
+  const int rs = blockIdx.y;
+  int RS = gridDim.y;
+  if constexpr (CLASSES) {
+    const QcClassRows& c = std::get<0>(std::tie(cw...));
+    const int z = blockIdx.z;
+    const int lo = z == 0 ? 0 : (z == 1 ? c.lo_ic : c.lo_bc), n = z == 0 ? c.n_res : (z == 1 ? c.n_ic : c.n_bc);
+    RS = n < 32 ? n : 32;
+    if (rs >= RS) return;   // (the whole block: nobody waits at the barrier below)
+    part += (int64_t)lo * stride;
+    rows = n;
+  }
   // rows r, r + hop, r + 2 hop, ... of this wave: the first EIGHT are requested together (config 2 has ~7 per wave: one
   // memory round trip instead of four dependent ones), then summed in the same fixed order as a two-chain loop
   float a0 = 0.f, a1 = 0.f;
@@ -567,4 +587,197 @@ int qc_opt_causal_fold(float* part, int64_t rows, int64_t rows_res, int64_t stri
   hipLaunchKernelGGL((k_fold_rows<QcCausalRows>), dim3(qc_ceil_div(ncols, 64), RS), dim3(64 * QC_RED_WAVES), 0, st, part, rows,
                      stride, ncols, cw);
   return RS;
+}
+
+// ------------------------------------------------------------------ gradient-norm loss weights (the gradient-norm step)
+// Wang, Teng, Perdikaris 2021, Algorithm 1.  The rows of a tile belong to one loss class, so the class fold above leaves
+// the three per-class gradients in at most 32 rows each; one single-block launch adds them, moves the weights and writes
+// the combined gradient the unchanged optimiser launch then takes.
+namespace {
+
+struct QcClassSurv {   // the surviving rows of the class fold: class c in rows [lo_c, lo_c + RS_c), lo_res = 0
+  int lo_ic, lo_bc;
+  int RS_res, RS_ic, RS_bc;
+  int n_ic, n_bc;        // rows of the value classes before the fold (0: an empty class keeps its weight)
+};
+
+// The three class sums of columns i0, i0 + 1024, .. (K of them) of one thread: G_c[i] = the left-to-right sum of the class's
+// RS_c <= 32 surviving rows.  R rows of all 3 K streams are requested together (a single-block kernel is a chain of
+// memory latencies: the small batches take one round trip, 32 rows per class 32 / R); a row a class does not have adds +0.f.
+template <int K>
+__device__ __forceinline__ void qc_class_sums(const float* __restrict__ part, const int64_t stride, const QcClassSurv& sv,
+                                              const int ncols, const int i0, float (&gr)[K], float (&gi)[K], float (&gb)[K]) {
+  const float* p_ic = part + (int64_t)sv.lo_ic * stride;
+  const float* p_bc = part + (int64_t)sv.lo_bc * stride;
+  const int RS = sv.RS_res > sv.RS_ic ? (sv.RS_res > sv.RS_bc ? sv.RS_res : sv.RS_bc) : (sv.RS_ic > sv.RS_bc ? sv.RS_ic : sv.RS_bc);
+#pragma unroll
+  for (int k = 0; k < K; ++k) gr[k] = gi[k] = gb[k] = 0.f;
+  constexpr int R = K > 1 ? 4 : 8;   // 36 or 24 loads in flight: what the 128 registers of a 1024-thread block hold
+  for (int j = 0; j < RS; j += R) {
+    float xr[K][R], xi[K][R], xb[K][R];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = i0 + k * 1024;
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const int64_t o = (int64_t)(j + q) * stride + i;
+        xr[k][q] = (i < ncols && j + q < sv.RS_res) ? part[o] : 0.f;
+        xi[k][q] = (i < ncols && j + q < sv.RS_ic) ? p_ic[o] : 0.f;
+        xb[k][q] = (i < ncols && j + q < sv.RS_bc) ? p_bc[o] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        gr[k] += xr[k][q];
+        gi[k] += xi[k][q];
+        gb[k] += xb[k][q];
+      }
+  }
+}
+// max that keeps a NaN once it has seen one (fmaxf would drop it, and a NaN must stop the update)
+__device__ __forceinline__ float qc_max_nan(const float m, const float x) { return (x > m || x != x) ? x : m; }
+
+// One block.  FAST (ncols <= 3 * 1024): thread t owns columns t, t + 1024, t + 2048 and keeps their three class sums in
+// registers; else it strides over the columns and forms the sums a second time behind the barrier (same order, same
+// bits).  With n_steps % every == 0 the statistics m_r = max |G_res|, a_k = mean |G_k| over the NP gradient columns: one
+// value per thread (columns ascending, sums in double), a butterfly over lane distances 32 .. 1, then the 16 wave values
+// in ascending order on every thread; lam_k = min(lam_max, (1 - alpha) lam_k + alpha m_r / a_k) in double, stored as
+// float, unless class k is empty, a_k is 0 or m_r or a_k is not finite.  Everything of the record that is read is read
+// ahead of the barrier, written behind it.
+template <bool FAST>
+__global__ void __launch_bounds__(1024) k_gradnorm_combine(const float* __restrict__ part, int64_t stride, int ncols,
+                                                           QcClassSurv sv, QcGradnorm g, float* __restrict__ flat,
+                                                           float* __restrict__ class_out) {
+  __shared__ float s_m[16];
+  __shared__ double s_a[2][16];
+  __shared__ float s_loss[3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NP = ncols - 3;
+  int* irec = reinterpret_cast<int*>(g.rec);
+  const float lam_bc0 = g.rec[0], lam_ic0 = g.rec[1];
+  const int n_steps = irec[2], hist_base = irec[3], n_updates = irec[4];
+  float m_r = g.rec[5], a_bc = g.rec[6], a_ic = g.rec[7], hat_bc = g.rec[8], hat_ic = g.rec[9];
+  const bool update = n_steps % g.every == 0;
+  constexpr int K = FAST ? QC_ADAM_K : 1;
+  float gr[K], gi[K], gb[K];
+  float mx = 0.f;
+  double sb = 0.0, si = 0.0;
+  for (int i0 = tid; i0 < ncols; i0 += K * 1024) {   // FAST: one pass
+    qc_class_sums<K>(part, stride, sv, ncols, i0, gr, gi, gb);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = i0 + k * 1024;
+      if (i < NP) {
+        mx = qc_max_nan(mx, fabsf(gr[k]));
+        sb += (double)fabsf(gb[k]);
+        si += (double)fabsf(gi[k]);
+      } else if (i < ncols) {
+        s_loss[i - NP] = (gr[k] + gi[k]) + gb[k];
+      }
+    }
+  }
+  if (update) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      mx = qc_max_nan(mx, __shfl_xor(mx, o));
+      sb += __shfl_xor(sb, o);
+      si += __shfl_xor(si, o);
+    }
+    if (lane == 0) {
+      s_m[wave] = mx;
+      s_a[0][wave] = sb;
+      s_a[1][wave] = si;
+    }
+  }
+  __syncthreads();
+  float lam_bc = lam_bc0, lam_ic = lam_ic0;
+  if (update) {
+    float m = s_m[0];
+    double b = s_a[0][0], c = s_a[1][0];
+    for (int w = 1; w < 16; ++w) {
+      m = qc_max_nan(m, s_m[w]);
+      b += s_a[0][w];
+      c += s_a[1][w];
+    }
+    const double mr = (double)m, ab = b / (double)NP, ai = c / (double)NP, al = (double)g.alpha;
+    const bool ok_bc = sv.n_bc > 0 && isfinite(mr) && isfinite(ab) && ab > 0.0;
+    const bool ok_ic = sv.n_ic > 0 && isfinite(mr) && isfinite(ai) && ai > 0.0;
+    const double hb = ok_bc ? mr / ab : 0.0, hi_ = ok_ic ? mr / ai : 0.0;
+    if (ok_bc) lam_bc = (float)fmin((double)g.lam_max, (1.0 - al) * (double)lam_bc0 + al * hb);
+    if (ok_ic) lam_ic = (float)fmin((double)g.lam_max, (1.0 - al) * (double)lam_ic0 + al * hi_);
+    m_r = m;
+    a_bc = (float)ab;
+    a_ic = (float)ai;
+    hat_bc = (float)hb;
+    hat_ic = (float)hi_;
+  }
+  for (int i0 = tid; i0 < ncols; i0 += K * 1024) {
+    if constexpr (!FAST) qc_class_sums<K>(part, stride, sv, ncols, i0, gr, gi, gb);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = i0 + k * 1024;
+      if (i >= ncols) continue;
+      flat[i] = i < NP ? fmaf(lam_ic, gi[k], fmaf(lam_bc, gb[k], gr[k])) : s_loss[i - NP];
+      if (class_out != nullptr) {
+        class_out[i] = gr[k];
+        class_out[(int64_t)ncols + i] = gi[k];
+        class_out[2 * (int64_t)ncols + i] = gb[k];
+      }
+    }
+  }
+  if (tid == 0) {
+    const float wl = fmaf(lam_ic * g.w[2], s_loss[2], fmaf(lam_bc * g.w[1], s_loss[1], g.w[0] * s_loss[0]));
+    g.rec[0] = lam_bc;
+    g.rec[1] = lam_ic;
+    irec[2] = n_steps + 1;
+    if (update) {
+      irec[4] = n_updates + 1;
+      g.rec[5] = m_r;
+      g.rec[6] = a_bc;
+      g.rec[7] = a_ic;
+      g.rec[8] = hat_bc;
+      g.rec[9] = hat_ic;
+    }
+    const int hi = n_steps - hist_base;
+    if (g.hist != nullptr && hi >= 0 && hi < g.hist_cap) {
+      float* row = g.hist + (int64_t)hi * QC_GRADNORM_COLS;
+      row[0] = lam_bc;
+      row[1] = lam_ic;
+      row[2] = m_r;
+      row[3] = a_bc;
+      row[4] = a_ic;
+      row[5] = wl;
+      row[6] = update ? 1.f : 0.f;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) k_gradnorm_init(float* __restrict__ rec, float lam_bc, float lam_ic) {
+  const int i = threadIdx.x;
+  if (i < QC_GRADNORM_WORDS) rec[i] = i == 0 ? lam_bc : (i == 1 ? lam_ic : 0.f);   // (0.f: the zero word of the counters too)
+}
+
+}  // namespace
+
+int qc_opt_gradnorm_init(float* rec, float lam_bc, float lam_ic, hipStream_t st) {
+  hipLaunchKernelGGL(k_gradnorm_init, dim3(1), dim3(64), 0, st, rec, lam_bc, lam_ic);
+  return QC_OK;
+}
+
+int qc_opt_gradnorm_fold(float* part, int64_t n_res, int64_t n_ic, int64_t n_bc, int64_t stride, int ncols, const QcGradnorm& gn,
+                         float* flat, float* class_out, hipStream_t st) {
+  const auto surv = [](int64_t n) { return (int)(n < 32 ? n : 32); };
+  const QcClassSurv sv = {(int)n_res, (int)(n_res + n_ic), surv(n_res), surv(n_ic), surv(n_bc), (int)n_ic, (int)n_bc};
+  const int RS = sv.RS_res > sv.RS_ic ? (sv.RS_res > sv.RS_bc ? sv.RS_res : sv.RS_bc) : (sv.RS_ic > sv.RS_bc ? sv.RS_ic : sv.RS_bc);
+  if (RS > 0) {
+    const QcClassRows cr = {sv.lo_ic, sv.lo_bc, (int)n_res, (int)n_ic, (int)n_bc};
+    hipLaunchKernelGGL((k_fold_rows<QcClassRows>), dim3(qc_ceil_div(ncols, 64), RS, 3), dim3(64 * QC_RED_WAVES), 0, st, part,
+                       n_res + n_ic + n_bc, stride, ncols, cr);
+  }
+  if (ncols <= QC_ADAM_K * 1024)
+    hipLaunchKernelGGL((k_gradnorm_combine<true>), dim3(1), dim3(1024), 0, st, (const float*)part, stride, ncols, sv, gn, flat, class_out);
+  else
+    hipLaunchKernelGGL((k_gradnorm_combine<false>), dim3(1), dim3(1024), 0, st, (const float*)part, stride, ncols, sv, gn, flat, class_out);
+  return QC_OK;
 }

@@ -882,3 +882,57 @@ class CausalStep(FusedStep):
             rec = self.read_state()
             steps = rec["n_steps"] - rec["hist_base"]
         return self.causal_hist[: max(0, min(int(steps), self.causal_cap))].cpu().numpy()
+
+
+class GradNormStep(FusedStep):
+    """One ``qc_fused_pinn_gradnorm_step`` descriptor over fixed-size resident batches: the analytic, the tabulated or the
+    coefficient step (whichever the engine is configured for, as ``FusedStep``) under gradient-norm loss weights (Wang,
+    Teng, Perdikaris 2021): lam_k <- (1 - alpha) lam_k + alpha max|G_res| / mean|G_k| for k = BC, IC every ``every`` steps,
+    and the update along G_res + lam_bc G_bc + lam_ic G_ic.  With both value classes present ``n_ic`` must be a multiple
+    of 64, so that no 64-point tile of the value batch mixes IC and BC points.  ``state`` is the device record {lam_bc,
+    lam_ic, n_steps, hist_base, n_updates, m_r, a_bc, a_ic, hat_bc, hat_ic, 0..}; ``gradnorm_hist`` [capacity, 7] receives
+    (lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated) of every step."""
+
+    _FLOATS = ("m_r", "a_bc", "a_ic", "hat_bc", "hat_ic")
+
+    def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, alpha: float = 0.1,
+                 every: int = 10, lam_max: float = 1e4, init=(1.0, 1.0), capacity: int = 0, counts=None):
+        if n_ic > 0 and n_bc > 0 and n_ic % 64:
+            raise L.QcError(f"the gradient-norm step needs n_ic a multiple of 64 when IC and BC points are both present, got {n_ic}")
+        dev = eng.device
+        self.gradnorm_cap = int(capacity)
+        self.state = torch.zeros(L.QC_GRADNORM_STATE_WORDS, dtype=torch.float32, device=dev)
+        self.gradnorm_hist = torch.zeros(max(self.gradnorm_cap, 1), L.QC_GRADNORM_HIST_COLS, dtype=torch.float32, device=dev)
+        self.gn = L.QcStepGradnorm(float(alpha), float(lam_max), int(every), float(init[0]), float(init[1]),
+                                   self.state.data_ptr(), self.gradnorm_hist.data_ptr() if self.gradnorm_cap > 0 else None,
+                                   self.gradnorm_cap)
+        super().__init__(eng, B_res, n_ic, n_bc, opt, counts)
+        L.check(eng.lib.qc_gradnorm_init(self.state.data_ptr(), C.byref(self.gn), _stream(dev)), "qc_gradnorm_init")
+
+    def set_adaptive(self, power: int = 1, floor: float = 1.0) -> None:
+        raise L.QcError("the gradient-norm step does not support adaptive sampling")
+
+    def _bind(self) -> None:
+        self._bind_entry("qc_fused_pinn_gradnorm_step", self.data if self.tabulated else None,
+                         self.coef if self.coef_mode else None, self.gn)
+
+    def set_hist_base(self, n_steps: int, hist_base: int) -> None:
+        """Rewrites the two counters of the record (a new history buffer starts at step ``hist_base``)."""
+        self.state[2:4] = torch.tensor([n_steps, hist_base], dtype=torch.int32).view(torch.float32).to(self.state.device)
+
+    def read_state(self) -> dict:
+        """The record as a dict (a host read): the weights of the NEXT step, the counters, the statistics of the last update."""
+        raw = self.state.cpu().numpy()
+        ints = raw.view(np.int32)
+        out = {"lam_bc": float(raw[0]), "lam_ic": float(raw[1]), "n_steps": int(ints[2]), "hist_base": int(ints[3]),
+               "n_updates": int(ints[4])}
+        out.update({k: float(raw[5 + i]) for i, k in enumerate(self._FLOATS)})
+        return out
+
+    def history(self, steps: Optional[int] = None) -> np.ndarray:
+        """Rows (lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated) of the first ``steps`` steps of the
+        history buffer (default: all taken so far)."""
+        if steps is None:
+            rec = self.read_state()
+            steps = rec["n_steps"] - rec["hist_base"]
+        return self.gradnorm_hist[: max(0, min(int(steps), self.gradnorm_cap))].cpu().numpy()

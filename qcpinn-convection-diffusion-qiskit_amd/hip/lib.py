@@ -36,6 +36,7 @@ EXPORTS = (
     "qc_lbfgs_workspace_bytes", "qc_lbfgs_init", "qc_lbfgs_restart", "qc_lbfgs_step",
     "qc_post_balance", "qc_balance_adam_step", "qc_fused_pinn_balanced_step",
     "qc_causal_init", "qc_sample_dataset_slabs", "qc_causal_fold", "qc_fused_pinn_causal_step",
+    "qc_gradnorm_init", "qc_gradnorm_fold", "qc_fused_pinn_gradnorm_step",
 )
 
 
@@ -45,6 +46,8 @@ QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_
 QC_BAL_TERMS = 3                # loss terms of a balancer: residual, BC, IC (qc_step_balance)
 QC_CAUSAL_MAX_SLABS = 64        # most time slabs of a causal record (qc_step_causal)
 QC_CAUSAL_HEAD = 4              # words {eps, n_raised, n_steps, hist_base} ahead of W[M], L[M] in a causal record
+QC_GRADNORM_STATE_WORDS = 16    # 4-byte words of a gradient-norm record (qc_step_gradnorm)
+QC_GRADNORM_HIST_COLS = 7       # lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated: a row of its history
 QC_ADAPT_BLOCK = 1024           # rows per entry of the coarse table of an adaptive-sampling buffer (qc_adapt_bytes)
 QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
 QC_KMAX, QC_EQMAX, QC_TERMS_MAX = 4, 4, 32            # outputs, equations and terms of a system (qc_step_system)
@@ -139,6 +142,14 @@ class QcStepCausal(C.Structure):
     _fields_ = [("n_slabs", C.c_int32), ("eps0", C.c_float), ("eps_growth", C.c_float), ("eps_max", C.c_float),
                 ("delta", C.c_float), ("slab_lo_dev", C.c_void_p), ("state_dev", C.c_void_p), ("hist_dev", C.c_void_p),
                 ("hist_cap", C.c_int32)]
+
+
+class QcStepGradnorm(C.Structure):
+    """qc_step_gradnorm: the moving average (alpha), the cap of the weights, the update period, the starting weights of the
+    BC and the IC term, the device record {lam_bc, lam_ic, n_steps, hist_base, n_updates, m_r, a_bc, a_ic, hat_bc, hat_ic, 0..}
+    of QC_GRADNORM_STATE_WORDS words and the optional [cap][QC_GRADNORM_HIST_COLS] history."""
+    _fields_ = [("alpha", C.c_float), ("lam_max", C.c_float), ("every", C.c_int32), ("lam0_bc", C.c_float),
+                ("lam0_ic", C.c_float), ("state_dev", C.c_void_p), ("hist_dev", C.c_void_p), ("hist_cap", C.c_int32)]
 
 
 class QcStepAdapt(C.Structure):
@@ -273,6 +284,10 @@ def load() -> C.CDLL:
                                             C.c_uint64, C.c_uint64, vp]
     lib.qc_causal_fold.argtypes = [fp, i64, i64, i64, i32, C.POINTER(QcStepCausal), fp, vp]
     lib.qc_fused_pinn_causal_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCausal), i32, vp]
+    lib.qc_gradnorm_init.argtypes = [vp, C.POINTER(QcStepGradnorm), vp]
+    lib.qc_gradnorm_fold.argtypes = [fp, i64, i64, i64, i64, i32, C.POINTER(QcStepGradnorm), fp, fp, vp]
+    lib.qc_fused_pinn_gradnorm_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef),
+                                                C.POINTER(QcStepGradnorm), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

@@ -60,3 +60,32 @@ class AdaptiveMultiLoss(torch.nn.Module):
     def weights(self) -> Dict[str, float]:
         """``exp(-s_k)`` per name: the factor on the term's base weight."""
         return {name: float(torch.exp(-s).item()) for name, s in self.log_variances().items()}
+
+
+class GradNormWeighting:
+    """Gradient-norm loss weights (Wang, Teng, Perdikaris 2021, "learning-rate annealing"): every ``every`` steps
+
+        lam_k <- (1 - alpha) lam_k + alpha max|grad L_r| / mean|grad L_k|,      k = BC, IC,
+
+    capped at ``lam_max``, and the step descends along grad L_r + lam_bc grad L_bc + lam_ic grad L_ic
+    (``qc_fused_pinn_gradnorm_step``, ``trainer.gradnorm_train``).  ``init`` = the starting (lam_bc, lam_ic).  A plain
+    value object: the weights are no parameters, nothing here reaches an optimiser."""
+
+    def __init__(self, alpha: float = 0.1, every: int = 10, lam_max: float = 1e4, init=(1.0, 1.0)):
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"gradient-norm weighting: every must be an integer >= 1, got {every!r}")
+        alpha, lam_max = float(alpha), float(lam_max)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"gradient-norm weighting: alpha must lie in [0, 1], got {alpha!r}")
+        if not (math.isfinite(lam_max) and lam_max > 0.0):
+            raise ValueError(f"gradient-norm weighting: lam_max must be a finite number > 0, got {lam_max!r}")
+        try:
+            init = tuple(float(v) for v in init)
+        except TypeError:
+            init = ()
+        if len(init) != 2 or not all(math.isfinite(v) and v > 0.0 for v in init):
+            raise ValueError(f"gradient-norm weighting: init must be two finite numbers > 0 (lam_bc, lam_ic), got {init!r}")
+        self.alpha, self.every, self.lam_max, self.init = alpha, every, lam_max, init
+
+    def __repr__(self):
+        return f"GradNormWeighting(alpha={self.alpha}, every={self.every}, lam_max={self.lam_max}, init={self.init})"

@@ -38,6 +38,10 @@ the device (``qc_fused_pinn_balanced_step``, ``trainer.balanced_train``): ``DVPD
 ``causal=`` (keyword-only, a ``data.tabulated.CausalWeighting``, with ``dataset=``) weighs the residual of every time slab
 by how well the earlier slabs are fitted, on the device (``qc_fused_pinn_causal_step``, ``trainer.causal_train``):
 ``DVPDESolver`` models only, not together with ``adaptive=``, ``lbfgs=`` or ``balance=``.
+
+``gradnorm=`` (keyword-only, an ``nn.loss_balance.GradNormWeighting``, with ``dataset=`` or on the analytic problem) weighs
+the BC and the IC term from the ratio of this step's per-class gradient statistics, on the device
+(``qc_fused_pinn_gradnorm_step``, ``trainer.gradnorm_train``): ``DVPDESolver`` models only, alone.
 """
 from __future__ import annotations
 
@@ -604,7 +608,7 @@ def _train_generic(model, batch_size, dataset=None, adaptive=None):
 
 
 def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *, batches=None, dataset=None,
-          adaptive=None, lbfgs=None, balance=None, causal=None):
+          adaptive=None, lbfgs=None, balance=None, causal=None, gradnorm=None):
     """``batches`` (keyword-only, not in the reference): a per-iteration list of
     ``(X_ic, X_bc, X_res)`` tensors to use instead of sampling — for parity tests; with a dataset each entry carries a
     fourth element, the targets ``(u_ic, u_bc, r_res)``.  ``dataset`` (keyword-only): a ``TabulatedProblem`` whose targets
@@ -618,7 +622,18 @@ def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *
     ``data.tabulated.CausalWeighting``; the residual of a late time slab is then held back on the device until the earlier
     slabs are fitted (``trainer.causal_train``; needs ``dataset`` and a batch size that is a multiple of 64 * n_slabs,
     ``DVPDESolver`` models only, not with ``adaptive``, ``lbfgs`` or ``balance``); ``model.causal_history`` receives the
-    rows (eps, W, L) of the steps.  ``update_lam`` stays unused."""
+    rows (eps, W, L) of the steps.  ``gradnorm`` (keyword-only): an ``nn.loss_balance.GradNormWeighting``; the BC and the IC
+    term are then weighted on the device from the ratio of this step's per-class gradient statistics (Wang, Teng,
+    Perdikaris 2021; ``trainer.gradnorm_train``; with ``dataset`` or, without one, on the analytic problem; ``DVPDESolver``
+    models only, not with ``adaptive``, ``lbfgs``, ``balance`` or ``causal``; ``batch_size // 3`` must be a multiple of 64);
+    ``model.gradnorm_history`` receives the rows (lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated) of the
+    steps.  ``update_lam`` stays unused: the reference carries the flag of this algorithm without reading it, and it
+    switches nothing on here either."""
+    if gradnorm is not None:
+        from .gradnorm_train import check_gradnorm, train_gradnorm
+        check_gradnorm(model, dataset, gradnorm, batch_size, adaptive, lbfgs, balance, causal)
+        train_gradnorm(model, batch_size, batches, dataset, gradnorm)
+        return
     if causal is not None:
         from .causal_train import check_causal, train_causal
         check_causal(model, dataset, causal, batch_size, adaptive, lbfgs, balance)
