@@ -81,6 +81,124 @@ __device__ inline void qc_fill_diag_tables(const QcGate* __restrict__ prog, int 
   }
 }
 
+// ---- the same tables in a one-block kernel that moves theta itself (k_adam_fast, k_lbfgs: T threads)
+// Such a kernel is one chain of memory latencies, so everything the tables need besides theta is requested at kernel
+// entry, in the round trip of the kernel's other loads (qc_gate_stage_load): the gate record whose sincosf a thread will
+// compute stays in its registers, and where the program has phase tables (runs.n > 0, n <= 8) the records and the device
+// run list are parked in dynamic LDS (qc_gate_stage_store, ahead of any barrier the kernel passes before
+// qc_gate_stage_tables).  Behind the update the tables then come from LDS alone: no global or scalar load, and no wait
+// for the per-gate stores.  A program without tables takes no LDS.
+// LDS image at `lds` (16-byte aligned), in words: gate records [n_gates][4], (cos, sin) [n_gates][2], run list [n_list].
+struct QcGateStage {
+  QcGate mine;     // gate `tid` of the program (tid < n_gates): its sincosf is this thread's
+  int list_mine;   // entry `tid` of the device run list (tid < n_list)
+  int n_list;      // 0: the runs are gate ranges
+  bool tables;     // the program has phase tables: the LDS image exists
+  int words;       // words of the image (what follows it in a kernel's dynamic LDS starts there)
+  QcGate* gates;
+  float* cs;
+  int* list;
+};
+__host__ __device__ inline bool qc_gate_stage_has_tables(const int n_qubits, const QcDiagRuns& runs) {
+  return runs.n > 0 && n_qubits <= 8;   // (qc_fill_diag_tables' condition)
+}
+__host__ __device__ inline int qc_gate_stage_list_len(const QcDiagRuns& runs) {
+  int e = 0;   // g1 of the last run (run_off of qc_wave_sched.h: ascending), without a run-time index into the arguments
+#pragma unroll
+  for (int q = 0; q < QC_MAX_DIAG_RUNS; ++q)
+    if (q < runs.n) e = runs.g1[q];
+  return runs.list != nullptr ? e : 0;
+}
+// words of the image: the kernels' dynamic LDS starts with them
+__host__ __device__ inline int qc_gate_stage_words(const int n_gates, const int n_qubits, const QcDiagRuns& runs) {
+  return qc_gate_stage_has_tables(n_qubits, runs) ? 6 * n_gates + qc_gate_stage_list_len(runs) : 0;
+}
+inline size_t qc_gate_stage_words(const qc_program* pg) {
+  return pg ? (size_t)qc_gate_stage_words(pg->n_gates, pg->n_qubits, qc_diag_runs_of(pg)) : 0;
+}
+__device__ __forceinline__ QcGateStage qc_gate_stage_load(const QcGate* __restrict__ prog, const int n_gates, const int n_qubits,
+                                                          const QcDiagRuns& runs, float* lds, const int tid) {
+  QcGateStage sg;
+  sg.mine = QcGate{0, 0, 0, -1};
+  sg.list_mine = 0;
+  sg.tables = prog != nullptr && qc_gate_stage_has_tables(n_qubits, runs);
+  sg.n_list = sg.tables ? qc_gate_stage_list_len(runs) : 0;
+  sg.words = sg.tables ? 6 * n_gates + sg.n_list : 0;   // == qc_gate_stage_words
+  sg.gates = reinterpret_cast<QcGate*>(lds);
+  sg.cs = lds + 4 * n_gates;
+  sg.list = reinterpret_cast<int*>(lds + 6 * n_gates);
+  if (prog != nullptr && tid < n_gates) sg.mine = prog[tid];
+  if (tid < sg.n_list) sg.list_mine = runs.list[tid];
+  return sg;
+}
+template <int T>
+__device__ __forceinline__ void qc_gate_stage_store(const QcGateStage& sg, const QcGate* __restrict__ prog, const int n_gates,
+                                                    const QcDiagRuns& runs, const int tid) {
+  if (!sg.tables) return;
+  if (tid < n_gates) sg.gates[tid] = sg.mine;
+  if (tid < sg.n_list) sg.list[tid] = sg.list_mine;
+  // (more than T gates or entries: no program with tables has them)
+#pragma unroll 1
+  for (int g = tid + T; g < n_gates; g += T) sg.gates[g] = prog[g];
+#pragma unroll 1
+  for (int e = tid + T; e < sg.n_list; e += T) sg.list[e] = runs.list[e];
+}
+// LDS traffic of this wave complete, then the block's barrier: what a __syncthreads() is without its wait for the
+// outstanding global stores (nothing behind it reads what they wrote)
+__device__ __forceinline__ void qc_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// `theta`: the NEW [n_theta], block-visible (LDS, or global behind a __syncthreads()).  Per-gate entries as k_prep_trig
+// forms them; then one thread per (run, amplitude) pair, the product over the run's gates in qc_fill_diag_tables' order
+// and expressions, so every entry has that function's bits.
+template <int T>
+__device__ __forceinline__ void qc_gate_stage_tables(const QcGateStage& sg, const QcGate* __restrict__ prog, const int n_gates,
+                                                     const int n_qubits, const int n_theta, QcTrig* __restrict__ trig,
+                                                     const QcDiagRuns& runs, const float* theta, const int tid) {
+  const bool tables = sg.tables;
+  for (int gi = tid; gi < n_gates; gi += T) {
+    // (gates T, T + 1, ..: only a program without tables has them, and it has no image)
+    const QcGate gt = gi == tid ? sg.mine : (tables ? sg.gates[gi] : prog[gi]);
+    QcTrig tr = {1.f, 0.f, 0.f, 0.f};
+    if (gt.op != QC_U4 && gt.slot >= 0 && gt.slot < n_theta) {
+      tr.th = theta[gt.slot];
+      sincosf(0.5f * tr.th, &tr.s, &tr.c);
+    }
+    trig[gi] = tr;
+    if (tables) {
+      sg.cs[2 * gi] = tr.c;
+      sg.cs[2 * gi + 1] = tr.s;
+    }
+  }
+  if (!tables) return;
+  qc_lds_barrier();
+  const int A = 1 << n_qubits;
+  for (int p = tid; p < runs.n * A; p += T) {
+    const int r = p >> n_qubits, k = p & (A - 1);
+    int g0 = 0, g1 = 0;   // (a compile-time chain: a run-time index would fetch them from the kernel's argument segment)
+#pragma unroll
+    for (int q = 0; q < QC_MAX_DIAG_RUNS; ++q)
+      if (r == q) {
+        g0 = runs.g0[q];
+        g1 = runs.g1[q];
+      }
+    float dr = 1.f, di = 0.f;
+    for (int hh = g0; hh < g1; ++hh) {
+      const int h = sg.n_list > 0 ? sg.list[hh] : hh;
+      const QcGate gt = sg.gates[h];
+      const bool ctl = gt.op == 6;
+      const int tb = ctl ? gt.bb : gt.ba;
+      const float c = sg.cs[2 * h], s0 = sg.cs[2 * h + 1];
+      if (ctl && !((k >> gt.ba) & 1)) continue;
+      const float s = ((k >> tb) & 1) ? s0 : -s0;
+      const float nr = dr * c - di * s, ni = dr * s + di * c;
+      dr = nr;
+      di = ni;
+    }
+    QcTrig t = {dr, di, 0.f, 0.f};
+    trig[n_gates + r * A + k] = t;
+  }
+}
+
 // Sum over the 64 lanes of a wave with DPP row operations (no LDS traffic).  The total is
 // valid in lane 63 (and only there).
 __device__ __forceinline__ float qc_wave_sum_to_lane63(float v) {

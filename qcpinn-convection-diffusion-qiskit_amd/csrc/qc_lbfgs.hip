@@ -79,30 +79,8 @@ __device__ __forceinline__ void lb_each(int NP, int tid, F&& f) {
   }
 }
 
-// The tail of k_adam_fast (qc_optim.hip), word for word: the per-gate entries from the NEW theta, which the caller has made
-// block-visible (`theta`: [n_theta], LDS or global, a barrier behind its last write), then the diagonal-run tables from the
-// (cos, sin) pairs kept in `cs` (LDS, [n_gates][2]).  k_adam_fast keeps its own copy: calling this function from it moved
-// its register allocation, and its instruction stream is pinned.
-__device__ __forceinline__ void lb_refresh_gate_tables(const QcGate* prog, int n_gates, int n_qubits, int n_theta, QcTrig* trig,
-                                                       const QcDiagRuns& runs, const float* theta, float* cs, int tid) {
-  for (int gi = tid; gi < n_gates; gi += LB_T) {
-    const QcGate gt = prog[gi];
-    QcTrig tr = {1.f, 0.f, 0.f, 0.f};
-    if (gt.op != QC_U4 && gt.slot >= 0 && gt.slot < n_theta) {
-      tr.th = theta[gt.slot];
-      sincosf(0.5f * tr.th, &tr.s, &tr.c);
-    }
-    trig[gi] = tr;
-    if (runs.n > 0) {
-      cs[2 * gi] = tr.c;
-      cs[2 * gi + 1] = tr.s;
-    }
-  }
-  if (runs.n > 0) {
-    __syncthreads();
-    qc_fill_diag_tables(prog, n_gates, n_qubits, trig, tid, runs, cs);
-  }
-}
+// (The trig buffer's tail, the per-gate entries and the diagonal-run tables from the NEW theta, is the one k_adam_fast
+// runs: the gate stage of qc_common.h, loaded at kernel entry and read back from LDS behind the move.)
 
 __device__ __forceinline__ float lb_first_t(float lr, float g1) { return lr * fminf(1.f, 1.f / g1); }
 
@@ -114,12 +92,13 @@ __global__ void __launch_bounds__(LB_T) k_lbfgs(QcLbfgsArgs a) {
   __shared__ double s_red[LB_WAVES];
   // register path: g, g_k and s = t d of the call for the row sweeps, later the new theta for the tables
   __shared__ float s_v[K > 0 ? 3 * K * LB_T : 1];
-  extern __shared__ float s_cs[];   // (cos, sin)[n_gates][2]
+  extern __shared__ __attribute__((aligned(16))) float s_stage[];   // the gate stage (qc_common.h)
   constexpr int KC = K > 0 ? K : 1;
   const int NP = a.NP, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const QcLbfgsHyper& hp = a.hp;
   const int m = hp.history;
   const QcLbfgsRec rec = *reinterpret_cast<const QcLbfgsRec*>(a.ws);
+  const QcGateStage sg = qc_gate_stage_load(a.prog, a.n_gates, a.n_qubits, a.runs, s_stage, tid);
   float* const xk = a.ws + QC_LBFGS_REC_WORDS;
   float* const gk = xk + NP;
   float* const dd = gk + NP;
@@ -158,6 +137,7 @@ __global__ void __launch_bounds__(LB_T) k_lbfgs(QcLbfgsArgs a) {
   // ---- the batch of dot products.  Row r of [S | Y] (wave r mod 16): S_j.g, S_j.y or Y_j.g, Y_j.y, s.Y_j  (s = t d,
   // y = g - g_k); the nine extras go to waves 15, 14, ...  Lane l sums elements l, l + 64, ... in double, then the wave.
   float *const vg = s_v, *const vk = s_v + K * LB_T, *const vs = s_v + 2 * K * LB_T;
+  qc_gate_stage_store<LB_T>(sg, a.prog, a.n_gates, a.runs, tid);   // (published by the barriers below)
   if constexpr (K > 0) {
     lb_each<K>(NP, tid, [&](int i, int k) {
       vg[i] = gv[k];
@@ -418,7 +398,7 @@ __global__ void __launch_bounds__(LB_T) k_lbfgs(QcLbfgsArgs a) {
       });
     }
     __syncthreads();
-    lb_refresh_gate_tables(a.prog, a.n_gates, a.n_qubits, n_theta, a.trig, a.runs, K > 0 ? s_v : a.prm + a.theta_off, s_cs, tid);
+    qc_gate_stage_tables<LB_T>(sg, a.prog, a.n_gates, a.n_qubits, n_theta, a.trig, a.runs, K > 0 ? s_v : a.prm + a.theta_off, tid);
   }
   if (tid == 0) {
     const int e = rec.n_eval;
@@ -487,7 +467,7 @@ int qc_lbfgs_step_launch(const float* flat, int NP, float* prm, void* ws, QcLbfg
   a.prog = pg ? pg->d_gates : nullptr; a.n_gates = pg ? pg->n_gates : 0; a.theta_off = theta_off; a.trig = trig;
   a.n_qubits = pg ? pg->n_qubits : 0;
   a.runs = qc_diag_runs_of(pg);
-  const size_t lds = sizeof(float) * (pg ? 2 * pg->n_gates : 0);
+  const size_t lds = sizeof(float) * qc_gate_stage_words(pg);
   if (NP + 3 <= 3 * LB_T)
     hipLaunchKernelGGL((k_lbfgs<3>), dim3(1), dim3(LB_T), lds, st, a);
   else

@@ -60,6 +60,20 @@ __device__ __forceinline__ float block_sum_1024(float v, float* s_red) {
   return t;
 }
 
+// the same sum where the block is known to be 16 waves (k_adam_fast): the wave count is not fetched from the dispatch
+// packet behind the second barrier
+__device__ __forceinline__ float block_sum_16_waves(float v, float* s_red) {
+  v = qc_wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) s_red[wave] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) t += s_red[w];
+  return t;
+}
+
 // One block.  flat = [grad[NP] | L_r, L_bc, L_ic].  Updates prm/m/v in place, advances the
 // scheduler, appends the loss to hist[step], and rebuilds the gate trig table from the NEW theta.
 struct QcAdamArgs {
@@ -267,13 +281,16 @@ __global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows(float* __restri
 constexpr auto k_fold_rows_plain = k_fold_rows<>;
 
 // The optimiser update with everything it reads fetched in ONE round trip (state record, gradient or the
-// RS folded rows of it, moments, parameters), for NP + 3 <= 3 * 1024: a single-block kernel is a chain of
-// memory latencies, so the loads are issued together up front and the new theta reaches the trig table
-// through LDS instead of a store -> load of global memory.  Arithmetic identical to adam_block.
+// RS folded rows of it, moments, parameters, and the gate records and run list the tables need: qc_common.h), for
+// NP + 3 <= 3 * 1024: a single-block kernel is a chain of memory latencies, so the loads are issued together up front
+// and the new theta reaches the trig table through LDS instead of a store -> load of global memory.  What depends on
+// the state record alone (the bias corrections) is computed under those loads' latency, and the record is written by a
+// thread of the last wave as soon as the loss is known; behind the update nothing is loaded from global memory and no
+// store is waited for.  Arithmetic identical to adam_block.
 // FOLD: flat[c] = part[0][c] + ... + part[RS-1][c] (second reduction level, fixed order) is formed here.
 // BL = (QcBal): BAL as in adam_block; the owner of a balancer entry holds its value in a register and finds the loss
 // columns in LDS.  (A trailing pack, as the post kernels take their target kinds: the plain instantiations carry no
-// argument for it and keep their code.)
+// argument for it.)
 constexpr int QC_ADAM_K = 3;
 template <bool FOLD, class... BL>
 __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* __restrict__ part, int64_t stride, int RS,
@@ -283,7 +300,7 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
   __shared__ float s_red[16];
   __shared__ float s_loss[BAL ? 3 + QC_BAL_N : 3];   // BAL: the terms of F behind the loss columns
   [[maybe_unused]] float* s_term = s_loss + 3;
-  extern __shared__ float s_theta[];   // [n_theta], then (cos, sin)[n_gates][2]
+  extern __shared__ __attribute__((aligned(16))) float s_dyn[];   // the gate stage (qc_common.h), then theta [n_theta]
   const int NP = a.NP, tid = threadIdx.x;
   const int NPn = BAL ? NP - QC_BAL_N : NP;   // the clipped (network) entries
   const QcOptHyper& hp = a.hp;
@@ -292,9 +309,20 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
   float best = a.st->best;
   int bad = a.st->num_bad;
   const int hist_base = a.st->hist_base;
+  // every argument the requests below need, fetched from the argument segment in one round trip (left alone the compiler
+  // fetches each where it is first used: five dependent scalar waits ahead of the last request).  Behind the reads of
+  // the record: a uniform load that follows an asm statement is no longer a scalar load
+  asm volatile("" ::"s"(a.NP), "s"(a.m), "s"(a.v), "s"(a.prm), "s"(a.flat), "s"(a.prog), "s"(a.n_gates), "s"(a.n_qubits),
+               "s"(a.runs.n), "s"(a.runs.list), "s"(part), "s"(stride), "s"(RS));
+  const int n_theta = NPn - a.theta_off;
+  const QcGateStage sg = qc_gate_stage_load(a.prog, a.n_gates, a.n_qubits, a.runs, s_dyn, tid);
+  float* s_theta = s_dyn + sg.words;
   float g[QC_ADAM_K], mi[QC_ADAM_K], vi[QC_ADAM_K], pi[QC_ADAM_K];
-#pragma unroll
-  for (int k = 0; k < QC_ADAM_K; ++k) {
+  [[maybe_unused]] float x[QC_ADAM_K][32];   // FOLD: the (<= 32) folded rows of each column block
+  // all (<= 32) folded rows of every live column block requested together, unconditionally: one memory round trip.
+  // RS < 32: the rows past RS - 1 load row RS - 1 again and are replaced by +0.f below
+  const bool full = RS >= 32;
+  auto request = [&](const int k) {
     const int i = tid + k * 1024;
     g[k] = mi[k] = vi[k] = pi[k] = 0.f;
     if (i < NP) {
@@ -304,17 +332,55 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
     }
     if (i < NP + 3) {
       if constexpr (FOLD) {
-        // all (<= 32) folded rows requested together: one memory round trip, then the same left-to-right sum
-        float t = 0.f;
-        float x[32];
+        // (the row pointer walks in scalar registers, pinned there and read as the global pointer it is: one lane offset
+        // serves all 32 loads, where 32 per-lane 64-bit addresses did not fit beside the values in flight)
+        const float* row = part;
+        if (full) {
 #pragma unroll
-        for (int j = 0; j < 32; ++j) x[j] = j < RS ? part[(int64_t)j * stride + i] : 0.f;
+          for (int j = 0; j < 32; ++j) {
+            x[k][j] = ((const __attribute__((address_space(1))) float*)row)[i];
+            if (j < 31) row += stride;
+            asm volatile("" : "+s"(row));
+          }
+        } else if (RS > 0) {
 #pragma unroll
-        for (int j = 0; j < 32; ++j) t += x[j];       // (rows >= RS add +0.f: the sum is unchanged)
-        for (int q = 32; q < RS; ++q) t += part[(int64_t)q * stride + i];
-        g[k] = t;
+          for (int j = 0; j < 32; ++j) {
+            x[k][j] = ((const __attribute__((address_space(1))) float*)row)[i];
+            if (j + 1 < RS) row += stride;
+            asm volatile("" : "+s"(row));
+          }
+        }
       } else {
         g[k] = a.flat[i];
+      }
+    }
+  };
+  request(0);
+  request(1);
+  // under the latency of those loads: what needs the state record alone (pinned: sunk behind the norm's barriers otherwise)
+  const float b1 = (float)hp.beta1, b2 = (float)hp.beta2;
+  const double bc1 = 1.0 - qc_ipow(hp.beta1, step);
+  float bc2s = (float)sqrt(1.0 - qc_ipow(hp.beta2, step));
+  float step_size = (float)((double)lr / bc1);
+  asm volatile("" : "+v"(bc2s), "+v"(step_size));
+  // the third column block (NP + 3 > 2048) behind that arithmetic, still ahead of the first wait: 96 rows in flight
+  // beside the double-precision temporaries are more than the 128 registers of a 1024-thread block
+  request(2);
+  if constexpr (FOLD) {
+#pragma unroll
+    for (int k = 0; k < QC_ADAM_K; ++k) {
+      const int i = tid + k * 1024;
+      if (i < NP + 3) {
+        float t = 0.f;
+        if (full) {
+#pragma unroll
+          for (int j = 0; j < 32; ++j) t += x[k][j];      // the same left-to-right sum
+        } else if (RS > 0) {
+#pragma unroll
+          for (int j = 0; j < 32; ++j) t += j < RS ? x[k][j] : 0.f;   // (rows >= RS add +0.f: the sum is unchanged)
+        }
+        for (int q = 32; q < RS; ++q) t += part[(int64_t)q * stride + i];
+        g[k] = t;
       }
     }
   }
@@ -325,55 +391,13 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
     if (i < NPn) ss += g[k] * g[k];
     else if ((!BAL || i >= NP) && i < NP + 3) s_loss[i - NP] = g[k];
   }
-  const float norm = sqrtf(block_sum_1024(ss, s_red));   // (its barriers also publish s_loss)
+  qc_gate_stage_store<1024>(sg, a.prog, a.n_gates, a.runs, tid);
+  const float norm = sqrtf(block_sum_16_waves(ss, s_red));   // (its barriers also publish s_loss and the gate stage)
   float coef = hp.max_norm / (norm + 1e-6f);
   coef = coef > 1.f ? 1.f : coef;
-  const float b1 = (float)hp.beta1, b2 = (float)hp.beta2;
-  const double bc1 = 1.0 - qc_ipow(hp.beta1, step);
-  const float bc2s = (float)sqrt(1.0 - qc_ipow(hp.beta2, step));
-  const float step_size = (float)((double)lr / bc1);
-  const int n_theta = NPn - a.theta_off;
-  float* s_cs = s_theta + (a.prog != nullptr ? n_theta : 0);
-#pragma unroll
-  for (int k = 0; k < QC_ADAM_K; ++k) {
-    const int i = tid + k * 1024;
-    if (i < NP) {
-      float gc = g[k] * coef;
-      if constexpr (BAL)
-        if (i >= NPn) gc = bal_entry(i - NPn, pi[k], s_loss[i - NPn], hp, bl..., step - 1 - hist_base, s_term);
-      const float mn = mi[k] + (1.f - b1) * (gc - mi[k]);
-      const float vn = b2 * vi[k] + (1.f - b2) * gc * gc;
-      const float denom = sqrtf(vn) / bc2s + hp.eps;
-      const float pn = pi[k] - step_size * (mn / denom);
-      a.flat[i] = gc;
-      a.m[i] = mn;
-      a.v[i] = vn;
-      a.prm[i] = pn;
-      if (a.prog != nullptr && i >= a.theta_off && (!BAL || i < NPn)) s_theta[i - a.theta_off] = pn;
-    } else if (FOLD && i < NP + 3) {
-      a.flat[i] = g[k];
-    }
-  }
-  __syncthreads();
-  if (a.prog != nullptr)
-    for (int gi = tid; gi < a.n_gates; gi += 1024) {
-      const QcGate gt = a.prog[gi];
-      QcTrig tr = {1.f, 0.f, 0.f, 0.f};
-      if (gt.op != QC_U4 && gt.slot >= 0 && gt.slot < n_theta) {
-        tr.th = s_theta[gt.slot];
-        sincosf(0.5f * tr.th, &tr.s, &tr.c);
-      }
-      a.trig[gi] = tr;
-      if (a.runs.n > 0) {             // (cos, sin) of every gate also to LDS, for the diagonal-run tables below
-        s_cs[2 * gi] = tr.c;
-        s_cs[2 * gi + 1] = tr.s;
-      }
-    }
-  if (a.prog != nullptr && a.runs.n > 0) {
-    __syncthreads();
-    qc_fill_diag_tables(a.prog, a.n_gates, a.n_qubits, a.trig, tid, a.runs, s_cs);
-  }
-  if (tid == 0) {
+  // the scheduler, the state record and the history entry: one thread of the last wave (the first waves have the gates),
+  // as soon as the loss is known.  (Every thread's reads of the record lie ahead of the norm's barriers.)
+  auto write_state = [&]() {
     const float lr_ = s_loss[0], lb = s_loss[1], li = s_loss[2];
     float loss = hp.w_res * lr_ + hp.w_bc * lb + hp.w_ic * li;
     if constexpr (BAL) loss = (s_term[0] + s_term[1]) + s_term[2];
@@ -405,7 +429,34 @@ __global__ void __launch_bounds__(1024) k_adam_fast(QcAdamArgs a, const float* _
     *a.st = o;
     const int hi = step - 1 - hist_base;
     if (a.hist != nullptr && hi >= 0 && hi < a.hist_cap) a.hist[hi] = loss;
+  };
+  if constexpr (!BAL)
+    if (tid == 1023) write_state();
+#pragma unroll
+  for (int k = 0; k < QC_ADAM_K; ++k) {
+    const int i = tid + k * 1024;
+    if (i < NP) {
+      float gc = g[k] * coef;
+      if constexpr (BAL)
+        if (i >= NPn) gc = bal_entry(i - NPn, pi[k], s_loss[i - NPn], hp, bl..., step - 1 - hist_base, s_term);
+      const float mn = mi[k] + (1.f - b1) * (gc - mi[k]);
+      const float vn = b2 * vi[k] + (1.f - b2) * gc * gc;
+      const float denom = sqrtf(vn) / bc2s + hp.eps;
+      const float pn = pi[k] - step_size * (mn / denom);
+      a.flat[i] = gc;
+      a.m[i] = mn;
+      a.v[i] = vn;
+      a.prm[i] = pn;
+      if (a.prog != nullptr && i >= a.theta_off && (!BAL || i < NPn)) s_theta[i - a.theta_off] = pn;
+    } else if (FOLD && i < NP + 3) {
+      a.flat[i] = g[k];
+    }
   }
+  if (a.prog == nullptr && !BAL) return;
+  qc_lds_barrier();   // theta (and BAL: the terms of F) through LDS
+  if constexpr (BAL)
+    if (tid == 1023) write_state();
+  if (a.prog != nullptr) qc_gate_stage_tables<1024>(sg, a.prog, a.n_gates, a.n_qubits, n_theta, a.trig, a.runs, s_theta, tid);
 }
 
 // one block: per-gate (cos, sin, theta) entries, then the phase tables of the fused diagonal runs
@@ -443,6 +494,10 @@ static QcAdamArgs adam_args(float* flat, int NP, float* prm, float* m, float* v,
 }
 
 static bool adam_fast_ok(int NP) { return NP + 3 <= QC_ADAM_K * 1024; }
+// dynamic LDS of a k_adam_fast launch: the gate stage, then theta
+static size_t adam_fast_lds(const qc_program* pg, int NP, int theta_off) {
+  return pg ? sizeof(float) * (qc_gate_stage_words(pg) + (size_t)(NP - theta_off)) : 0;
+}
 
 // the balanced launches of both entry points below: defined at the end of this file, so that their kernels lie behind
 // every other kernel of the code object
@@ -454,9 +509,9 @@ int qc_opt_adam(float* flat, int NP, float* prm, float* m, float* v, QcOptState*
                 const QcBal* bal) {
   const QcAdamArgs a = adam_args(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig);
   if (bal)
-    adam_bal_launch(a, false, nullptr, 0, 0, sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0), *bal, st);
+    adam_bal_launch(a, false, nullptr, 0, 0, adam_fast_lds(pg, NP, theta_off), *bal, st);
   else if (adam_fast_ok(NP))
-    hipLaunchKernelGGL((k_adam_fast<false>), dim3(1), dim3(1024), sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0), st, a,
+    hipLaunchKernelGGL((k_adam_fast<false>), dim3(1), dim3(1024), adam_fast_lds(pg, NP, theta_off), st, a,
                        (const float*)nullptr, (int64_t)0, 0);
   else
     hipLaunchKernelGGL(k_adam, dim3(1), dim3(1024), 0, st, a);
@@ -475,7 +530,7 @@ int qc_opt_adam_fold(const float* part, int64_t stride, int RS, float* flat, int
                      QcOptState* state, QcOptHyper hp, float* hist, int hist_cap, const qc_program* pg, int theta_off,
                      QcTrig* trig, hipStream_t st, const QcBal* bal) {
   if (adam_fast_ok(NP)) {
-    const size_t lds = sizeof(float) * (pg ? NP - theta_off + 2 * pg->n_gates : 0);
+    const size_t lds = adam_fast_lds(pg, NP, theta_off);
     const QcAdamArgs a = adam_args(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig);
     if (bal) adam_bal_launch(a, true, part, stride, RS, lds, *bal, st);
     else hipLaunchKernelGGL((k_adam_fast<true>), dim3(1), dim3(1024), lds, st, a, part, stride, RS);
