@@ -99,7 +99,7 @@ struct DynProg {
       const QcGate gt = prog[g];
       const QcTrig tr = trig[g];
       if (gt.op != QC_U4 && gt.slot >= 0) {
-        const float gr = qc_wave_sum_to_lane63(qc_gate_grad<NQ>(cl[1], cl[0], gt));
+        const float gr = qc_wave_sum6_to_lane63(qc_gate_grad<NQ>(cl[1], cl[0], gt));
         if (lane == 63) acc_wave[gt.slot] += gr;
       }
       qc_apply_gate<NQ, 2, true>(cl, gt, tr.c, tr.s, umat);
@@ -211,8 +211,10 @@ struct StatProg {
   }
   // gradient terms of the gates H, H+1, ..., E-1 of one run from t[k] = Im(conj(lam_k) chi_k) (invariant under
   // the other diagonal gates of the run): signed by the target bit, masked by the control bit
+  // (the run's terms, one per gate, come from the same t and are reduced over the wave together: the six steps of
+  // every value in their own order, interleaved, the totals in lane 63)
   template <int H, int E>
-  __device__ static __forceinline__ void run_grads(const QcPk<(1 << N)>& t, float (&gacc)[SP::P > 0 ? SP::P : 1]) {
+  __device__ static __forceinline__ void run_terms(const QcPk<(1 << N)>& t, float (&term)[E - run_begin(E - 1)]) {
     if constexpr (H < E) {
       constexpr SGate g = SP::g[H];
       constexpr bool ctl = g.op == QC_CRZ;
@@ -226,10 +228,21 @@ struct StatProg {
         else a2 += t.p[j];
       }
       // target on bit 0: the halves carry opposite signs; control on bit 0: only the upper halves count
-      const float acc = tb == 0 ? a2.x - a2.y : (cb == 0 ? a2.y : a2.x + a2.y);
-      if constexpr (g.slot >= 0) gacc[g.slot] += qc_wave_sum_to_lane63(acc);
-      run_grads<H + 1, E>(t, gacc);
+      term[H - run_begin(H)] = tb == 0 ? a2.x - a2.y : (cb == 0 ? a2.y : a2.x + a2.y);
+      run_terms<H + 1, E>(t, term);
     }
+  }
+  template <int H, int E, int... Is>
+  __device__ static __forceinline__ void run_grads(const QcPk<(1 << N)>& t, float (&gacc)[SP::P > 0 ? SP::P : 1],
+                                                   std::integer_sequence<int, Is...>) {
+    float term[E - H];
+    run_terms<H, E>(t, term);
+    qc_wave_sum_multi_to_lane63<E - H>(term);
+    (run_add<H + Is>(gacc, term[Is]), ...);   // in gate order, as the sums were added one by one
+  }
+  template <int I>
+  __device__ static __forceinline__ void run_add(float (&gacc)[SP::P > 0 ? SP::P : 1], const float tot) {
+    if constexpr (SP::g[I].slot >= 0) gacc[SP::g[I].slot] += tot;
   }
   // one non-diagonal gate; PIN: the 32 scalars of a U4 block are requested here, inside the gate that consumes them
   template <int I, int K, bool ADJ, bool PIN = true>
@@ -299,13 +312,13 @@ struct StatProg {
           const qf2 m = cl[1].a[k] * qc_swp(cl[0].a[k]);
           tk[k] = m.x - m.y;
         }
-        run_grads<run_begin(I), run_end(I)>(tk, gacc);
+        run_grads<run_begin(I), run_end(I)>(tk, gacc, std::make_integer_sequence<int, run_end(I) - run_begin(I)>{});
         apply_table<I, true, 2>(cl, trig);
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
       if constexpr (g.op != QC_U4 && g.slot >= 0)
-        gacc[g.slot] += qc_wave_sum_to_lane63(qc_static_grad<N, g.op, g.ba, g.bb>(cl[1], cl[0]));
+        gacc[g.slot] += qc_wave_sum6_to_lane63(qc_static_grad<N, g.op, g.ba, g.bb>(cl[1], cl[0]));
       gate<I, 2, true>(cl, t, umat);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -494,7 +507,7 @@ __device__ __forceinline__ void k_value_bwd_body(const int64_t bid, const QcGate
   if (qc_flag<AB>(absorb)) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
 #pragma unroll
     for (int w = 0; w < N; ++w) {
-      const float tot = qc_wave_sum_to_lane63(live ? T[w] : 0.f);
+      const float tot = qc_wave_sum6_to_lane63(live ? T[w] : 0.f);
       if (lane == 63) smem[wave * n_params + (AB < 0 ? prog[w].slot : PG::lead_slot(prog, w))] += tot;
     }
   }
@@ -756,7 +769,7 @@ __device__ __forceinline__ void k_jets_bwd_body(const int64_t bid, const QcGate*
         r = at(ch, 2, w);
       if (live) abar[((int64_t)ch * N + w) * B + p] = r;
       if ((amp >> 1) && ch == 0) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
-        const float tot = qc_wave_sum_to_lane63(live ? r : 0.f);
+        const float tot = qc_wave_sum6_to_lane63(live ? r : 0.f);
         if (lane == 63) s_acc[prog[w].slot] += tot;
       }
     }
@@ -946,14 +959,18 @@ __device__ __forceinline__ void k_jets_bwd2_body(const int64_t bid, const QcGate
   }
   __syncthreads();
   if (wt == 0) {
+    float tot[N];
 #pragma unroll
     for (int w = 0; w < N; ++w) {
       const float r = (t_own[w] + s_t0[w * 64 + lane]) + s_t0[(N + w) * 64 + lane];
       if (live) abar[(int64_t)w * B + p] = r;
-      if constexpr (ABSORB) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
-        const float tot = qc_wave_sum_to_lane63(live ? r : 0.f);
-        if (lane == 63) s_acc[PG::lead_slot(prog, w)] += tot;
-      }
+      tot[w] = live ? r : 0.f;
+    }
+    if constexpr (ABSORB) {   // folded RX layer: d L / d theta_w = sum over points of d L / d angle_w
+      qc_wave_sum_merged<N>(tot);   // the N sums together; each total in its home lane
+#pragma unroll
+      for (int w = 0; w < N; ++w)
+        if (lane == qc_wave_sum_home_lane(N, w)) s_acc[PG::lead_slot(prog, w)] += tot[qc_wave_sum_home_reg(N, w)];
     }
   }
   __syncthreads();

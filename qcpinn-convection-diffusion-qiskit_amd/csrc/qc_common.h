@@ -234,6 +234,200 @@ __device__ __forceinline__ void qc_wave_sum_multi_to_lane63(float (&v)[NV]) {
   for (int k = 0; k < NV; ++k) asm volatile("v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(v[k]));
 }
 
+// One value, lane 63, in six VALU instructions: the chain above with both row_bcast steps as single v_add_f32_dpp.
+__device__ __forceinline__ float qc_wave_sum6_to_lane63(float v) {
+  float t[1] = {v};
+  qc_wave_sum_multi_to_lane63<1>(t);
+  return t[0];
+}
+
+// ------------------------------------------------------------------ merged wave sums
+// qc_wave_sum_merged<NV>(v): the NV sums of qc_wave_sum_to_lane63 with the SAME association tree, in fewer
+// instructions: from the third level on, several values share one register and the level runs once for all of them.
+//
+// The tree of qc_wave_sum_to_lane63, by the lane bit a level folds:
+//   bit 0  quad_perm[1,0,3,2]     s1[l] = x[l] + x[l^1]
+//   bit 1  quad_perm[2,3,0,1]     q  = s1[l] + s1[l^2]             (one value per quad, in all four of its lanes)
+//   bit 2  row_half_mirror        h  = q(bank 2j) + q(bank 2j+1)   (one value per 8-lane half-row)
+//   bit 3  row_mirror             r  = h(half-row 0) + h(half-row 1)   (one value per 16-lane row)
+//   bit 4  row_bcast15, rows 1,3  p  = r(row 2j) + r(row 2j+1)
+//   bit 5  row_bcast31, rows 2,3  total = p(rows 0,1) + p(rows 2,3)
+// Every level adds two partial sums of the level before, and which two is all the tree fixes.  fp32 addition is
+// commutative (a + b and b + a are the same bits), so neither the lane that forms a sum nor the order of its two operands
+// changes it.  The merged schedule forms, at every level, sums of exactly these pairs; hence every total has the bits
+// of qc_wave_sum_to_lane63's.  (tools/ubench/wave_sum_merge.hip compares them bitwise on the device for NV = 1..16.)
+//
+// Schedule for a chunk of up to 16 values k = 0..15 (a longer array is cut into chunks of 16):
+//   bits 0, 1  per value, as above: DPP has no mask finer than a bank (4 lanes), nothing can be merged yet.
+//   bit 2      value 2i: row_half_mirror add to all banks; value 2i+1: the same add with bank_mask 0xa INTO the register
+//              of 2i.  Banks 0, 2 now carry h of value 2i, banks 1, 3 h of value 2i+1.
+//   bit 3      row_ror:8 pairs bank 0 with 2 and bank 1 with 3, i.e. the two half-rows of the SAME value (row_mirror
+//              would pair bank 0 with bank 3: two different values).  The second pair's add goes with bank_mask 0xc into
+//              the first pair's register: bank b of register 4i carries r of value 4i + b.
+//   bit 4      v_permlane16_swap of registers 8i and 8i+4 exchanges the odd rows of the first with the even rows of
+//              the second; one plain add then leaves p of values 8i..8i+3 in rows 0, 2 and of 8i+4..8i+7 in rows 1, 3.
+//   bit 5      v_permlane32_swap of registers 0 and 8 plus one add: lanes 0..31 carry the totals of values 0..7, lanes
+//              32..63 those of values 8..15.
+//   A register without a partner is swapped with a dead one (a value register already folded away): the lanes that
+//   receive the dead register's content are not home lanes.  row_bcast15/31 cannot serve here, they broadcast one
+//   lane and with it one bank's value.
+// Home lanes: value k of a merged chunk ends in the four lanes 4 j .. 4 j + 3, j = k % 16, of register v[16 (k / 16)], and
+// its HOME lane is the first of them for even j and the last for odd j: lane 4 j + 3 (j & 1), that is lanes 0, 7, 8, 15
+// of a row.  A chunk of one or two values (NV < 3, or the tail of a longer array) is cheaper unmerged
+// and keeps lane 63 of its own register.  Both maps are the constexpr functions below; callers store from there.
+// Why not any lane of the bank: where the summed value is a product, -ffp-contract=fast lets the compiler contract the
+// multiply into the first step, s1[l] = fma(a[l], b[l], round(a b)[l^1]), and then s1[l] != s1[l^1]: the lanes of a
+// quad hold two versions of the quad sum (even lanes one, odd lanes the other), and so on up the tree.  The arguments
+// above still hold lane by lane with x[l^1] replaced by "what lane l^1 holds", and they give: after bit 2 lanes l and
+// l^7 agree (h[l] = q[l] + q[l^7]); lane 63's total is built from r[15] = h[15] + h[0] of each row; row_ror:8 forms
+// h[l] + h[l^8], which in lanes 0, 7, 8, 15 is h[0] + h[15] (h[7] = h[0], h[8] = h[15]) and elsewhere is not.  Bits 4 and
+// 5 add lane-for-lane across rows.  So the home lanes, and only they, carry the bits of lane 63 of
+// qc_wave_sum_to_lane63 for contracted inputs too.
+// Cost in VALU instructions: 2 NV + NV + ceil(NV/2) + 2 ceil(NV/8) + 2 per chunk; 25 for NV = 6 (36 unmerged), 18 for
+// NV = 4 (24), 48 for NV = 12 (72), plus an s_nop 1 in front of each swap whose operands the step before wrote.
+__host__ __device__ constexpr int qc_ws_chunk_len(int NV, int k) { return NV - k / 16 * 16 < 16 ? NV - k / 16 * 16 : 16; }
+__host__ __device__ constexpr bool qc_ws_merged(int NV, int k) { return qc_ws_chunk_len(NV, k) >= 3; }
+__host__ __device__ constexpr int qc_wave_sum_home_lane(int NV, int k) {
+  return qc_ws_merged(NV, k) ? 4 * (k % 16) + 3 * (k & 1) : 63;
+}
+// the inverse map within a merged chunk: is `lane` a home lane, and of which value of the chunk
+__host__ __device__ constexpr bool qc_wave_sum_is_home(int lane) { return (lane & 3) == 3 * ((lane >> 2) & 1); }
+__host__ __device__ constexpr int qc_wave_sum_home_index(int lane) { return lane >> 2; }
+__host__ __device__ constexpr int qc_wave_sum_home_reg(int NV, int k) { return qc_ws_merged(NV, k) ? k / 16 * 16 : k; }
+
+// The levels from bit 2 on are hand-written instructions (a bank-masked add into another value's register has no
+// builtin form), and inside asm neither the assembler nor the compiler pads the hazards: a DPP or permlane-swap read of a
+// register needs two wait states behind the VALU write of it (the s_nop 0 the compiler puts between two asm statements
+// that share a register answers another hazard and is one state short).  The order of a chunk's instructions and the
+// s_nop in front of those that would read too early are worked out at compile time by a small list scheduler.
+enum : int { QC_WS_HM, QC_WS_HMM, QC_WS_ROR, QC_WS_RORM, QC_WS_SW16, QC_WS_SW32 };
+struct QcWsOp {
+  int kind, a, b, pad;   // a: register written (and folded); b: second register; pad: wait states in front
+};
+struct QcWsPlan {
+  QcWsOp op[32];
+  int n;
+};
+__host__ __device__ constexpr QcWsPlan qc_ws_plan(int n) {
+  QcWsOp prog[32] = {};
+  int np = 0;
+  for (int a = 0; a < n; a += 2) {
+    prog[np++] = {QC_WS_HM, a, a, 0};
+    if (a + 1 < n) prog[np++] = {QC_WS_HMM, a, a + 1, 0};
+  }
+  for (int a = 0; a < n; a += 4) {
+    prog[np++] = {QC_WS_ROR, a, a, 0};
+    if (a + 2 < n) prog[np++] = {QC_WS_RORM, a, a + 2, 0};
+  }
+  // dead registers for the swaps without a partner: 1 (read last by the bit-2 step of register 0) and 2 (bit 3)
+  for (int a = 0; a < n; a += 8) prog[np++] = {QC_WS_SW16, a, a + 4 < n ? a + 4 : 1, 0};
+  prog[np++] = {QC_WS_SW32, 0, 8 < n ? 8 : (n <= 4 ? 2 : 1), 0};
+  QcWsPlan P = {};
+  int age[16] = {};
+  for (int r = 0; r < 16; ++r) age[r] = 99;
+  bool done[32] = {};
+  int pad = 0;
+  while (P.n < np) {
+    int pick = -1;
+    for (int i = 0; i < np && pick < 0; ++i) {
+      if (done[i]) continue;
+      const QcWsOp o = prog[i];
+      const bool swap = o.kind == QC_WS_SW16 || o.kind == QC_WS_SW32;
+      bool ok = true;
+      // every earlier instruction that touches one of this one's registers has been issued
+      for (int j = 0; j < i; ++j)
+        if (!done[j] && (prog[j].a == o.a || prog[j].a == o.b || prog[j].b == o.a || prog[j].b == o.b)) ok = false;
+      // the registers it reads across lanes were written two wait states ago
+      if (age[o.b] < 2 || ((swap || o.a == o.b) && age[o.a] < 2)) ok = false;
+      if (ok) pick = i;
+    }
+    if (pick < 0) {
+      ++pad;
+      for (int r = 0; r < 16; ++r) ++age[r];
+      continue;
+    }
+    QcWsOp o = prog[pick];
+    const bool swap = o.kind == QC_WS_SW16 || o.kind == QC_WS_SW32;
+    o.pad = pad;
+    pad = 0;
+    done[pick] = true;
+    P.op[P.n++] = o;
+    for (int r = 0; r < 16; ++r) age[r] += swap ? 2 : 1;   // a swap comes with its add
+    age[o.a] = 0;
+    if (swap) age[o.b] = 1;
+  }
+  return P;
+}
+
+template <int NV, int C0, int I>
+__device__ __forceinline__ void qc_ws_emit(float (&v)[NV]) {
+  constexpr QcWsPlan P = qc_ws_plan(qc_ws_chunk_len(NV, C0));
+  if constexpr (I < P.n) {
+    constexpr QcWsOp o = P.op[I];
+    static_assert(o.pad >= 0 && o.pad <= 2, "a hazard is two wait states");
+    float& x = v[C0 + o.a];
+    float& y = v[C0 + o.b];
+#define QC_WS_ASM_(INS, ...)                                                   \
+  do {                                                                         \
+    if constexpr (o.pad == 0) asm volatile(INS : __VA_ARGS__);                 \
+    else if constexpr (o.pad == 1) asm volatile("s_nop 0\n\t" INS : __VA_ARGS__); \
+    else asm volatile("s_nop 1\n\t" INS : __VA_ARGS__);                        \
+  } while (0)
+    if constexpr (o.kind == QC_WS_HM)
+      QC_WS_ASM_("v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf", "+v"(x));
+    else if constexpr (o.kind == QC_WS_HMM)
+      QC_WS_ASM_("v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa", "+v"(x) : "v"(y));
+    else if constexpr (o.kind == QC_WS_ROR)
+      QC_WS_ASM_("v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf", "+v"(x));
+    else if constexpr (o.kind == QC_WS_RORM)
+      QC_WS_ASM_("v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc", "+v"(x) : "v"(y));
+    else if constexpr (o.kind == QC_WS_SW16)
+      QC_WS_ASM_("v_permlane16_swap_b32 %0, %1\n\tv_add_f32 %0, %0, %1", "+v"(x), "+v"(y));
+    else
+      QC_WS_ASM_("v_permlane32_swap_b32 %0, %1\n\tv_add_f32 %0, %0, %1", "+v"(x), "+v"(y));
+#undef QC_WS_ASM_
+    qc_ws_emit<NV, C0, I + 1>(v);
+  }
+}
+template <int NV, int C0>
+__device__ __forceinline__ void qc_ws_chunks(float (&v)[NV]) {
+  if constexpr (C0 < NV) {
+    if constexpr (qc_ws_merged(NV, C0)) {
+      qc_ws_emit<NV, C0, 0>(v);
+    } else {
+      constexpr int R = NV - C0;
+      float t[R];
+#pragma unroll
+      for (int k = 0; k < R; ++k) t[k] = v[C0 + k];
+      qc_wave_sum_multi_to_lane63<R>(t);
+#pragma unroll
+      for (int k = 0; k < R; ++k) v[C0 + k] = t[k];
+    }
+    qc_ws_chunks<NV, C0 + 16>(v);
+  }
+}
+// On return value k's total is in lane qc_wave_sum_home_lane(NV, k) of v[qc_wave_sum_home_reg(NV, k)]; every other
+// lane and register of v holds no defined value.
+template <int NV>
+__device__ __forceinline__ void qc_wave_sum_merged(float (&v)[NV]) {
+  if constexpr (NV < 3) {
+    qc_wave_sum_multi_to_lane63<NV>(v);
+  } else {
+    constexpr int NM = NV - (qc_ws_merged(NV, NV - 1) ? 0 : NV % 16);   // values in merged chunks
+#pragma unroll
+    for (int k = 0; k < NM; ++k)
+      v[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[k]), 0xB1, 0xF, 0xF, true));
+#pragma unroll
+    for (int k = 0; k < NM; ++k)
+      v[k] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[k]), 0x4E, 0xF, 0xF, true));
+    // every value's quad sum is complete, and two wait states old, before the first hand-written DPP read
+#pragma unroll
+    for (int k = 0; k < NM; ++k) asm volatile("" : "+v"(v[k]));
+    asm volatile("s_nop 1");
+    qc_ws_chunks<NV, 0>(v);
+  }
+}
+
 // Sum over the wave, result broadcast to every lane (uniform value).
 __device__ __forceinline__ float qc_wave_sum(float v) {
   v = qc_wave_sum_to_lane63(v);

@@ -691,6 +691,24 @@ __device__ __forceinline__ void expand_ub(float (&ub)[NCH], float ub0, float gsc
   }
 }
 
+// The N + 1 sums of one hidden unit of the K-output kernels (dW3[m][0..N), db3[m]) after qc_wave_sum_merged: sum r is in
+// its home lane and register (csrc/qc_common.h), and that lane stores its column of the tile row: one store per chunk of
+// sixteen sums; a chunk of one or two is unmerged and stored from lane 63.
+template <int N, int C = 0>
+__device__ __forceinline__ void post_store_w3b3(float* __restrict__ row, const QcLayout& L, const float (&wg)[N + 1], const int m,
+                                                const int lane) {
+  if constexpr (C * 16 < N + 1) {
+    if constexpr (qc_ws_merged(N + 1, C * 16)) {
+      const int r = C * 16 + qc_wave_sum_home_index(lane);
+      if (qc_wave_sum_is_home(lane) && r <= N) row[r < N ? L.oW3 + m * N + r : L.ob3 + m] = wg[C * 16];
+    } else if (lane == 63) {
+#pragma unroll
+      for (int r = C * 16; r <= N; ++r) row[r < N ? L.oW3 + m * N + r : L.ob3 + m] = wg[r];
+    }
+    post_store_w3b3<N, C + 1>(row, L, wg, m, lane);
+  }
+}
+
 // LEARN (the inverse step): the operator is global and trainable.  The seven c_k = fmaf(scale_k, p_k, base_k) are formed once
 // per wave from the wave-uniform p = prm[NP_L - 7 ..] (L.NP counts them) and take the place of a coefficient row.
 __device__ __forceinline__ void learn_coefs(float (&cf)[QC_COEF_N], const float* __restrict__ prm, const QcLayout& L,
@@ -707,6 +725,7 @@ __device__ __forceinline__ void learn_columns(float* __restrict__ row, const QcL
                                               const float (&scale)[QC_COEF_N], const float (&cf)[QC_COEF_N], const float gsc,
                                               const float (&u)[6], const int lane, const bool tile0) {
   float gv[QC_COEF_N] = {gsc * u[0], gsc * u[1], gsc * u[2], gsc * u[3], -gsc * u[4], -gsc * u[5], gsc * (u[0] * u[0] * u[0])};
+  // (unmerged: a per-lane pick of scale[k] for the home lanes costs these kernels scratch, and wave 0 runs this once per tile)
   qc_wave_sum_multi_to_lane63<QC_COEF_N>(gv);
   if (lane == 63) {
 #pragma unroll
@@ -1472,6 +1491,49 @@ constexpr int qc_post_ub_a(int n) { return n == 3 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 
 constexpr bool qc_post_pf(int n) { return n <= 8; }   // prefetch of the next block
 constexpr int qc_post_ub_vb(int n) { return n <= 8 ? 2 : 1; }                 // phase B of a value tile: two reductions side by side
 
+// The weight-gradient sums of one block of K hidden units, reduced by qc_wave_sum_merged: value j (N + 2) + r is unit
+// m + j's dW3[r] (r < N), db3 (r = N) or dW4 (r = N + 1), and ends in its home lane of register 16 (k / 16) (k = the
+// value's index; the home-lane map of csrc/qc_common.h).  Every home lane stores its own column of the tile row, one store per
+// sixteen values; the column is col0 + m cstep, two lane constants formed once per wave.
+template <int N, int KMAX>
+struct QcPostCols {
+  static constexpr int NC = (KMAX * (N + 2) + 15) / 16;
+  unsigned col0[NC], cstep[NC];
+  bool home;
+  __device__ __forceinline__ QcPostCols(const QcLayout& L, const int lane) {
+    home = qc_wave_sum_is_home(lane);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int k = 16 * c + qc_wave_sum_home_index(lane), j = k / (N + 2), r = k % (N + 2);
+      col0[c] = r < N ? L.oW3 + j * N + r : (r == N ? L.ob3 : L.oW4) + j;
+      cstep[c] = r < N ? N : 1;
+    }
+  }
+  template <int K>
+  __device__ __forceinline__ void store(float* __restrict__ row, const QcLayout& L, const float (&wg)[K * (N + 2)], const int m,
+                                        const int lane) const {
+    static_assert(K <= KMAX, "columns formed for KMAX units");
+    store_chunk<K, 0>(row, L, wg, m, lane);
+  }
+  template <int K, int C>
+  __device__ __forceinline__ void store_chunk(float* __restrict__ row, const QcLayout& L, const float (&wg)[K * (N + 2)],
+                                              const int m, const int lane) const {
+    constexpr int NV = K * (N + 2);
+    if constexpr (C * 16 < NV) {
+      if constexpr (qc_ws_merged(NV, C * 16)) {
+        if (home && 16 * C + qc_wave_sum_home_index(lane) < NV) row[col0[C] + __umul24(m, cstep[C])] = wg[qc_wave_sum_home_reg(NV, C * 16)];
+      } else if (lane == 63) {   // one or two values left over: unmerged, in lane 63 of their own registers
+#pragma unroll
+        for (int k = C * 16; k < NV; ++k) {
+          const int j = k / (N + 2), r = k % (N + 2);
+          row[r < N ? L.oW3 + (m + j) * N + r : (r == N ? L.ob3 : L.oW4) + m + j] = wg[k];
+        }
+      }
+      store_chunk<K, C + 1>(row, L, wg, m, lane);
+    }
+  }
+};
+
 template <int N, int TPB, bool DATA = false, bool LEARN = false, bool BAL = false>
 __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const float* __restrict__ X,
                                                         const float* __restrict__ prm, QcLayout L, QcPde pde,
@@ -1564,7 +1626,8 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
   // ---------------- phase B over the same hidden units: weight gradients; gb parked in place of tanh
   float ub[1];
   expand_ub<1>(ub, ub0, 0.f, pde);
-  // W4 only: K values per block; the K units' reductions run side by side (each value's six steps in their own order)
+  // W4 only: K values per block; the K units' reductions run as one merged reduction (same tree for every value)
+  const QcPostCols<N, qc_post_ub_vb(N)> cols(L, lane);
   qc_unit_blocks<QcColW, qc_post_ub_vb(N), false>(
       m0, m1,
       [&](auto& w, const int m) {
@@ -1585,16 +1648,8 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
           wg[j * (N + 2) + N] = gb[0];
           wg[j * (N + 2) + N + 1] = gw4;
         }
-        qc_wave_sum_multi_to_lane63<K * (N + 2)>(wg);
-        if (lane == 63) {
-#pragma unroll
-          for (int j = 0; j < K; ++j) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) row[L.oW3 + (m + j) * N + i] = wg[j * (N + 2) + i];
-            row[L.ob3 + m + j] = wg[j * (N + 2) + N];
-            row[L.oW4 + m + j] = wg[j * (N + 2) + N + 1];
-          }
-        }
+        qc_wave_sum_merged<K * (N + 2)>(wg);
+        cols.template store<K>(row, L, wg, m, lane);
       });
   __syncthreads();
   // ---------------- qbar[i] = sum over m of W3[m][i] gb(m), one chain per i
@@ -1802,7 +1857,8 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
   for (int cp = 0; cp < 3; ++cp)
 #pragma unroll
     for (int i = 0; i < N; ++i) qb2[cp][i] = (mf2){0.f, 0.f};
-  // the K units' weight-gradient reductions run side by side (each value's six steps in their own order)
+  // the K units' weight-gradient reductions run as one merged reduction (same tree for every value)
+  const QcPostCols<N, QC_POST6_UB_B<N>> cols(L, lane);
   qc_unit_blocks<QcPostW<N>, QC_POST6_UB_B<N>, QC_POST6_PF_B<N>>(m0, m1, load_blk, [&](const auto& w, const int m) {
     constexpr int K = std::remove_reference_t<decltype(w)>::count;
     float wg[K * (N + 2)];
@@ -1829,16 +1885,8 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
       wg[j * (N + 2) + N] = gb[0];
       wg[j * (N + 2) + N + 1] = gw4;
     }
-    qc_wave_sum_multi_to_lane63<K * (N + 2)>(wg);
-    if (lane == 63) {
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) row[L.oW3 + (m + j) * N + i] = wg[j * (N + 2) + i];
-        row[L.ob3 + m + j] = wg[j * (N + 2) + N];
-        row[L.oW4 + m + j] = wg[j * (N + 2) + N + 1];
-      }
-    }
+    qc_wave_sum_merged<K * (N + 2)>(wg);
+    cols.template store<K>(row, L, wg, m, lane);
   });
   __syncthreads();   // every wave is done with s_z and s_u: the qbar partials overwrite them
 #pragma unroll
@@ -2035,14 +2083,12 @@ __global__ void __launch_bounds__(256) k_post_multi(const float* __restrict__ pr
         wg[i] = sum;
       }
       wg[N] = gb[0];
-      qc_wave_sum_multi_to_lane63<N + 1>(wg);
+      qc_wave_sum_merged<N + 1>(wg);
+      post_store_w3b3<N>(row, L, wg, m, lane);
 #pragma unroll
       for (int k = 0; k < QC_KMAX; ++k)
         if (k < K) gk[k] = qc_wave_sum_to_lane63(gk[k]);
       if (lane == 63) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) row[L.oW3 + m * N + i] = wg[i];
-        row[L.ob3 + m] = wg[N];
 #pragma unroll
         for (int k = 0; k < QC_KMAX; ++k)
           if (k < K) rowk[k * H1 + m] = gk[k];
@@ -2596,14 +2642,12 @@ __global__ void __launch_bounds__(256) k_post_system(const float* __restrict__ p
       wg[i] = sum;
     }
     wg[N] = gb[0];
-    qc_wave_sum_multi_to_lane63<N + 1>(wg);
+    qc_wave_sum_merged<N + 1>(wg);
+    post_store_w3b3<N>(row, L, wg, m, lane);
 #pragma unroll
     for (int k = 0; k < QC_KMAX; ++k)
       if (k < K) gk[k] = qc_wave_sum_to_lane63(gk[k]);
     if (lane == 63) {
-#pragma unroll
-      for (int i = 0; i < N; ++i) row[L.oW3 + m * N + i] = wg[i];
-      row[L.ob3 + m] = wg[N];
 #pragma unroll
       for (int k = 0; k < QC_KMAX; ++k)
         if (k < K) row[L.oW4 + k * L.H + m] = gk[k];
