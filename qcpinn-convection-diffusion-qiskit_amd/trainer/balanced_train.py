@@ -13,12 +13,10 @@ covers the model's parameters only.  The reference's script uses AdamW; this ste
 """
 from __future__ import annotations
 
-import time
-
 from ..data.tabulated import TabulatedProblem
 from ..hip import engine as _engine
 from ..nn.loss_balance import TERMS, AdaptiveMultiLoss
-from .diffusion_train import _dist_info, _log_line
+from .diffusion_train import _dist_info, check_fused_single, load_with_targets, run_fused_loop
 from .inverse_train import InverseTrainer
 
 
@@ -36,13 +34,7 @@ def check_balance(model, dataset, balancer, adaptive=None, lbfgs=None):
         raise ValueError("balance= cannot be combined with adaptive= sampling")
     if lbfgs is not None:
         raise ValueError("balance= cannot be combined with an lbfgs= phase")
-    world, _ = _dist_info()
-    if world > 1:
-        raise ValueError("balance= is single-process: world_size > 1 is not supported")
-    if not (hasattr(model, "_engine_for") and hasattr(model, "quantum_layer")):
-        raise ValueError("balance= runs in the fused step: it is only supported for DVPDESolver models")
-    if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
-        raise ValueError("balance= needs classic_network = [3, H, 1]")
+    check_fused_single(model, "balance", _dist_info()[0])
 
 
 class BalancedTrainer(InverseTrainer):
@@ -98,34 +90,7 @@ class BalancedTrainer(InverseTrainer):
 
 def train_balanced(model, batch_size, batches, dataset, balancer):
     """The loop of ``trainer.diffusion_train.train`` over a ``BalancedTrainer``: the logged loss is F."""
-    steps = model.epochs + 1
-    tr = BalancedTrainer(model, batch_size, dataset, balancer, capacity=steps)
-    t0 = time.time()
-    model.logger.print(f"Starting training for {model.epochs} epochs with learned loss weights...")
-    model.logger.print(f"Batch size: {batch_size}")
-    pe = model.args["print_every"]
-    done = 0
-    for it in range(steps):
-        if batches is None:
-            tr.sample()
-        else:
-            tr.load_batches(*batches[it][:3], targets=batches[it][3])
-        tr.step()
-        if it % pe == 0 or it == 0:
-            parts, lr = tr.losses()
-            el = time.time() - t0
-            _log_line(model, it, parts, lr, el / (it + 1), el)
-            w = tr.weights()
-            model.logger.print("  loss weights: " + ", ".join(f"{k} {v:.3e}" for k, v in w.items()))
-            if it > 0 and it % pe == 0:
-                hist = tr.loss_history(it + 1)
-                model.loss_history.extend(hist[done:])
-                done = len(hist)
-                model.save_state()
-    hist = tr.loss_history(steps)
-    model.loss_history.extend(hist[done:])
-    tr.sync_to_torch()
-    total = time.time() - t0
-    model.total_training_time += total
-    model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
-    return tr
+    tr = BalancedTrainer(model, batch_size, dataset, balancer, capacity=model.epochs + 1)
+    return run_fused_loop(model, tr, f"Starting training for {model.epochs} epochs with learned loss weights...", batch_size,
+                          batches, load_with_targets,
+                          lambda tr: "  loss weights: " + ", ".join(f"{k} {v:.3e}" for k, v in tr.weights().items()))

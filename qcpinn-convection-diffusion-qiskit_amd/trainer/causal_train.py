@@ -13,11 +13,9 @@ fold sums the rows of slab i with W_i, formed on the device from the loss column
 """
 from __future__ import annotations
 
-import time
-
 from ..data.tabulated import CausalWeighting, TabulatedProblem
 from ..hip import engine as _engine
-from .diffusion_train import FusedTrainer, _dist_info, _log_line
+from .diffusion_train import FusedTrainer, _dist_info, check_fused_single, load_with_targets, run_fused_loop
 
 
 def check_causal(model, dataset, causal, batch_size, adaptive=None, lbfgs=None, balance=None, operator=None):
@@ -38,13 +36,7 @@ def check_causal(model, dataset, causal, batch_size, adaptive=None, lbfgs=None, 
         raise ValueError("causal= cannot be combined with balance=")
     if operator is not None:
         raise ValueError("causal= cannot be combined with a learned operator (the inverse step)")
-    world, _ = _dist_info()
-    if world > 1:
-        raise ValueError("causal= is single-process: world_size > 1 is not supported")
-    if not (hasattr(model, "_engine_for") and hasattr(model, "quantum_layer")):
-        raise ValueError("causal= runs in the fused step: it is only supported for DVPDESolver models")
-    if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
-        raise ValueError("causal= needs classic_network = [3, H, 1]")
+    check_fused_single(model, "causal", _dist_info()[0])
     tile = 64 * causal.n_slabs
     if isinstance(batch_size, bool) or int(batch_size) <= 0 or int(batch_size) % tile:
         raise ValueError(f"causal= needs a batch size that is a positive multiple of 64 * n_slabs = {tile}, got {batch_size}")
@@ -95,34 +87,13 @@ def train_causal(model, batch_size, batches, dataset, causal):
     """The loop of ``trainer.diffusion_train.train`` over a ``CausalTrainer``."""
     steps = model.epochs + 1
     tr = CausalTrainer(model, batch_size, dataset, causal, capacity=steps)
-    t0 = time.time()
-    model.logger.print(f"Starting training for {model.epochs} epochs with causal weights over {causal.n_slabs} time slabs...")
-    model.logger.print(f"Batch size: {batch_size}")
-    pe = model.args["print_every"]
-    done = 0
-    for it in range(steps):
-        if batches is None:
-            tr.sample()
-        else:
-            tr.load_batches(*batches[it][:3], targets=batches[it][3])
-        tr.step()
-        if it % pe == 0 or it == 0:
-            parts, lr = tr.losses()
-            el = time.time() - t0
-            _log_line(model, it, parts, lr, el / (it + 1), el)
-            eps, raised = tr.epsilon()
-            w = tr.causal_weights()
-            model.logger.print(f"  causal weights: min {float(w.min()):.3e} | eps (next step): {eps:.3e}, raised {raised} times")
-            if it > 0 and it % pe == 0:
-                hist = tr.opt.loss_history(it + 1)
-                model.loss_history.extend(hist[done:])
-                done = len(hist)
-                model.save_state()
-    hist = tr.opt.loss_history(steps)
-    model.loss_history.extend(hist[done:])
-    model.causal_history = tr.causal_history(steps)
-    tr.sync_to_torch()
-    total = time.time() - t0
-    model.total_training_time += total
-    model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
-    return tr
+
+    def extra_line(tr):
+        eps, raised = tr.epsilon()
+        w = tr.causal_weights()
+        return f"  causal weights: min {float(w.min()):.3e} | eps (next step): {eps:.3e}, raised {raised} times"
+
+    def finish(tr, steps):
+        model.causal_history = tr.causal_history(steps)
+    return run_fused_loop(model, tr, f"Starting training for {model.epochs} epochs with causal weights over "
+                          f"{causal.n_slabs} time slabs...", batch_size, batches, load_with_targets, extra_line, finish)

@@ -426,6 +426,9 @@ class FusedTrainer:
             dist.all_reduce(self.fs.flat_grad)          # one small all-reduce: [grads | L_r, L_bc, L_ic]
             self.fs.run(_lib.QC_PHASE_UPDATE)
 
+    def loss_history(self, steps=None):
+        return self.opt.loss_history(steps)
+
     def losses(self):
         rec = self.opt.read()
         return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
@@ -445,13 +448,36 @@ def _check_adaptive(adaptive, dataset, batch_size, sampler="device"):
         raise ValueError("adaptive= draws on the device: it cannot be combined with sampler='torch'")
 
 
-def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None, lbfgs=None):
-    if lbfgs is not None and adaptive is not None:
-        raise ValueError("lbfgs= needs a fixed objective: it cannot be combined with adaptive= sampling")
+def check_fused_single(model, what, world):
+    """The common tail of the argument checks of ``gradnorm=``, ``causal=`` and ``balance=``: single process (``world``
+    = the caller's ``_dist_info()[0]``), a DVPDESolver, classic_network = [3, H, 1]."""
+    if world > 1:
+        raise ValueError(f"{what}= is single-process: world_size > 1 is not supported")
+    if not (hasattr(model, "_engine_for") and hasattr(model, "quantum_layer")):
+        raise ValueError(f"{what}= runs in the fused step: it is only supported for DVPDESolver models")
+    if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
+        raise ValueError(f"{what}= needs classic_network = [3, H, 1]")
+
+
+def load_explicit(tr, batch):
+    """A step's explicit batch (X_ic, X_bc, X_res[, targets[, coef]]) into a FusedTrainer."""
+    tr.load_batches(*batch[:3], targets=batch[3] if len(batch) > 3 else None, coef=batch[4] if len(batch) > 4 else None)
+
+
+def load_with_targets(tr, batch):
+    """A step's explicit batch (X_ic, X_bc, X_res, targets) into a trainer on a dataset."""
+    tr.load_batches(*batch[:3], targets=batch[3])
+
+
+def run_fused_loop(model, tr, banner, batch_size, batches=None, load=load_explicit, extra_line=None, finish=None):
+    """The training loop around a constructed fused trainer ``tr`` (``sample`` / ``load_batches``, ``step``, ``losses``,
+    ``loss_history``, ``sync_to_torch``): ``model.epochs + 1`` steps on sampled batches or, with ``batches``, on
+    ``load(tr, batches[it])``; the log line at iteration 0 and every ``print_every``, followed by ``extra_line(tr)`` if
+    given; ``model.loss_history`` extended and ``save_state`` at every later multiple of ``print_every``; ``finish(tr,
+    steps)`` (what else is stored on the model) ahead of the copy back to torch.  Returns ``tr``."""
     steps = model.epochs + 1
-    tr = FusedTrainer(model, batch_size, capacity=steps, dataset=dataset, adaptive=adaptive)
     t0 = time.time()
-    model.logger.print(f"Starting training for {model.epochs} epochs...")
+    model.logger.print(banner)
     model.logger.print(f"Batch size: {batch_size}")
     pe = model.args["print_every"]
     done = 0
@@ -459,8 +485,7 @@ def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None, l
         if batches is None:
             tr.sample()
         else:
-            tr.load_batches(*batches[it][:3], targets=batches[it][3] if len(batches[it]) > 3 else None,
-                            coef=batches[it][4] if len(batches[it]) > 4 else None)
+            load(tr, batches[it])
         tr.step()
         if it % pe == 0 or it == 0:
             # the reference logs the loss of iteration `it` BEFORE its optimiser step; the fused step has
@@ -468,14 +493,30 @@ def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None, l
             parts, lr = tr.losses()
             el = time.time() - t0
             _log_line(model, it, parts, lr, el / (it + 1), el)
+            if extra_line is not None:
+                model.logger.print(extra_line(tr))
             if it > 0 and it % pe == 0:
-                hist = tr.opt.loss_history(it + 1)
+                hist = tr.loss_history(it + 1)
                 model.loss_history.extend(hist[done:])
                 done = len(hist)
                 model.save_state()
-    hist = tr.opt.loss_history(steps)
+    hist = tr.loss_history(steps)
     model.loss_history.extend(hist[done:])
-    if lbfgs is not None:
+    if finish is not None:
+        finish(tr, steps)
+    tr.sync_to_torch()
+    total = time.time() - t0
+    model.total_training_time += total
+    model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
+    return tr
+
+
+def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None, lbfgs=None):
+    if lbfgs is not None and adaptive is not None:
+        raise ValueError("lbfgs= needs a fixed objective: it cannot be combined with adaptive= sampling")
+    tr = FusedTrainer(model, batch_size, capacity=model.epochs + 1, dataset=dataset, adaptive=adaptive)
+
+    def lbfgs_phase(tr, steps):
         # the second phase: L-BFGS evaluations on the batches of the last Adam step (explicit batches) or on a fresh draw;
         # the model is left at the last accepted point and the accepted losses continue the history
         from .lbfgs_train import run_phase
@@ -485,11 +526,8 @@ def _train_fused(model, batch_size, batches=None, dataset=None, adaptive=None, l
         model.logger.print("L-BFGS: %d evaluations, %d accepted, %d rejected trials, %d resets%s | Loss: %.2e"
                            % (rec["n_eval"], rec["n_iter"], rec["n_rejected"], rec["n_resets"],
                               ", stalled" if rec["stalled"] else "", rec["f0"]))
-    tr.sync_to_torch()
-    total = time.time() - t0
-    model.total_training_time += total
-    model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
-    return tr
+    return run_fused_loop(model, tr, f"Starting training for {model.epochs} epochs...", batch_size, batches,
+                          finish=None if lbfgs is None else lbfgs_phase)
 
 
 # ---------------------------------------------------------------------------------------------

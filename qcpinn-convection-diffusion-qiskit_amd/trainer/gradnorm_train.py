@@ -15,11 +15,9 @@ step; the lambda-weighted loss goes into the history of the weights.
 """
 from __future__ import annotations
 
-import time
-
 from ..hip import engine as _engine
 from ..nn.loss_balance import GradNormWeighting
-from .diffusion_train import FusedTrainer, _dist_info, _log_line
+from .diffusion_train import FusedTrainer, _dist_info, check_fused_single, load_with_targets, run_fused_loop
 
 
 def check_gradnorm(model, dataset, gradnorm, batch_size, adaptive=None, lbfgs=None, balance=None, causal=None, operator=None,
@@ -40,13 +38,7 @@ def check_gradnorm(model, dataset, gradnorm, batch_size, adaptive=None, lbfgs=No
         raise ValueError("gradnorm= cannot be combined with causal=")
     if operator is not None:
         raise ValueError("gradnorm= cannot be combined with a learned operator (the inverse step)")
-    world, _ = _dist_info()
-    if world > 1:
-        raise ValueError("gradnorm= is single-process: world_size > 1 is not supported")
-    if not (hasattr(model, "_engine_for") and hasattr(model, "quantum_layer")):
-        raise ValueError("gradnorm= runs in the fused step: it is only supported for DVPDESolver models")
-    if getattr(model, "input_dim", 3) != 3 or int(getattr(model, "n_out", 1)) != 1:
-        raise ValueError("gradnorm= needs classic_network = [3, H, 1]")
+    check_fused_single(model, "gradnorm", _dist_info()[0])
     n3 = int(batch_size) // 3
     n_ic, n_bc = (n3 if n_ic is None else int(n_ic)), (n3 if n_bc is None else int(n_bc))
     if n_ic > 0 and n_bc > 0 and n_ic % 64:
@@ -93,36 +85,10 @@ def train_gradnorm(model, batch_size, batches, dataset, gradnorm):
     """The loop of ``trainer.diffusion_train.train`` over a ``GradNormTrainer``."""
     steps = model.epochs + 1
     tr = GradNormTrainer(model, batch_size, gradnorm, dataset, capacity=steps)
-    t0 = time.time()
-    model.logger.print(f"Starting training for {model.epochs} epochs with gradient-norm loss weights "
-                       f"(alpha {gradnorm.alpha}, every {gradnorm.every} steps)...")
-    model.logger.print(f"Batch size: {batch_size}")
-    pe = model.args["print_every"]
-    done = 0
-    for it in range(steps):
-        if batches is None:
-            tr.sample()
-        elif dataset is not None:
-            tr.load_batches(*batches[it][:3], targets=batches[it][3])
-        else:
-            tr.load_batches(*batches[it][:3])
-        tr.step()
-        if it % pe == 0 or it == 0:
-            parts, lr = tr.losses()
-            el = time.time() - t0
-            _log_line(model, it, parts, lr, el / (it + 1), el)
-            lam_bc, lam_ic = tr.weights()
-            model.logger.print(f"  gradient-norm weights: lam_bc {lam_bc:.3e} | lam_ic {lam_ic:.3e}")
-            if it > 0 and it % pe == 0:
-                hist = tr.opt.loss_history(it + 1)
-                model.loss_history.extend(hist[done:])
-                done = len(hist)
-                model.save_state()
-    hist = tr.opt.loss_history(steps)
-    model.loss_history.extend(hist[done:])
-    model.gradnorm_history = tr.gradnorm_history(steps)
-    tr.sync_to_torch()
-    total = time.time() - t0
-    model.total_training_time += total
-    model.logger.print(f"Training completed in {total:.2f} seconds ({total / 60:.2f} minutes)")
-    return tr
+
+    def finish(tr, steps):
+        model.gradnorm_history = tr.gradnorm_history(steps)
+    return run_fused_loop(model, tr, f"Starting training for {model.epochs} epochs with gradient-norm loss weights "
+                          f"(alpha {gradnorm.alpha}, every {gradnorm.every} steps)...", batch_size, batches,
+                          load_with_targets if dataset is not None else (lambda tr, b: tr.load_batches(*b[:3])),
+                          lambda tr: "  gradient-norm weights: lam_bc %.3e | lam_ic %.3e" % tr.weights(), finish)

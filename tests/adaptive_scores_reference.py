@@ -1,6 +1,6 @@
 """Float64 reference of qc_dataset_scores (include/qcpinn_hip.h): the six channels of u on the residual rows of a seeded
 dataset, from tests/mlp_reference.py and the circuit oracle like tests/tabulated_reference.py, cached through
-conftest.cached_oracle (arrays only; tests/golden/make_adaptive_oracle_cache.py writes the records).  Every residual
+conftest.cached_oracle (arrays only; tests/golden/make_oracle_cache.py writes the records).  Every residual
 the tests compare against is formed from those channels in float64:
 
   data step        C_U u + residual(u, COEFFS)                 (tests/tabulated_reference.py)
@@ -15,8 +15,8 @@ import torch
 import coef_reference as CR
 import mlp_reference as R
 import tabulated_reference as T
-from conftest import cached_oracle, pkg
-from step_reference import haar_for, step_inputs
+from conftest import pkg
+from step_reference import Step, haar_for, record, step_inputs
 
 B_RES = 64
 N_MAX = 2 * B_RES + 3
@@ -36,19 +36,24 @@ def case_inputs(case):
     return flat, X, T.r_star(X), CR.coef_star(X)
 
 
-def case_ujets(case):
-    """(6, N_MAX) float64 channels of u on the case's rows."""
+def ujets_job(case):
     ans, n, L, enc = CASES[case]
     P = int(pkg("circuits").params_per_layer(ans, n))
     flat, X, _, _ = case_inputs(case)
 
     def compute():
-        from oracle import jets as oj
-        Pm = R.unpack(flat, T.H, n, L * P)
-        a = R.pre_jets(Pm, torch.as_tensor(X).double(), 6)
-        q = oj.qjets_from_ajets(a, Pm["theta"].reshape(L, P), ans, n, haar_for(n, 1), enc)
-        return {"ujets": R.post_jets(Pm, q).detach().numpy()}
-    return cached_oracle(f"adapt_ujets_{ans}_n{n}_L{L}_{enc}_N{N_MAX}", (np.asarray(flat, np.float32), X), compute)["ujets"]
+        Xr = torch.as_tensor(X).double()
+        return {"ujets": Step(flat, T.H, n, L * P, (L, P), ans, haar_for(n, 1), Xr[:0], Xr[:0], Xr, encoding=enc).u_res.detach().numpy()}
+    return record(f"adapt_ujets_{ans}_n{n}_L{L}_{enc}_N{N_MAX}", (flat, X), compute)
+
+
+def case_ujets(case):
+    """(6, N_MAX) float64 channels of u on the case's rows."""
+    return ujets_job(case).get()["ujets"]
+
+
+def oracle_jobs():
+    return [ujets_job(c) for c in CASES]
 
 
 def residuals(case):

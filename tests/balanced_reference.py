@@ -16,10 +16,8 @@ exchanged).
 import numpy as np
 import torch
 
-import mlp_reference as R
 import tabulated_reference as T
-from conftest import cached_oracle, pkg
-from step_reference import haar_for
+from step_reference import Step, mse_to
 
 TERMS = ("residual", "bc", "ic")
 N_BAL = 3
@@ -77,59 +75,27 @@ def class_gradients(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, 
                     coeffs=T.DEFAULT_COEFFS, c_u=0.0, encoding="angle"):
     """tabulated_reference.reference_loss_data with the three losses differentiated one by one ->
     (grad L_r, grad L_bc, grad L_ic) each (NP,), parts (3,), float64."""
-    from oracle import jets as oj
-    from oracle import statevector as sv
-    P = R.unpack(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
-    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=R.F64)
-    leaves = [P[k] for k in R.NAMES]
-    NP = sum(int(l.numel()) for l in leaves)
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, encoding=encoding)
+    parts = s.losses(T.data_residual(r_res, coeffs, c_u), mse_to(u_bc, u_ic))
+    g_r, g_b, g_i = (s.grad(l) if l.requires_grad else np.zeros(len(flat)) for l in parts)     # an empty class: zeros
+    return g_r, g_b, g_i, np.array([l.item() for l in parts])
 
-    def grad_of(loss):
-        grads = torch.autograd.grad(loss, leaves, allow_unused=True)
-        return R.flatten(dict(zip(R.NAMES, grads)), H, n, n_theta)
-    out, parts = [], []
-    if len(X_res):
-        a = R.pre_jets(P, X_res, 6)
-        q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
-        u = R.post_jets(P, q)
-        res = c_u * u[0] + R.residual(u, coeffs)
-        l_r = ((res - as64(r_res)) ** 2).mean()
-        out.append(grad_of(l_r))
-        parts.append(l_r.item())
-    else:
-        out.append(np.zeros(NP))
-        parts.append(0.0)
-    for Xv, tv in ((X_bc, u_bc), (X_ic, u_ic)):
-        if not len(Xv):
-            out.append(np.zeros(NP))
-            parts.append(0.0)
-            continue
-        av = R.pre_jets(P, Xv, 1)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
-        uv = R.post_jets(P, qv)
-        l = ((uv[0] - as64(tv)) ** 2).mean()
-        out.append(grad_of(l))
-        parts.append(l.item())
-    return out[0], out[1], out[2], np.array(parts)
+
+def class_job(case):
+    def loss(*a, **k):
+        g_r, g_b, g_i, parts = class_gradients(*a, coeffs=T.COEFFS, c_u=T.C_U, **k)
+        return {"g_residual": g_r, "g_bc": g_b, "g_ic": g_i, "parts": parts}
+    return T.case_record("bal", case, case_inputs(case)[4:], (T.COEFFS + (T.C_U,),), loss)
 
 
 def class_reference(case):
     """class_gradients of one case through conftest.cached_oracle ->
     {"g_residual", "g_bc", "g_ic": (NP,), "parts": (3,)}."""
-    ans, n, L, enc, B_res, n_ic, n_bc = CASES[case]
-    P = int(pkg("circuits").params_per_layer(ans, n))
-    flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res = case_inputs(case)
+    return class_job(case).get()
 
-    def compute():
-        g_r, g_b, g_i, parts = class_gradients(flat, case_H(case), n, L * P, (L, P), ans, haar_for(n, 1),
-                                               *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), u_ic, u_bc,
-                                               r_res, coeffs=T.COEFFS, c_u=T.C_U, encoding=enc)
-        return {"g_residual": g_r, "g_bc": g_b, "g_ic": g_i, "parts": parts}
-    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
-        (u_ic, u_bc, r_res, np.asarray(T.COEFFS + (T.C_U,), dtype=np.float32))
-    key = f"bal_{ans}_n{n}_L{L}_{enc}_r{B_res}_i{n_ic}_b{n_bc}" + (f"_H{case_H(case)}" if case in T.CASE_H else "")
-    return cached_oracle(key, inputs, compute)
+
+def oracle_jobs():
+    return [class_job(c) for c in CASES]
 
 
 def block_error(got, ref, H, n, n_theta):

@@ -13,8 +13,8 @@ any eps, ``autograd_gradient`` differentiates 2 L_r^c + 4 L_bc + 2 L_ic with det
 compares the two).  ``weights`` and ``anneal`` restate the record's arithmetic: cumulative sums and exp in float64, W
 rounded to float32, W_{M-1} > delta compared in float32, eps = float32(min(eps * growth, eps_max)).
 
-``replay``: the training loop of tests/tabulated_training.py under those weights, with the annealing; ``unit=True`` is the
-control with every weight 1.
+``causal_run``: the training loop of tests/tabulated_training.py under those weights, with the annealing; ``unit=True`` is
+the control with every weight 1.
 """
 import numpy as np
 import torch
@@ -23,8 +23,8 @@ import mlp_reference as R
 import philox_reference as PR
 import tabulated_reference as T
 import tabulated_training as TT
-from conftest import cached_oracle, pkg
-from step_reference import haar_for, step_inputs
+from conftest import pkg
+from step_reference import Step, as64, batch_inputs, flat_of, haar_for, mse_to, record, step_inputs
 
 F32 = lambda a: np.asarray(a, dtype=np.float32)
 W3 = (2.0, 4.0, 2.0)
@@ -86,47 +86,24 @@ def anneal(eps, n_raised, W_last, growth, eps_max, delta):
 
 
 # ---------------------------------------------------------------- one step: per-slab gradients
-def _leaves(flat, H, n, n_theta):
-    P = R.unpack(flat, H, n, n_theta)
-    return P, [P[k] for k in R.NAMES]
+def _slab_losses(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res, M, coeffs, c_u):
+    """(the Step, [L_0 .. L_{M-1}], L_bc, L_ic): the data step's parts with the residual's mean taken slab by slab."""
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res)
+    slab = torch.as_tensor(slab_of_points(len(r_res), M))
 
-
-def _residual_sq(P, theta, ansatz, n, haar, X_res, r_res, coeffs, c_u, encoding="angle"):
-    from oracle import jets as oj
-    a = R.pre_jets(P, X_res, 6)
-    q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
-    u = R.post_jets(P, q)
-    res = c_u * u[0] + R.residual(u, coeffs)
-    return (res - torch.as_tensor(np.asarray(r_res), dtype=R.F64)) ** 2
-
-
-def _value_losses(P, theta, ansatz, n, haar, X_bc, X_ic, u_bc, u_ic, encoding="angle"):
-    from oracle import statevector as sv
-    out = []
-    for Xv, tv in ((X_bc, u_bc), (X_ic, u_ic)):
-        av = R.pre_jets(P, Xv, 1)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
-        uv = R.post_jets(P, qv)
-        out.append(((uv[0] - torch.as_tensor(np.asarray(tv), dtype=R.F64)) ** 2).mean())
-    return out
+    def slab_means(u):
+        sq = (c_u * u[0] + R.residual(u, coeffs) - as64(r_res)) ** 2
+        return [sq[slab == i].mean() for i in range(M)]
+    return (s,) + s.losses(slab_means, mse_to(u_bc, u_ic))
 
 
 def slab_gradients(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res, M, coeffs=T.COEFFS,
                    c_u=T.C_U):
     """{"g_slab": (M, NP) grad L_i, "L": (M,), "g_bc", "g_ic": (NP,), "vals": (L_bc, L_ic)} float64."""
-    P, leaves = _leaves(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
-    flatten = lambda grads: R.flatten(dict(zip(R.NAMES, grads)), H, n, n_theta)
-    sq = _residual_sq(P, theta, ansatz, n, haar, X_res, r_res, coeffs, c_u)
-    slab = torch.as_tensor(slab_of_points(len(r_res), M))
-    g_slab, L = [], []
-    for i in range(M):
-        Li = sq[slab == i].mean()
-        g_slab.append(flatten(torch.autograd.grad(Li, leaves, allow_unused=True, retain_graph=True)))
-        L.append(Li.item())
-    l_bc, l_ic = _value_losses(P, theta, ansatz, n, haar, X_bc, X_ic, u_bc, u_ic)
-    return {"g_slab": np.array(g_slab), "L": np.array(L), "g_bc": flatten(torch.autograd.grad(l_bc, leaves, allow_unused=True)),
-            "g_ic": flatten(torch.autograd.grad(l_ic, leaves, allow_unused=True)), "vals": np.array([l_bc.item(), l_ic.item()])}
+    s, Ls, l_bc, l_ic = _slab_losses(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res, M,
+                                     coeffs, c_u)
+    return {"g_slab": np.array([s.grad(Li, retain_graph=True) for Li in Ls]), "L": np.array([Li.item() for Li in Ls]),
+            "g_bc": s.grad(l_bc), "g_ic": s.grad(l_ic), "vals": np.array([l_bc.item(), l_ic.item()])}
 
 
 def combine(rec, eps, unit=False, w=W3):
@@ -141,16 +118,12 @@ def combine(rec, eps, unit=False, w=W3):
 def autograd_gradient(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res, M, eps,
                       coeffs=T.COEFFS, c_u=T.C_U, w=W3):
     """The same gradient in one piece: torch autograd of w_res L_r^c + w_bc L_bc + w_ic L_ic with the weights detached."""
-    P, leaves = _leaves(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
-    sq = _residual_sq(P, theta, ansatz, n, haar, X_res, r_res, coeffs, c_u)
-    slab = torch.as_tensor(slab_of_points(len(r_res), M))
-    L = torch.stack([sq[slab == i].mean() for i in range(M)])
+    s, Ls, l_bc, l_ic = _slab_losses(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res, M,
+                                     coeffs, c_u)
+    L = torch.stack(Ls)
     cum = torch.cumsum(L, 0) - L
     W = torch.exp(-float(np.float32(eps)) * cum).detach()
-    l_bc, l_ic = _value_losses(P, theta, ansatz, n, haar, X_bc, X_ic, u_bc, u_ic)
-    loss = w[0] * (W * L).mean() + w[1] * l_bc + w[2] * l_ic
-    return R.flatten(dict(zip(R.NAMES, torch.autograd.grad(loss, leaves, allow_unused=True))), H, n, n_theta)
+    return s.weighted(((W * L).mean(), l_bc, l_ic), w)[0]
 
 
 def step_case_inputs(ansatz, n, L, B_res, n_ic, n_bc, H=T.H, salt=11):
@@ -160,8 +133,7 @@ def step_case_inputs(ansatz, n, L, B_res, n_ic, n_bc, H=T.H, salt=11):
     return flat, X_ic, X_bc, X_res, T.u_star(X_ic), T.u_star(X_bc), T.r_star(X_res)
 
 
-def hbm_reference():
-    """slab_gradients of HBM_CASE through conftest.cached_oracle."""
+def hbm_job():
     ans, n, L, B_res, M, n_ic, n_bc = HBM_CASE
     P = int(pkg("circuits").params_per_layer(ans, n))
     flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res = step_case_inputs(ans, n, L, B_res, n_ic, n_bc)
@@ -169,9 +141,13 @@ def hbm_reference():
     def compute():
         return slab_gradients(flat, T.H, n, L * P, (L, P), ans, haar_for(n, 1),
                               *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), u_ic, u_bc, r_res, M)
-    inputs = (F32(flat),) + tuple(F32(x) for x in (X_ic, X_bc, X_res)) + (u_ic, u_bc, r_res, F32(T.COEFFS + (T.C_U,)),
-                                                                          np.asarray([M], dtype=np.float32))
-    return cached_oracle(f"causal_{ans}_n{n}_L{L}_r{B_res}_m{M}_i{n_ic}_b{n_bc}", inputs, compute)
+    return record(f"causal_{ans}_n{n}_L{L}_r{B_res}_m{M}_i{n_ic}_b{n_bc}",
+                  (flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res, T.COEFFS + (T.C_U,), [M]), compute)
+
+
+def hbm_reference():
+    """slab_gradients of HBM_CASE through conftest.cached_oracle."""
+    return hbm_job().get()
 
 
 # ---------------------------------------------------------------- training replay
@@ -207,62 +183,46 @@ def initial_model(case, batch):
     return osol.OracleSolver(base_args(ans, n, batch), device=torch.device("cpu"))
 
 
-def replay(model, batches, M, eps0, growth, eps_max, delta, unit=False, coeffs=T.COEFFS, c_u=T.C_U):
+def causal_run(model, batches, M, eps0, growth, eps_max, delta, unit=False, coeffs=T.COEFFS, c_u=T.C_U):
     """{"loss": (steps,), "W": (steps, M) float64 weights USED in each step, "L": (steps, M), "eps": (steps,) float32 eps
-    used in each step, "eps_end": (1,), "n_raised": (1,), "raised": (steps,) bool} of the float64 copy of ``model``."""
-    from oracle import statevector as sv
-    model = model.double()
-    ql = model.quantum_layer
+    used in each step, "eps_end": (1,), "n_raised": (1,), "raised": (steps,) bool} of the float64 copy of ``model``:
+    tabulated_training.replay with the residual part taken slab by slab under the weights, and the annealing."""
+    state = {"eps": np.float32(eps0), "n_raised": 0}
+    Wh, Lh, eh, rh = [], [], [], []
 
-    def net(x):
-        q = sv.circuit_expvals(model.preprocessor(x), ql.params, ql.q_ansatz, ql.num_qubits, ql._haar, "angle")
-        return model.postprocessor(q.T.reshape(-1, ql.num_qubits))
-
-    opt = torch.optim.Adam(model.parameters(), lr=model.args["lr"])
-    sch = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.9, patience=1000)
-    c_t, c_x, c_y, d_xx, d_yy = coeffs
-    g = lambda out, wrt: torch.autograd.grad(out, wrt, torch.ones_like(out), create_graph=True)[0]
-    mse = torch.nn.MSELoss()
-    eps, n_raised = np.float32(eps0), 0
-    hist, Wh, Lh, eh, rh = [], [], [], [], []
-    for X_ic, X_bc, X_res, u_ic, u_bc, r_res in batches:
-        as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
-        opt.zero_grad()
-        t, x, y = [as64(X_res)[:, k:k + 1].requires_grad_(True) for k in range(3)]
-        u = net(torch.cat((t, x, y), 1))
-        u_x, u_y = g(u, x), g(u, y)
-        res = c_u * u + c_t * g(u, t) + c_x * u_x + c_y * u_y - (d_xx * g(u_x, x) + d_yy * g(u_y, y))
-        sq = ((res - as64(r_res)[:, None]) ** 2).reshape(-1)
-        slab = torch.as_tensor(slab_of_points(len(r_res), M))
+    def residual(b, jets):      # once per step (the contract of TT.replay): it also advances the annealing
+        res = TT.operator_residual(jets[0], c_u, *coeffs)
+        sq = ((res - as64(b[5])[:, None]) ** 2).reshape(-1)
+        slab = torch.as_tensor(slab_of_points(len(b[5]), M))
         L = torch.stack([sq[slab == i].mean() for i in range(M)])
-        W32, W = weights(L.detach().numpy(), eps)
-        Wt = torch.ones(M, dtype=torch.float64) if unit else torch.as_tensor(W)
-        loss = 2.0 * (Wt * L).mean() + 4.0 * mse(net(as64(X_bc)), as64(u_bc)[:, None]) + \
-            2.0 * mse(net(as64(X_ic)), as64(u_ic)[:, None])
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1)
-        opt.step()
-        sch.step(loss)
-        hist.append(loss.item())
+        W32, W = weights(L.detach().numpy(), state["eps"])
         Wh.append(W)
         Lh.append(L.detach().numpy().copy())
-        eh.append(eps)
-        eps, now = anneal(eps, n_raised, W32[-1], growth, eps_max, delta)
-        rh.append(now != n_raised)
-        n_raised = now
-    return {"loss": np.array(hist), "W": np.array(Wh), "L": np.array(Lh), "eps": np.array(eh, dtype=np.float32),
-            "eps_end": np.array([eps], dtype=np.float32), "n_raised": np.array([n_raised]), "raised": np.array(rh)}
+        eh.append(state["eps"])
+        state["eps"], now = anneal(state["eps"], state["n_raised"], W32[-1], growth, eps_max, delta)
+        rh.append(now != state["n_raised"])
+        state["n_raised"] = now
+        return ((torch.ones(M, dtype=torch.float64) if unit else torch.as_tensor(W)) * L).mean()
+    hist = TT.replay(model, batches, residual)
+    return {"loss": hist, "W": np.array(Wh), "L": np.array(Lh), "eps": np.array(eh, dtype=np.float32),
+            "eps_end": np.array([state["eps"]], dtype=np.float32), "n_raised": np.array([state["n_raised"]]),
+            "raised": np.array(rh)}
 
 
-def training_reference(case, config, batches=None, unit=False):
-    """``replay`` of one case and configuration through conftest.cached_oracle, keyed on the initial weights, the
-    configuration and the batches."""
+def training_job(case, config, batches=None, unit=False):
     B_res, M, eps0, growth, eps_max, delta = CONFIGS[config]
     batches = expected_batches(config) if batches is None else batches
     model = initial_model(case, B_res)
-    flat0 = np.concatenate([p.detach().numpy().reshape(-1) for p in model.parameters()]).astype(np.float32)
-    inputs = [flat0, F32(T.COEFFS + (T.C_U,)), F32([M, eps0, growth, eps_max, delta])]
-    for b in batches:
-        inputs += [F32(a) for a in b]
-    return cached_oracle(f"causaltrain_{case}_{config}" + ("_unit" if unit else ""), inputs,
-                         lambda: replay(model, batches, M, eps0, growth, eps_max, delta, unit=unit))
+    return record(f"causaltrain_{case}_{config}",
+                  [flat_of(model), T.COEFFS + (T.C_U,), [M, eps0, growth, eps_max, delta]] + batch_inputs(*batches),
+                  lambda: causal_run(model, batches, M, eps0, growth, eps_max, delta, unit=unit), variant="unit" if unit else "")
+
+
+def training_reference(case, config, batches=None, unit=False):
+    """``causal_run`` of one case and configuration through conftest.cached_oracle, keyed on the initial weights, the
+    configuration and the batches."""
+    return training_job(case, config, batches, unit).get()
+
+
+def oracle_jobs():
+    return [hbm_job()] + [training_job(c, k, unit=u) for c in TRAIN_CASES for k in CONFIGS for u in (False, True)]

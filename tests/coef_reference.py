@@ -17,8 +17,7 @@ import torch
 
 import mlp_reference as R
 import tabulated_reference as T
-from conftest import cached_oracle, pkg
-from step_reference import haar_for
+from step_reference import Step, as64, mse_to
 
 COLS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")
 FLUX_ROW = np.array([0, 0, 1, 0, 0, 0, 0], dtype=np.float32)       # res = u_x: a Neumann / zero-flux point
@@ -61,43 +60,16 @@ def residual_coef(ujets, coef):
 
 def residual_points(flat, H, n, n_theta, theta_shape, ansatz, haar, X_res, coef, encoding="angle"):
     """(u (B,), res (B,)) float64 tensors of the residual points, and the parameter dict they hang on."""
-    from oracle import jets as oj
-    P = R.unpack(flat, H, n, n_theta)
-    a = R.pre_jets(P, X_res, 6)
-    q = oj.qjets_from_ajets(a, P["theta"].reshape(theta_shape), ansatz, n, haar, encoding)
-    u = R.post_jets(P, q)
-    return u[0], residual_coef(u, coef), P
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_res[:0], X_res[:0], X_res, encoding=encoding)
+    return s.u_res[0], residual_coef(s.u_res, coef), s.P
 
 
 def reference_loss_coef(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res, coef,
                         encoding="angle"):
     """flat (NP,) weights, three (B, 3) point sets, their (B,) targets and the (B_res, 7) rows -> (grad (NP,), parts (3,))
     float64: the gradient of 2 L_r + 4 L_bc + 2 L_ic and (L_r, L_bc, L_ic)."""
-    from oracle import jets as oj
-    from oracle import statevector as sv
-    P = R.unpack(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
-    zero = torch.zeros((), dtype=R.F64)
-    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=R.F64)
-    l_r = zero
-    if len(X_res):
-        a = R.pre_jets(P, X_res, 6)
-        q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
-        res = residual_coef(R.post_jets(P, q), coef)
-        l_r = ((res - as64(r_res)) ** 2).mean()
-    out = []
-    for Xv, tv in ((X_bc, u_bc), (X_ic, u_ic)):
-        if not len(Xv):
-            out.append(zero)
-            continue
-        av = R.pre_jets(P, Xv, 1)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
-        uv = R.post_jets(P, qv)
-        out.append(((uv[0] - as64(tv)) ** 2).mean())
-    l_bc, l_ic = out
-    loss = 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic
-    grads = torch.autograd.grad(loss, [P[k] for k in R.NAMES], allow_unused=True)
-    return R.flatten(dict(zip(R.NAMES, grads)), H, n, n_theta), np.array([l_r.item(), l_bc.item(), l_ic.item()])
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, encoding=encoding)
+    return s.weighted(s.losses(lambda u: ((residual_coef(u, coef) - as64(r_res)) ** 2).mean(), mse_to(u_bc, u_ic)))
 
 
 def variant_table(variant, coef):
@@ -118,23 +90,16 @@ def case_table(case):
     return coef_star(case_inputs(case)[3])
 
 
+def case_job(case, variant="", table=None, key=None):
+    """The record of reference_loss_coef on one case, under ``variant_table`` of its coef_star table or on ``table``."""
+    inp = case_inputs(case)
+    coef = variant_table(variant, coef_star(inp[3])) if table is None else table
+    return T.case_record("coef", case, inp[4:], (coef,), lambda *a, **k: reference_loss_coef(*a, coef, **k), variant, key)
+
+
 def case_reference(case, variant=""):
     """reference_loss_coef of one case through conftest.cached_oracle -> {"grad": (NP,), "parts": (3,)}."""
-    ans, n, L, enc, B_res, n_ic, n_bc = CASES[case]
-    P = int(pkg("circuits").params_per_layer(ans, n))
-    flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res = case_inputs(case)
-    coef = variant_table(variant, coef_star(X_res))
-
-    def compute():
-        g, parts = reference_loss_coef(flat, case_H(case), n, L * P, (L, P), ans, haar_for(n, 1),
-                                       *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), u_ic, u_bc, r_res,
-                                       coef, encoding=enc)
-        return {"grad": g, "parts": parts}
-    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
-        (u_ic, u_bc, r_res, coef)
-    key = f"coef_{ans}_n{n}_L{L}_{enc}_r{B_res}_i{n_ic}_b{n_bc}" + (f"_H{case_H(case)}" if case in T.CASE_H else "") + \
-        (f"_{variant}" if variant else "")
-    return cached_oracle(key, inputs, compute)
+    return case_job(case, variant).get()
 
 
 def uniform_reference(case="reg_cascade4"):
@@ -144,5 +109,4 @@ def uniform_reference(case="reg_cascade4"):
 
 
 def oracle_jobs():
-    """(case, variant) of every committed record (tests/golden/make_coef_oracle_cache.py)."""
-    return [(c, "") for c in CASES] + [(c, v) for c, vs in CONTROLS.items() for v in vs]
+    return T.controlled_jobs(case_job, CASES, CONTROLS)

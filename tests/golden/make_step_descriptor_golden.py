@@ -1,6 +1,6 @@
 """Writes tests/golden/step_descriptors.json: the records every kind of fused step hands to the library (QcStepDesc and
 its side records, pointers as null / the name of the tensor they address), for the cases of
-tests/test_gpu_step_descriptors.py.  The companion of the make_*_oracle_cache.py scripts, but it needs a GPU: the
+tests/test_gpu_step_descriptors.py.  The companion of make_oracle_cache.py, but it needs a GPU: the
 constructors allocate on the device and size the step workspace through the library.
 
     python tests/golden/make_step_descriptor_golden.py [-o FILE]

@@ -12,7 +12,7 @@ device's storage (weights rounded to float32, the combination as two fused multi
 everything in double (the CPU test compares that with Algorithm 1 written directly on torch).
 
 ``class_gradients``: the three per-class gradients of one step from three autograd passes over the float64 oracle (the
-tabulated, the analytic and the coefficient-table problem), through conftest.cached_oracle.  ``replay``: the training loop
+tabulated, the analytic and the coefficient-table problem), through conftest.cached_oracle.  ``gradnorm_run``: the training loop
 of tests/tabulated_training.py with three backward passes per step, the weights, clip, Adam and plateau; ``unit=True`` is
 the control with both weights held at 1.
 """
@@ -22,8 +22,8 @@ import torch
 import coef_reference as CF
 import tabulated_reference as T
 import tabulated_training as TT
-from conftest import cached_oracle, pkg
-from step_reference import haar_for, reference_loss, step_inputs
+from conftest import pkg
+from step_reference import batch_inputs, flat_of, haar_for, record, reference_loss, step_inputs
 
 F32 = lambda a: np.asarray(a, dtype=np.float32)
 W3 = (2.0, 4.0, 2.0)
@@ -154,16 +154,18 @@ def class_gradients(kind, flat, n, n_theta, theta_shape, ans, X_ic, X_bc, X_res,
     return out
 
 
-def step_reference(case, inputs=None):
-    """``class_gradients`` of one case (or of the given inputs under the case's shapes) through conftest.cached_oracle."""
+def step_job(case, inputs=None):
     kind, ans, n, L, B_res, n_ic, n_bc = STEP_CASES[case]
     P = int(pkg("circuits").params_per_layer(ans, n))
     flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res, coef = step_case_inputs(case) if inputs is None else inputs
-    digest = [F32(flat)] + [F32(x) for x in (X_ic, X_bc, X_res)] + [F32(u_ic), F32(u_bc), F32(r_res), F32(T.COEFFS + (T.C_U,))]
-    if coef is not None:
-        digest.append(F32(coef))
-    return cached_oracle(f"gradnorm_{case}", digest,
-                         lambda: class_gradients(kind, flat, n, L * P, (L, P), ans, X_ic, X_bc, X_res, u_ic, u_bc, r_res, coef))
+    return record(f"gradnorm_{case}",
+                  [flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res, T.COEFFS + (T.C_U,)] + ([] if coef is None else [coef]),
+                  lambda: class_gradients(kind, flat, n, L * P, (L, P), ans, X_ic, X_bc, X_res, u_ic, u_bc, r_res, coef))
+
+
+def step_reference(case, inputs=None):
+    """``class_gradients`` of one case (or of the given inputs under the case's shapes) through conftest.cached_oracle."""
+    return step_job(case, inputs).get()
 
 
 def expected_step(rec, n_ic, n_bc, cfg=STEP_CFG, unit=False, w=W3):
@@ -208,36 +210,16 @@ def initial_model():
     return osol.OracleSolver(base_args(), device=torch.device("cpu"))
 
 
-def replay(model, batches, cfg=TRAIN_CFG, unit=False, coeffs=T.COEFFS, c_u=T.C_U, w=W3):
+def gradnorm_run(model, batches, cfg=TRAIN_CFG, unit=False, coeffs=T.COEFFS, c_u=T.C_U, w=W3):
     """{"loss": (steps,) 2 L_r + 4 L_bc + 2 L_ic, "hist": (steps, 7) history rows, "g_abs": (steps, 3) mean |G_c|} of the
-    float64 copy of ``model``: three backward passes per step, the weights, then clip, Adam and plateau on the combined
-    gradient as tests/tabulated_training.py has them."""
-    from oracle import statevector as sv
-    model = model.double()
-    ql = model.quantum_layer
-    prm = list(model.parameters())
-
-    def net(x):
-        q = sv.circuit_expvals(model.preprocessor(x), ql.params, ql.q_ansatz, ql.num_qubits, ql._haar, "angle")
-        return model.postprocessor(q.T.reshape(-1, ql.num_qubits))
-
-    opt = torch.optim.Adam(prm, lr=model.args["lr"])
-    sch = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.9, patience=1000)
-    c_t, c_x, c_y, d_xx, d_yy = coeffs
-    g = lambda out, wrt: torch.autograd.grad(out, wrt, torch.ones_like(out), create_graph=True)[0]
-    mse = torch.nn.MSELoss()
+    float64 copy of ``model``: tabulated_training.replay with three backward passes per step and the combined gradient
+    written in place of ``loss.backward()``; clip, Adam and plateau on it as every replay has them."""
     rec = Record(**dict(cfg, alpha=0.0 if unit else cfg["alpha"]), dtype=np.float32, w=w)
-    sizes = [p.numel() for p in prm]
     hist, gabs = [], []
-    for X_ic, X_bc, X_res, u_ic, u_bc, r_res in batches:
-        as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
-        opt.zero_grad()
-        t, x, y = [as64(X_res)[:, k:k + 1].requires_grad_(True) for k in range(3)]
-        u = net(torch.cat((t, x, y), 1))
-        u_x, u_y = g(u, x), g(u, y)
-        res = c_u * u + c_t * g(u, t) + c_x * u_x + c_y * u_y - (d_xx * g(u_x, x) + d_yy * g(u_y, y))
-        l_r, l_bc, l_ic = mse(res, as64(r_res)[:, None]), mse(net(as64(X_bc)), as64(u_bc)[:, None]), \
-            mse(net(as64(X_ic)), as64(u_ic)[:, None])
+
+    def set_grads(parts, prm, b):
+        l_r, l_bc, l_ic = parts
+        sizes = [p.numel() for p in prm]
         flat = lambda L: np.concatenate([(torch.zeros_like(p) if q is None else q).reshape(-1).numpy()
                                          for p, q in zip(prm, torch.autograd.grad(L, prm, allow_unused=True))])
         G = np.zeros((3, sum(sizes) + 3))
@@ -248,7 +230,7 @@ def replay(model, batches, cfg=TRAIN_CFG, unit=False, coeffs=T.COEFFS, c_u=T.C_U
         r64 = Record(alpha=rec.alpha, every=rec.every, lam_max=rec.lam_max, dtype=np.float64, w=w)
         r64.lam_bc, r64.lam_ic, r64.n_steps = float(rec.lam_bc), float(rec.lam_ic), rec.n_steps
         r64.m_r, r64.a_bc, r64.a_ic = float(rec.m_r), float(rec.a_bc), float(rec.a_ic)
-        comb = r64.step(G, len(u_ic), len(u_bc))
+        comb = r64.step(G, len(b[3]), len(b[4]))
         rec.lam_bc, rec.lam_ic, rec.n_steps = np.float32(r64.lam_bc), np.float32(r64.lam_ic), r64.n_steps
         rec.m_r, rec.a_bc, rec.a_ic = np.float32(r64.m_r), np.float32(r64.a_bc), np.float32(r64.a_ic)
         row = r64.rows[-1]
@@ -257,24 +239,25 @@ def replay(model, batches, cfg=TRAIN_CFG, unit=False, coeffs=T.COEFFS, c_u=T.C_U
         for p, k in zip(prm, sizes):
             p.grad = torch.as_tensor(comb[off:off + k].reshape(p.shape).copy())
             off += k
-        loss = w[0] * l_r + w[1] * l_bc + w[2] * l_ic
-        torch.nn.utils.clip_grad_norm_(prm, max_norm=1)
-        opt.step()
-        sch.step(loss)
-        hist[-1].append(loss.item())
-    hist = np.array(hist)
-    return {"loss": hist[:, -1].copy(), "hist": hist[:, :HIST_COLS].copy(), "g_abs": np.array(gabs)}
+    loss = TT.replay(model, batches, TT.data_residual(coeffs, c_u), lambda l_r, l_bc, l_ic: w[0] * l_r + w[1] * l_bc + w[2] * l_ic,
+                     set_grads=set_grads)
+    return {"loss": loss, "hist": np.array(hist)[:, :HIST_COLS].copy(), "g_abs": np.array(gabs)}
+
+
+def training_job(batches=None, unit=False):
+    batches = expected_batches() if batches is None else batches
+    model = initial_model()
+    c = TRAIN_CFG
+    return record("gradnormtrain_cascade4_h16",
+                  [flat_of(model), T.COEFFS + (T.C_U,), [c["alpha"], c["every"], c["lam_max"], *c["init"]]] + batch_inputs(*batches),
+                  lambda: gradnorm_run(model, batches, unit=unit), variant="unit" if unit else "")
 
 
 def training_reference(batches=None, unit=False):
-    """``replay`` of the training case through conftest.cached_oracle, keyed on the initial weights, the configuration
-    and the batches."""
-    batches = expected_batches() if batches is None else batches
-    model = initial_model()
-    flat0 = np.concatenate([p.detach().numpy().reshape(-1) for p in model.parameters()]).astype(np.float32)
-    c = TRAIN_CFG
-    inputs = [flat0, F32(T.COEFFS + (T.C_U,)), F32([c["alpha"], c["every"], c["lam_max"], *c["init"]])]
-    for b in batches:
-        inputs += [F32(a) for a in b]
-    return cached_oracle("gradnormtrain_cascade4_h16" + ("_unit" if unit else ""), inputs,
-                         lambda: replay(model, batches, unit=unit))
+    """``gradnorm_run`` of the training case through conftest.cached_oracle, keyed on the initial weights, the
+    configuration and the batches."""
+    return training_job(batches, unit).get()
+
+
+def oracle_jobs():
+    return [step_job(c) for c in STEP_CASES] + [training_job(unit=u) for u in (False, True)]

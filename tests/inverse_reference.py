@@ -15,10 +15,8 @@ on the gradient), base ignored (c = scale p).
 import numpy as np
 import torch
 
-import mlp_reference as R
 import tabulated_reference as T
-from conftest import cached_oracle, pkg
-from step_reference import haar_for
+from step_reference import Step, as64, mse_to
 
 COLS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")
 N_OP = len(COLS)
@@ -62,76 +60,39 @@ def reference_loss_inverse(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic,
                            base=BASE, scale=SCALE, encoding="angle", variant=""):
     """flat (NP,) weights, three (B, 3) point sets, their (B,) targets and the operator -> (grad (NP + 7,), parts (3,))
     float64: the gradient of 2 L_r + 4 L_bc + 2 L_ic with respect to (weights, p) and (L_r, L_bc, L_ic)."""
-    from oracle import jets as oj
-    from oracle import statevector as sv
-    P = R.unpack(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
     pt = torch.tensor(_F32(p).astype(np.float64), requires_grad=True)
-    zero = torch.zeros((), dtype=R.F64)
-    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=R.F64)
-    l_r = zero
-    if len(X_res):
-        a = R.pre_jets(P, X_res, 6)
-        q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
-        res = residual_op(R.post_jets(P, q), operator(pt, base, scale, variant), variant)
-        l_r = ((res - as64(r_res)) ** 2).mean()
-    out = []
-    for Xv, tv in ((X_bc, u_bc), (X_ic, u_ic)):
-        if not len(Xv):
-            out.append(zero)
-            continue
-        av = R.pre_jets(P, Xv, 1)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
-        uv = R.post_jets(P, qv)
-        out.append(((uv[0] - as64(tv)) ** 2).mean())
-    l_bc, l_ic = out
-    loss = 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic
-    grads = torch.autograd.grad(loss, [P[k] for k in R.NAMES] + [pt], allow_unused=True)
-    gp = np.zeros(N_OP) if grads[-1] is None else grads[-1].numpy()
-    g = np.concatenate([R.flatten(dict(zip(R.NAMES, grads[:-1])), H, n, n_theta), gp])
-    return g, np.array([l_r.item(), l_bc.item(), l_ic.item()])
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, encoding=encoding, extra=[pt])
+
+    def l_r(u):
+        res = residual_op(u, operator(pt, base, scale, variant), variant)
+        return ((res - as64(r_res)) ** 2).mean()
+    return s.weighted(s.losses(l_r, mse_to(u_bc, u_ic)))
+
+
+def case_job(case, variant=""):
+    return T.case_record("inv", case, case_inputs(case)[4:], (BASE, SCALE, P0),
+                         lambda *a, **k: reference_loss_inverse(*a, variant=variant, **k), variant)
 
 
 def case_reference(case, variant=""):
     """reference_loss_inverse of one case through conftest.cached_oracle -> {"grad": (NP + 7,), "parts": (3,)}."""
-    ans, n, L, enc, B_res, n_ic, n_bc = CASES[case]
-    P = int(pkg("circuits").params_per_layer(ans, n))
-    flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res = case_inputs(case)
-
-    def compute():
-        g, parts = reference_loss_inverse(flat, case_H(case), n, L * P, (L, P), ans, haar_for(n, 1),
-                                          *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), u_ic, u_bc, r_res,
-                                          encoding=enc, variant=variant)
-        return {"grad": g, "parts": parts}
-    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
-        (u_ic, u_bc, r_res, _F32(BASE), _F32(SCALE), _F32(P0))
-    key = f"inv_{ans}_n{n}_L{L}_{enc}_r{B_res}_i{n_ic}_b{n_bc}" + (f"_H{case_H(case)}" if case in T.CASE_H else "") + \
-        (f"_{variant}" if variant else "")
-    return cached_oracle(key, inputs, compute)
+    return case_job(case, variant).get()
 
 
 UNIFORM_C3 = 0.4        # the cubic coefficient of the agreement test with the coefficient step
 
 
+def uniform_c3_job(case="reg_cascade4"):
+    import coef_reference as CR
+    table = CR.uniform_table(CASES[case][4], T.COEFFS, T.C_U, UNIFORM_C3)
+    return CR.case_job(case, table=table, key=f"inv_uniform_c3_{case}")
+
+
 def uniform_c3_reference(case="reg_cascade4"):
     """The coefficient step's own float64 reference (coef_reference.reference_loss_coef) on the uniform table of
     tabulated_reference's operator with c_3 = UNIFORM_C3, through conftest.cached_oracle."""
-    import coef_reference as CR
-    ans, n, L, enc, B_res, n_ic, n_bc = CASES[case]
-    P = int(pkg("circuits").params_per_layer(ans, n))
-    flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res = case_inputs(case)
-    table = CR.uniform_table(B_res, T.COEFFS, T.C_U, UNIFORM_C3)
-
-    def compute():
-        g, parts = CR.reference_loss_coef(flat, case_H(case), n, L * P, (L, P), ans, haar_for(n, 1),
-                                          *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), u_ic, u_bc, r_res,
-                                          table, encoding=enc)
-        return {"grad": g, "parts": parts}
-    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
-        (u_ic, u_bc, r_res, table)
-    return cached_oracle(f"inv_uniform_c3_{case}", inputs, compute)
+    return uniform_c3_job(case).get()
 
 
 def oracle_jobs():
-    """(case, variant) of every committed record (tests/golden/make_inverse_oracle_cache.py)."""
-    return [(c, "") for c in CASES] + [(c, v) for c, vs in CONTROLS.items() for v in vs]
+    return T.controlled_jobs(case_job, CASES, CONTROLS) + [uniform_c3_job()]

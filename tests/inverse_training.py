@@ -13,74 +13,51 @@ replay overshoots to 1.03 near step 800, is back at 0.84 by step 1 000 and 0.820
 over steps 3 000 .. 4 000 (the finite dataset and the 16-unit network leave a bias of about +0.015): the run is 4 000 steps
 long, twice the 2 000 a replay on torch.randint batches of a float64 dataset needed, and the learning rate stays 0.005.
 """
+import itertools
+
 import numpy as np
 import torch
 
 import inverse_reference as IR
 import tabulated_reference as T
 import tabulated_training as TT
-from conftest import cached_oracle
+from step_reference import as64, batch_inputs, flat_of, record
 
 TRAIN_CASES, BATCH, STEPS, N_IC, N_BC = TT.TRAIN_CASES, TT.BATCH, TT.STEPS, TT.N_IC, TT.N_BC
 dataset_arrays, expected_batches = TT.dataset_arrays, TT.expected_batches
 
 
-def _net(model):
-    from oracle import statevector as sv
-    ql = model.quantum_layer
-
-    def net(x):     # OracleSolver.forward without its float32 cast of the expectation values
-        q = sv.circuit_expvals(model.preprocessor(x), ql.params, ql.q_ansatz, ql.num_qubits, ql._haar, "angle")
-        return model.postprocessor(q.T.reshape(-1, ql.num_qubits))
-    return net
-
-
-def replay(model, batches, p0=IR.P0, base=IR.BASE, scale=IR.SCALE, hold=False, every=1):
+def operator_run(model, batches, p0=IR.P0, base=IR.BASE, scale=IR.SCALE, hold=False, every=1):
     """(loss history, (steps / every, 7) coefficients USED in steps 1, 1 + every, ...) of the float64 copy of ``model``
-    and the operator trained on ``batches`` (an iterable)."""
-    model = model.double()
-    net = _net(model)
+    and the operator trained on ``batches`` (an iterable): tabulated_training.replay with ``p`` in the model's param group
+    and under its clip."""
     p = torch.tensor(np.asarray(p0, dtype=np.float32).astype(np.float64), requires_grad=not hold)
-    params = list(model.parameters()) + ([] if hold else [p])
-    opt = torch.optim.Adam(params, lr=model.args["lr"])
-    sch = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.9, patience=1000)
-    g = lambda out, wrt: torch.autograd.grad(out, wrt, torch.ones_like(out), create_graph=True)[0]
-    mse = torch.nn.MSELoss()
-    hist, chist = [], []
-    for i, (X_ic, X_bc, X_res, u_ic, u_bc, r_res) in enumerate(batches):
-        as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+    chist, count = [], itertools.count()
+
+    def residual(b, jets):
         c = IR.operator(p, base, scale)
-        if i % every == 0:
+        if next(count) % every == 0:
             chist.append(c.detach().numpy().copy())
-        opt.zero_grad()
-        t, x, y = [as64(X_res)[:, k:k + 1].requires_grad_(True) for k in range(3)]
-        u = net(torch.cat((t, x, y), 1))
-        u_x, u_y = g(u, x), g(u, y)
-        res = c[0] * u + c[6] * u ** 3 + c[1] * g(u, t) + c[2] * u_x + c[3] * u_y - (c[4] * g(u_x, x) + c[5] * g(u_y, y))
-        loss = 2.0 * mse(res, as64(r_res)[:, None]) + 4.0 * mse(net(as64(X_bc)), as64(u_bc)[:, None]) + \
-            2.0 * mse(net(as64(X_ic)), as64(u_ic)[:, None])
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(params, max_norm=1)
-        opt.step()
-        sch.step(loss)
-        hist.append(loss.item())
-    return np.array(hist), np.array(chist)
+        return torch.nn.functional.mse_loss(TT.operator_residual(jets[0], *c), as64(b[5])[:, None])
+    hist = TT.replay(model, batches, residual, extra=[] if hold else [p], clip_extra=True)
+    return hist, np.array(chist)
+
+
+def training_job(case, batches=None, hold=False):
+    batches = expected_batches() if batches is None else batches
+    model = TT.initial_model(case)
+
+    def compute():
+        loss, coef = operator_run(model, batches, hold=hold)
+        return {"loss": loss, "coef": coef}
+    return record(f"invtrain_{case}", [flat_of(model), IR.BASE, IR.SCALE, IR.P0] + batch_inputs(*batches), compute,
+                  variant="hold" if hold else "")
 
 
 def training_reference(case, batches=None, hold=False):
     """{"loss": (STEPS,), "coef": (STEPS, 7)} of one case through conftest.cached_oracle, keyed on the initial weights,
     the operator and the batches."""
-    batches = expected_batches() if batches is None else batches
-    model = TT.initial_model(case)
-    flat0 = np.concatenate([p.detach().numpy().reshape(-1) for p in model.parameters()]).astype(np.float32)
-    inputs = [flat0] + [np.asarray(a, dtype=np.float32) for a in (IR.BASE, IR.SCALE, IR.P0)]
-    for b in batches:
-        inputs += [np.asarray(a, dtype=np.float32) for a in b]
-
-    def compute():
-        loss, coef = replay(model, batches, hold=hold)
-        return {"loss": loss, "coef": coef}
-    return cached_oracle(f"invtrain_{case}" + ("_hold" if hold else ""), inputs, compute)
+    return training_job(case, batches, hold).get()
 
 
 # ---- recovery of a transport coefficient
@@ -131,16 +108,24 @@ def recovery_operator():
     return base, scale
 
 
-def recovery_reference():
-    """{"c_x": (REC_STEPS / REC_EVERY,)}: c_x used in steps 1, 101, 201, ... of the float64 replay, through
-    conftest.cached_oracle, keyed on the dataset and the seed (the batches follow from both)."""
+def recovery_job():
     from oracle import solver as osol
-    inputs = list(recovery_dataset()) + [np.array([REC_SEED, REC_STEPS, REC_EVERY], dtype=np.int64)]
 
     def compute():
         torch.manual_seed(1)
         model = osol.OracleSolver(REC_ARGS, device=torch.device("cpu"))
         base, scale = recovery_operator()
-        _, coef = replay(model, recovery_batches(), p0=[0.0] * IR.N_OP, base=base, scale=scale, every=REC_EVERY)
+        _, coef = operator_run(model, recovery_batches(), p0=[0.0] * IR.N_OP, base=base, scale=scale, every=REC_EVERY)
         return {"c_x": coef[:, IR.COLS.index("c_x")]}
-    return cached_oracle("inv_recover_cascade2_H16", inputs, compute)
+    return record("inv_recover_cascade2_H16",
+                  list(recovery_dataset()) + [np.array([REC_SEED, REC_STEPS, REC_EVERY], dtype=np.int64)], compute, dtype=None)
+
+
+def recovery_reference():
+    """{"c_x": (REC_STEPS / REC_EVERY,)}: c_x used in steps 1, 101, 201, ... of the float64 replay, through
+    conftest.cached_oracle, keyed on the dataset and the seed (the batches follow from both)."""
+    return recovery_job().get()
+
+
+def oracle_jobs():
+    return [training_job(c, hold=h) for c in TRAIN_CASES for h in (False, True)] + [recovery_job()]

@@ -1,7 +1,7 @@
 """Float64 replay of an Adam -> L-BFGS run of the fused step on ONE explicit batch: ADAM clip + Adam steps in float64 on the
 flat vector, then EVALS evaluations of tests/lbfgs_reference.py (backtracking mode) driven by step_reference.reference_loss.
 The GPU test (tests/test_gpu_lbfgs_train.py) runs FusedTrainer + LbfgsTrainer on the same weights and batch; the records
-are committed under tests/golden/oracle/ (tests/golden/make_lbfgs_oracle_cache.py) and keyed on the inputs.
+are committed under tests/golden/oracle/ (tests/golden/make_oracle_cache.py) and keyed on the inputs.
 
 The generator asserts, on the replay: the Armijo slack |f - (f0 + c1 t gtd0)| >= 1e-3 max(1, |f0|) at every trial (fp32
 cannot flip a decision), and at least one rejected trial (the salt is chosen so that both hold).

@@ -7,7 +7,7 @@ q[k][c] channel c (value, t, x, y, xx, yy) of output k and u[k] = q[k][0].  ``ev
 ``reference_loss_system`` composes tests/mlp_reference.py (post_jets(..., w4=, b4=)) with the circuit oracles
 (oracle/jets.py, oracle/statevector.py) as tests/tabulated_reference.py does and differentiates by torch.autograd.
 
-The seeded cases of the GPU tests live here, so that the CPU tests and tests/golden/make_system_oracle_cache.py see the
+The seeded cases of the GPU tests live here, so that the CPU tests and tests/golden/make_oracle_cache.py see the
 same inputs.  The seeded system is a scaled Navier-Stokes (nu = 0.05, 1 / rho = 0.7: at the reference's 1 / rho = 1 / 1056 the
 pressure terms would not register at the tolerances) with w_eq = (1, 0.5, 2), w_out = (1, 0.5, 0), smooth non-zero
 residual targets and value targets that are no solution; the two-output case is the same system without the pressure
@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 import mlp_reference as R
-from conftest import cached_oracle, pkg
-from step_reference import haar_for, step_inputs
+from conftest import pkg
+from step_reference import Step, as64, case_key, haar_for, layout, record, step_inputs, unpack
 
 H = 50
 NU, INV_RHO = 0.05, 0.7
@@ -40,22 +40,6 @@ CONTROL_CASES = ("reg_cascade4", "wave_layered7")
 # seed of a case's weights and points (default 5).  On the layered circuit seed 5 leaves the v_yy term of f_v too light
 # for its control to clear ten tolerances in the post block (5.4 x); seeds 6 .. 13 all clear it, 7 by 33 x.
 CASE_SALT = {"wave_layered7": 7}
-
-
-def layout(H, n, n_theta, K):
-    """name -> (offset, shape) of the K-row flat vector W1 b1 W2 b2 | W3 b3 W4[K][H] b4[K] | theta, and its length."""
-    out, off = {}, 0
-    for name, shape in zip(NAMES, ((H, 3), (H,), (n, H), (n,), (H, n), (H,), (K, H), (K,), (n_theta,))):
-        out[name] = (off, shape)
-        off += int(np.prod(shape))
-    return out, off
-
-
-def unpack(flat, H, n, n_theta, K):
-    lay, NP = layout(H, n, n_theta, K)
-    flat = np.asarray(flat, dtype=np.float64)
-    assert flat.shape == (NP,)
-    return {k: torch.tensor(flat[o:o + int(np.prod(s))].reshape(s), dtype=R.F64, requires_grad=True) for k, (o, s) in lay.items()}
 
 
 def flatten(grads, H, n, n_theta, K):
@@ -91,37 +75,16 @@ def reference_loss_system(flat, H, n, n_theta, theta_shape, ansatz, haar, K, ter
     """flat (NP_K,), three (B, 3) point sets, value targets (B, K), residual targets (B, n_eq) or None -> (grad (NP_K,),
     parts (3,)) float64: the gradient of w_res L_r + w_bc L_bc + w_ic L_ic and (L_r, L_bc, L_ic), L_r = sum_e w_eq[e]
     mean (res_e - r_e)^2, L_bc / L_ic = sum_k w_out[k] mean (u_k - U_k)^2."""
-    from oracle import jets as oj
-    from oracle import statevector as sv
-    P = unpack(flat, H, n, n_theta, K)
-    theta = P["theta"].reshape(theta_shape)
-    zero = torch.zeros((), dtype=R.F64)
-    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=R.F64)
-    n_eq = len(w_eq)
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, encoding=encoding, K=K)
     we, wo = as64(w_eq), as64(w_out)
-    l_r = zero
-    if len(X_res):
-        a = R.pre_jets(P, X_res, 6)
-        q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
-        u = R.post_jets(P, q, w4=P["W4"], b4=P["b4"])                  # (K, 6, B)
-        res = eval_terms(u, terms, n_eq)
+    U_val = {"bc": U_bc, "ic": U_ic}
+
+    def l_r(u):                                                         # u (K, 6, B)
+        res = eval_terms(u, terms, len(w_eq))
         if R_res is not None:
             res = res - as64(R_res).T
-        l_r = (we * (res ** 2).mean(1)).sum()
-    out = []
-    for Xv, Uv in ((X_bc, U_bc), (X_ic, U_ic)):
-        if not len(Xv):
-            out.append(zero)
-            continue
-        av = R.pre_jets(P, Xv, 1)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
-        uv = R.post_jets(P, qv, w4=P["W4"], b4=P["b4"])[:, 0]          # (K, B)
-        out.append((wo * ((uv - as64(Uv).T) ** 2).mean(1)).sum())
-    l_bc, l_ic = out
-    w_r, w_b, w_i = loss_weights
-    loss = w_r * l_r + w_b * l_bc + w_i * l_ic
-    grads = torch.autograd.grad(loss, [P[k] for k in NAMES], allow_unused=True)
-    return flatten(dict(zip(NAMES, grads)), H, n, n_theta, K), np.array([l_r.item(), l_bc.item(), l_ic.item()])
+        return (we * (res ** 2).mean(1)).sum()
+    return s.weighted(s.losses(l_r, lambda u, which: (wo * ((u - as64(U_val[which]).T) ** 2).mean(1)).sum()), loss_weights)
 
 
 # ---- the seeded system
@@ -222,8 +185,7 @@ def control(variant, terms, w_eq, w_out, R_res):
     return terms, w_eq, w_out, R_res
 
 
-def case_reference(case, variant=""):
-    """reference_loss_system of one case through conftest.cached_oracle -> {"grad": (NP_K,), "parts": (3,)}."""
+def case_job(case, variant=""):
     ans, n, L, enc, B_res, n_ic, n_bc, K = CASES[case]
     P = int(pkg("circuits").params_per_layer(ans, n))
     flat, X_ic, X_bc, X_res, U_ic, U_bc, R_res = case_inputs(case)
@@ -234,15 +196,17 @@ def case_reference(case, variant=""):
                                          *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), U_ic, U_bc, Rr,
                                          encoding=enc)
         return {"grad": g, "parts": parts}
-    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
-        (U_ic, U_bc, Rr, np.asarray(terms, dtype=np.float32), np.asarray(w_eq + w_out, dtype=np.float32))
-    key = f"sys_{ans}_n{n}_L{L}_{enc}_r{B_res}_i{n_ic}_b{n_bc}_K{K}" + (f"_{variant}" if variant else "")
-    return cached_oracle(key, inputs, compute)
+    return record(case_key("sys", CASES[case]) + f"_K{K}", (flat, X_ic, X_bc, X_res, U_ic, U_bc, Rr, terms, w_eq + w_out),
+                  compute, variant=variant, case=case)
+
+
+def case_reference(case, variant=""):
+    """reference_loss_system of one case through conftest.cached_oracle -> {"grad": (NP_K,), "parts": (3,)}."""
+    return case_job(case, variant).get()
 
 
 def oracle_jobs():
-    """(case, variant) of every committed record (tests/golden/make_system_oracle_cache.py)."""
-    return [(c, "") for c in CASES] + [(c, v) for c in CONTROL_CASES for v in CONTROLS]
+    return [case_job(c) for c in CASES] + [case_job(c, v) for c in CONTROL_CASES for v in CONTROLS]
 
 
 def errors(got, want_g, want_p, H, n, n_theta, K, tol_g=2e-4, tol_l=1e-4):

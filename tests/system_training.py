@@ -4,13 +4,12 @@ gather picks (tabulated_reference.dataset_indices) and the loss history of a flo
 ([3, 50, 3]) trained on them: the term list evaluated on autograd derivatives, loss = 2 L_r + 4 L_bc + 2 L_ic,
 clip_grad_norm_(1), Adam, ReduceLROnPlateau, as in tests/coef_training.py.
 """
-import numpy as np
 import torch
 
 import system_reference as S
 import tabulated_reference as T
 import tabulated_training as TT
-from conftest import cached_oracle
+from step_reference import as64, batch_inputs, flat_of, record
 
 DS_SIZES, BATCH, STEPS, N_IC, N_BC = TT.DS_SIZES, TT.BATCH, TT.STEPS, TT.N_IC, TT.N_BC
 K, N_EQ = 3, 3
@@ -47,51 +46,29 @@ def initial_model():
     return osol.OracleSolver(base_args(), device=torch.device("cpu"))
 
 
-def replay(model, batches):
-    """Loss history of the float64 copy of ``model`` trained on ``batches``."""
-    from oracle import statevector as sv
-    model = model.double()
-    ql = model.quantum_layer
+def system_run(model, batches):
+    """Loss history of the float64 copy of ``model`` trained on ``batches``: tabulated_training.replay with the term list
+    as the residual and the parts weighted per equation and per output."""
     terms, w_eq, w_out = S.system_of(K)
-
-    def net(x):
-        q = sv.circuit_expvals(model.preprocessor(x), ql.params, ql.q_ansatz, ql.num_qubits, ql._haar, "angle")
-        return model.postprocessor(q.T.reshape(-1, ql.num_qubits))
-
-    opt = torch.optim.Adam(model.parameters(), lr=model.args["lr"])
-    sch = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.9, patience=1000)
-    g = lambda out, wrt: torch.autograd.grad(out, wrt, torch.ones_like(out), create_graph=True)[0]
-    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
     we, wo = as64(w_eq), as64(w_out)
-    hist = []
-    for X_ic, X_bc, X_res, U_ic, U_bc, R_res in batches:
-        opt.zero_grad()
-        t, x, y = [as64(X_res)[:, k:k + 1].requires_grad_(True) for k in range(3)]
-        f = net(torch.cat((t, x, y), 1))
-        jets = []
-        for k in range(K):
-            u = f[:, k:k + 1]
-            u_x, u_y = g(u, x), g(u, y)
-            jets.append(torch.stack([u, g(u, t), u_x, u_y, g(u_x, x), g(u_y, y)])[:, :, 0])
-        res = S.eval_terms(torch.stack(jets), terms, N_EQ) - as64(R_res).T
-        l_r = (we * (res ** 2).mean(1)).sum()
-        l_bc = (wo * ((net(as64(X_bc)) - as64(U_bc)) ** 2).mean(0)).sum()
-        l_ic = (wo * ((net(as64(X_ic)) - as64(U_ic)) ** 2).mean(0)).sum()
-        loss = 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1)
-        opt.step()
-        sch.step(loss)
-        hist.append(loss.item())
-    return np.array(hist)
+
+    def residual(b, jets):
+        res = S.eval_terms(torch.stack([torch.stack(j)[:, :, 0] for j in jets]), terms, N_EQ) - as64(b[5]).T
+        return (we * (res ** 2).mean(1)).sum()
+    return TT.replay(model, batches, residual, value=lambda net, X, U: (wo * ((net(as64(X)) - as64(U)) ** 2).mean(0)).sum())
+
+
+def training_job(batches=None):
+    batches = expected_batches() if batches is None else batches
+    model = initial_model()
+    return record(f"systrain_{ANSATZ}{N_QUBITS}_K{K}", [flat_of(model)] + batch_inputs(*batches),
+                  lambda: {"loss": system_run(model, batches)})
 
 
 def training_reference(batches=None):
     """{"loss": (STEPS,)} through conftest.cached_oracle, keyed on the initial weights and the batches."""
-    batches = expected_batches() if batches is None else batches
-    model = initial_model()
-    flat0 = np.concatenate([p.detach().numpy().reshape(-1) for p in model.parameters()]).astype(np.float32)
-    inputs = [flat0]
-    for b in batches:
-        inputs += [np.asarray(a, dtype=np.float32) for a in b]
-    return cached_oracle(f"systrain_{ANSATZ}{N_QUBITS}_K{K}", inputs, lambda: {"loss": replay(model, batches)})
+    return training_job(batches).get()
+
+
+def oracle_jobs():
+    return [training_job()]

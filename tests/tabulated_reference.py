@@ -9,7 +9,7 @@ c_u u + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy); composed from tes
 oracles in the same way, differentiated by torch.autograd.
 
 The seeded cases of the GPU tests (tests/test_gpu_tabulated.py) live here too, so that the CPU tests and
-tests/golden/make_tabulated_oracle_cache.py see the same inputs: weights and points from step_reference.step_inputs,
+tests/golden/make_oracle_cache.py see the same inputs: weights and points from step_reference.step_inputs,
 targets the float32 roundings of two smooth functions that are no solution of the operator.
 """
 import numpy as np
@@ -17,8 +17,8 @@ import torch
 
 import mlp_reference as R
 import philox_reference as PR
-from conftest import cached_oracle, pkg
-from step_reference import haar_for, step_inputs
+from conftest import pkg
+from step_reference import Step, as64, case_key, haar_for, mse_to, record, step_inputs
 
 H = 50
 # c_t, c_x, c_y, d_xx, d_yy and the zeroth-order coefficient: none at its default
@@ -74,36 +74,20 @@ def r_star(X):
     return (1.5 * np.cos(3.0 * X[:, 0] + X[:, 1] - 2.0 * X[:, 2])).astype(np.float32)
 
 
+def data_residual(r_res, coeffs=DEFAULT_COEFFS, c_u=0.0):
+    """The residual loss of the data step for Step.losses: mean (c_u u + c_t u_t + ... - r)^2 of the u jets."""
+    def l_r(u):
+        res = c_u * u[0] + R.residual(u, coeffs)
+        return ((res - as64(r_res)) ** 2).mean()
+    return l_r
+
+
 def reference_loss_data(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, u_ic, u_bc, r_res,
                         coeffs=DEFAULT_COEFFS, c_u=0.0, encoding="angle"):
     """flat (NP,) weights, three (B, 3) point sets and their (B,) targets -> (grad (NP,), parts (3,)) float64: the
     gradient of 2 L_r + 4 L_bc + 2 L_ic and (L_r, L_bc, L_ic), L_r on c_u u + c_t u_t + ... - r."""
-    from oracle import jets as oj
-    from oracle import statevector as sv
-    P = R.unpack(flat, H, n, n_theta)
-    theta = P["theta"].reshape(theta_shape)
-    zero = torch.zeros((), dtype=R.F64)
-    as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=R.F64)
-    l_r = zero
-    if len(X_res):
-        a = R.pre_jets(P, X_res, 6)
-        q = oj.qjets_from_ajets(a, theta, ansatz, n, haar, encoding)
-        u = R.post_jets(P, q)
-        res = c_u * u[0] + R.residual(u, coeffs)
-        l_r = ((res - as64(r_res)) ** 2).mean()
-    out = []
-    for Xv, tv in ((X_bc, u_bc), (X_ic, u_ic)):
-        if not len(Xv):
-            out.append(zero)
-            continue
-        av = R.pre_jets(P, Xv, 1)
-        qv = sv.circuit_expvals(av[0].T, theta, ansatz, n, haar, encoding)[None]
-        uv = R.post_jets(P, qv)
-        out.append(((uv[0] - as64(tv)) ** 2).mean())
-    l_bc, l_ic = out
-    loss = 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic
-    grads = torch.autograd.grad(loss, [P[k] for k in R.NAMES], allow_unused=True)
-    return R.flatten(dict(zip(R.NAMES, grads)), H, n, n_theta), np.array([l_r.item(), l_bc.item(), l_ic.item()])
+    s = Step(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, encoding=encoding)
+    return s.weighted(s.losses(data_residual(r_res, coeffs, c_u), mse_to(u_bc, u_ic)))
 
 
 def case_inputs(case):
@@ -128,25 +112,38 @@ def variant_targets(variant, u_ic, u_bc, r_res, c_u=C_U):
     return u_ic, u_bc, r_res, c_u
 
 
-def case_reference(case, variant=""):
-    """reference_loss_data of one case through conftest.cached_oracle -> {"grad": (NP,), "parts": (3,)}."""
-    ans, n, L, enc, B_res, n_ic, n_bc = CASES[case]
+def case_record(prefix, case, targets, tail, loss, variant="", key=None):
+    """The record ``<prefix>_<case>[_H<H>][_<variant>]`` of one reference of this family of cases (data, coefficient,
+    inverse, balanced step).  Its inputs: the case's weights and points, ``targets`` = (u_ic, u_bc, r_res) and ``tail``.
+    ``loss(flat, H, n, n_theta, theta_shape, ansatz, haar, X_ic, X_bc, X_res, *targets, encoding=)`` gives (grad, parts)
+    or the record's dict."""
+    ans, n, L, enc, *_ = CASES[case]
     P = int(pkg("circuits").params_per_layer(ans, n))
-    flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res = case_inputs(case)
-    ui, ub, rr, c_u = variant_targets(variant, u_ic, u_bc, r_res)
+    flat, X_ic, X_bc, X_res = case_inputs(case)[:4]
 
     def compute():
-        g, parts = reference_loss_data(flat, case_H(case), n, L * P, (L, P), ans, haar_for(n, 1),
-                                       *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), ui, ub, rr,
-                                       coeffs=COEFFS, c_u=c_u, encoding=enc)
-        return {"grad": g, "parts": parts}
-    inputs = (np.asarray(flat, dtype=np.float32),) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res)) + \
-        (ui, ub, rr, np.asarray(COEFFS + (c_u,), dtype=np.float32))
-    key = f"tab_{ans}_n{n}_L{L}_{enc}_r{B_res}_i{n_ic}_b{n_bc}" + (f"_H{case_H(case)}" if case in CASE_H else "") + \
-        (f"_{variant}" if variant else "")
-    return cached_oracle(key, inputs, compute)
+        out = loss(flat, case_H(case), n, L * P, (L, P), ans, haar_for(n, 1),
+                   *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), *targets, encoding=enc)
+        return out if isinstance(out, dict) else {"grad": out[0], "parts": out[1]}
+    return record(key or case_key(prefix, CASES[case]), (flat, X_ic, X_bc, X_res) + tuple(targets) + tuple(tail), compute,
+                  H=CASE_H.get(case), variant=variant, case=case)
+
+
+def case_job(case, variant=""):
+    ui, ub, rr, c_u = variant_targets(variant, *case_inputs(case)[4:])
+    return case_record("tab", case, (ui, ub, rr), (COEFFS + (c_u,),),
+                       lambda *a, **k: reference_loss_data(*a, coeffs=COEFFS, c_u=c_u, **k), variant)
+
+
+def case_reference(case, variant=""):
+    """reference_loss_data of one case through conftest.cached_oracle -> {"grad": (NP,), "parts": (3,)}."""
+    return case_job(case, variant).get()
+
+
+def controlled_jobs(job, cases, controls):
+    """``job(case)`` of every case and ``job(case, variant)`` of every negative control: a module's committed records."""
+    return [job(c) for c in cases] + [job(c, v) for c, vs in controls.items() for v in vs]
 
 
 def oracle_jobs():
-    """(case, variant) of every committed record (tests/golden/make_tabulated_oracle_cache.py)."""
-    return [(c, "") for c in CASES] + [(c, v) for c, vs in CONTROLS.items() for v in vs]
+    return controlled_jobs(case_job, CASES, CONTROLS)

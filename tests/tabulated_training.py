@@ -5,14 +5,14 @@ clip_grad_norm_(1), Adam, ReduceLROnPlateau, with the dataset's targets and its 
 c_u u + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy).
 
 The GPU test reads the batches back from the step's buffers and hands them to ``training_reference``; the records
-committed under tests/golden/oracle/ (make_tabulated_oracle_cache.py) are computed from ``expected_batches``, which the
+committed under tests/golden/oracle/ (make_oracle_cache.py) are computed from ``expected_batches``, which the
 device must reproduce bit for bit for a record's digest to match.
 """
 import numpy as np
 import torch
 
 import tabulated_reference as T
-from conftest import cached_oracle
+from step_reference import as64, batch_inputs, flat_of, record
 
 TRAIN_CASES = {"cascade4": ("cascade", 4), "layered8": ("layered", 8)}
 DS_SIZES = (256, 64, 64)            # residual, IC, BC rows
@@ -63,8 +63,21 @@ def initial_model(case):
     return osol.OracleSolver(base_args(ans, n), device=torch.device("cpu"))
 
 
-def replay(model, batches, coeffs=T.COEFFS, c_u=T.C_U):
-    """Loss history of the float64 copy of ``model`` trained on ``batches``."""
+def replay(model, batches, residual, objective=None, value=None, extra=(), extra_group=False, clip_extra=False,
+           set_grads=None):
+    """Loss history (steps,) of the float64 copy of ``model`` trained on ``batches``, one step per batch: Adam at the
+    model's lr, ReduceLROnPlateau(0.9, 1000), the derivatives of the residual by autograd, clip_grad_norm_(1) and the step.
+    A batch is (X_ic, X_bc, X_res, ic targets, bc targets, residual targets, ...).  Every replay of the suite but L-BFGS's
+    is a call of this one with what is its own:
+
+    ``residual(batch, jets)``: the residual part of the loss; ``jets[k]`` = (u, u_t, u_x, u_y, u_xx, u_yy), (B, 1) each, of
+    output k at the batch's residual points.  ``value(net, X, target)``: the BC / IC part (default: the MSE).
+    ``objective(l_r, l_bc, l_ic)``: the scalar that is descended, handed to the scheduler and recorded (default
+    2 l_r + 4 l_bc + 2 l_ic).  ``extra``: tensors trained next to the model's, in its param group or (``extra_group``) in
+    one of their own; the clip covers the model's parameters only unless ``clip_extra``.  ``set_grads(parts, params,
+    batch)`` writes the parameters' ``.grad`` itself, in place of ``loss.backward()``.  Each callable runs exactly once per
+    step, in the order residual, value (BC), value (IC), objective, set_grads; the variants rely on that to record what
+    else they keep per step (coefficients, weights, the annealing of eps)."""
     from oracle import statevector as sv
     model = model.double()
     ql = model.quantum_layer
@@ -73,35 +86,60 @@ def replay(model, batches, coeffs=T.COEFFS, c_u=T.C_U):
         q = sv.circuit_expvals(model.preprocessor(x), ql.params, ql.q_ansatz, ql.num_qubits, ql._haar, "angle")
         return model.postprocessor(q.T.reshape(-1, ql.num_qubits))
 
-    opt = torch.optim.Adam(model.parameters(), lr=model.args["lr"])
-    sch = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.9, patience=1000)
-    c_t, c_x, c_y, d_xx, d_yy = coeffs
-    g = lambda out, wrt: torch.autograd.grad(out, wrt, torch.ones_like(out), create_graph=True)[0]
     mse = torch.nn.MSELoss()
+    value = value or (lambda net, X, target: mse(net(as64(X)), as64(target)[:, None]))
+    objective = objective or (lambda l_r, l_bc, l_ic: 2.0 * l_r + 4.0 * l_bc + 2.0 * l_ic)
+    prm, extra = list(model.parameters()), list(extra)
+    groups = [prm, extra] if extra_group else [prm + extra]
+    opt = torch.optim.Adam([{"params": g} for g in groups if g], lr=model.args["lr"])
+    sch = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.9, patience=1000)
+    g = lambda out, wrt: torch.autograd.grad(out, wrt, torch.ones_like(out), create_graph=True)[0]
     hist = []
-    for X_ic, X_bc, X_res, u_ic, u_bc, r_res in batches:
-        as64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+    for b in batches:
         opt.zero_grad()
-        t, x, y = [as64(X_res)[:, k:k + 1].requires_grad_(True) for k in range(3)]
-        u = net(torch.cat((t, x, y), 1))
-        u_x, u_y = g(u, x), g(u, y)
-        res = c_u * u + c_t * g(u, t) + c_x * u_x + c_y * u_y - (d_xx * g(u_x, x) + d_yy * g(u_y, y))
-        loss = 2.0 * mse(res, as64(r_res)[:, None]) + 4.0 * mse(net(as64(X_bc)), as64(u_bc)[:, None]) + \
-            2.0 * mse(net(as64(X_ic)), as64(u_ic)[:, None])
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1)
+        t, x, y = [as64(b[2])[:, k:k + 1].requires_grad_(True) for k in range(3)]
+        f = net(torch.cat((t, x, y), 1))
+        jets = []
+        for k in range(f.shape[1]):
+            u = f[:, k:k + 1]
+            u_x, u_y = g(u, x), g(u, y)
+            jets.append((u, g(u, t), u_x, u_y, g(u_x, x), g(u_y, y)))
+        parts = (residual(b, jets), value(net, b[1], b[4]), value(net, b[0], b[3]))
+        loss = objective(*parts)
+        if set_grads is None:
+            loss.backward()
+        else:
+            set_grads(parts, prm, b)
+        torch.nn.utils.clip_grad_norm_(prm + extra if clip_extra else prm, max_norm=1)
         opt.step()
         sch.step(loss)
         hist.append(loss.item())
     return np.array(hist)
 
 
-def training_reference(case, batches=None):
-    """{"loss": (STEPS,)} of one case through conftest.cached_oracle, keyed on the initial weights and the batches."""
+def operator_residual(jets, c_u, c_t, c_x, c_y, d_xx, d_yy, c_3=None):
+    """c_u u [+ c_3 u^3] + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy) of one output's jets."""
+    u, u_t, u_x, u_y, u_xx, u_yy = jets
+    head = c_u * u if c_3 is None else c_u * u + c_3 * u ** 3
+    return head + c_t * u_t + c_x * u_x + c_y * u_y - (d_xx * u_xx + d_yy * u_yy)
+
+
+def data_residual(coeffs=T.COEFFS, c_u=T.C_U):
+    """The ``residual`` of ``replay`` on a dataset's scalar operator: the MSE against the batch's residual targets."""
+    return lambda b, jets: torch.nn.functional.mse_loss(operator_residual(jets[0], c_u, *coeffs), as64(b[5])[:, None])
+
+
+def training_job(case, batches=None):
     batches = expected_batches() if batches is None else batches
     model = initial_model(case)
-    flat0 = np.concatenate([p.detach().numpy().reshape(-1) for p in model.parameters()]).astype(np.float32)
-    inputs = [flat0, np.asarray(T.COEFFS + (T.C_U,), dtype=np.float32)]
-    for b in batches:
-        inputs += [np.asarray(a, dtype=np.float32) for a in b]
-    return cached_oracle(f"tabtrain_{case}", inputs, lambda: {"loss": replay(model, batches)})
+    return record(f"tabtrain_{case}", [flat_of(model), T.COEFFS + (T.C_U,)] + batch_inputs(*batches),
+                  lambda: {"loss": replay(model, batches, data_residual())})
+
+
+def training_reference(case, batches=None):
+    """{"loss": (STEPS,)} of one case through conftest.cached_oracle, keyed on the initial weights and the batches."""
+    return training_job(case, batches).get()
+
+
+def oracle_jobs():
+    return [training_job(c) for c in TRAIN_CASES]

@@ -22,7 +22,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, pkg
-from step_reference import cached_step_reference, layout_from_fixture, step_inputs
+from step_reference import layout_from_fixture, step_inputs, step_record
 from test_gpu_fullsize import Log, base_args, grads_for
 
 pytestmark = pytest.mark.gpu
@@ -69,9 +69,8 @@ STATIC = ("reg_cascade4", "reg_farhi4", "reg_alternate5", "wave_cascade6", "wave
 
 
 def oracle_jobs():
-    """(case, variant) of every committed record (tests/golden/make_oracle_cache.py)."""
-    out = [(c, "") for c in CASES] + [(c, v) for c, vs in CONTROLS.items() for v in vs]
-    return out + [(N16, "")]
+    """Every committed record (tests/golden/make_oracle_cache.py)."""
+    return [case_job(c) for c in CASES] + [case_job(c, v) for c, vs in CONTROLS.items() for v in vs] + [n16_value_job()]
 
 
 def case_inputs(case):
@@ -80,12 +79,13 @@ def case_inputs(case):
     return step_inputs(H, n, n_theta, B_res, n_ic, n_bc, salt=1)
 
 
-def case_reference(case, variant=""):
-    if case == N16:
-        return n16_value_reference()
+def case_job(case, variant=""):
     ans, n, L, enc, *_ = CASES[case]
-    flat, X_ic, X_bc, X_res = case_inputs(case)
-    return cached_step_reference(ans, n, L, 1, enc, flat, X_ic, X_bc, X_res, H=H, variant=variant)
+    return step_record(ans, n, L, 1, enc, *case_inputs(case), H=H, variant=variant)._replace(case=case)
+
+
+def case_reference(case, variant=""):
+    return case_job(case, variant).get()
 
 
 def _model(gpu_device, ans, n, L, enc, flat=None):
@@ -216,13 +216,16 @@ def _n16_points():
             for b in (osol.BOX_IC, osol.BOX_BC1)]
 
 
-def n16_value_reference():
-    """fp64 reference of the value points alone on the fixture's weights (cheap at n = 16: no derivative channels)."""
+def n16_value_job():
     z = np.load(os.path.join(GOLDEN, "operator_cross_mesh_n16.npz"))
     n_theta = pkg("circuits").params_per_layer("cross_mesh", 16)
     X_ic, X_bc = _n16_points()
-    return cached_step_reference("cross_mesh", 16, 1, 1, "angle", layout_from_fixture(z, "w__", H, 16, n_theta),
-                                 X_ic, X_bc, X_ic[:0], H=H)
+    return step_record("cross_mesh", 16, 1, 1, "angle", layout_from_fixture(z, "w__", H, 16, n_theta), X_ic, X_bc, X_ic[:0], H=H)
+
+
+def n16_value_reference():
+    """fp64 reference of the value points alone on the fixture's weights (cheap at n = 16: no derivative channels)."""
+    return n16_value_job().get()
 
 
 def test_config5_step_matches_reference_pde(gpu_device):

@@ -16,8 +16,7 @@ tests/test_gpu_fused_widths.py and tests/test_gpu_fused_families.py (2e-4 on the
 relative to max(1, max |ref|)), with a dropped hidden unit and, where one point weighs enough, a dropped residual point
 as controls.  Inputs come from
 seeded CPU generators; the step references are cached through conftest.cached_oracle (records under
-tests/golden/oracle/, written by ``QC_WRITE_ORACLE_CACHE=1 python -c "import test_gpu_mlp_blocked_loops as t;
-t.write_oracle_records()"`` from tests/)."""
+tests/golden/oracle/, written by tests/golden/make_oracle_cache.py)."""
 import numpy as np
 import pytest
 import torch
@@ -25,8 +24,8 @@ import torch
 import hybrid_pinn_reference as HR
 import mlp_reference as R
 import test_gpu_mlp_shapes as S
-from conftest import cached_oracle, pkg
-from step_reference import cached_step_reference, haar_for, reference_loss, step_inputs, step_key
+from conftest import pkg
+from step_reference import step_inputs, step_record
 
 POINT_TOL, ROW_TOL = S.POINT_TOL, S.ROW_TOL      # tests/test_gpu_mlp_shapes.py
 TOL_G, TOL_L = 2e-4, 1e-4                        # tests/test_gpu_fused_widths.py, tests/test_gpu_fused_families.py
@@ -96,27 +95,18 @@ def _step_inputs(tag):
     return step_inputs(H, n, n_theta, B_res, n_ic, n_bc, salt=5)
 
 
+def _step_job(tag, variant=""):
+    ans, n, H, B_res, n_ic, n_bc = STEP_CASES[tag]
+    return step_record(ans, n, 1, 1, "angle", *_step_inputs(tag), H=H, variant=variant)
+
+
 def _step_reference(tag, variant=""):
     """{"grad", "parts"} of the step reference; variant "drop_unit" (hidden unit H - 1 of both networks) or "drop_res"."""
-    ans, n, H, B_res, n_ic, n_bc = STEP_CASES[tag]
-    flat, X_ic, X_bc, X_res = _step_inputs(tag)
-    if variant != "drop_unit":
-        return cached_step_reference(ans, n, 1, 1, "angle", flat, X_ic, X_bc, X_res, H=H, variant=variant)
-    P = int(pkg("circuits").params_per_layer(ans, n))
-
-    def compute():
-        g, parts = reference_loss(flat, H, n, P, (1, P), ans, haar_for(n, 1),
-                                  *(torch.as_tensor(x).double() for x in (X_ic, X_bc, X_res)), drop_unit=True)
-        return {"grad": g, "parts": parts}
-    inputs = (flat,) + tuple(np.asarray(x, dtype=np.float32) for x in (X_ic, X_bc, X_res))
-    return cached_oracle(step_key(ans, n, 1, 1, "angle", B_res, n_ic, n_bc, "drop_unit"), inputs, compute)
+    return _step_job(tag, variant).get()
 
 
-def write_oracle_records():
-    for tag in STEP_CASES:
-        for v in ("",) + _controls(tag):
-            _step_reference(tag, v)
-            print("done:", tag, v, flush=True)
+def oracle_jobs():
+    return [_step_job(tag, v) for tag in STEP_CASES for v in ("",) + _controls(tag)]
 
 
 def _rel(got, want, tol):

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from conftest import pkg
-from step_reference import cached_step_reference, step_inputs
+from step_reference import step_inputs, step_record
 from test_gpu_fullsize import Log, base_args, grads_for
 
 pytestmark = pytest.mark.gpu
@@ -56,10 +56,17 @@ def case_inputs(case):
     return step_inputs(H, n, n_theta, B_res, n_ic, n_bc, salt=4)
 
 
-def case_reference(case):
+def case_job(case):
     ans, n, H, *_ = CASES[case]
-    flat, X_ic, X_bc, X_res = case_inputs(case)
-    return cached_step_reference(ans, n, 1, 1, "angle", flat, X_ic, X_bc, X_res, H=H)
+    return step_record(ans, n, 1, 1, "angle", *case_inputs(case), H=H)
+
+
+def case_reference(case):
+    return case_job(case).get()
+
+
+def oracle_jobs():
+    return [case_job(c) for c in CASES]
 
 
 def case_grads(case, gpu_device):

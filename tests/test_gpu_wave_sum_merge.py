@@ -23,7 +23,7 @@
     such exchange can pass (b).
     The seeds (``salt`` of step_inputs) were chosen for that on the CPU, from the reference alone; the check needs no GPU.
 
-The reference records are committed under tests/golden/oracle/ (tests/golden/make_wave_sum_merge_oracle_cache.py)."""
+The reference records are committed under tests/golden/oracle/ (tests/golden/make_oracle_cache.py)."""
 import ctypes as C
 import itertools
 import os
