@@ -13,6 +13,41 @@
 
 static inline int qc_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+typedef float qf2 __attribute__((ext_vector_type(2)));   // an amplitude (re, im), or two fp32 lanes of a packed instruction
+
+// ------------------------------------------------------------------ write-through stores of stage outputs
+// qc_store_wt(p, v): *p = v as a relaxed agent-scope store, global_store_dword / _dwordx2 ... sc1 on gfx950, with no
+// fence and no wait.  A plain store stays dirty in the writing XCD's L2 until the release at the end of the kernel
+// writes it back, after the last wave has stopped computing; an sc1 store goes through to memory when it is issued, so
+// that write-back has nothing left to do for it.  The stored bits are those of the plain store.  Rules:
+//   * for outputs whose consumer is a LATER launch (its plain loads are then valid: the launch boundary makes every
+//     completed store visible) and where one wave instruction writes whole 128-byte lines (lane = consecutive element);
+//     a partial line goes to memory as a partial write;
+//   * never for a value that another block reads back within the SAME launch: the store drops the line from this XCD's
+//     L2 and orders nothing;
+//   * never together with nt (nt is no write-through).
+// A site takes the policy only where a kernel trace shows its kernel shorter and its consumers no longer (DESIGN
+// section 8.0000000): the angle jets of the pre-network forward bodies and qbar of the fused post bodies.  The
+// final-state hand-off (qc_chi_write, the only 8-byte site tried), the <Z> jets and the adjoint stage's abar / d_angles
+// stay plain: written through, the first made the kernels that read it longer by more than the writer gained, the
+// second made its own kernel longer, the third gained no more than the control runs differ.
+// The host pass sees a plain store.  tools/ubench/store_policy.hip checks both forms across launches and XCDs.
+__host__ __device__ __forceinline__ void qc_store_wt(float* p, const float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *p = v;
+#endif
+}
+__host__ __device__ __forceinline__ void qc_store_wt(qf2* p, const qf2 v) {   // 8-byte aligned, as every qf2 is
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_store(reinterpret_cast<uint64_t*>(p), __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *p = v;
+#endif
+}
+
 // ------------------------------------------------------------------ wave-level reductions
 // ---- fused diagonal runs (register family, n <= 5; compile-time programs of the wave family: qc_wave_sched.h)
 // A run of >= 2 consecutive RZ / CRZ gates is one element-wise multiply by D[k] = prod_g phase_g(k), phase =

@@ -22,7 +22,7 @@
 // (cos, sin) / (re, im) coefficient pairs of the trig and Haar tables are adjacent in memory and reach the packed
 // instructions as SGPR pairs with broadcast / negate modifiers (no repacking).  The layout is also the (re, im)
 // record of the statevectors in LDS and HBM (n >= 9 family, final-state hand-off), so loads and stores are 64-bit.
-typedef float qf2 __attribute__((ext_vector_type(2)));
+// (qf2, the (re, im) register pair: qc_common.h)
 __device__ __forceinline__ qf2 qc_swp(const qf2 a) { return __builtin_shufflevector(a, a, 1, 0); }
 __device__ __forceinline__ qf2 qc_dup(const float a) { return (qf2){a, a}; }
 __device__ __forceinline__ qf2 qc_pm(const float a) { return (qf2){a, -a}; }     // {a, -a}

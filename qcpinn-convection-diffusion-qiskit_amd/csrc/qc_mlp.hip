@@ -302,14 +302,14 @@ __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* _
           const int f = wave + QC_MS * j;
           if (f < NCH * N) {
             if (f < N) v[j] += prm[L.ob2 + f];
-            ajets[(int64_t)f * B + p] = v[j];
+            qc_store_wt(&ajets[(int64_t)f * B + p], v[j]);
           }
         }
       } else {
         for (int f = wave; f < NCH * N; f += QC_MS) {
           float v = (s_part[0][f][lane] + s_part[1][f][lane]) + (s_part[2][f][lane] + s_part[3][f][lane]);
           if (f < N) v += prm[L.ob2 + f];
-          ajets[(int64_t)f * B + p] = v;
+          qc_store_wt(&ajets[(int64_t)f * B + p], v);
         }
       }
     } else {
@@ -324,7 +324,7 @@ __device__ __forceinline__ void k_pre_fwd_body(const int64_t bid, const float* _
         v[0] += prm[L.ob2 + i];
         angle_map_fwd<NCH>(v, a);
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) ajets[(int64_t)(c * N + i) * B + p] = a[c];
+        for (int c = 0; c < NCH; ++c) qc_store_wt(&ajets[(int64_t)(c * N + i) * B + p], a[c]);
       }
     }
   }
@@ -1354,12 +1354,12 @@ __device__ __forceinline__ void k_pre_fwd_value4(const int64_t bid, const float*
     for (int i = 0; i < N; ++i) {
       const float v = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) + prm[L.ob2 + i];
       if constexpr (MAP == 0) {
-        ajets[(int64_t)i * B + p] = v;
+        qc_store_wt(&ajets[(int64_t)i * B + p], v);
       } else {
         const float vv[1] = {v};
         float a[1];
         angle_map_fwd<1>(vv, a);
-        ajets[(int64_t)i * B + p] = a[0];
+        qc_store_wt(&ajets[(int64_t)i * B + p], a[0]);
       }
     }
   }
@@ -1672,7 +1672,7 @@ __device__ __forceinline__ void k_post_fused_value_body(const int64_t bid, const
 #pragma unroll
             for (int j = 0; j < K; ++j) qb = fmaf(w.c[j], gbv[j], qb);
           });
-      qbar[(int64_t)i * B + p] = qb;
+      qc_store_wt(&qbar[(int64_t)i * B + p], qb);
     }
   }
 }
@@ -1910,11 +1910,11 @@ __device__ __forceinline__ void k_post_fused6_body(const int64_t bid, const floa
 #pragma unroll
       for (int j = 0; j < NF; ++j) {
         const int f = wave + QC_MS * j;
-        if (f < NCH * N) qbar[(int64_t)f * B + p] = v[j];
+        if (f < NCH * N) qc_store_wt(&qbar[(int64_t)f * B + p], v[j]);
       }
     } else {
       for (int f = wave; f < NCH * N; f += QC_MS)
-        qbar[(int64_t)f * B + p] = (s_q[0][f][lane] + s_q[1][f][lane]) + (s_q[2][f][lane] + s_q[3][f][lane]);
+        qc_store_wt(&qbar[(int64_t)f * B + p], (s_q[0][f][lane] + s_q[1][f][lane]) + (s_q[2][f][lane] + s_q[3][f][lane]));
     }
   }
 }
