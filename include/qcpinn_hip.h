@@ -132,6 +132,27 @@ int qc_pre_backward_map(const float* X_dev, const float* params_dev, int H, int 
 /* The map the fused step applies between this program's pre network and its embedding (default QC_ANGLE_MAP_NONE). */
 int qc_program_set_angle_map(qc_program* prog, int angle_map);
 
+/* Fourier-feature input encoding of the pre network (Tancik et al. 2020; the reference's FourierFeatures modules):
+ *   gamma(X) = [sin(2 pi X B), cos(2 pi X B)],  B = freq [3][m] fp32 (rows t, x, y), not trained,
+ * in front of Linear(2m, H): W1 is then [H][2m] row-major (sines, then cosines, the order of torch.cat) and the flat
+ * vector is  W1[H][2m] b1[H] W2[n][H] b2[n] | W3 ... as before, every later offset (2m - 3) H further on.  The derivative
+ * channels of the first layer follow in closed form, with r_j = sum_k B_kj X_k reduced by its nearest integer before
+ * the sine and cosine (exact in fp32), so the scale of B costs no accuracy in the argument reduction.
+ * qc_program_set_input_map: the library keeps its own device copy of freq_host; m = 0 removes the map; m < 0,
+ * m > QC_FF_MAX or a non-finite frequency: QC_ERR_ARG.  Every fused step entry point and qc_fused_step_stage read the
+ * map from desc->prog, in the merged and in the two-stream form, as does qc_dataset_scores; the system step refuses a
+ * program with a map (QC_ERR_UNSUPPORTED).  Amplitude encoding is supported: its pre stage goes through the same
+ * launchers.  part_stride and the optimiser follow the longer vector: NP + 3 > 3072 takes the two-launch tail.
+ * The _ff forms are the _map forms with the map given explicitly (freq_dev on the device, 1 <= m <= QC_FF_MAX, else
+ * QC_ERR_ARG); shape limits and error codes are those of the _map forms, checked before any launch. */
+#define QC_FF_MAX 64
+int qc_program_set_input_map(qc_program* prog, const float* freq_host /*[3][m]*/, int m);
+int qc_pre_forward_ff(const float* X_dev, const float* params_dev, int H, int n, int n_theta, int angle_map,
+                      const float* freq_dev /*[3][m]*/, int m, float* ajets_dev, int64_t B, int nch, void* stream);
+int qc_pre_backward_ff(const float* X_dev, const float* params_dev, int H, int n, int n_theta, int angle_map,
+                       const float* freq_dev /*[3][m]*/, int m, const float* ajets_dev, const float* abar_dev,
+                       float* part_dev, int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream);
+
 typedef struct qc_pde {
   float D, vx, vy;        /* nn/pde.py:53-55 defaults 0.01, 1, 1: the constants of the analytic targets (mode 2) */
   /* operator coefficients, residual = c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy): with the sigma scalings of

@@ -33,6 +33,9 @@ static inline int after_launch() {
 }
 
 static QcLayout make_layout(int H, int n, int n_theta) { return qc_layout(H, n, n_theta); }
+// columns of W1 in the flat vector of the network in front of this program: 2 m behind a Fourier-feature map, else 3
+static int prog_n_in(const qc_program* p) { return p->ff_m > 0 ? 2 * p->ff_m : 3; }
+static_assert(QC_FF_MAX == 64, "the trig rows of a tile at QC_FF_MAX (32 KB) are sized into the stages' LDS budget");
 static QcPde to_pde(const qc_pde* p) {
   QcPde q;
   memcpy(&q, p, sizeof(q));
@@ -214,6 +217,7 @@ int qc_program_destroy(qc_program* p) {
   if (p->h2) qc_h2_destroy(p->h2);
   if (p->d_gates) (void)hipFree(p->d_gates);
   if (p->d_diag_list) (void)hipFree(p->d_diag_list);
+  if (p->d_ff_freq) (void)hipFree(p->d_ff_freq);
   free(p->h_gates);
   free(p);
   return QC_OK;
@@ -237,6 +241,28 @@ static bool problem_ok(int pb) { return pb >= QC_PROBLEM_CONVECTION_DIFFUSION &&
 int qc_program_set_angle_map(qc_program* p, int angle_map) {
   if (!p || !angle_map_ok(angle_map)) return QC_ERR_ARG;
   p->angle_map = angle_map;
+  return QC_OK;
+}
+
+// The Fourier-feature input map of the pre network in front of this program.  Both encodings: with amplitude encoding
+// the pre stage goes through the same launchers (pipe_forward).  The program changes only when the copy has succeeded.
+int qc_program_set_input_map(qc_program* p, const float* freq_host, int m) {
+  if (!p || m < 0 || m > QC_FF_MAX || (m > 0 && !freq_host)) return QC_ERR_ARG;
+  float* d = nullptr;
+  if (m > 0) {
+    for (int i = 0; i < 3 * m; ++i)
+      if (!isfinite(freq_host[i])) return QC_ERR_ARG;
+    hipError_t e = hipMalloc((void**)&d, sizeof(float) * 3 * m);
+    if (e != hipSuccess) return QC_ERR_ALLOC;
+    e = hipMemcpy(d, freq_host, sizeof(float) * 3 * m, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return hip_fail(e);
+    }
+  }
+  if (p->d_ff_freq) (void)hipFree(p->d_ff_freq);
+  p->d_ff_freq = d;
+  p->ff_m = m;
   return QC_OK;
 }
 
@@ -481,15 +507,51 @@ int qc_pre_backward(const float* X, const float* prm, int H, int n, int n_theta,
                              stream);
 }
 
+int qc_pre_forward_ff(const float* X, const float* prm, int H, int n, int n_theta, int angle_map, const float* freq_dev, int m,
+                      float* ajets, int64_t B, int nch, void* stream) {
+  int rc = check_mlp(H, n, n_theta, B, nch);
+  if (rc) return rc;
+  if (!X || !prm || !ajets || !angle_map_ok(angle_map) || !freq_dev || m < 1 || m > QC_FF_MAX) return QC_ERR_ARG;
+  rc = qc_mlp_pre_ff_fwd(X, prm, qc_layout(H, n, n_theta, 1, 0, 2 * m), ajets, B, nch, (hipStream_t)stream, angle_map, freq_dev, m);
+  return rc ? rc : after_launch();
+}
+
+int qc_pre_backward_ff(const float* X, const float* prm, int H, int n, int n_theta, int angle_map, const float* freq_dev, int m,
+                       const float* ajets, const float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch,
+                       void* stream) {
+  int rc = check_mlp(H, n, n_theta, B, nch);
+  if (rc) return rc;
+  if (!freq_dev || m < 1 || m > QC_FF_MAX) return QC_ERR_ARG;
+  const QcLayout L = qc_layout(H, n, n_theta, 1, 0, 2 * m);
+  if (!X || !prm || !abar || !part || part_stride < L.NP || row0 < 0 || !angle_map_ok(angle_map)) return QC_ERR_ARG;
+  if (angle_map != QC_ANGLE_MAP_NONE && !ajets) return QC_ERR_ARG;
+  rc = qc_mlp_pre_ff_bwd(X, prm, L, abar, part, part_stride, row0, B, nch, (hipStream_t)stream, angle_map, ajets, freq_dev, m);
+  return rc ? rc : after_launch();
+}
+
+// the pre stage in front of program p: the plain launchers, or the Fourier-feature ones with the program's map
+static int prog_pre_forward(const qc_program* p, const float* X, const float* prm, int H, int n, int n_theta, float* ajets,
+                            int64_t B, int nch, void* stream) {
+  if (p->ff_m > 0) return qc_pre_forward_ff(X, prm, H, n, n_theta, p->angle_map, p->d_ff_freq, p->ff_m, ajets, B, nch, stream);
+  return qc_pre_forward_map(X, prm, H, n, n_theta, p->angle_map, ajets, B, nch, stream);
+}
+static int prog_pre_backward(const qc_program* p, const float* X, const float* prm, int H, int n, int n_theta, const float* ajets,
+                             const float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream) {
+  if (p->ff_m > 0)
+    return qc_pre_backward_ff(X, prm, H, n, n_theta, p->angle_map, p->d_ff_freq, p->ff_m, ajets, abar, part, part_stride, row0, B,
+                              nch, stream);
+  return qc_pre_backward_map(X, prm, H, n, n_theta, p->angle_map, ajets, abar, part, part_stride, row0, B, nch, stream);
+}
+
 // qc_post, and by `tg` qc_post_data (mode 2 on tabulated targets: X is not read) or qc_post_coef (out_u = the [6][B]
 // cotangents, out_res not used)
 static int post_impl(int mode, const float* X, const float* prm, int H, int n, int n_theta, const qc_pde* pde,
                      const float* qjets, float* out_u, float* out_res, const float* in_ubar, const float* in_rbar,
                      float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, void* stream,
-                     const QcTarget& tg) {
+                     const QcTarget& tg, int n_in = 3) {
   int rc = check_mlp(H, n, n_theta, B, nch);
   if (rc) return rc;
-  const QcLayout L = qc_layout(H, n, n_theta, 1, tg.n_op());
+  const QcLayout L = qc_layout(H, n, n_theta, 1, tg.n_op(), n_in);
   const bool analytic = tg.kind == QC_TARGET_ANALYTIC;
   if (mode < 0 || mode > 4 || (!X && analytic) || !prm || !pde || !qjets) return QC_ERR_ARG;
   // the analytic targets are defined for 0..2 only; the tabulated ones by the rule of their type
@@ -781,7 +843,8 @@ static int check_step_desc(const qc_step_desc* d, bool need_umat, bool (*support
 }
 
 static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool draw, const QcTarget& tg) {
-  const QcLayout L = qc_layout(d->H, d->n, d->n_theta, 1, tg.n_op());
+  const qc_program* pg = d->prog;
+  const QcLayout L = qc_layout(d->H, d->n, d->n_theta, 1, tg.n_op(), prog_n_in(pg));
   const int64_t rows_res = qc_ceil_div(d->B_res, 64);
   const QcTrig* trig = (const QcTrig*)d->trig_dev;
   const float* prm = d->params_dev;
@@ -790,6 +853,9 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
   memcpy(&pde, &d->pde, sizeof(pde));
   switch (stage) {
     case QC_STAGE_PRE_FWD:
+      if (pg->ff_m > 0)
+        return qc_mlp_pre_ff_fwd_both(step_batches(d, nullptr), draw ? 1 : 0, d->sample_bc_face_points, prm, L, d->ajets_res_dev,
+                                      d->ajets_val_dev, st, pg->angle_map, pg->d_ff_freq, pg->ff_m);
       return qc_mlp_pre_fwd_both(step_batches(d, nullptr), draw ? 1 : 0, d->sample_bc_face_points, prm, L, d->ajets_res_dev,
                                  d->ajets_val_dev, st, d->prog->angle_map);
     case QC_STAGE_CIRCUIT_FWD:
@@ -807,6 +873,10 @@ static int merged_stage(const qc_step_desc* d, int stage, hipStream_t st, bool d
                                   chi_store, d->ajets_val_dev, d->qbar_val_dev, d->abar_val_dev, rows_res, d->B_val,
                                   d->part_dev + L.oTh, d->part_stride, st);
     case QC_STAGE_PRE_BWD:
+      if (pg->ff_m > 0)
+        return qc_mlp_pre_ff_bwd_both((const float*)d->X_res_dev, (const float*)d->X_val_dev, prm, L, d->abar_res_dev,
+                                      d->abar_val_dev, d->part_dev, d->part_stride, 0, rows_res, d->B_res, d->B_val, st,
+                                      pg->angle_map, d->ajets_res_dev, d->ajets_val_dev, pg->d_ff_freq, pg->ff_m);
       return qc_mlp_pre_bwd_both((const float*)d->X_res_dev, (const float*)d->X_val_dev, prm, L, d->abar_res_dev,
                                  d->abar_val_dev, d->part_dev, d->part_stride, 0, rows_res, d->B_res, d->B_val, st,
                                  d->prog->angle_map, d->ajets_res_dev, d->ajets_val_dev);
@@ -897,7 +967,7 @@ struct QcPipe {
 static int pipe_forward(const qc_step_desc* d, const QcPipe& q, hipStream_t st) {
   const qc_program* p = d->prog;
   int rc;
-  if ((rc = qc_pre_forward_map(q.X, d->params_dev, d->H, d->n, d->n_theta, p->angle_map, q.ajets, q.B, q.nch, st))) return rc;
+  if ((rc = prog_pre_forward(p, q.X, d->params_dev, d->H, d->n, d->n_theta, q.ajets, q.B, q.nch, st))) return rc;
   if (q.u && (rc = qc_amp_forward(q.ajets, q.u, d->n, q.B, q.nch, st))) return rc;
   rc = p->fam->fwd(p, (const QcTrig*)d->trig_dev, d->umat_dev, q.u ? q.u : q.ajets, q.qjets, q.B, q.nch, q.store, st);
   return rc ? rc : after_launch();
@@ -910,7 +980,7 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
   const qc_program* p = d->prog;
   const int n = d->n, H = d->H;
   const QcTrig* trig = (const QcTrig*)d->trig_dev;
-  float* part_theta = d->part_dev + qc_layout(H, n, d->n_theta, sys ? sys->K : 1).oTh;
+  float* part_theta = d->part_dev + qc_layout(H, n, d->n_theta, sys ? sys->K : 1, 0, prog_n_in(p)).oTh;
   if (!q.X || !q.ajets || !q.qjets || !q.qbar || !q.abar || (p->n_u4 > 0 && !d->umat_dev)) return QC_ERR_ARG;
   int rc;
   if ((rc = pipe_forward(d, q, st))) return rc;
@@ -922,12 +992,12 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
                              q.nch == 6 ? sys->target_res_dev : sys->target_val_dev, q.qbar, d->part_dev, d->part_stride,
                              q.row0, q.B, q.nch, st))) return rc;
   } else if ((rc = post_impl(2, q.X, d->params_dev, H, n, d->n_theta, &d->pde, q.qjets, q.abar, q.nch == 6 ? q.abar + q.B : nullptr,
-                             nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tg))) return rc;
+                             nullptr, nullptr, q.qbar, d->part_dev, d->part_stride, q.row0, q.B, q.nch, st, tg, prog_n_in(p)))) return rc;
   if ((rc = p->fam->bwd(p, trig, d->umat_dev, cin, q.qbar, cout, part_theta, d->part_stride, q.row0, q.B, q.nch, q.store, st)) ||
       (rc = after_launch())) return rc;
   if (q.u && (rc = qc_amp_backward(q.ajets, q.ub, q.abar, n, q.B, q.nch, st))) return rc;
-  return qc_pre_backward_map(q.X, d->params_dev, H, n, d->n_theta, p->angle_map, q.ajets, q.abar, d->part_dev, d->part_stride,
-                             q.row0, q.B, q.nch, st);
+  return prog_pre_backward(p, q.X, d->params_dev, H, n, d->n_theta, q.ajets, q.abar, d->part_dev, d->part_stride, q.row0, q.B,
+                           q.nch, st);
 }
 
 // The step behind the four step entry points, which differ in `tg`, where the post stage takes its targets and its
@@ -947,7 +1017,7 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   int rc = check_step_desc(d, false, nullptr);
   if (rc) return rc;
   const int n = d->n, H = d->H;
-  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1, sys ? 0 : tg.n_op());
+  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1, sys ? 0 : tg.n_op(), prog_n_in(d->prog));
   const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
   const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
   const int64_t rows = rows_res + rows_val;
@@ -1077,6 +1147,7 @@ int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data,
 
 int qc_fused_pinn_system_step(const qc_step_desc* d, const qc_step_system* sys, int phases, void* stream) {
   if (!d || !sys_ok(sys) || (d->B_val > 0 && !sys->target_val_dev)) return QC_ERR_ARG;
+  if (d->prog && d->prog->ff_m > 0) return QC_ERR_UNSUPPORTED;   // the system post stage lays W1 out as [H][3]
   const QcBatches b = {(float*)d->X_res_dev, sys->target_res_dev, d->B_res, d->sample_off_res, (float*)d->X_val_dev,
                        sys->target_val_dev, d->n_ic, d->sample_off_ic, d->B_val - d->n_ic, d->sample_off_bc, d->sample_seed,
                        d->sample_step};
@@ -1230,7 +1301,7 @@ int qc_dataset_scores(const qc_step_desc* d, const qc_step_data* t, const qc_ste
                       {ws.res.p, ws.res.bytes, false}};
     if ((rc = pipe_forward(d, q, st))) return rc;
     if ((rc = post_impl(4, q.X, d->params_dev, d->H, d->n, d->n_theta, &d->pde, q.qjets, uj, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, 0, 0, c, 6, st, QcTarget{}))) return rc;
+                        nullptr, 0, 0, c, 6, st, QcTarget{}, prog_n_in(d->prog)))) return rc;
     qc_adapt_score_launch(uj, c, pde, t->c_u, cf ? cf->ds_coef + (size_t)QC_COEF_N * r : nullptr, t->ds_r + r, score + r, st);
     if ((rc = after_launch())) return rc;
   }

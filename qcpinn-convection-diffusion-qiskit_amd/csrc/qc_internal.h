@@ -9,12 +9,13 @@ struct QcLayout {  // column offsets of the flat parameter / gradient vector
 
 // K: rows of the last layer (outputs of the post network), W4[K][H] b4[K]; K = 1 is the single-output layout
 // n_op: trainable entries behind theta (the inverse step: QC_COEF_N; the balanced step: QC_BAL_N), counted in NP; no offset moves
-inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1, int n_op = 0) {
+// n_in: columns of W1: 3 (t, x, y), or 2 m behind a Fourier-feature map of m frequencies (W1[H][2m], sines then cosines)
+inline QcLayout qc_layout(int H, int n, int n_theta, int K = 1, int n_op = 0, int n_in = 3) {
   QcLayout L;
   L.H = H;
   L.n = n;
   L.oW1 = 0;
-  L.ob1 = 3 * H;
+  L.ob1 = n_in * H;
   L.oW2 = L.ob1 + H;
   L.ob2 = L.oW2 + n * H;
   L.oW3 = L.ob2 + n;
@@ -317,6 +318,17 @@ int qc_mlp_post(int mode, const float* X, const float* prm, QcLayout L, QcPde pd
                 float* out_u, float* out_res, const float* in_ubar, const float* in_rbar, float* qbar,
                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t,
                 const QcTarget& tg);
+// The pre stages behind a Fourier-feature input map (freq: [3][m] on the device, 1 <= m <= QC_FF_MAX; L laid out with
+// n_in = 2 m): the same arguments as the plain launchers, which serve the programs without a map
+int qc_mlp_pre_ff_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t, int map,
+                      const float* freq, int m);
+int qc_mlp_pre_ff_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part, int64_t part_stride,
+                      int64_t row0, int64_t B, int nch, hipStream_t, int map, const float* aj, const float* freq, int m);
+int qc_mlp_pre_ff_fwd_both(const QcBatches& b, int draw, int64_t face_pts, const float* prm, QcLayout L, float* ajr, float* ajv,
+                           hipStream_t st, int map, const float* freq, int m);
+int qc_mlp_pre_ff_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
+                           float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
+                           hipStream_t st, int map, const float* ajr, const float* ajv, const float* freq, int m);
 // the system post stage (k_post_system): forward, terms, loss columns, cotangents and reverse of one batch in one kernel;
 // L is the K-row layout; nch = 6: tg = [n_eq][B] residual targets or null (zero); nch = 1: tg = [K][B] value targets
 int qc_mlp_post_system(const float* prm, QcLayout L, const QcSys& sys, QcPde pde, const float* qjets, const float* tg,

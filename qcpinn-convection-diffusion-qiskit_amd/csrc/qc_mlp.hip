@@ -2788,3 +2788,559 @@ static int post_both_bal(const float* prm, QcLayout L, QcPde pde, const QcPostSe
     }
   });
 }
+
+// ================================================================== Fourier-feature input encoding of the pre network
+// gamma(X) = [sin(2 pi X B), cos(2 pi X B)] in front of Linear(2m, H) (Tancik et al. 2020; the reference's
+// hybrid_testing/modified_qpinn_cg.py:75-95).  B is [3][m] fp32, not trained; W1 is [H][2m] row-major in the order of
+// torch.cat([sin, cos]).  Per point r_j = B_tj t + B_xj x + B_yj y (turns), s_j = sin 2 pi r_j, c_j = cos 2 pi r_j,
+// w_jk = 2 pi B_kj; hidden unit u with P_j = W1[u][j], Q_j = W1[u][m + j], A_j = P_j s_j + Q_j c_j, D_j = P_j c_j - Q_j s_j:
+//   h = b1[u] + sum_j A_j,   h_k = sum_j w_jk D_j (k = t, x, y),   h_kk = -sum_j w_jk^2 A_j (kk = xx, yy)
+// and from the six channels of h on the stage is the plain one (tanh jets, W2, angle map).  These kernels stand behind
+// every other kernel of the code object; the plain stages keep their code.  m is a run-time value (1 .. QC_FF_MAX).
+namespace {
+
+constexpr int QC_FF_FB = 8;    // frequencies per block of the forward pass (a block's P, Q: two runs of eight scalar loads)
+constexpr int QC_FF_BB = 16;   // frequencies per block of the reverse pass (2 x 16 accumulators)
+constexpr float QC_2PI_F = 6.28318530717958647692f;
+
+struct QcFF {
+  const float* freq;   // [3][m], device
+  int m;
+};
+
+// sine and cosine of frequency j at a point.  r minus its nearest integer is exact in fp32, so the argument is at most half
+// a turn whatever the scale of B; sinpif / cospif reduce exactly as well and take no private array (the large-argument
+// path of sinf does), so these kernels stay without scratch.
+__device__ __forceinline__ void ff_trig(const float* __restrict__ fq, const int m, const int j, const float t, const float x,
+                                        const float y, float& s, float& c) {
+  float r = fmaf(fq[j], t, fmaf(fq[m + j], x, fq[2 * m + j] * y));
+  r -= rintf(r);
+  s = sinpif(2.f * r);
+  c = cospif(2.f * r);
+}
+
+// the table of the five factors a channel takes per frequency: w_t, w_x, w_y, w_x^2, w_y^2 as [5][mp], zero from m to mp
+__device__ __forceinline__ void ff_stage_omega(float* __restrict__ s_om, const QcFF& ff, const int mp) {
+  for (int i = threadIdx.x; i < 5 * mp; i += blockDim.x) {
+    const int k = i / mp, j = i - k * mp;
+    float w = 0.f;
+    if (j < ff.m) {
+      w = QC_2PI_F * ff.freq[(k < 3 ? k : k - 2) * ff.m + j];
+      if (k >= 3) w = w * w;
+    }
+    s_om[i] = w;
+  }
+}
+
+// Forward.  Block = 4 waves on one 64-point tile, lane = point, as k_pre_fwd_body (the same draw, the same Xout).  Wave w
+// forms s_j, c_j for j = w, w + 4, ... once per tile and parks them in LDS as [2][mp][64] (lane-contiguous rows); then each
+// wave walks its quarter of the hidden units over frequency blocks of QC_FF_FB.  The row of W1 is wave-uniform and
+// contiguous: P and Q of a block arrive as scalar loads.  The tail block reads on past m (still inside the flat vector:
+// at least seven entries follow W1 in every layout) and takes zero weights; the LDS rows from m to mp (m rounded up to a
+// block) hold zeros, so a block's rows sit at constant offsets from one base.
+// s_dyn: [2][mp][64] trig rows (sines, cosines), then the [5][mp] factor table; s_part: [QC_MS][NCH * N][64].
+template <int N, int NCH, int MAP, bool RF>
+__device__ __forceinline__ void k_pre_ff_fwd_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
+                                                  QcLayout L, float* __restrict__ ajets, int64_t B, const QcFF ff,
+                                                  float* __restrict__ s_dyn, float* __restrict__ s_part,
+                                                  const QcDraw* __restrict__ draw, float* __restrict__ Xout) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m = ff.m, mp = (m + QC_FF_FB - 1) & ~(QC_FF_FB - 1);
+  float* __restrict__ s_trig = s_dyn;
+  float* __restrict__ s_om = s_dyn + (size_t)2 * mp * 64;
+  const int64_t p = (int64_t)bid * 64 + lane;
+  const int64_t pc = p < B ? p : B - 1;
+  float t, x, y;
+  if (draw != nullptr && draw->enabled) {
+    if (NCH == 6) qc_draw_point(0, draw->off_res + pc, 0, draw->seed, draw->step, t, x, y);
+    else if (pc < draw->n_ic) qc_draw_point(1, draw->off_ic + pc, 0, draw->seed, draw->step, t, x, y);
+    else qc_draw_point<RF>(2, draw->off_bc + (pc - draw->n_ic), draw->face_pts, draw->seed, draw->step, t, x, y);
+    if (wave == 0 && p < B) {
+      Xout[p * 3 + 0] = t;
+      Xout[p * 3 + 1] = x;
+      Xout[p * 3 + 2] = y;
+    }
+  } else {
+    t = X[pc * 3 + 0];
+    x = X[pc * 3 + 1];
+    y = X[pc * 3 + 2];
+  }
+  ff_stage_omega(s_om, ff, mp);
+  for (int j = wave; j < mp; j += QC_MS) {
+    float s = 0.f, c = 0.f;
+    if (j < m) ff_trig(ff.freq, m, j, t, x, y, s, c);
+    s_trig[j * 64 + lane] = s;
+    s_trig[(mp + j) * 64 + lane] = c;
+  }
+  __syncthreads();
+  constexpr int NP2 = NCH == 6 ? 3 : 1;
+  mf2 acc2[NP2][N];
+#pragma unroll
+  for (int cp = 0; cp < NP2; ++cp)
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc2[cp][i] = (mf2){0.f, 0.f};
+  const float* __restrict__ W1 = prm + L.oW1;
+  const float* __restrict__ b1 = prm + L.ob1;
+  const float* __restrict__ W2 = prm + L.oW2;
+  const int hq = (L.H + QC_MS - 1) / QC_MS;
+  const int u0 = wave * hq, u1 = (u0 + hq) < L.H ? (u0 + hq) : L.H;
+  for (int u = u0; u < u1; ++u) {
+    const float* __restrict__ Pr = W1 + (size_t)u * 2 * m;
+    const float b1u = b1[u];
+    float w2u[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) w2u[i] = W2[i * L.H + u];
+    float h[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) h[c] = 0.f;
+    for (int jb = 0; jb < m; jb += QC_FF_FB) {
+      float P[QC_FF_FB], Q[QC_FF_FB];
+      const float* __restrict__ pp = Pr + jb;
+      const float* __restrict__ pq = Pr + m + jb;
+#pragma unroll
+      for (int i = 0; i < QC_FF_FB; ++i) P[i] = pp[i];
+#pragma unroll
+      for (int i = 0; i < QC_FF_FB; ++i) Q[i] = pq[i];
+      const float* __restrict__ ts = s_trig + jb * 64 + lane;
+      const float* __restrict__ tc = ts + mp * 64;
+      const float* __restrict__ om = s_om + jb;
+#pragma unroll
+      for (int i = 0; i < QC_FF_FB; ++i) {
+        const bool ok = jb + i < m;
+        const float pj = ok ? P[i] : 0.f, qj = ok ? Q[i] : 0.f;
+        const float s = ts[i * 64], c = tc[i * 64];
+        if constexpr (NCH == 6) {
+          const float A = fmaf(pj, s, qj * c), D = fmaf(pj, c, -(qj * s));
+          h[0] += A;
+          h[1] = fmaf(om[i], D, h[1]);
+          h[2] = fmaf(om[mp + i], D, h[2]);
+          h[3] = fmaf(om[2 * mp + i], D, h[3]);
+          h[4] = fmaf(-om[3 * mp + i], A, h[4]);
+          h[5] = fmaf(-om[4 * mp + i], A, h[5]);
+        } else {
+          h[0] = fmaf(pj, s, fmaf(qj, c, h[0]));
+        }
+      }
+    }
+    const float z = qc_tanh(h[0] + b1u);
+    if constexpr (NCH == 6) {
+      const float d1 = 1.f - z * z, d2 = -2.f * z * d1;
+      const mf2 zc2[3] = {(mf2){z, d1 * h[1]}, (mf2){d1 * h[2], d1 * h[3]},
+                          (mf2){fmaf(d2 * h[2], h[2], d1 * h[4]), fmaf(d2 * h[3], h[3], d1 * h[5])}};
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const mf2 wi = m_dup(w2u[i]);
+#pragma unroll
+        for (int cp = 0; cp < 3; ++cp) acc2[cp][i] = m_fma(wi, zc2[cp], acc2[cp][i]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) acc2[0][i].x = fmaf(w2u[i], z, acc2[0][i].x);
+    }
+  }
+  // from here the plain stage's epilogue: the four partial jets meet in LDS, b2, the optional angle map
+  constexpr int NF = NCH * N;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      s_part[(wave * NF + c * N + i) * 64 + lane] = (c & 1) ? acc2[c >> 1][i].y : acc2[c >> 1][i].x;
+  __syncthreads();
+  if (p < B) {
+    auto total = [&](const int f) {
+      return (s_part[f * 64 + lane] + s_part[(NF + f) * 64 + lane]) + (s_part[(2 * NF + f) * 64 + lane] + s_part[(3 * NF + f) * 64 + lane]);
+    };
+    if constexpr (MAP == 0) {
+      for (int f = wave; f < NF; f += QC_MS) {
+        float v = total(f);
+        if (f < N) v += prm[L.ob2 + f];
+        qc_store_wt(&ajets[(int64_t)f * B + p], v);
+      }
+    } else {
+      for (int i = wave; i < N; i += QC_MS) {
+        float v[NCH], a[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) v[c] = total(c * N + i);
+        v[0] += prm[L.ob2 + i];
+        angle_map_fwd<NCH>(v, a);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) qc_store_wt(&ajets[(int64_t)(c * N + i) * B + p], a[c]);
+      }
+    }
+  }
+}
+
+template <int N, int NCH, int MAP>
+__global__ void __launch_bounds__(256) k_pre_ff_fwd(const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
+                                                    float* __restrict__ ajets, int64_t B, QcFF ff) {
+  extern __shared__ float s_dyn[];
+  __shared__ float s_part[QC_MS * NCH * N * 64];
+  k_pre_ff_fwd_body<N, NCH, MAP, false>(blockIdx.x, X, prm, L, ajets, B, ff, s_dyn, s_part, nullptr, nullptr);
+}
+
+// merged launch: the value tiles first (one tile per block here as well: a tile's trig rows are shared by its four waves)
+template <int N, int MAP, bool RF>
+__global__ void __launch_bounds__(256) k_pre_ff_fwd_both(float* __restrict__ Xr, float* __restrict__ Xv,
+                                                         const float* __restrict__ prm, QcLayout L, float* __restrict__ ajr,
+                                                         float* __restrict__ ajv, int64_t Br, int64_t Bv, int n_val, QcDraw draw,
+                                                         QcFF ff) {
+  extern __shared__ float s_dyn[];
+  __shared__ float s_part[QC_MS * 6 * N * 64];
+  if ((int)blockIdx.x >= n_val) k_pre_ff_fwd_body<N, 6, MAP, RF>(blockIdx.x - n_val, Xr, prm, L, ajr, Br, ff, s_dyn, s_part, &draw, Xr);
+  else k_pre_ff_fwd_body<N, 1, MAP, RF>(blockIdx.x, Xv, prm, L, ajv, Bv, ff, s_dyn, s_part, &draw, Xv);
+}
+
+// Reverse.  Lane = hidden unit, PS groups of HB threads share the tile's 64 points (ff_geometry).  The tile's s, c rows are
+// formed once into LDS and read as broadcasts; pre-activations and tanh are recomputed.  dP, dQ are accumulated per block
+// of QC_FF_BB frequencies with the point loop inside the block, so m = 64 needs 32 live accumulators, not 128; every block
+// after the first recomputes the unit's six channels at each point (m <= 16: one block, nothing recomputed twice).
+// Group sums: qc_group_sums, ascending in the group; PS = 1 stores from registers.  Fixed order, no atomics.
+// s_dyn: [2][mp][64] trig rows (mp: m rounded up to QC_FF_BB; zeros from m on), [5][mp] factor table, s_acc [PS][2 QC_FF_BB][HB]
+// (PS > 1).
+template <int N, int NCH, int MAP>
+__device__ __forceinline__ void k_pre_ff_bwd_body(const int64_t bid, const float* __restrict__ X, const float* __restrict__ prm,
+                                                  QcLayout L, const float* __restrict__ abar, float* __restrict__ part,
+                                                  int64_t part_stride, int64_t row0, int64_t B, int HB, int PS,
+                                                  const float* __restrict__ aj, const QcFF ff, float* __restrict__ s_dyn,
+                                                  float* __restrict__ sX, mf2* __restrict__ sA2) {
+  constexpr int KA = 2 * QC_FF_BB;
+  static_assert(KA >= 1 + N, "the b1 / W2 sums pass through the same buffer");
+  const int m = ff.m, mp = (m + QC_FF_BB - 1) & ~(QC_FF_BB - 1);
+  float* __restrict__ s_trig = s_dyn;
+  float* __restrict__ s_om = s_dyn + (size_t)2 * mp * 64;
+  float* __restrict__ s_acc = s_om + 5 * mp;
+  const int64_t base = (int64_t)bid * 64;
+  const int cnt = (int)((B - base) < 64 ? (B - base) : 64);
+  for (int i = threadIdx.x; i < 64 * 3; i += blockDim.x) {
+    const int pp = i / 3, k = i % 3;
+    sX[k * 64 + pp] = pp < cnt ? X[(base + pp) * 3 + k] : 0.f;
+  }
+  if constexpr (MAP == 0) {
+    for (int i = threadIdx.x; i < NCH * N * 64; i += blockDim.x) {
+      const int f = i >> 6, pp = i & 63;      // f = c * N + wire
+      const int c = f / N, w = f % N;
+      const float v = pp < cnt ? abar[(int64_t)f * B + base + pp] : 0.f;
+      if (c & 1) sA2[((c >> 1) * N + w) * 64 + pp].y = v;
+      else sA2[((c >> 1) * N + w) * 64 + pp].x = v;
+    }
+  } else {
+    for (int i = threadIdx.x; i < N * 64; i += blockDim.x) {
+      const int w = i >> 6, pp = i & 63;
+      float ab[NCH], a[NCH], vb[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int64_t o = (int64_t)(c * N + w) * B + base + pp;
+        ab[c] = pp < cnt ? abar[o] : 0.f;
+        a[c] = pp < cnt ? aj[o] : 0.f;
+      }
+      angle_map_bwd<NCH>(ab, a, vb);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        if (c & 1) sA2[((c >> 1) * N + w) * 64 + pp].y = vb[c];
+        else sA2[((c >> 1) * N + w) * 64 + pp].x = vb[c];
+      }
+    }
+  }
+  ff_stage_omega(s_om, ff, mp);
+  __syncthreads();
+  for (int i = threadIdx.x; i < mp * 64; i += blockDim.x) {
+    const int j = i >> 6, pp = i & 63;
+    float s = 0.f, c = 0.f;
+    if (j < m) ff_trig(ff.freq, m, j, sX[pp], sX[64 + pp], sX[128 + pp], s, c);
+    s_trig[j * 64 + pp] = s;
+    s_trig[(mp + j) * 64 + pp] = c;
+  }
+  __syncthreads();
+
+  const int grp = threadIdx.x / HB, u = threadIdx.x % HB;
+  const bool active = grp < PS && u < L.H;
+  // a group walks `per` points from p0 on: a wave-uniform trip count (a wave may hold lanes of two groups).  Points from
+  // cnt to 63 were staged as zero cotangents and add exact zeros; a point index past 63 (PS does not divide 64) is skipped
+  const int per = (64 + PS - 1) / PS;
+  const int p0 = grp * per;
+  const int uc = u < L.H ? u : L.H - 1;       // (a thread without a hidden unit reads the last one's and stores nothing)
+  const float* __restrict__ Pr = prm + L.oW1 + (size_t)uc * 2 * m;
+  const float b1u = prm[L.ob1 + uc];
+  float w2c[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) w2c[i] = prm[L.oW2 + i * L.H + uc];
+  float gb1 = 0.f, gW2[N];   // (one register per wire, not a pair: the frequency block needs the rest)
+#pragma unroll
+  for (int i = 0; i < N; ++i) gW2[i] = 0.f;
+  float* row = part + (row0 + bid) * part_stride;
+
+  for (int f0 = 0; f0 < m; f0 += QC_FF_BB) {
+    float gP[QC_FF_BB], gQ[QC_FF_BB];
+#pragma unroll
+    for (int i = 0; i < QC_FF_BB; ++i) gP[i] = gQ[i] = 0.f;
+    {
+      for (int k = 0; k < per; ++k) {
+        const int pp = p0 + k;
+        if (pp >= 64) continue;
+        float h[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) h[c] = 0.f;
+#pragma unroll 1
+        for (int j = 0; j < m; ++j) {
+          const float pj = Pr[j], qj = Pr[m + j];
+          const float s = s_trig[j * 64 + pp], c = s_trig[(mp + j) * 64 + pp];
+          if constexpr (NCH == 6) {
+            const float A = fmaf(pj, s, qj * c), D = fmaf(pj, c, -(qj * s));
+            h[0] += A;
+            h[1] = fmaf(s_om[j], D, h[1]);
+            h[2] = fmaf(s_om[mp + j], D, h[2]);
+            h[3] = fmaf(s_om[2 * mp + j], D, h[3]);
+            h[4] = fmaf(-s_om[3 * mp + j], A, h[4]);
+            h[5] = fmaf(-s_om[4 * mp + j], A, h[5]);
+          } else {
+            h[0] = fmaf(pj, s, fmaf(qj, c, h[0]));
+          }
+        }
+        const float z = qc_tanh(h[0] + b1u);
+        const float d1 = 1.f - z * z;
+        float hb[NCH];
+        if constexpr (NCH == 6) {
+          const float d2 = -2.f * z * d1;
+          const float d3 = -2.f * (d1 * d1 + z * d2);
+          const mf2 zc2[3] = {(mf2){z, d1 * h[1]}, (mf2){d1 * h[2], d1 * h[3]},
+                              (mf2){fmaf(d2 * h[2], h[2], d1 * h[4]), fmaf(d2 * h[3], h[3], d1 * h[5])}};
+          mf2 zb2[3] = {(mf2){0.f, 0.f}, (mf2){0.f, 0.f}, (mf2){0.f, 0.f}};
+          // a cotangent pair is read once and used twice (never kept: 6 N registers the frequency block needs)
+#pragma unroll
+          for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int cp = 0; cp < 3; ++cp) {
+              const mf2 a2 = sA2[(cp * N + i) * 64 + pp];
+              zb2[cp] = m_fma(m_dup(w2c[i]), a2, zb2[cp]);
+              if (f0 == 0) gW2[i] = fmaf(a2.x, zc2[cp].x, fmaf(a2.y, zc2[cp].y, gW2[i]));
+            }
+          const float zb[6] = {zb2[0].x, zb2[0].y, zb2[1].x, zb2[1].y, zb2[2].x, zb2[2].y};
+          hb[0] = zb[0] * d1 + (zb[1] * h[1] + zb[2] * h[2] + zb[3] * h[3]) * d2 +
+                  zb[4] * (d3 * h[2] * h[2] + d2 * h[4]) + zb[5] * (d3 * h[3] * h[3] + d2 * h[5]);
+          hb[1] = zb[1] * d1;
+          hb[2] = zb[2] * d1 + 2.f * zb[4] * d2 * h[2];
+          hb[3] = zb[3] * d1 + 2.f * zb[5] * d2 * h[3];
+          hb[4] = zb[4] * d1;
+          hb[5] = zb[5] * d1;
+        } else {
+          float zb0 = 0.f;
+#pragma unroll
+          for (int i = 0; i < N; ++i) {
+            const float a = sA2[i * 64 + pp].x;
+            zb0 = fmaf(w2c[i], a, zb0);
+            if (f0 == 0) gW2[i] = fmaf(a, z, gW2[i]);
+          }
+          hb[0] = zb0 * d1;
+        }
+        if (f0 == 0) gb1 += hb[0];
+        const float* __restrict__ ts = s_trig + f0 * 64 + pp;
+        const float* __restrict__ tc = ts + mp * 64;
+        // the block's eighty factors do not depend on the point: read here they stay LDS broadcasts; hoisted out of the point
+        // loop they would be eighty registers, so the address passes through an empty asm at every point
+#if defined(__HIP_DEVICE_COMPILE__)
+        const __attribute__((address_space(3))) float* om = (const __attribute__((address_space(3))) float*)(s_om + f0);
+        asm volatile("" : "+v"(om));
+#else
+        const float* om = s_om + f0;
+#endif
+#pragma unroll
+        for (int i = 0; i < QC_FF_BB; ++i) {
+          const float s = ts[i * 64], c = tc[i * 64];
+          if constexpr (NCH == 6) {
+            const float al = fmaf(-om[4 * mp + i], hb[5], fmaf(-om[3 * mp + i], hb[4], hb[0]));
+            const float be = fmaf(om[2 * mp + i], hb[3], fmaf(om[mp + i], hb[2], om[i] * hb[1]));
+            gP[i] += fmaf(s, al, c * be);
+            gQ[i] += fmaf(c, al, -(s * be));
+          } else {
+            gP[i] = fmaf(s, hb[0], gP[i]);
+            gQ[i] = fmaf(c, hb[0], gQ[i]);
+          }
+        }
+      }
+    }
+    if (PS == 1) {
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < QC_FF_BB; ++i)
+          if (f0 + i < m) {
+            row[L.oW1 + (size_t)u * 2 * m + f0 + i] = gP[i];
+            row[L.oW1 + (size_t)u * 2 * m + m + f0 + i] = gQ[i];
+          }
+      }
+    } else {
+      __syncthreads();   // the previous block's sums have been read
+      if (grp < PS) {
+        float* mine = s_acc + (size_t)grp * KA * HB;
+#pragma unroll
+        for (int i = 0; i < QC_FF_BB; ++i) {
+          mine[i * HB + u] = gP[i];
+          mine[(QC_FF_BB + i) * HB + u] = gQ[i];
+        }
+      }
+      __syncthreads();
+      if (grp == 0 && u < L.H) {
+        float tot[KA];
+        qc_group_sums<KA>(s_acc, PS, HB, u, tot);
+#pragma unroll
+        for (int i = 0; i < QC_FF_BB; ++i)
+          if (f0 + i < m) {
+            row[L.oW1 + (size_t)u * 2 * m + f0 + i] = tot[i];
+            row[L.oW1 + (size_t)u * 2 * m + m + f0 + i] = tot[QC_FF_BB + i];
+          }
+      }
+    }
+  }
+  // b1 and W2: one more pass through the buffer (its first 1 + N rows of each group, stride KA as before)
+  if (PS == 1) {
+    if (active) {
+      row[L.ob1 + u] = gb1;
+#pragma unroll
+      for (int i = 0; i < N; ++i) row[L.oW2 + i * L.H + u] = gW2[i];
+    }
+  } else {
+    __syncthreads();
+    if (grp < PS) {
+      float* mine = s_acc + (size_t)grp * KA * HB;
+      mine[u] = gb1;
+#pragma unroll
+      for (int i = 0; i < N; ++i) mine[(1 + i) * HB + u] = gW2[i];
+    }
+    __syncthreads();
+    if (grp == 0 && u < L.H) {
+      float tb = 0.f, tw[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) tw[i] = 0.f;
+      for (int g = 0; g < PS; ++g) {
+        const float* his = s_acc + (size_t)g * KA * HB;
+        tb += his[u];
+#pragma unroll
+        for (int i = 0; i < N; ++i) tw[i] += his[(1 + i) * HB + u];
+      }
+      row[L.ob1 + u] = tb;
+#pragma unroll
+      for (int i = 0; i < N; ++i) row[L.oW2 + i * L.H + u] = tw[i];
+    }
+  }
+  if (threadIdx.x < N) {  // b2 only feeds the value channel
+    float sum = 0.f;
+    for (int pp = 0; pp < cnt; ++pp) sum += sA2[threadIdx.x * 64 + pp].x;
+    row[L.ob2 + threadIdx.x] = sum;
+  }
+}
+
+template <int N, int NCH, int MAP>
+__global__ void k_pre_ff_bwd(const float* __restrict__ X, const float* __restrict__ prm, QcLayout L,
+                             const float* __restrict__ abar, float* __restrict__ part, int64_t part_stride, int64_t row0,
+                             int64_t B, int HB, int PS, const float* __restrict__ aj, QcFF ff) {
+  extern __shared__ float s_dyn[];
+  __shared__ float sX[3 * 64];
+  __shared__ mf2 sA2[(NCH == 6 ? 3 : 1) * N * 64];
+  k_pre_ff_bwd_body<N, NCH, MAP>(blockIdx.x, X, prm, L, abar, part, part_stride, row0, B, HB, PS, aj, ff, s_dyn, sX, sA2);
+}
+
+template <int N, int MAP>
+__global__ void k_pre_ff_bwd_both(const float* __restrict__ Xr, const float* __restrict__ Xv, const float* __restrict__ prm,
+                                  QcLayout L, const float* __restrict__ abr, const float* __restrict__ abv,
+                                  float* __restrict__ part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br,
+                                  int64_t Bv, int HB, int PS, int n_val, const float* __restrict__ ajr,
+                                  const float* __restrict__ ajv, QcFF ff) {
+  extern __shared__ float s_dyn[];
+  __shared__ float sX[3 * 64];
+  __shared__ mf2 sA2[3 * N * 64];
+  if ((int)blockIdx.x >= n_val)
+    k_pre_ff_bwd_body<N, 6, MAP>(blockIdx.x - n_val, Xr, prm, L, abr, part, part_stride, row0_r, Br, HB, PS, ajr, ff, s_dyn, sX, sA2);
+  else
+    k_pre_ff_bwd_body<N, 1, MAP>(blockIdx.x, Xv, prm, L, abv, part, part_stride, row0_v, Bv, HB, PS, ajv, ff, s_dyn, sX, sA2);
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ launchers of the Fourier-feature stages
+static inline size_t ff_fwd_lds(const int m) {
+  return (size_t)(2 * 64 + 5) * ((m + QC_FF_FB - 1) & ~(QC_FF_FB - 1)) * sizeof(float);
+}
+// the plain stage's geometry, with as many groups as keep the [PS][2 QC_FF_BB][HB] sums within 64 KB (PS HB <= 512); one
+// group stores from registers and keeps no sums
+static inline void ff_geometry(int H, int* HB, int* PS, int* threads) {
+  hidden_geometry(H, HB, PS, threads);
+  while (*PS > 1 && *HB * *PS > 512) *PS /= 2;
+  *threads = 64 * qc_ceil_div(*HB * *PS, 64);
+}
+static inline size_t ff_bwd_lds(const int m, const int HB, const int PS) {
+  const size_t acc = PS > 1 ? (size_t)PS * 2 * QC_FF_BB * HB : 0;
+  return ((size_t)(2 * 64 + 5) * ((m + QC_FF_BB - 1) & ~(QC_FF_BB - 1)) + acc) * sizeof(float);
+}
+
+int qc_mlp_pre_ff_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, int nch, hipStream_t st, int map,
+                      const float* freq, int m) {
+  const int grid = qc_ceil_div(B, 64);
+  const QcFF ff = {freq, m};
+  const size_t sh = ff_fwd_lds(m);
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c, auto mp) {
+      hipLaunchKernelGGL((k_pre_ff_fwd<n(), c(), mp()>), dim3(grid), dim3(256), sh, st, X, prm, L, ajets, B, ff);
+    };
+    if (map) { if (nch == 6) launch(qc_int<6>{}, qc_int<1>{}); else launch(qc_int<1>{}, qc_int<1>{}); }
+    else if (nch == 6) launch(qc_int<6>{}, qc_int<0>{});
+    else launch(qc_int<1>{}, qc_int<0>{});
+  });
+}
+
+int qc_mlp_pre_ff_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part, int64_t part_stride,
+                      int64_t row0, int64_t B, int nch, hipStream_t st, int map, const float* aj, const float* freq, int m) {
+  const int grid = qc_ceil_div(B, 64);
+  if (L.H > 1024 || L.n > 64) return QC_ERR_UNSUPPORTED;
+  int HB, PS, threads;
+  ff_geometry(L.H, &HB, &PS, &threads);
+  const QcFF ff = {freq, m};
+  const size_t sh = ff_bwd_lds(m, HB, PS);
+  return qc_dispatch_n<1, QC_MLP_NMAX>(L.n, [&](auto n) {
+    auto launch = [&](auto c, auto mp) {
+      hipLaunchKernelGGL((k_pre_ff_bwd<n(), c(), mp()>), dim3(grid), dim3(threads), sh, st, X, prm, L, abar, part, part_stride,
+                         row0, B, HB, PS, aj, ff);
+    };
+    if (map) { if (nch == 6) launch(qc_int<6>{}, qc_int<1>{}); else launch(qc_int<1>{}, qc_int<1>{}); }
+    else if (nch == 6) launch(qc_int<6>{}, qc_int<0>{});
+    else launch(qc_int<1>{}, qc_int<0>{});
+  });
+}
+
+int qc_mlp_pre_ff_fwd_both(const QcBatches& b, int draw, int64_t face_pts, const float* prm, QcLayout L, float* ajr, float* ajv,
+                           hipStream_t st, int map, const float* freq, int m) {
+  float *Xr = b.X_res, *Xv = b.X_val;
+  const int64_t Br = b.n_res, Bv = b.n_ic + b.n_bc;
+  const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
+  const QcDraw dr = {draw, b.n_ic, b.off_res, b.off_ic, b.off_bc, face_pts, b.seed, b.step};
+  const bool rf = draw && face_pts < 0;
+  const QcFF ff = {freq, m};
+  const size_t sh = ff_fwd_lds(m);
+  // the merged form exists for the register family only (n = 2 .. 5)
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    auto launch = [&](auto mp, auto r) {
+      hipLaunchKernelGGL((k_pre_ff_fwd_both<n(), mp(), r()>), dim3(nr + nv), dim3(256), sh, st, Xr, Xv, prm, L, ajr, ajv, Br, Bv,
+                         nv, dr, ff);
+    };
+    if (map) { if (rf) launch(qc_int<1>{}, std::true_type{}); else launch(qc_int<1>{}, std::false_type{}); }
+    else if (rf) launch(qc_int<0>{}, std::true_type{});
+    else launch(qc_int<0>{}, std::false_type{});
+  });
+}
+
+int qc_mlp_pre_ff_bwd_both(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
+                           float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv,
+                           hipStream_t st, int map, const float* ajr, const float* ajv, const float* freq, int m) {
+  if (L.H > 1024 || L.n > 64) return QC_ERR_UNSUPPORTED;
+  const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
+  int HB, PS, threads;
+  ff_geometry(L.H, &HB, &PS, &threads);
+  const QcFF ff = {freq, m};
+  const size_t sh = ff_bwd_lds(m, HB, PS);
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    auto launch = [&](auto mp) {
+      hipLaunchKernelGGL((k_pre_ff_bwd_both<n(), mp()>), dim3(nr + nv), dim3(threads), sh, st, Xr, Xv, prm, L, abr, abv, part,
+                         part_stride, row0_r, row0_v, Br, Bv, HB, PS, nv, ajr, ajv, ff);
+    };
+    if (map) launch(qc_int<1>{}); else launch(qc_int<0>{});
+  });
+}

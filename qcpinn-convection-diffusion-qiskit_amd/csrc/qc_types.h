@@ -51,4 +51,6 @@ struct qc_program {
   int* d_diag_list;                                           // ranges of this device list of gate indices
   const QcFamily* fam;  // the kernel family that runs this program (qc_internal.h), or null (n > 20: unsupported)
   int angle_map;        // output map of the pre network that feeds this circuit in the fused step (QC_ANGLE_MAP_*)
+  int ff_m;             // Fourier-feature input map of that pre network: frequencies (0: none) and the library's device
+  float* d_ff_freq;     // copy of B, [3][ff_m] (qc_program_set_input_map)
 };

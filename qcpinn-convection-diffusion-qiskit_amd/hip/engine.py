@@ -30,11 +30,12 @@ def _need(t: torch.Tensor, device, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def param_layout(H: int, n: int, n_theta: int, K: int = 1) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
+def param_layout(H: int, n: int, n_theta: int, K: int = 1, n_in: int = 3) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
     """Offsets/shapes of the flat parameter vector = the reference's ``model.parameters()`` order
-    (nn/DVPDESolver.py:28-57: preprocessor, postprocessor, quantum_layer); ``K`` outputs: K rows in the last layer."""
+    (nn/DVPDESolver.py:28-57: preprocessor, postprocessor, quantum_layer); ``K`` outputs: K rows in the last layer;
+    ``n_in`` columns of the first layer: 3, or 2 m behind a Fourier-feature map of m frequencies (sines, then cosines)."""
     out, off = {}, 0
-    for name, shape in (("preprocessor.0.weight", (H, 3)), ("preprocessor.0.bias", (H,)),
+    for name, shape in (("preprocessor.0.weight", (H, n_in)), ("preprocessor.0.bias", (H,)),
                         ("preprocessor.2.weight", (n, H)), ("preprocessor.2.bias", (n,)),
                         ("postprocessor.0.weight", (H, n)), ("postprocessor.0.bias", (H,)),
                         ("postprocessor.2.weight", (K, H)), ("postprocessor.2.bias", (K,)),
@@ -85,6 +86,7 @@ class Circuit:
         self.angle_map = int(angle_map)
         if self.angle_map != L.QC_ANGLE_MAP_NONE:
             L.check(self.lib.qc_program_set_angle_map(self.handle, self.angle_map), "qc_program_set_angle_map")
+        self.ff_m, self.ff_freq = 0, None      # Fourier-feature input map of the pre network (set_input_map)
         self.trig = torch.zeros(int(self.lib.qc_trig_bytes(self.handle)) // 4, dtype=torch.float32, device=device)
         self.umat = None
         if program.use_haar:
@@ -94,6 +96,27 @@ class Circuit:
             both = np.stack([u, np.conj(np.transpose(u, (0, 2, 1)))], axis=1)  # [slot][fwd|adj][4][4]
             packed = np.stack([both.real, both.imag], axis=-1).astype(np.float32)
             self.umat = torch.from_numpy(np.ascontiguousarray(packed)).to(device)
+
+    @property
+    def n_in(self) -> int:
+        """Columns of the first layer of the pre network in front of this circuit: 2 m behind an input map, else 3."""
+        return 2 * self.ff_m if self.ff_m else 3
+
+    def set_input_map(self, freq) -> None:
+        """The Fourier-feature input map gamma(X) = [sin(2 pi X B), cos(2 pi X B)] of the pre network in front of this
+        circuit: ``freq`` = B, (3, m) with 1 <= m <= ``QC_FF_MAX`` (rows t, x, y), or None to remove it.  The fused step
+        reads it from the program; the separate entry points take the device copy kept here (``ff_freq``)."""
+        if freq is None:
+            L.check(self.lib.qc_program_set_input_map(self.handle, None, 0), "qc_program_set_input_map")
+            self.ff_m, self.ff_freq = 0, None
+            return
+        B = np.ascontiguousarray(torch.as_tensor(freq).detach().cpu().numpy(), dtype=np.float32)
+        if B.ndim != 2 or B.shape[0] != 3 or not 1 <= B.shape[1] <= L.QC_FF_MAX:
+            raise ValueError(f"the frequency matrix must be (3, m) with 1 <= m <= {L.QC_FF_MAX}, got {B.shape}")
+        with torch.cuda.device(self.device):
+            L.check(self.lib.qc_program_set_input_map(self.handle, B.ctypes.data_as(C.c_void_p), B.shape[1]),
+                    "qc_program_set_input_map")
+        self.ff_m, self.ff_freq = int(B.shape[1]), torch.from_numpy(B).to(self.device)
 
     def __del__(self):
         try:
@@ -215,7 +238,11 @@ class SolverEngine:
         self.H = int(hidden)
         check_network_shape(self.H, self.n)
         self.n_theta = circuit.n_params
-        self.layout = param_layout(self.H, self.n, self.n_theta)
+        # behind an input map the first layer is [H][2m]; the post stage addresses nothing in front of W3, so qc_post* take
+        # the flat vector and the gradient rows from `post_shift` entries further on and see their own [H][3] offsets
+        self.ff_m = circuit.ff_m
+        self.layout = param_layout(self.H, self.n, self.n_theta, n_in=circuit.n_in)
+        self.post_shift = (circuit.n_in - 3) * self.H
         self.NP = self.layout["__total__"][0]
         self.theta_off = self.layout["quantum_layer.params"][0]
         if flat_params.numel() != self.NP:
@@ -243,11 +270,27 @@ class SolverEngine:
     def refresh_gates(self) -> None:
         self.circuit.prepare(self.flat[self.theta_off: self.theta_off + self.n_theta])
 
+    def _post_flat(self) -> int:
+        return self.flat.data_ptr() + 4 * self.post_shift
+
     def _pre_forward(self, X, ajets, B, nch, st) -> None:
+        c = self.circuit
+        if c.ff_m != self.ff_m:
+            raise L.QcError("the circuit's input map changed size after this engine was built")
+        if c.ff_m:
+            L.check(self.lib.qc_pre_forward_ff(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, self.angle_map,
+                                               c.ff_freq.data_ptr(), c.ff_m, ajets.data_ptr(), B, nch, st), "qc_pre_forward_ff")
+            return
         L.check(self.lib.qc_pre_forward_map(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, self.angle_map,
                                             ajets.data_ptr(), B, nch, st), "qc_pre_forward_map")
 
     def _pre_backward(self, X, ajets, abar, part, B, nch, st) -> None:
+        c = self.circuit
+        if c.ff_m:
+            L.check(self.lib.qc_pre_backward_ff(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, self.angle_map,
+                                                c.ff_freq.data_ptr(), c.ff_m, ajets.data_ptr(), abar.data_ptr(),
+                                                part.data_ptr(), self.NP, 0, B, nch, st), "qc_pre_backward_ff")
+            return
         L.check(self.lib.qc_pre_backward_map(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
                                              self.angle_map, ajets.data_ptr(), abar.data_ptr(), part.data_ptr(), self.NP, 0,
                                              B, nch, st), "qc_pre_backward_map")
@@ -276,13 +319,13 @@ class SolverEngine:
         pde = self._pde()
         if ujets:      # all six derivative channels of u (qc_post mode 4) instead of (u, residual)
             uj = torch.empty(NCH, B, dtype=torch.float32, device=self.device)
-            L.check(self.lib.qc_post(4, X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
+            L.check(self.lib.qc_post(4, X.data_ptr(), self._post_flat(), self.H, self.n, self.n_theta,
                                      C.byref(pde), qjets.data_ptr(), uj.data_ptr(), None, None, None, None, None,
                                      0, 0, B, nch, st), "qc_post(forward, six channels)")
             return uj, None, ajets, qjets
         u = torch.empty(B, 1, dtype=torch.float32, device=self.device)
         res = torch.empty(B, 1, dtype=torch.float32, device=self.device) if nch == NCH else None
-        L.check(self.lib.qc_post(0, X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
+        L.check(self.lib.qc_post(0, X.data_ptr(), self._post_flat(), self.H, self.n, self.n_theta,
                                  C.byref(pde), qjets.data_ptr(), u.data_ptr(), _ptr(res), None, None, None, None,
                                  0, 0, B, nch, st), "qc_post(forward)")
         return u, res, ajets, qjets
@@ -302,9 +345,9 @@ class SolverEngine:
         rb = None if (rbar is None or ujets) else _need(rbar.reshape(-1), self.device, "rbar")
         if ujets and (ub is None or ub.numel() != NCH * B or nch != NCH):
             raise L.QcError("the six-channel cotangent must be a [6, B] tensor")
-        L.check(self.lib.qc_post(3 if ujets else 1, X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta,
+        L.check(self.lib.qc_post(3 if ujets else 1, X.data_ptr(), self._post_flat(), self.H, self.n, self.n_theta,
                                  C.byref(pde), qjets.data_ptr(), None, None, _ptr(ub), _ptr(rb), qbar.data_ptr(),
-                                 part.data_ptr(), self.NP, 0, B, nch, st), "qc_post(backward)")
+                                 part.data_ptr() + 4 * self.post_shift, self.NP, 0, B, nch, st), "qc_post(backward)")
         abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, nch)
         self._pre_backward(X, ajets, abar, part, B, nch, st)
         d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
@@ -326,7 +369,7 @@ class SolverEngine:
         self._pre_forward(X, ajets, B, NCH, st)
         qjets = self.circuit.forward_jets(ajets)
         uj = torch.empty(K, NCH, B, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_post_multi(4, self.flat.data_ptr(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
+        L.check(self.lib.qc_post_multi(4, self._post_flat(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
                                        qjets.data_ptr(), uj.data_ptr(), None, None, None, 0, None, 0, 0, B, st),
                 "qc_post_multi(forward)")
         return uj, ajets, qjets
@@ -346,8 +389,9 @@ class SolverEngine:
         if ub.numel() != K * NCH * B:
             raise L.QcError("the cotangent must be a [K, 6, B] tensor")
         w4k = _need(w4k, self.device, "last-layer rows")
-        L.check(self.lib.qc_post_multi(3, self.flat.data_ptr(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
-                                       qjets.data_ptr(), None, ub.data_ptr(), qbar.data_ptr(), part.data_ptr(), self.NP,
+        L.check(self.lib.qc_post_multi(3, self._post_flat(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
+                                       qjets.data_ptr(), None, ub.data_ptr(), qbar.data_ptr(),
+                                       part.data_ptr() + 4 * self.post_shift, self.NP,
                                        partk.data_ptr(), KW, 0, B, st), "qc_post_multi(backward)")
         abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, NCH)
         self._pre_backward(X, ajets, abar, part, B, NCH, st)
@@ -360,7 +404,7 @@ class SolverEngine:
     # ------------------------------------------------------------------ fused training step
     def fused(self, B_res: int, n_ic: int, n_bc: int, opt: "OptimState", counts=None) -> "FusedStep":
         key = (B_res, n_ic, n_bc, id(opt), counts, self.problem, self.D, self.vx, self.vy, self.sigma, self.coeffs,
-               self.loss_weights, self.c_u, self.coef_mode)
+               self.loss_weights, self.c_u, self.coef_mode, self.ff_m)
         if key not in self._fused:
             self._fused[key] = FusedStep(self, B_res, n_ic, n_bc, opt, counts)
         return self._fused[key]
@@ -491,7 +535,7 @@ class _Step:
         dev, n = circuit.device, circuit.n
         self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
         check_network_shape(self.H, n)
-        self.layout = param_layout(self.H, n, self.n_theta, K)
+        self.layout = param_layout(self.H, n, self.n_theta, K, n_in=circuit.n_in)     # the step reads the map from the program
         self.NP = self.layout["__total__"][0]
         self.theta_off = self.layout["quantum_layer.params"][0]
         NP_total = self.NP + self.N_OWN
@@ -742,6 +786,8 @@ class SystemStep(_Step):
     def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, system: "L.QcStepSystem", B_res: int, n_ic: int,
                  n_bc: int, opt: OptimState, counts=None, loss_weights=(2.0, 4.0, 2.0), res_targets: bool = True):
         self.K, self.n_eq = int(system.K), int(system.n_eq)
+        if circuit.ff_m:
+            raise ValueError("the system step does not serve a pre network behind a Fourier-feature input map")
         if not (1 <= self.K <= L.QC_KMAX and 1 <= self.n_eq <= L.QC_EQMAX):
             raise L.QcError(f"a system has 1..{L.QC_KMAX} outputs and 1..{L.QC_EQMAX} equations, got {self.K} and {self.n_eq}")
         # the operator coefficients and the problem id of the record are not read

@@ -37,6 +37,7 @@ EXPORTS = (
     "qc_post_balance", "qc_balance_adam_step", "qc_fused_pinn_balanced_step",
     "qc_causal_init", "qc_sample_dataset_slabs", "qc_causal_fold", "qc_fused_pinn_causal_step",
     "qc_gradnorm_init", "qc_gradnorm_fold", "qc_fused_pinn_gradnorm_step",
+    "qc_program_set_input_map", "qc_pre_forward_ff", "qc_pre_backward_ff",
 )
 
 
@@ -52,6 +53,7 @@ QC_ADAPT_BLOCK = 1024           # rows per entry of the coarse table of an adapt
 QC_ADAPT_FLOOR_MAX = 256.0      # largest floor_c qc_adapt_build accepts
 QC_KMAX, QC_EQMAX, QC_TERMS_MAX = 4, 4, 32            # outputs, equations and terms of a system (qc_step_system)
 QC_ANGLE_MAP_NONE, QC_ANGLE_MAP_TANH_PI = 0, 1       # output map of the pre network (qc_program_set_angle_map)
+QC_FF_MAX = 64                                       # most frequencies of an input map (qc_program_set_input_map)
 QC_BC_RANDOM_FACE = -1                               # sample_bc_face_points: a random face per boundary point
 QC_LBFGS_MAX_HISTORY = 32                            # most curvature pairs of an L-BFGS workspace (qc_lbfgs_init)
 QC_LBFGS_FIXED, QC_LBFGS_ARMIJO = 0, 1               # qc_lbfgs_hyper.line_search
@@ -231,6 +233,9 @@ def load() -> C.CDLL:
     lib.qc_pre_forward_map.argtypes = [fp, fp, i32, i32, i32, i32, fp, i64, i32, vp]
     lib.qc_pre_backward_map.argtypes = [fp, fp, i32, i32, i32, i32, fp, fp, fp, i64, i64, i64, i32, vp]
     lib.qc_program_set_angle_map.argtypes = [vp, i32]
+    lib.qc_program_set_input_map.argtypes = [vp, fp, i32]
+    lib.qc_pre_forward_ff.argtypes = [fp, fp, i32, i32, i32, i32, fp, i32, fp, i64, i32, vp]
+    lib.qc_pre_backward_ff.argtypes = [fp, fp, i32, i32, i32, i32, fp, i32, fp, fp, fp, i64, i64, i64, i32, vp]
     lib.qc_post.argtypes = [i32, fp, fp, i32, i32, i32, C.POINTER(QcPde), fp, fp, fp, fp, fp, fp, fp, i64, i64,
                             i64, i32, vp]
     lib.qc_post_multi.argtypes = [i32, fp, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, i64, fp, i64, i64, i64, vp]

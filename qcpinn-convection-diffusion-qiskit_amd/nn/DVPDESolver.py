@@ -16,8 +16,9 @@ import torch
 import torch.nn as nn
 
 from ..hip import engine as _engine
-from ..hip.lib import QcError
+from ..hip.lib import QC_FF_MAX, QcError
 from .DVQuantumLayer import DVQuantumLayer
+from .fourier import FourierFeatures
 
 
 def _flat_param_list(model):
@@ -192,8 +193,23 @@ class DVPDESolver(nn.Module):
         hidden = self.classic_network[-2]
         _engine.check_network_shape(hidden, self.num_qubits)
 
+        # args["fourier_features"] = m > 0: the random Fourier feature map gamma(X) = [sin(2 pi X B), cos(2 pi X B)] in front
+        # of the preprocessor, whose first layer is then Linear(2m, H); created before it, as the reference's models do
+        # (hybrid_testing/modified_qpinn_cg.py:89-95).  The kernels' coordinate slots are (t, x, y): a two-input model keeps
+        # in_dim = 3 with a zero t row, its two inputs in the x and y slots (see _pad_inputs).  Absent or 0: no map, and
+        # nothing here draws a random number, so the parameters under a seed are those of the model without the key.
+        self.n_fourier = int(self.args.get("fourier_features", 0) or 0)
+        if not 0 <= self.n_fourier <= QC_FF_MAX:
+            raise ValueError(f"fourier_features must lie in 0 .. {QC_FF_MAX}, got {self.n_fourier}")
+        self.fourier = None
+        if self.n_fourier:
+            self.fourier = FourierFeatures(3, self.n_fourier, float(self.args.get("fourier_scale", 1.0)))
+            if self.input_dim == 2:
+                self.fourier.B[0].zero_()
+        first_in = 2 * self.n_fourier if self.n_fourier else self.classic_network[0]
+
         # same construction order as the reference => same RNG consumption (nn/DVPDESolver.py:28-57)
-        self.preprocessor = nn.Sequential(nn.Linear(self.classic_network[0], hidden), nn.Tanh(),
+        self.preprocessor = nn.Sequential(nn.Linear(first_in, hidden), nn.Tanh(),
                                           nn.Linear(hidden, self.num_qubits))
         self.postprocessor = nn.Sequential(nn.Linear(self.num_qubits, hidden), nn.Tanh(),
                                            nn.Linear(hidden, self.classic_network[-1]))
@@ -246,7 +262,7 @@ class DVPDESolver(nn.Module):
         the two inputs ride in the x and y slots, the ones with second derivatives)."""
         out = []
         for p in _flat_param_list(self):
-            pad = self.input_dim == 2 and p is self.preprocessor[0].weight
+            pad = self.input_dim == 2 and not self.n_fourier and p is self.preprocessor[0].weight
             out.append((p, p.shape[0] * 3 if pad else p.numel(), pad))
         return out
 
@@ -295,10 +311,12 @@ class DVPDESolver(nn.Module):
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         key = device.index
+        circ = self._circuit(device)
+        if key in self._jet_engines and self._jet_engines[key].ff_m != circ.ff_m:
+            del self._jet_engines[key]
         if key not in self._jet_engines:
-            circ = self.quantum_layer._circuit_for(device)
             H, n = self.hidden_width, self.num_qubits
-            NP = 3 * H + H + n * H + n + H * n + H + H + 1 + circ.n_params
+            NP = circ.n_in * H + H + n * H + n + H * n + H + H + 1 + circ.n_params
             self._jet_engines[key] = _engine.SolverEngine(circ, H, torch.zeros(NP, dtype=torch.float32, device=device))
         return self._jet_engines[key]
 
@@ -308,7 +326,7 @@ class DVPDESolver(nn.Module):
         pre0, pre2 = self.preprocessor[0], self.preprocessor[2]
         post0, post2 = self.postprocessor[0], self.postprocessor[2]
         W1 = pre0.weight
-        if self.input_dim == 2:
+        if self.input_dim == 2 and not self.n_fourier:
             W1 = torch.cat([torch.zeros_like(W1[:, :1]), W1], dim=1)
         parts = [W1.reshape(-1), pre0.bias, pre2.weight.reshape(-1), pre2.bias, post0.weight.reshape(-1), post0.bias,
                  post2.weight[out], post2.bias[out:out + 1]]
@@ -352,10 +370,25 @@ class DVPDESolver(nn.Module):
         if not self._packed_ok() or self._flat.device != device:
             self._pack(device)           # e.g. after model.to(...), load_state_dict into new tensors
         key = device.index
+        circ = self._circuit(device)
         if key not in self._engines:
-            circ = self.quantum_layer._circuit_for(device)
             self._engines[key] = _engine.SolverEngine(circ, self.hidden_width, self._flat)
         return self._engines[key]
+
+    def _circuit(self, device) -> "_engine.Circuit":
+        """The quantum layer's circuit on ``device`` with this model's input map handed to its program; the map is handed
+        over again whenever the buffer ``fourier.B`` has been replaced or written (``load_state_dict``, ``.to``)."""
+        circ = self.quantum_layer._circuit_for(device)
+        if self.fourier is None:
+            if circ.ff_m:
+                circ.set_input_map(None)
+            return circ
+        B = self.fourier.B
+        stamp = (B.data_ptr(), B._version)
+        if getattr(circ, "_ff_stamp", None) != stamp:
+            circ.set_input_map(B)
+            circ._ff_stamp = stamp
+        return circ
 
     def _split_flat(self, d_flat):
         out, off = [], 0
@@ -441,6 +474,7 @@ class DVPDESolver(nn.Module):
             "preprocessor": self.preprocessor.state_dict(),
             "quantum_layer": self.quantum_layer.state_dict(),
             "postprocessor": self.postprocessor.state_dict(),
+            **({"fourier": self.fourier.state_dict()} if self.fourier is not None else {}),
             "optimizer": self.optimizer.state_dict(),
             "scheduler": self.scheduler.state_dict(),
             "loss_history": self.loss_history,

@@ -67,7 +67,7 @@ class InverseTrainer:
         self.max_norm = max_norm
         self.loss_weights = tuple(float(w) for w in loss_weights)
         self._pack()
-        self.circuit = model.quantum_layer._circuit_for(dev)
+        self.circuit = model._circuit(dev)
         self.optimizer, self.scheduler = model.optimizer, model.scheduler
         self.attach(model, operator)
         self.opt = self._make_opt_state(int(capacity))

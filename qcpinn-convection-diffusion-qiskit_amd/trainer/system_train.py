@@ -49,7 +49,7 @@ class SystemTrainer:
         if not model._packed_ok() or model._flat.device != dev:
             model._pack(dev)             # one flat buffer in model.parameters() order, parameters re-pointed at views
         self.flat = model._flat
-        self.circuit = model.quantum_layer._circuit_for(dev)
+        self.circuit = model._circuit(dev)
         self.NP = self.flat.numel()
         self.optimizer, self.scheduler = model.optimizer, model.scheduler
         self.opt = self._make_opt_state(int(capacity))
