@@ -38,7 +38,12 @@ int qc_last_hip_error(void); /* hipError_t of the last failing runtime call, 0 i
  * (reference nn/DVQuantumLayer.py:176-214 and the builders :246-371).
  * gate_rows: host int32 [n_gates][4] = (opcode, wire_a, wire_b, slot); opcodes
  * RX=0 RY=1 RZ=2 H=3 CNOT=4 CRX=5 CRZ=6 U4=7 (fixed two-wire unitary, slot 0 on wires [0,1],
- * slot 1 on wires [2,3]).  The embedding RX(x_i) is implicit. */
+ * slot 1 on wires [2,3]).  The embedding RX(x_i) is implicit.
+ * EMBED=8 (wire_a = wire, wire_b = -1, slot = -1): data re-uploading, RX(x_wire) of the SAME per-point angle (and angle
+ * jet) at this position of the program.  A program that holds one is served for 2 <= n_qubits <= 5 by its own kernel
+ * family (run-time interpreter, angle encoding, nothing kept between the forward and the adjoint pass, the fused step in
+ * its two-stream form); for any other n_qubits the program is created but every circuit and step entry point returns
+ * QC_ERR_UNSUPPORTED, and so does qc_program_set_encoding(prog, 1). */
 int qc_program_create(const int32_t* gate_rows, int n_gates, int n_qubits, int n_params, qc_program** out);
 int qc_program_destroy(qc_program* prog);
 size_t qc_trig_bytes(const qc_program* prog); /* size of the per-gate cos/sin workspace */

@@ -23,7 +23,10 @@ import numpy as np
 
 # opcodes -- must match csrc/qc_gates.h
 OP_RX, OP_RY, OP_RZ, OP_H, OP_CNOT, OP_CRX, OP_CRZ, OP_U4 = range(8)
-OP_NAMES = ("RX", "RY", "RZ", "H", "CNOT", "CRX", "CRZ", "U4")
+# data re-uploading: RX(a_w(X)) on wire ``a`` at this position of the program, a_w the same per-point angle (and angle
+# jet) that the implicit initial embedding uses.  Not trainable: slot -1, not in PARAMETRIC.
+OP_EMBED = 8
+OP_NAMES = ("RX", "RY", "RZ", "H", "CNOT", "CRX", "CRZ", "U4", "EMBED")
 PARAMETRIC = (OP_RX, OP_RY, OP_RZ, OP_CRX, OP_CRZ)
 
 ANSATZ_NAMES = ("layered", "alternate", "cascade", "farhi", "sim_circ_15", "cross_mesh")
@@ -193,22 +196,29 @@ class GateProgram:
 
     def algorithmic_flops(self) -> int:
         """Real flops of one circuit evaluation under SURVEY.md §8(d)'s per-gate model
-        (FMA = 2): embedding RX 6N each, RX/RY/RZ 6N, CRX/CRZ 3N, CNOT 0, H 4N,
+        (FMA = 2): embedding RX 6N each (EMBED gates too), RX/RY/RZ 6N, CRX/CRZ 3N, CNOT 0, H 4N,
         4x4 two-wire unitary 30N, <Z> for all wires (3+n)N, N = 2**n."""
         n, N = self.n_qubits, 1 << self.n_qubits
-        per = {OP_RX: 6, OP_RY: 6, OP_RZ: 6, OP_H: 4, OP_CNOT: 0, OP_CRX: 3, OP_CRZ: 3, OP_U4: 30}
+        per = {OP_RX: 6, OP_RY: 6, OP_RZ: 6, OP_H: 4, OP_CNOT: 0, OP_CRX: 3, OP_CRZ: 3, OP_U4: 30, OP_EMBED: 6}
         return (6 * n + sum(per[g.op] for g in self.gates) + 3 + n) * N
 
 
-def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool) -> GateProgram:
+def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool, reupload: bool = False) -> GateProgram:
     """Lower ``q_ansatz`` on ``n_qubits`` wires x ``n_layers`` into a gate program.
 
     ``use_haar`` mirrors the reference's gating (``nn/DVQuantumLayer.py:88-94,203-209``):
     the two fixed unitaries are present iff ``num_qubits >= 4`` and ``args['seed']`` is given.
+
+    ``reupload`` (data re-uploading, Perez-Salinas et al. 2020; the reference's ``hybrid_testing/hqpinn_pennylane.py:46-59``
+    embeds in front of every entangling layer): an EMBED layer on wires 0..n-1 in front of every ansatz layer after the
+    first; layer 0 keeps the implicit embedding.  Slots, ``n_params``, the fixed unitaries and the final Hadamard do not
+    change, and with one layer the program is the plain one.
     """
     P = params_per_layer(q_ansatz, n_qubits)
     gates: List[Gate] = []
     for layer in range(n_layers):
+        if reupload and layer > 0:
+            gates += [Gate(OP_EMBED, w, -1, -1) for w in range(n_qubits)]
         e = _Emitter(n_qubits, layer * P, P)
         _BUILDERS[q_ansatz](e)
         gates += e.gates

@@ -120,12 +120,18 @@ const char* qc_error_string(int code) {
 
 int qc_last_hip_error(void) { return g_last_hip; }
 
-// gate rows (opcode, wire_a, wire_b, slot) -> bit-indexed gates; returns false on an invalid row
-static bool parse_rows(const int32_t* rows, int n_gates, int n_qubits, int n_params, QcGate* h, int* n_u4_out) {
-  int n_u4 = 0;
+// gate rows (opcode, wire_a, wire_b, slot) -> bit-indexed gates; returns false on an invalid row.  EMBED rows
+// (wire, -1, -1) are valid only for a caller that counts them (n_embed_out): the plan describers never see one
+static bool parse_rows(const int32_t* rows, int n_gates, int n_qubits, int n_params, QcGate* h, int* n_u4_out,
+                       int* n_embed_out = nullptr) {
+  int n_u4 = 0, n_embed = 0;
   for (int g = 0; g < n_gates; ++g) {
     const int op = rows[4 * g], a = rows[4 * g + 1], b = rows[4 * g + 2], slot = rows[4 * g + 3];
-    bool ok = op >= QC_RX && op <= QC_U4 && a >= 0 && a < n_qubits;
+    bool ok = op >= QC_RX && op <= QC_EMBED && a >= 0 && a < n_qubits;
+    if (op == QC_EMBED) {
+      ok = ok && n_embed_out != nullptr && b == -1 && slot == -1;
+      ++n_embed;
+    }
     const bool two = (op == QC_CNOT || op == QC_CRX || op == QC_CRZ || op == QC_U4);
     if (two) ok = ok && b >= 0 && b < n_qubits && b != a;
     const bool par = (op == QC_RX || op == QC_RY || op == QC_RZ || op == QC_CRX || op == QC_CRZ);
@@ -141,6 +147,7 @@ static bool parse_rows(const int32_t* rows, int n_gates, int n_qubits, int n_par
     h[g].slot = (par || op == QC_U4) ? slot : -1;
   }
   *n_u4_out = n_u4;
+  if (n_embed_out) *n_embed_out = n_embed;
   return true;
 }
 // RX(p_w) right after the embedding RX(a_w), wire by wire, distinct slots
@@ -174,15 +181,22 @@ int qc_program_create(const int32_t* rows, int n_gates, int n_qubits, int n_para
   }
   p->n_qubits = n_qubits; p->n_gates = n_gates; p->n_params = n_params;
   p->h_gates = h;
-  if (!parse_rows(rows, n_gates, n_qubits, n_params, h, &p->n_u4)) {
+  if (!parse_rows(rows, n_gates, n_qubits, n_params, h, &p->n_u4, &p->n_embed)) {
     qc_program_destroy(p);
     return QC_ERR_ARG;
   }
-  p->fam = pick_family(n_qubits);
-  p->static_id = (n_qubits >= 2 && n_qubits <= 5) ? qc_reg_match_static(p)
-                 : ((n_qubits >= 6 && n_qubits <= 8) ? qc_wave_match_static(p) : -1);
+  if (p->n_embed > 0) {
+    // data re-uploading: its own family for 2 <= n <= 5 (whatever QC_FORCE_WAVE says), no family otherwise - no other
+    // interpreter knows the opcode.  No compile-time program, no folded leading RX layer.
+    p->fam = (n_qubits >= 2 && n_qubits <= 5) ? &qc_family_reup : nullptr;
+    p->static_id = -1;
+  } else {
+    p->fam = pick_family(n_qubits);
+    p->static_id = (n_qubits >= 2 && n_qubits <= 5) ? qc_reg_match_static(p)
+                   : ((n_qubits >= 6 && n_qubits <= 8) ? qc_wave_match_static(p) : -1);
+  }
   qc_find_diag_runs(p);
-  p->lead_rx = detect_lead_rx(h, n_gates, n_qubits);
+  p->lead_rx = p->n_embed > 0 ? 0 : detect_lead_rx(h, n_gates, n_qubits);
   hipError_t e = hipMalloc((void**)&p->d_gates, sizeof(QcGate) * n_gates);
   if (e == hipSuccess) e = hipMemcpy(p->d_gates, h, sizeof(QcGate) * n_gates, hipMemcpyHostToDevice);
 #ifndef QC_WAVE_NO_RUNS
@@ -226,6 +240,7 @@ int qc_program_destroy(qc_program* p) {
 int qc_program_set_encoding(qc_program* p, int amplitude) {
   if (!p || (amplitude != 0 && amplitude != 1)) return QC_ERR_ARG;
   if (amplitude && ((int64_t)1 << p->n_qubits) < p->n_qubits) return QC_ERR_ARG;
+  if (amplitude && p->n_embed > 0) return QC_ERR_UNSUPPORTED;   // no angle to re-upload
   if (p->amplitude != amplitude && p->h2) {   // a plan for the new encoding first; the program changes only with it
     void* h2 = h2_plan(p, amplitude);
     if (!h2) return QC_ERR_ALLOC;
@@ -1016,6 +1031,8 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
   if (!sys && ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem))) return QC_ERR_ARG;
   int rc = check_step_desc(d, false, nullptr);
   if (rc) return rc;
+  // no kernel family: n > 20 (refused above by the network's shape) or EMBED gates outside 2 <= n <= 5 (qc_program_create)
+  if (!d->prog->fam) return QC_ERR_UNSUPPORTED;
   const int n = d->n, H = d->H;
   const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1, sys ? 0 : tg.n_op(), prog_n_in(d->prog));
   const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;

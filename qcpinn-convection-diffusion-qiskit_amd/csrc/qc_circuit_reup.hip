@@ -1,0 +1,66 @@
+// Re-uploading family dispatch: run-time interpreter kernels for gate programs with EMBED gates, 2 <= n <= 5.
+#include "qc_circuit_reup_kernels.h"
+
+template <int N>
+struct ReupLaunch {
+  static int fwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* in, float* out, int64_t B, int nch,
+                 hipStream_t st) {
+    if (nch == 1)
+      hipLaunchKernelGGL(k_reup_value_fwd<N>, dim3(qc_ceil_div(B, 256)), dim3(256), 0, st, pg->d_gates, trig, umat,
+                         pg->n_gates, in, out, B);
+    else
+      hipLaunchKernelGGL(k_reup_jets_fwd<N>, dim3(qc_ceil_div(B, 64)), dim3(384), 0, st, pg->d_gates, trig, umat,
+                         pg->n_gates, in, out, B);
+    return QC_OK;
+  }
+  static int bwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* in, const float* cot, float* d_in,
+                 float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, hipStream_t st) {
+    if (nch == 1) {
+      const size_t sh = (size_t)4 * pg->n_params * sizeof(float);
+      if (sh > 64 * 1024) return QC_ERR_UNSUPPORTED;
+      hipLaunchKernelGGL(k_reup_value_bwd<N>, dim3(qc_ceil_div(B, 256)), dim3(256), sh, st, pg->d_gates, trig, umat,
+                         pg->n_gates, pg->n_params, in, cot, d_in, part, part_stride, row0, B);
+      return QC_OK;
+    }
+    // the six-vector exchange is sized by the template parameter: 96 KB at n = 5
+    const size_t sh = ((size_t)6 * (2u << N) * 64 + (size_t)6 * pg->n_params + 2 * N * 64) * sizeof(float);
+    if (sh > 160 * 1024) return QC_ERR_UNSUPPORTED;
+    static bool attr_set = false;   // (one process per device, as k_jets_bwd's launcher)
+    if (!attr_set) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reup_jets_bwd<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024) != hipSuccess)
+        return QC_ERR_HIP;
+      attr_set = true;
+    }
+    hipLaunchKernelGGL(k_reup_jets_bwd<N>, dim3(qc_ceil_div(B, 64)), dim3(384), sh, st, pg->d_gates, trig, umat, pg->n_gates,
+                       pg->n_params, in, cot, d_in, part, part_stride, row0, B);
+    return QC_OK;
+  }
+};
+
+// nch = 1: value kernels; 6: jet kernels.  Nothing is kept: the adjoint kernels recompute the forward sweep.
+static int reup_fwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* in, float* out, int64_t B,
+                    int nch, QcCircStore, hipStream_t st) {
+  if (pg->amplitude) return QC_ERR_UNSUPPORTED;
+  switch (pg->n_qubits) {
+    case 2: return ReupLaunch<2>::fwd(pg, trig, umat, in, out, B, nch, st);
+    case 3: return ReupLaunch<3>::fwd(pg, trig, umat, in, out, B, nch, st);
+    case 4: return ReupLaunch<4>::fwd(pg, trig, umat, in, out, B, nch, st);
+    case 5: return ReupLaunch<5>::fwd(pg, trig, umat, in, out, B, nch, st);
+    default: return QC_ERR_UNSUPPORTED;
+  }
+}
+static int reup_bwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* in, const float* cot,
+                    float* d_in, float* part, int64_t part_stride, int64_t row0, int64_t B, int nch, QcCircStore,
+                    hipStream_t st) {
+  if (pg->amplitude) return QC_ERR_UNSUPPORTED;
+  switch (pg->n_qubits) {
+    case 2: return ReupLaunch<2>::bwd(pg, trig, umat, in, cot, d_in, part, part_stride, row0, B, nch, st);
+    case 3: return ReupLaunch<3>::bwd(pg, trig, umat, in, cot, d_in, part, part_stride, row0, B, nch, st);
+    case 4: return ReupLaunch<4>::bwd(pg, trig, umat, in, cot, d_in, part, part_stride, row0, B, nch, st);
+    case 5: return ReupLaunch<5>::bwd(pg, trig, umat, in, cot, d_in, part, part_stride, row0, B, nch, st);
+    default: return QC_ERR_UNSUPPORTED;
+  }
+}
+static size_t reup_store_bytes(const qc_program*, int, int64_t) { return 0; }
+QcFamily qc_family_reup = {reup_fwd, reup_bwd, reup_store_bytes};

@@ -282,6 +282,7 @@ struct QcFamily {
 extern QcFamily qc_family_reg;    // registers, one lane per statevector: 2 <= n <= 5 (qc_circuit_reg.hip)
 extern QcFamily qc_family_wave;   // lanes as amplitudes: n = 1, 6..8 (qc_circuit_wave.hip)
 extern QcFamily qc_family_hbm;    // statevector tiles in HBM: n = 9..20 (qc_circuit_hbm2.hip)
+extern QcFamily qc_family_reup;   // programs with EMBED gates (data re-uploading): 2 <= n <= 5 (qc_circuit_reup.hip)
 
 // the generated program whose rows (n_gates x (op, ba, bb, slot), device encoding) are this program's gates;
 // never with QC_NO_STATIC=1 (read once)

@@ -17,6 +17,11 @@ Derivatives: the reverse pass w.r.t. angles and parameters is the HIP adjoint sw
 re-expressed through the exact trigonometric-interpolation form of the layer, so second and higher
 input derivatives work as with the reference's backprop simulator (angle encoding, n <= 7).
 
+``args["reupload"] = True`` (data re-uploading, angle encoding, 2 <= num_qubits <= 5): the RX angle embedding again in
+front of every ansatz layer after the first (``circuits.OP_EMBED``; the reference's hybrid_testing/hqpinn_pennylane.py:46-59).
+Parameters, their count and their initial values are those of the plain layer; ``create_graph=True`` goes through the
+derivative-channel kernels, since such a layer is a degree-L trigonometric polynomial per wire.
+
 Out of scope, by design: IBM Runtime devices / shot-based execution
 (``use_ibm_hardware=True``) are refused with an explicit error.
 """
@@ -162,7 +167,8 @@ class _ExpvalFn(torch.autograd.Function):
         x, params = ctx.saved_tensors
         circ, layer = ctx.circ, ctx.layer
         if torch.is_grad_enabled():          # create_graph=True: the result must itself be differentiable
-            if layer.encoding == "amplitude" or layer.num_qubits > TRIG_INTERP_MAX_QUBITS:
+            if layer.encoding == "amplitude" or layer.num_qubits > TRIG_INTERP_MAX_QUBITS or layer.has_embed_gates:
+                # (a re-uploaded layer is a degree-L polynomial per wire: the degree-1 interpolant is wrong for it)
                 # second-order input derivatives from the derivative-channel kernels (any size, both encodings); the
                 # interpolant below additionally carries third and higher orders
                 gx, gp = _LayerVjpFn.apply(x, params, grad_out, layer)
@@ -194,6 +200,13 @@ class DVQuantumLayer(nn.Module):
         self.ibm_backend = args.get("ibm_backend", "ibmq_qasm_simulator")
         self.ibm_instance = args.get("ibm_instance", None)
         self.diff_method = diff_method          # accepted and ignored, as in the reference (:10,:143-145)
+        # data re-uploading: the angle embedding again in front of every ansatz layer after the first (circuits.py)
+        self.reupload = bool(args.get("reupload", False))
+        if self.reupload:
+            if self.encoding == "amplitude":
+                raise ValueError("reupload=True needs the angle encoding: amplitude encoding has no angle to re-upload")
+            if not 2 <= self.num_qubits <= 5:
+                raise ValueError(f"reupload=True is built for 2 <= num_qubits <= 5, got num_qubits={self.num_qubits}")
 
         per_layer = circuits.params_per_layer(self.q_ansatz, self.num_qubits)   # ValueError on unknown ansatz
         self.params = nn.Parameter(torch.empty(self.num_quantum_layers, per_layer, dtype=torch.float32))
@@ -211,7 +224,8 @@ class DVQuantumLayer(nn.Module):
         self.dev = "hip.statevector"
         # lowered once; raises the same IndexError the reference hits for over-indexed ansaetze
         self.program = circuits.build_program(self.q_ansatz, self.num_qubits, self.num_quantum_layers,
-                                              self.haar_seed1 is not None)
+                                              self.haar_seed1 is not None, reupload=self.reupload)
+        self.has_embed_gates = any(g.op == circuits.OP_EMBED for g in self.program.gates)
         self._haar = circuits.haar_unitaries(self.haar_seed1, self.haar_seed2)
         self._circuits = {}
 
@@ -235,6 +249,9 @@ class DVQuantumLayer(nn.Module):
         """The same (n, B) expectation values as ``forward`` written as a trigonometric polynomial of the
         embedding angles (coefficients from the HIP kernels, see ``_TrigCoeffFn``): built from torch ops, so
         derivatives with respect to ``x`` exist to any order.  Used for the create_graph=True reverse pass."""
+        if self.has_embed_gates:
+            raise ValueError("trig_interpolant: a re-uploaded layer is a degree-L trigonometric polynomial per wire, not "
+                             "the degree-1 form interpolated here")
         params = self.params if params is None else params
         C = _TrigCoeffFn.apply(params, self, x.device)                       # (n, 3^n)
         return C @ _trig_features(x.to(torch.float32)).t()

@@ -35,6 +35,8 @@ class SystemTrainer:
         if getattr(model, "input_dim", 3) != 3:
             raise ValueError("SystemTrainer needs classic_network = [3, H, K]: a two-input model keeps a zero-padded t column "
                              "in W1 that the step would train")
+        if getattr(getattr(model, "quantum_layer", None), "reupload", False):
+            raise ValueError("SystemTrainer does not take a re-uploaded circuit (args['reupload']): train it with FusedTrainer")
         K = int(getattr(model, "n_out", 1))
         if K != dataset.K:
             raise ValueError(f"the model has {K} outputs but the dataset prescribes {dataset.K}")
