@@ -867,7 +867,28 @@ class BalancedStep(_Step):
         self._bind_entry("qc_fused_pinn_balanced_step", self.data, self.bal)
 
 
-class CausalStep(FusedStep):
+def history_rows(hist: torch.Tensor, steps: Optional[int], cap: int, read, counter: str = "step") -> torch.Tensor:
+    """The first ``steps`` rows of the history buffer ``hist`` of ``cap`` rows, on the host.  ``steps`` None: all steps
+    of THIS buffer so far, ``read()[counter] - read()["hist_base"]`` of the device record (a host read)."""
+    if steps is None:
+        rec = read()
+        steps = rec[counter] - rec["hist_base"]
+    return hist[: max(0, min(int(steps), cap))].cpu()
+
+
+class _WeightedStep(FusedStep):
+    """A ``FusedStep`` with a device record ``state`` of its own (``read_state()``) whose words 2 and 3 are the int32
+    counters {n_steps, hist_base} of its history buffer."""
+
+    def set_hist_base(self, n_steps: int, hist_base: int) -> None:
+        """Rewrites the two counters of the record (a new history buffer starts at step ``hist_base``)."""
+        self.state[2:4] = torch.tensor([n_steps, hist_base], dtype=torch.int32).view(torch.float32).to(self.state.device)
+
+    def _history(self, hist: torch.Tensor, steps: Optional[int], cap: int) -> np.ndarray:
+        return history_rows(hist, steps, cap, self.read_state, "n_steps").numpy()
+
+
+class CausalStep(_WeightedStep):
     """One ``qc_fused_pinn_causal_step`` descriptor over fixed-size resident batches: the tabulated step (the engine's
     problem must be ``QC_PROBLEM_TABULATED``, without coefficient mode) with the residual of time slab i weighted by
     W_i = exp(-eps sum_{k<i} L_k).  ``B_res`` must be a multiple of ``64 * n_slabs``: tile r of the residual batch holds
@@ -911,10 +932,6 @@ class CausalStep(FusedStep):
     def _bind(self) -> None:
         self._bind_entry("qc_fused_pinn_causal_step", self.data, self.causal)
 
-    def set_hist_base(self, n_steps: int, hist_base: int) -> None:
-        """Rewrites the two counters of the record (a new history buffer starts at step ``hist_base``)."""
-        self.state[2:4] = torch.tensor([n_steps, hist_base], dtype=torch.int32).view(torch.float32).to(self.state.device)
-
     def read_state(self) -> dict:
         """The record as a dict (a host read): eps of the NEXT step, the counters, W and L of the last step."""
         raw = self.state.cpu().numpy()
@@ -924,13 +941,10 @@ class CausalStep(FusedStep):
 
     def history(self, steps: Optional[int] = None) -> np.ndarray:
         """Rows (eps, W[M], L[M]) of the first ``steps`` steps of the history buffer (default: all taken so far)."""
-        if steps is None:
-            rec = self.read_state()
-            steps = rec["n_steps"] - rec["hist_base"]
-        return self.causal_hist[: max(0, min(int(steps), self.causal_cap))].cpu().numpy()
+        return self._history(self.causal_hist, steps, self.causal_cap)
 
 
-class GradNormStep(FusedStep):
+class GradNormStep(_WeightedStep):
     """One ``qc_fused_pinn_gradnorm_step`` descriptor over fixed-size resident batches: the analytic, the tabulated or the
     coefficient step (whichever the engine is configured for, as ``FusedStep``) under gradient-norm loss weights (Wang,
     Teng, Perdikaris 2021): lam_k <- (1 - alpha) lam_k + alpha max|G_res| / mean|G_k| for k = BC, IC every ``every`` steps,
@@ -962,10 +976,6 @@ class GradNormStep(FusedStep):
         self._bind_entry("qc_fused_pinn_gradnorm_step", self.data if self.tabulated else None,
                          self.coef if self.coef_mode else None, self.gn)
 
-    def set_hist_base(self, n_steps: int, hist_base: int) -> None:
-        """Rewrites the two counters of the record (a new history buffer starts at step ``hist_base``)."""
-        self.state[2:4] = torch.tensor([n_steps, hist_base], dtype=torch.int32).view(torch.float32).to(self.state.device)
-
     def read_state(self) -> dict:
         """The record as a dict (a host read): the weights of the NEXT step, the counters, the statistics of the last update."""
         raw = self.state.cpu().numpy()
@@ -978,7 +988,4 @@ class GradNormStep(FusedStep):
     def history(self, steps: Optional[int] = None) -> np.ndarray:
         """Rows (lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated) of the first ``steps`` steps of the
         history buffer (default: all taken so far)."""
-        if steps is None:
-            rec = self.read_state()
-            steps = rec["n_steps"] - rec["hist_base"]
-        return self.gradnorm_hist[: max(0, min(int(steps), self.gradnorm_cap))].cpu().numpy()
+        return self._history(self.gradnorm_hist, steps, self.gradnorm_cap)

@@ -72,10 +72,7 @@ class BalancedTrainer(InverseTrainer):
     def weight_history(self, steps=None):
         """(steps, 3) tensor: row i holds the effective weights w_k exp(-s_k) (residual, BC, IC) the i-th step of THIS
         history buffer used, next to ``loss_history()[i]`` (default: all steps taken so far)."""
-        if steps is None:
-            rec = self.opt.read()
-            steps = rec["step"] - rec["hist_base"]
-        return self.fs.weight_hist[: max(0, min(int(steps), self.opt.hist_cap))].cpu()
+        return _engine.history_rows(self.fs.weight_hist, steps, self.opt.hist_cap, self.opt.read)
 
     def weights(self):
         """The current effective weights w_k exp(-s_k) as a dict over the three terms."""

@@ -166,8 +166,142 @@ def gather_rows(fs, segments, counts, batch_minor=False, coef=None):
                 fs.coef_res[:, :n] = coef[idx].t()
 
 
+def fill_batches(fs, counts, points, targets=None, batch_minor=False, coef=None, shard=None):
+    """Given batches into the step ``fs``: ``points`` = (X_ic, X_bc, X_res) go to ``X_val[:n_ic]``, ``X_val[n_ic:n_ic + n_bc]``
+    and ``X_res[:B_res]`` (``counts`` = (B_res, n_ic, n_bc)), ``targets`` = (y_ic, y_bc, y_res | None) to the matching
+    slices of ``target_val`` / ``target_res``: one value per point, or with ``batch_minor`` rows [n, w] into [w, B]
+    targets; ``coef``: the (n, 7) operator rows of ``X_res`` into ``fs.coef_res[:, :B_res]``.  ``shard`` = (world, rank):
+    the arrays hold GLOBAL batches and this rank takes its ``shard_slice`` of each; None: they hold this step's batches."""
+    B_res, n_ic, n_bc = counts
+    for k, (n, dX, dY, o) in enumerate(((n_ic, fs.X_val, fs.target_val, 0), (n_bc, fs.X_val, fs.target_val, n_ic),
+                                        (B_res, fs.X_res, fs.target_res, 0))):
+        if not n:
+            continue
+        s = slice(None) if shard is None else shard_slice(points[k].shape[0], *shard)
+        take = lambda a: torch.as_tensor(a, dtype=torch.float32)[s].to(dX.device)
+        dX[o:o + n] = take(points[k])
+        if targets is not None and targets[k] is not None:
+            if batch_minor:
+                dY[:, o:o + n] = take(targets[k]).t()
+            else:
+                dY[o:o + n] = take(torch.as_tensor(targets[k]).reshape(-1))
+        if coef is not None and dX is fs.X_res:
+            fs.coef_res[:, :n] = take(coef).t()
+
+
+class StepTrainer:
+    """What every fused trainer shares around its step descriptor ``fs`` and its optimiser record ``opt``: the bridge to
+    the torch optimiser over ``_params()``, the end of the constructor, sampling from a resident dataset, ``step()`` and
+    the readers of the loss.  A subclass sets ``model``, ``device``, ``optimizer``, ``scheduler``, ``max_norm``,
+    ``loss_weights``, ``sampler``, ``dataset``, the batch sizes ``B_res`` / ``n_ic`` / ``n_bc``, ``opt`` and ``fs``."""
+
+    world, _comm = 1, None              # single-process unless the subclass shards its batches (FusedTrainer)
+    adaptive, _steps = None, 0          # an AdaptiveSampling and the sampled steps taken under it (FusedTrainer)
+    _sampled = True                     # False: a dataset segment is empty behind a non-empty batch, load_batches only
+    batch_minor = False                 # target rows [N, w] of the dataset go into [w, B] targets
+
+    def _params(self):
+        """The tensors behind the flat vector, in its order."""
+        return list(self.model.parameters())
+
+    # -- optimiser state: continue from the torch optimiser / scheduler objects
+    def _make_opt_state(self, capacity):
+        return opt_state_from_torch(self._params(), self.optimizer, self.scheduler, self.device, capacity, self.max_norm,
+                                    self.loss_weights)
+
+    def sync_to_torch(self):
+        """Mirror the device optimiser record into the torch optimiser / scheduler so that ``save_state`` writes a
+        checkpoint interchangeable with the reference's."""
+        sync_opt_state_to_torch(self.opt, self._params(), self.optimizer, self.scheduler)
+
+    def _arm(self, *offsets):
+        """The end of every constructor: gate tables from the current parameters, the device sampler seeded once from
+        torch's CPU generator (so ``torch.manual_seed`` still controls the run; ``offsets``: ``set_sampler``'s), sampled
+        batches until ``load_batches`` says otherwise, and ``save_state``'s way back to the torch optimiser."""
+        self.fs.refresh_gates()
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if self.world > 1:                                        # every rank must draw the same seed
+            import torch.distributed as dist
+            t = torch.tensor([seed], dtype=torch.int64, device=self.device)
+            dist.broadcast(t, 0)
+            seed = int(t.item())
+        self.fs.set_sampler(seed, *offsets)
+        self._explicit = False
+        self.model._sync_fused_to_torch = self.sync_to_torch
+
+    # -- batches
+    def sample(self):
+        """Rows of the dataset, drawn with replacement.  With the device sampler this only arms the next ``step()``; the
+        "torch" sampler draws ``torch.randint`` rows IC -> BC -> residual and copies them."""
+        if not self._sampled:
+            raise ValueError("the dataset has an empty segment behind a non-empty batch: use load_batches(...)")
+        self._explicit = False
+        if self.sampler == "device":
+            return
+        self._explicit = True
+        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), self.batch_minor,
+                    getattr(self.dataset, "coef_res", None))
+
+    def step(self):
+        draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
+        if self.adaptive is not None:
+            # scores of all residual rows and their CDF, enqueued ahead of the step on its stream: nothing is read back
+            # (steps on explicit batches draw nothing and do not count towards the cadence)
+            if draw:
+                if self._steps % self.adaptive.every == 0:
+                    self.fs.rescore()
+                self._steps += 1
+        if self.world == 1 or self._comm is not None:
+            self.fs.run(draw | _lib.QC_PHASE_GRADS | _lib.QC_PHASE_UPDATE)
+        else:
+            import torch.distributed as dist
+            self.fs.run(draw | _lib.QC_PHASE_GRADS)
+            dist.all_reduce(self.fs.flat_grad)          # one small all-reduce: [grads | L_r, L_bc, L_ic]
+            self.fs.run(_lib.QC_PHASE_UPDATE)
+
+    def loss_history(self, steps=None):
+        return self.opt.loss_history(steps)
+
+    def losses(self):
+        rec = self.opt.read()
+        return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
+
+
+class DatasetTrainer(StepTrainer):
+    """A single-process trainer on a resident dataset whose step is built over the model's flat buffer and circuit (the
+    system, the inverse and the balanced trainer).  The constructor runs, in this order: batch sizes and device
+    (``batch_prologue``), the dataset to the device, ``_pack()`` (``flat`` and ``NP``), the circuit, the optimiser record,
+    ``_make_step()``, the dataset handed to the step unless a segment is empty behind a non-empty batch, ``_arm()``.  A
+    subclass raises its argument errors ahead of it and provides ``_make_step``."""
+
+    def __init__(self, model, batch_size, dataset, n_ic, n_bc, loss_weights, max_norm, capacity, sampler):
+        self.B_res, self.n_ic, self.n_bc, dev = batch_prologue(model, batch_size, n_ic, n_bc, sampler)
+        self.model, self.device, self.sampler = model, dev, sampler
+        self.dataset = dataset.to(dev)
+        self.max_norm = max_norm
+        self.loss_weights = tuple(float(w) for w in loss_weights)
+        self.optimizer, self.scheduler = model.optimizer, model.scheduler
+        self._pack()
+        self.circuit = model._circuit(dev)
+        self.opt = self._make_opt_state(int(capacity))
+        self.fs = self._make_step()
+        self._sampled = all(n_rows > 0 or n_batch == 0
+                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), self.dataset.sizes()))
+        if self._sampled:
+            self.fs.set_dataset(self.dataset.segments())
+        self._arm()
+
+    def _pack(self):
+        """The model's own flat buffer (``model.parameters()`` order, the parameters re-pointed at views of it) as
+        ``self.flat``, its ``self.NP`` entries."""
+        if not self.model._packed_ok() or self.model._flat.device != self.device:
+            self.model._pack(self.device)
+        self.flat = self.model._flat
+        self.NP = self.flat.numel()
+
+
 # ---------------------------------------------------------------------------------------------
-class FusedTrainer:
+class FusedTrainer(StepTrainer):
     """Device-resident training state of one DVPDESolver: sampler boxes, optimiser record,
     the fused-step descriptor.  ``step()`` = one reference iteration, no host synchronisation.
 
@@ -210,7 +344,7 @@ class FusedTrainer:
         self.eng = model._engine_for(dev)
         self.eng.sigma = (1.0, 1.0, 1.0)          # the trainers call the operator with its default scalings
         self.eng.coeffs = None
-        self.eng.loss_weights = tuple(float(w) for w in loss_weights)
+        self.eng.loss_weights = self.loss_weights = tuple(float(w) for w in loss_weights)
         # a tabulated step leaves the engine as it found it: the descriptor built below keeps what it needs
         before = (self.eng.problem, self.eng.c_u)
         self.eng.coef_mode = False
@@ -254,28 +388,18 @@ class FusedTrainer:
                 if n_batch > 0 and n_rows == 0:
                     raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
             self.fs.set_dataset(self.dataset.segments(), self.dataset.coef_res)
-        self.adaptive, self._steps = adaptive, 0
+        self.adaptive = adaptive
         if adaptive is not None:
             self.fs.set_adaptive(adaptive.power, adaptive.floor)
         self.lo = {k: box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
         self.span = {k: box(k, dev)[1:2] - box(k, dev)[0:1] for k in ("ics", "bc1", "dom")}
-        self.eng.refresh_gates()
-        model._sync_fused_to_torch = self.sync_to_torch
         if sampler not in ("device", "torch"):
             raise ValueError("sampler must be 'device' or 'torch'")
         self.sampler = sampler
-        self._explicit = False
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())        # every rank must draw the same seed
-        if self.world > 1:
-            import torch.distributed as dist
-            t = torch.tensor([seed], dtype=torch.int64, device=dev)
-            dist.broadcast(t, 0)
-            seed = int(t.item())
-        self.fs.set_sampler(seed, shard_slice(batch_size, self.world, self.rank).start,
-                            shard_slice(ni, self.world, self.rank).start, self.bc_start, self.bc_face_points)
+        self._arm(shard_slice(batch_size, self.world, self.rank).start, shard_slice(ni, self.world, self.rank).start,
+                  self.bc_start, self.bc_face_points)
         # QC_DP_COLLECTIVE=rccl: the all-reduce runs INSIDE the library call (qc_comm_*: RCCL on the step's own stream,
         # one host call per step); default: torch.distributed between the two phases
-        self._comm = None
         if self.world > 1 and os.environ.get("QC_DP_COLLECTIVE", "torch") == "rccl":
             self._comm = self._make_comm()
             self.fs.set_comm(self._comm)
@@ -314,29 +438,19 @@ class FusedTrainer:
     def __del__(self):
         self.close()
 
-    def _make_opt_state(self, capacity):
-        return opt_state_from_torch(self.model.parameters(), self.optimizer, self.scheduler, self.device, capacity,
-                                    self.max_norm, self.eng.loss_weights)
-
-    def sync_to_torch(self):
-        """Mirror the device optimiser record into model.optimizer / model.scheduler so that
-        ``save_state`` writes a checkpoint interchangeable with the reference's."""
-        sync_opt_state_to_torch(self.opt, self.model.parameters(), self.optimizer, self.scheduler)
-
     # -- batches
     def sample(self):
-        """IC -> BC -> residual, uniform in the reference's boxes (trainer/diffusion_train.py:9-20,34-36).
-        With the device sampler this only arms the next ``step()``."""
+        """IC -> BC -> residual, uniform in the reference's boxes (trainer/diffusion_train.py:9-20,34-36), or rows of the
+        dataset.  With the device sampler this only arms the next ``step()``."""
+        if self.tabulated:
+            if self.dataset is None:
+                raise ValueError("a tabulated step without dataset= has nothing to sample from: use load_batches(..., targets=)")
+            return super().sample()
         self._explicit = False
-        if self.tabulated and self.dataset is None:
-            raise ValueError("a tabulated step without dataset= has nothing to sample from: use load_batches(..., targets=)")
         if self.sampler == "device":
             return
         self._explicit = True
         fs, dev = self.fs, self.device
-        if self.dataset is not None:     # torch.randint minibatches, IC -> BC -> residual like the draws below
-            gather_rows(fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), coef=self.dataset.coef_res)
-            return
         if self.n_ic:
             fs.X_val[: self.n_ic] = self.lo["ics"] + self.span["ics"] * torch.rand(self.n_ic, 3, device=dev)
         if self.n_bc and self.bc_face_points == _lib.QC_BC_RANDOM_FACE:      # a random face per point, one draw
@@ -368,33 +482,14 @@ class FusedTrainer:
             raise ValueError("targets need a tabulated step: construct the trainer with dataset= or pde={'problem': 3, ...}")
         if targets is None and self.tabulated:
             raise ValueError("a tabulated step needs targets=(u_ic, u_bc, r_res) with its batches")
+        if targets is not None and tuple(torch.as_tensor(t).numel() for t in targets) != (X_ic.shape[0], X_bc.shape[0],
+                                                                                          X_res.shape[0]):
+            raise ValueError("targets=(u_ic, u_bc, r_res) must hold one value per point of (X_ic, X_bc, X_res)")
+        if coef is not None and tuple(torch.as_tensor(coef).shape) != (X_res.shape[0], _lib.QC_COEF_COLS):
+            raise ValueError(f"coef must be ({X_res.shape[0]}, {_lib.QC_COEF_COLS}): one operator row per point of X_res")
         self._explicit = True
-        fs, dev = self.fs, self.device
-        s_ic = shard_slice(X_ic.shape[0], self.world, self.rank)
-        s_bc = shard_slice(X_bc.shape[0], self.world, self.rank)
-        s_rs = shard_slice(X_res.shape[0], self.world, self.rank)
-        if self.n_ic:
-            fs.X_val[: self.n_ic] = X_ic[s_ic].to(dev)
-        if self.n_bc:
-            fs.X_val[self.n_ic: self.n_ic + self.n_bc] = X_bc[s_bc].to(dev)
-        if self.B_res:
-            fs.X_res[: self.B_res] = X_res[s_rs].to(dev)
-        if targets is not None:
-            u_ic, u_bc, r_res = (torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in targets)
-            if (u_ic.numel(), u_bc.numel(), r_res.numel()) != (X_ic.shape[0], X_bc.shape[0], X_res.shape[0]):
-                raise ValueError("targets=(u_ic, u_bc, r_res) must hold one value per point of (X_ic, X_bc, X_res)")
-            if self.n_ic:
-                fs.target_val[: self.n_ic] = u_ic[s_ic].to(dev)
-            if self.n_bc:
-                fs.target_val[self.n_ic: self.n_ic + self.n_bc] = u_bc[s_bc].to(dev)
-            if self.B_res:
-                fs.target_res[: self.B_res] = r_res[s_rs].to(dev)
-        if coef is not None:
-            coef = torch.as_tensor(coef, dtype=torch.float32)
-            if tuple(coef.shape) != (X_res.shape[0], _lib.QC_COEF_COLS):
-                raise ValueError(f"coef must be ({X_res.shape[0]}, {_lib.QC_COEF_COLS}): one operator row per point of X_res")
-            if self.B_res:
-                fs.coef_res[:, : self.B_res] = coef[s_rs].to(dev).t()
+        fill_batches(self.fs, (self.B_res, self.n_ic, self.n_bc), (X_ic, X_bc, X_res), targets, coef=coef,
+                     shard=(self.world, self.rank))
 
     def dataset_scores(self):
         """The fp32 scores |res_j - r_j| of the dataset's residual rows as of the last rescoring (a device tensor; its
@@ -408,30 +503,6 @@ class FusedTrainer:
         if self.adaptive is None:
             raise ValueError("adaptive_state() needs adaptive= sampling")
         return self.fs.adaptive_state()
-
-    def step(self):
-        draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
-        if self.adaptive is not None:
-            # scores of all residual rows and their CDF, enqueued ahead of the step on its stream: nothing is read back
-            # (steps on explicit batches draw nothing and do not count towards the cadence)
-            if draw:
-                if self._steps % self.adaptive.every == 0:
-                    self.fs.rescore()
-                self._steps += 1
-        if self.world == 1 or self._comm is not None:
-            self.fs.run(draw | _lib.QC_PHASE_GRADS | _lib.QC_PHASE_UPDATE)
-        else:
-            import torch.distributed as dist
-            self.fs.run(draw | _lib.QC_PHASE_GRADS)
-            dist.all_reduce(self.fs.flat_grad)          # one small all-reduce: [grads | L_r, L_bc, L_ic]
-            self.fs.run(_lib.QC_PHASE_UPDATE)
-
-    def loss_history(self, steps=None):
-        return self.opt.loss_history(steps)
-
-    def losses(self):
-        rec = self.opt.read()
-        return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
 
 
 def _check_adaptive(adaptive, dataset, batch_size, sampler="device"):

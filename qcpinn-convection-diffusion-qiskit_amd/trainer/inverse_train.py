@@ -17,8 +17,7 @@ import torch
 
 from ..data.tabulated import LearnedOperator, TabulatedProblem, _SCALARS
 from ..hip import engine as _engine
-from ..hip import lib as _lib
-from .diffusion_train import _dist_info, batch_prologue, gather_rows, opt_state_from_torch, sync_opt_state_to_torch
+from .diffusion_train import DatasetTrainer, _dist_info, fill_batches
 
 
 def pack_with_tail(model, tail, attr, dev):
@@ -45,7 +44,7 @@ def pack_with_tail(model, tail, attr, dev):
     return big
 
 
-class InverseTrainer:
+class InverseTrainer(DatasetTrainer):
     """Device-resident training state of one single-output DVPDESolver and one LearnedOperator: ONE flat buffer of
     ``NP + 7`` entries with the model's parameters in its head (``model.parameters()`` order, re-pointed at views of it)
     and ``operator.p`` in its tail, so ``model(X)``, ``model.residual``, ``save_state`` and ``operator.coefficients()`` see
@@ -61,26 +60,8 @@ class InverseTrainer:
         None: no clipping; ``capacity``: length of the loss and coefficient histories; ``sampler`` = "device" (the
         library's gather) or "torch" (``torch.randint`` rows and a copy)."""
         self._check(model, dataset, operator)
-        self.B_res, self.n_ic, self.n_bc, dev = batch_prologue(model, batch_size, n_ic, n_bc, sampler)
-        self.model, self.operator, self.device, self.sampler = model, operator, dev, sampler
-        self.dataset = dataset.to(dev)
-        self.max_norm = max_norm
-        self.loss_weights = tuple(float(w) for w in loss_weights)
-        self._pack()
-        self.circuit = model._circuit(dev)
-        self.optimizer, self.scheduler = model.optimizer, model.scheduler
-        self.attach(model, operator)
-        self.opt = self._make_opt_state(int(capacity))
-        self.fs = self._make_step()
-        ds = self.dataset
-        self._sampled = all(n_rows > 0 or n_batch == 0
-                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
-        if self._sampled:
-            self.fs.set_dataset(ds.segments())
-        self.fs.refresh_gates()
-        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
-        self._explicit = False
-        model._sync_fused_to_torch = self.sync_to_torch
+        self.operator = operator
+        super().__init__(model, batch_size, dataset, n_ic, n_bc, loss_weights, max_norm, capacity, sampler)
 
     FLAT_ATTR = "_inverse_flat"     # where the model keeps the flat buffer [model parameters | own entries]
 
@@ -127,74 +108,31 @@ class InverseTrainer:
             sch.min_lrs = list(sch.min_lrs) + [sch.min_lrs[0]] * (len(opt.param_groups) - len(sch.min_lrs))
 
     def _params(self):
-        return list(self.model.parameters()) + self._own(self.operator)
+        return super()._params() + self._own(self.operator)
 
     def _pack(self):
-        """One flat buffer [model parameters | own entries]: ``self.flat``, with ``self.NP`` model parameters in its head."""
+        """One flat buffer [model parameters | own entries]: ``self.flat``, with ``self.NP`` model parameters in its head;
+        the own entries join the optimiser behind it."""
         self.flat = pack_with_tail(self.model, self._own(self.operator), self.FLAT_ATTR, self.device)
         self.NP = self.model._flat.numel()
         for b in self.operator.buffers():       # base / scale follow to the device
             b.data = b.to(self.device)
-
-    # -- optimiser state: continue from the torch optimiser / scheduler objects of the model (FusedTrainer's rule)
-    def _make_opt_state(self, capacity):
-        return opt_state_from_torch(self._params(), self.optimizer, self.scheduler, self.device, capacity, self.max_norm,
-                                    self.loss_weights)
-
-    def sync_to_torch(self):
-        """Mirror the device optimiser record into model.optimizer / model.scheduler (``save_state`` calls this)."""
-        sync_opt_state_to_torch(self.opt, self._params(), self.optimizer, self.scheduler)
-
-    # -- batches
-    def sample(self):
-        """Rows of the dataset, drawn with replacement.  With the device sampler this only arms the next ``step()``."""
-        if not self._sampled:
-            raise ValueError("the dataset has an empty segment behind a non-empty batch: use load_batches(...)")
-        self._explicit = False
-        if self.sampler == "device":
-            return
-        self._explicit = True
-        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc))
+        self.attach(self.model, self.operator)
 
     def load_batches(self, X_ic, X_bc, X_res, targets):
         """Use given batches: ``targets`` = (u_ic (n_ic,), u_bc (n_bc,), r_res (B_res,))."""
-        u_ic, u_bc, r = targets
-        fs, dev = self.fs, self.device
         if (X_ic.shape[0], X_bc.shape[0], X_res.shape[0]) != (self.n_ic, self.n_bc, self.B_res):
             raise ValueError(f"batches must hold ({self.n_ic}, {self.n_bc}, {self.B_res}) points")
-        as32 = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev)
-        for y, n, name in ((u_ic, self.n_ic, "u_ic"), (u_bc, self.n_bc, "u_bc"), (r, self.B_res, "r_res")):
+        for y, n, name in zip(targets, (self.n_ic, self.n_bc, self.B_res), ("u_ic", "u_bc", "r_res")):
             if n and torch.as_tensor(y).numel() != n:
                 raise ValueError(f"{name} must hold {n} values: one per point")
         self._explicit = True
-        if self.n_ic:
-            fs.X_val[: self.n_ic] = as32(X_ic)
-            fs.target_val[: self.n_ic] = as32(u_ic).reshape(-1)
-        if self.n_bc:
-            fs.X_val[self.n_ic: self.n_ic + self.n_bc] = as32(X_bc)
-            fs.target_val[self.n_ic: self.n_ic + self.n_bc] = as32(u_bc).reshape(-1)
-        if self.B_res:
-            fs.X_res[: self.B_res] = as32(X_res)
-            fs.target_res[: self.B_res] = as32(r).reshape(-1)
-
-    def step(self):
-        draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
-        self.fs.run(draw | _lib.QC_PHASE_GRADS | _lib.QC_PHASE_UPDATE)
-
-    def loss_history(self, steps=None):
-        return self.opt.loss_history(steps)
-
-    def losses(self):
-        rec = self.opt.read()
-        return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
+        fill_batches(self.fs, (self.B_res, self.n_ic, self.n_bc), (X_ic, X_bc, X_res), targets)
 
     def coefficient_history(self, steps=None):
         """(steps, 7) tensor: row i holds the coefficients (``COEF_COLUMNS`` order) the i-th step of THIS history buffer
         used, next to ``loss_history()[i]`` (default: all steps taken so far)."""
-        if steps is None:
-            rec = self.opt.read()
-            steps = rec["step"] - rec["hist_base"]
-        return self.fs.coef_hist[: max(0, min(int(steps), self.opt.hist_cap))].cpu()
+        return _engine.history_rows(self.fs.coef_hist, steps, self.opt.hist_cap, self.opt.read)
 
     def coefficients(self):
         """The current effective coefficients as a dict over ``COEF_COLUMNS``."""

@@ -15,14 +15,16 @@ import torch
 from ..data.tabulated import TabulatedSystem
 from ..hip import engine as _engine
 from ..hip import lib as _lib
-from .diffusion_train import _dist_info, batch_prologue, gather_rows, opt_state_from_torch, sync_opt_state_to_torch
+from .diffusion_train import DatasetTrainer, _dist_info, fill_batches
 
 
-class SystemTrainer:
+class SystemTrainer(DatasetTrainer):
     """Device-resident training state of one K-output DVPDESolver: the flat parameter buffer (``model.parameters()``
     order, the parameters re-pointed at views of it, so ``model.jets_all`` and the state dict keep working), the optimiser
     record taken from the model's torch Adam / ReduceLROnPlateau, and the step descriptor.  ``step()`` is one training
     iteration without host synchronisation."""
+
+    batch_minor = True      # target rows [N, K] / [N, n_eq] go into [K][B] / [n_eq][B] targets
 
     def __init__(self, model, batch_size: int, dataset: TabulatedSystem, *, n_ic: int = None, n_bc: int = None,
                  loss_weights=(2.0, 4.0, 2.0), max_norm=1.0, capacity: int = 0, sampler: str = "device"):
@@ -37,91 +39,33 @@ class SystemTrainer:
                              "in W1 that the step would train")
         if getattr(getattr(model, "quantum_layer", None), "reupload", False):
             raise ValueError("SystemTrainer does not take a re-uploaded circuit (args['reupload']): train it with FusedTrainer")
-        K = int(getattr(model, "n_out", 1))
-        if K != dataset.K:
-            raise ValueError(f"the model has {K} outputs but the dataset prescribes {dataset.K}")
+        self.K = int(getattr(model, "n_out", 1))
+        if self.K != dataset.K:
+            raise ValueError(f"the model has {self.K} outputs but the dataset prescribes {dataset.K}")
         world, _ = _dist_info()
         if world > 1:
             raise ValueError("SystemTrainer is single-process: world_size > 1 is not supported")
-        self.B_res, self.n_ic, self.n_bc, dev = batch_prologue(model, batch_size, n_ic, n_bc, sampler)
-        self.model, self.device, self.K, self.sampler = model, dev, K, sampler
-        self.dataset = dataset.to(dev)
-        self.max_norm = max_norm
-        self.loss_weights = tuple(float(w) for w in loss_weights)
-        if not model._packed_ok() or model._flat.device != dev:
-            model._pack(dev)             # one flat buffer in model.parameters() order, parameters re-pointed at views
-        self.flat = model._flat
-        self.circuit = model._circuit(dev)
-        self.NP = self.flat.numel()
-        self.optimizer, self.scheduler = model.optimizer, model.scheduler
-        self.opt = self._make_opt_state(int(capacity))
+        self.has_r = dataset.R is not None
+        super().__init__(model, batch_size, dataset, n_ic, n_bc, loss_weights, max_norm, capacity, sampler)
+
+    def _make_step(self):
         ds = self.dataset
-        self.system = _lib.system_record(K, ds.n_eq, ds.terms, ds.eq_weights, ds.out_weights)
-        self.has_r = ds.R is not None
-        self.fs = _engine.SystemStep(self.circuit, model.hidden_width, self.flat, self.system, self.B_res, self.n_ic,
-                                     self.n_bc, self.opt, loss_weights=self.loss_weights, res_targets=self.has_r)
-        self._sampled = all(n_rows > 0 or n_batch == 0
-                            for n_batch, n_rows in zip((self.B_res, self.n_ic, self.n_bc), ds.sizes()))
-        if self._sampled:
-            self.fs.set_dataset(ds.segments())
-        self.fs.refresh_gates()
-        self.fs.set_sampler(int(torch.randint(0, 2 ** 62, (1,)).item()))
-        self._explicit = False
-        model._sync_fused_to_torch = self.sync_to_torch
-
-    # -- optimiser state: continue from the torch optimiser / scheduler objects of the model (FusedTrainer's rule)
-    def _make_opt_state(self, capacity):
-        return opt_state_from_torch(self.model.parameters(), self.optimizer, self.scheduler, self.device, capacity,
-                                    self.max_norm, self.loss_weights)
-
-    def sync_to_torch(self):
-        """Mirror the device optimiser record into model.optimizer / model.scheduler (``save_state`` calls this)."""
-        sync_opt_state_to_torch(self.opt, self.model.parameters(), self.optimizer, self.scheduler)
-
-    # -- batches
-    def sample(self):
-        """Rows of the dataset, drawn with replacement.  With the device sampler this only arms the next ``step()``."""
-        if not self._sampled:
-            raise ValueError("the dataset has an empty segment behind a non-empty batch: use load_batches(...)")
-        self._explicit = False
-        if self.sampler == "device":
-            return
-        self._explicit = True
-        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), batch_minor=True)
+        self.system = _lib.system_record(self.K, ds.n_eq, ds.terms, ds.eq_weights, ds.out_weights)
+        return _engine.SystemStep(self.circuit, self.model.hidden_width, self.flat, self.system, self.B_res, self.n_ic,
+                                  self.n_bc, self.opt, loss_weights=self.loss_weights, res_targets=self.has_r)
 
     def load_batches(self, X_ic, X_bc, X_res, targets):
         """Use given batches: ``targets`` = (U_ic (n_ic, K), U_bc (n_bc, K), R_res (B_res, n_eq) | None)."""
         U_ic, U_bc, R = targets
-        fs, dev, ds = self.fs, self.device, self.dataset
         if (X_ic.shape[0], X_bc.shape[0], X_res.shape[0]) != (self.n_ic, self.n_bc, self.B_res):
             raise ValueError(f"batches must hold ({self.n_ic}, {self.n_bc}, {self.B_res}) points")
         if (R is None) != (not self.has_r):
             raise ValueError("residual targets are given exactly when the dataset has them (R is None: zero targets)")
-        as32 = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev)
         for U, n, name in ((U_ic, self.n_ic, "U_ic"), (U_bc, self.n_bc, "U_bc")):
             if n and tuple(torch.as_tensor(U).shape) != (n, self.K):
                 raise ValueError(f"{name} must be ({n}, {self.K}): one value per point and output")
-        if R is not None and self.B_res and tuple(torch.as_tensor(R).shape) != (self.B_res, ds.n_eq):
-            raise ValueError(f"R_res must be ({self.B_res}, {ds.n_eq}): one value per point and equation")
+        n_eq = self.dataset.n_eq
+        if R is not None and self.B_res and tuple(torch.as_tensor(R).shape) != (self.B_res, n_eq):
+            raise ValueError(f"R_res must be ({self.B_res}, {n_eq}): one value per point and equation")
         self._explicit = True
-        if self.n_ic:
-            fs.X_val[: self.n_ic] = as32(X_ic)
-            fs.target_val[:, : self.n_ic] = as32(U_ic).t()
-        if self.n_bc:
-            fs.X_val[self.n_ic: self.n_ic + self.n_bc] = as32(X_bc)
-            fs.target_val[:, self.n_ic: self.n_ic + self.n_bc] = as32(U_bc).t()
-        if self.B_res:
-            fs.X_res[: self.B_res] = as32(X_res)
-            if R is not None:
-                fs.target_res[:, : self.B_res] = as32(R).t()
-
-    def step(self):
-        draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
-        self.fs.run(draw | _lib.QC_PHASE_GRADS | _lib.QC_PHASE_UPDATE)
-
-    def loss_history(self, steps=None):
-        return self.opt.loss_history(steps)
-
-    def losses(self):
-        rec = self.opt.read()
-        return (rec["loss"], rec["loss_res"], rec["loss_bc"], rec["loss_ic"]), rec["lr"]
+        fill_batches(self.fs, (self.B_res, self.n_ic, self.n_bc), (X_ic, X_bc, X_res), targets, batch_minor=True)

@@ -2,7 +2,7 @@
 qc_fused_pinn_balanced_step, the three log-variances trained on the device) beside the tabulated step (fixed weights,
 qc_fused_pinn_data_step) at the same shapes: cascade, 4 qubits, H = 50, B residual + B // 3 initial + B // 3 boundary points
 at B = 64 and B = 65 536 (BASELINE config 2).  The two steps alternate window by window on one device; each number is the
-min of `repeats` windows of `steps` steps after `warmup` steps, the method of tools/bench_inverse.py.  Prints one JSON
+min of `repeats` windows of `steps` steps after `warmup` steps, the method of tools/step_bench.py.  Prints one JSON
 object per batch size.
 
 ``--root DIR`` imports the package from another checkout of this repository (built there), and ``--modes`` selects the
@@ -12,88 +12,34 @@ steps: an A/B run of a parent commit that has no balanced step is
     python tools/bench_balanced.py --label change
 
 alternated in one call (profiles/balanced_step_bench_runs.txt)."""
-import argparse
-import importlib
 import json
-import os
-import sys
-import time
 
 import torch
 
-PKG = "qcpinn-convection-diffusion-qiskit_amd"
+import step_bench as sb
+
 MODES = ("tabulated", "balanced")
 
 
-class _Log:
-    def print(self, *a):
-        pass
-
-    def get_output_dir(self):
-        return "/tmp"
-
-
-def _model(dev):
-    Solver = importlib.import_module(PKG + ".nn.DVPDESolver").DVPDESolver
-    args = {"batch_size": 64, "epochs": 0, "lr": 0.005, "seed": 1, "print_every": 10 ** 9, "num_qubits": 4,
-            "num_quantum_layers": 1, "classic_network": [3, 50, 1], "q_ansatz": "cascade", "shots": 1024,
-            "problem": "diffusion", "solver": "DV", "encoding": "None", "use_ibm_hardware": False}
-    torch.manual_seed(1)
-    return Solver(args, _Log(), device=dev)
-
-
 def run(B, rows, steps, warmup, repeats, modes, label):
-    trainer = importlib.import_module(PKG + ".trainer.diffusion_train")
-    data = importlib.import_module(PKG + ".data.diffusion_dataset")
-    tab = importlib.import_module(PKG + ".data.tabulated")
     dev = torch.device("cuda", 0)
-    # the analytic problem's own targets and operator, tabulated: both steps train towards the same functions
-    gen = lambda: torch.Generator().manual_seed(0)
-    dataset = lambda: tab.TabulatedProblem.from_functions(data.u, data.u, data.r, rows, rows // 3, rows // 3, generator=gen())
     trs = {}
     if "tabulated" in modes:
-        trs["tabulated"] = trainer.FusedTrainer(_model(dev), B, capacity=0, dataset=dataset())
+        trs["tabulated"] = sb.pkg("trainer.diffusion_train").FusedTrainer(sb.model(dev), B, capacity=0, dataset=sb.dataset(rows))
     if "balanced" in modes:
-        balanced = importlib.import_module(PKG + ".trainer.balanced_train")
-        bal = importlib.import_module(PKG + ".nn.loss_balance").AdaptiveMultiLoss()
-        trs["balanced"] = balanced.BalancedTrainer(_model(dev), B, dataset(), bal, capacity=0)
-    for tr in trs.values():
-        for _ in range(warmup):
-            tr.sample()
-            tr.step()
-    torch.cuda.synchronize()
-    windows = {k: [] for k in trs}
-    for _ in range(repeats):
-        for k, tr in trs.items():
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                tr.sample()
-                tr.step()
-            torch.cuda.synchronize()
-            windows[k].append((time.perf_counter() - t0) / steps)
-    out = {"config": "balanced_vs_tabulated", "label": label, "n_qubits": 4, "B_res": B, "B_ic": B // 3, "B_bc": B // 3,
-           "dataset_rows": [rows, rows // 3, rows // 3],
-           "ms_per_step": {k: min(w) * 1e3 for k, w in windows.items()},
-           "ms_per_step_median": {k: sorted(w)[len(w) // 2] * 1e3 for k, w in windows.items()},
-           "ms_per_step_windows": {k: [round(x * 1e3, 5) for x in w] for k, w in windows.items()},
-           "loss": {k: tr.opt.read()["loss"] for k, tr in trs.items()}}
+        bal = sb.pkg("nn.loss_balance").AdaptiveMultiLoss()
+        trs["balanced"] = sb.pkg("trainer.balanced_train").BalancedTrainer(sb.model(dev), B, sb.dataset(rows), bal, capacity=0)
+    out = sb.report("balanced_vs_tabulated", sb.warm_up_and_alternate(trs, steps, warmup, repeats), label=label, n_qubits=4,
+                    B_res=B, B_ic=B // 3, B_bc=B // 3, dataset_rows=[rows, rows // 3, rows // 3])
+    out["loss"] = sb.losses(trs)
     if "balanced" in trs:
         out["weights"] = trs["balanced"].weights()
     print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = sb.arguments(modes=MODES)
     ap.add_argument("--batches", default="64,65536")
-    ap.add_argument("--rows", type=int, default=1 << 20, help="residual rows of the resident dataset (a third per value segment)")
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--modes", default=",".join(MODES))
-    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                    help="checkout to import the package (and its built library) from")
-    ap.add_argument("--label", default="")
-    a = ap.parse_args()
-    sys.path.insert(0, os.path.abspath(a.root))
+    a = sb.parse(ap)
     for b in a.batches.split(","):
         run(int(b), a.rows, a.steps, a.warmup, a.repeats, a.modes.split(","), a.label)

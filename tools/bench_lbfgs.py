@@ -12,33 +12,12 @@ against k_adam_fast.
 Convergence (``--convergence``): the same model on ONE fixed batch gathered from a TabulatedProblem of the analytic
 problem's targets: ``--adam`` Adam steps, then ``--evals`` more Adam steps against ``--evals`` L-BFGS evaluations; the loss
 every ``--every`` evaluations.  Prints one JSON object per line (profiles/lbfgs_step_bench_runs.txt)."""
-import argparse
-import importlib
 import json
-import os
-import sys
-import time
+import types
 
 import torch
 
-PKG = "qcpinn-convection-diffusion-qiskit_amd"
-
-
-class _Log:
-    def print(self, *a):
-        pass
-
-    def get_output_dir(self):
-        return "/tmp"
-
-
-def _model(dev):
-    Solver = importlib.import_module(PKG + ".nn.DVPDESolver").DVPDESolver
-    args = {"batch_size": 64, "epochs": 0, "lr": 0.005, "seed": 1, "print_every": 10 ** 9, "num_qubits": 4,
-            "num_quantum_layers": 1, "classic_network": [3, 50, 1], "q_ansatz": "cascade", "shots": 1024,
-            "problem": "diffusion", "solver": "DV", "encoding": "None", "use_ibm_hardware": False}
-    torch.manual_seed(1)
-    return Solver(args, _Log(), device=dev)
+import step_bench as sb
 
 
 def _fixed_batch(tr, L):
@@ -49,13 +28,11 @@ def _fixed_batch(tr, L):
 
 
 def time_steps(B, steps, warmup, repeats):
-    trainer = importlib.import_module(PKG + ".trainer.diffusion_train")
-    lbt = importlib.import_module(PKG + ".trainer.lbfgs_train")
-    L = importlib.import_module(PKG + ".hip.lib")
+    trainer, lbt, L = sb.pkg("trainer.diffusion_train"), sb.pkg("trainer.lbfgs_train"), sb.pkg("hip.lib")
     dev = torch.device("cuda", 0)
     loops, keep, lbs = {}, [], {}
     for name in ("adam", "adam_two_call", "lbfgs_m10", "lbfgs_m32"):
-        tr = trainer.FusedTrainer(_model(dev), B, capacity=0)
+        tr = trainer.FusedTrainer(sb.model(dev), B, capacity=0)
         _fixed_batch(tr, L)
         keep.append(tr)
         if name == "adam":
@@ -66,44 +43,30 @@ def time_steps(B, steps, warmup, repeats):
             lb = lbt.LbfgsTrainer(tr, history=int(name.split("_m")[1]), capacity=0)
             lbs[name] = lb
             loops[name] = lb.step
-    for fn in loops.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    windows = {k: [] for k in loops}
-    for _ in range(repeats):
-        for k, fn in loops.items():
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            torch.cuda.synchronize()
-            windows[k].append((time.perf_counter() - t0) / steps)
-    ms = {k: min(w) * 1e3 for k, w in windows.items()}
-    print(json.dumps({"config": "lbfgs_vs_adam_time", "n_qubits": 4, "B_res": B, "B_ic": B // 3, "B_bc": B // 3,
+    # the batches are fixed: a loop's "sample" does nothing
+    r = sb.report("lbfgs_vs_adam_time", sb.warm_up_and_alternate(
+        {k: types.SimpleNamespace(sample=lambda: None, step=fn) for k, fn in loops.items()}, steps, warmup, repeats))
+    ms = r["ms_per_step"]
+    print(json.dumps({"config": r["config"], "n_qubits": 4, "B_res": B, "B_ic": B // 3, "B_bc": B // 3,
                       "ms_per_evaluation": ms,
                       "two_call_form_ms": ms["adam_two_call"] - ms["adam"],
                       "kernel_vs_adam_tail_ms": {k: ms[k] - ms["adam_two_call"] for k in ("lbfgs_m10", "lbfgs_m32")},
-                      "ms_per_evaluation_windows": {k: [round(x * 1e3, 5) for x in w] for k, w in windows.items()},
+                      "ms_per_evaluation_windows": r["ms_per_step_windows"],
                       "lbfgs_records": {k: {f: v for f, v in o.state().items()
                                             if f in ("n_eval", "n_iter", "n_rejected", "n_pairs", "stalled", "f0")} for k, o in lbs.items()}}),
           flush=True)
 
 
 def convergence(B, rows, n_adam, evals, every, m):
-    trainer = importlib.import_module(PKG + ".trainer.diffusion_train")
-    lbt = importlib.import_module(PKG + ".trainer.lbfgs_train")
-    data = importlib.import_module(PKG + ".data.diffusion_dataset")
-    tab = importlib.import_module(PKG + ".data.tabulated")
-    L = importlib.import_module(PKG + ".hip.lib")
+    trainer, lbt, L = sb.pkg("trainer.diffusion_train"), sb.pkg("trainer.lbfgs_train"), sb.pkg("hip.lib")
     dev = torch.device("cuda", 0)
     out = {"config": "lbfgs_vs_adam_convergence", "n_qubits": 4, "B_res": B, "adam_steps_first": n_adam, "history": m,
            "evaluations": list(range(every, evals + 1, every))}
 
     def start():
-        ds = tab.TabulatedProblem.from_functions(data.u, data.u, data.r, rows, rows // 3, rows // 3,
-                                                 generator=torch.Generator().manual_seed(0))
+        ds = sb.dataset(rows)
         torch.manual_seed(3)
-        tr = trainer.FusedTrainer(_model(dev), B, capacity=0, dataset=ds)
+        tr = trainer.FusedTrainer(sb.model(dev), B, capacity=0, dataset=ds)
         _fixed_batch(tr, L)
         for _ in range(n_adam):
             tr.step()
@@ -137,21 +100,16 @@ def convergence(B, rows, n_adam, evals, every, m):
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = sb.arguments(rows=None)
     ap.add_argument("--batches", default="64,65536")
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--convergence", action="store_true")
     ap.add_argument("--rows", type=int, default=1 << 16, help="residual rows of the convergence run's dataset")
     ap.add_argument("--adam", type=int, default=1000)
     ap.add_argument("--evals", type=int, default=500)
     ap.add_argument("--every", type=int, default=50)
     ap.add_argument("--history", type=int, default=10)
-    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                    help="checkout to import the package (and its built library) from")
-    a = ap.parse_args()
-    sys.path.insert(0, os.path.abspath(a.root))
+    ap.add_argument("--root", default=sb.ROOT, help="checkout to import the package (and its built library) from")
+    a = sb.parse(ap)
     for b in a.batches.split(","):
         if a.convergence:
             convergence(int(b), a.rows, a.adam, a.evals, a.every, a.history)

@@ -5,38 +5,15 @@ SystemTrainer: device gather from a resident dataset + qc_fused_pinn_system_step
     outputs from qc_post_multi) -> three MSEs + the value MSEs -> backward -> clip_grad_norm_ -> torch Adam -> scheduler,
     on batches drawn with torch.randint from the same dataset,
 at B residual + B // 3 initial + B // 3 boundary points, B = 64 and B = 65 536.  The three alternate window by window on
-one device; each number is the min of `repeats` windows of `steps` steps after `warmup` steps, the protocol of
-tools/bench_tabulated.py.  Prints one JSON object per batch size."""
-import argparse
-import importlib
+one device; each number is the min of `repeats` windows of `steps` steps after `warmup` steps, the method of
+tools/step_bench.py.  Prints one JSON object per batch size."""
 import json
-import os
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-PKG = "qcpinn-convection-diffusion-qiskit_amd"
+import step_bench as sb
+
 W_EQ, W_OUT = (1.0, 1.0, 1.0), (1.0, 1.0, 0.0)       # the pressure is not prescribed on the boundary
-
-
-class _Log:
-    def print(self, *a):
-        pass
-
-    def get_output_dir(self):
-        return "/tmp"
-
-
-def _model(dev, K):
-    Solver = importlib.import_module(PKG + ".nn.DVPDESolver").DVPDESolver
-    args = {"batch_size": 64, "epochs": 0, "lr": 0.005, "seed": 1, "print_every": 10 ** 9, "num_qubits": 4,
-            "num_quantum_layers": 1, "classic_network": [3, 50, K], "q_ansatz": "cascade", "shots": 1024,
-            "problem": "diffusion", "solver": "DV", "encoding": "None", "use_ibm_hardware": False}
-    torch.manual_seed(1)
-    return Solver(args, _Log(), device=dev)
 
 
 class TorchLoop:
@@ -44,7 +21,7 @@ class TorchLoop:
 
     def __init__(self, model, B, ds):
         self.model, self.B, self.ds = model, B, ds
-        self.pde = importlib.import_module(PKG + ".nn.pde")
+        self.pde = sb.pkg("nn.pde")
         self.w_out = torch.tensor(W_OUT, device=ds.X_ic.device)
         self.loss = None
 
@@ -70,53 +47,32 @@ class TorchLoop:
 
 
 def run(B, rows, steps, warmup, repeats, torch_steps):
-    trainer = importlib.import_module(PKG + ".trainer.diffusion_train")
-    system_train = importlib.import_module(PKG + ".trainer.system_train")
-    data = importlib.import_module(PKG + ".data.diffusion_dataset")
-    tab = importlib.import_module(PKG + ".data.tabulated")
-    terms = importlib.import_module(PKG + ".nn.pde").navier_stokes_2D_terms()
+    tab = sb.pkg("data.tabulated")
+    terms = sb.pkg("nn.pde").navier_stokes_2D_terms()
     dev = torch.device("cuda", 0)
-    tp = tab.TabulatedProblem.from_functions(data.u, data.u, data.r, rows, rows // 3, rows // 3,
-                                             generator=torch.Generator().manual_seed(0))
+    tp = sb.dataset(rows)
     three = lambda u: torch.stack([u, 0.5 * u, torch.zeros_like(u)], 1).contiguous()
     ts = tab.TabulatedSystem((tp.X_res, None), (tp.X_ic, three(tp.u_ic)), (tp.X_bc, three(tp.u_bc)), terms, W_EQ, W_OUT).to(dev)
-    trs = {"system": system_train.SystemTrainer(_model(dev, 3), B, dataset=ts, capacity=0),
-           "tabulated_k1": trainer.FusedTrainer(_model(dev, 1), B, capacity=0, dataset=tp),
-           "torch_loop": TorchLoop(_model(dev, 3), B, ts)}
+    K3 = dict(classic_network=[3, 50, 3])
+    trs = {"system": sb.pkg("trainer.system_train").SystemTrainer(sb.model(dev, **K3), B, dataset=ts, capacity=0),
+           "tabulated_k1": sb.pkg("trainer.diffusion_train").FusedTrainer(sb.model(dev), B, capacity=0, dataset=tp),
+           "torch_loop": TorchLoop(sb.model(dev, **K3), B, ts)}
     n_steps = {"system": steps, "tabulated_k1": steps, "torch_loop": torch_steps}
-    for k, tr in trs.items():
-        for _ in range(min(warmup, n_steps[k])):
-            tr.sample()
-            tr.step()
-    torch.cuda.synchronize()
-    windows = {k: [] for k in trs}
-    for _ in range(repeats):
-        for k, tr in trs.items():
-            t0 = time.perf_counter()
-            for _ in range(n_steps[k]):
-                tr.sample()
-                tr.step()
-            torch.cuda.synchronize()
-            windows[k].append((time.perf_counter() - t0) / n_steps[k])
-    ms = {k: min(w) * 1e3 for k, w in windows.items()}
-    out = {"config": "navier_stokes_system", "n_qubits": 4, "hidden": 50, "outputs": 3, "B_res": B, "B_ic": B // 3, "B_bc": B // 3,
+    r = sb.report("navier_stokes_system", sb.warm_up_and_alternate(trs, steps, warmup, repeats, n_steps))
+    ms = r["ms_per_step"]
+    out = {"config": r["config"], "n_qubits": 4, "hidden": 50, "outputs": 3, "B_res": B, "B_ic": B // 3, "B_bc": B // 3,
            "dataset_rows": [rows, rows // 3, rows // 3], "steps_per_window": n_steps,
            "ms_per_step_system": ms["system"], "ms_per_step_tabulated_k1": ms["tabulated_k1"],
-           "ms_per_step_torch_loop": ms["torch_loop"],
-           "ms_per_step_median": {k: sorted(w)[len(w) // 2] * 1e3 for k, w in windows.items()},
+           "ms_per_step_torch_loop": ms["torch_loop"], "ms_per_step_median": r["ms_per_step_median"],
            "loss": {"system": trs["system"].opt.read()["loss"], "tabulated_k1": trs["tabulated_k1"].opt.read()["loss"],
                     "torch_loop": float(trs["torch_loop"].loss)}}
     print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = sb.arguments()
     ap.add_argument("--batches", default="64,65536")
-    ap.add_argument("--rows", type=int, default=1 << 20, help="residual rows of the resident dataset (a third per value segment)")
-    ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--torch-steps", type=int, default=20, help="steps per window of the torch loop (milliseconds per step)")
-    ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5)
-    a = ap.parse_args()
+    a = sb.parse(ap)
     for b in a.batches.split(","):
         run(int(b), a.rows, a.steps, a.warmup, a.repeats, a.torch_steps)
