@@ -43,7 +43,11 @@ int qc_last_hip_error(void); /* hipError_t of the last failing runtime call, 0 i
  * jet) at this position of the program.  A program that holds one is served for 2 <= n_qubits <= 5 by its own kernel
  * family (run-time interpreter, angle encoding, nothing kept between the forward and the adjoint pass, the fused step in
  * its two-stream form); for any other n_qubits the program is created but every circuit and step entry point returns
- * QC_ERR_UNSUPPORTED, and so does qc_program_set_encoding(prog, 1). */
+ * QC_ERR_UNSUPPORTED, and so does qc_program_set_encoding(prog, 1).
+ * EMBEDS=9 (wire_a = wire, wire_b = -1, 0 <= slot < n_params): the same gate with a trainable input scaling,
+ * RX(theta[slot] * x_wire); theta[slot] is a parameter like a gate angle (its gradient comes back in the same d_theta
+ * entry, several gates may share a slot).  Any other row with opcode 9 is QC_ERR_ARG.  It counts as an EMBED gate in
+ * everything above: the same family, the same refusals; an EMBED gate beside it keeps scale 1. */
 int qc_program_create(const int32_t* gate_rows, int n_gates, int n_qubits, int n_params, qc_program** out);
 int qc_program_destroy(qc_program* prog);
 size_t qc_trig_bytes(const qc_program* prog); /* size of the per-gate cos/sin workspace */

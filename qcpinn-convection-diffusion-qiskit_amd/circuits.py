@@ -26,8 +26,11 @@ OP_RX, OP_RY, OP_RZ, OP_H, OP_CNOT, OP_CRX, OP_CRZ, OP_U4 = range(8)
 # data re-uploading: RX(a_w(X)) on wire ``a`` at this position of the program, a_w the same per-point angle (and angle
 # jet) that the implicit initial embedding uses.  Not trainable: slot -1, not in PARAMETRIC.
 OP_EMBED = 8
-OP_NAMES = ("RX", "RY", "RZ", "H", "CNOT", "CRX", "CRZ", "U4", "EMBED")
-PARAMETRIC = (OP_RX, OP_RY, OP_RZ, OP_CRX, OP_CRZ)
+# the same gate with a trainable input scaling (Perez-Salinas et al. upload w.x): RX(theta[slot] * a_w(X)), slot >= 0.
+OP_EMBED_S = 9
+OP_NAMES = ("RX", "RY", "RZ", "H", "CNOT", "CRX", "CRZ", "U4", "EMBED", "EMBEDS")
+PARAMETRIC = (OP_RX, OP_RY, OP_RZ, OP_CRX, OP_CRZ, OP_EMBED_S)
+REUPLOAD_SCALES = (None, "wire", "layer")
 
 ANSATZ_NAMES = ("layered", "alternate", "cascade", "farhi", "sim_circ_15", "cross_mesh")
 
@@ -53,7 +56,7 @@ class Gate:
     op: int
     a: int          # target wire (1q gates), control wire (controlled), first wire (U4)
     b: int          # target wire (controlled), second wire (U4), -1 otherwise
-    slot: int       # flat parameter index (layer*P + k) for parametric gates, U4 slot, else -1
+    slot: int       # flat parameter index (layer*P + k) for parametric gates, U4 slot, EMBEDS scaling slot, else -1
 
     def as_row(self) -> Tuple[int, int, int, int]:
         return (self.op, self.a, self.b, self.slot)
@@ -182,7 +185,7 @@ class GateProgram:
     n_qubits: int
     n_layers: int
     q_ansatz: str
-    n_params: int                 # total trainable angles = n_layers * params_per_layer
+    n_params: int                 # total trainable angles = n_layers * params_per_layer (+ the EMBEDS scalings)
     use_haar: bool
     gates: List[Gate]
 
@@ -196,14 +199,16 @@ class GateProgram:
 
     def algorithmic_flops(self) -> int:
         """Real flops of one circuit evaluation under SURVEY.md §8(d)'s per-gate model
-        (FMA = 2): embedding RX 6N each (EMBED gates too), RX/RY/RZ 6N, CRX/CRZ 3N, CNOT 0, H 4N,
+        (FMA = 2): embedding RX 6N each (EMBED / EMBEDS gates too), RX/RY/RZ 6N, CRX/CRZ 3N, CNOT 0, H 4N,
         4x4 two-wire unitary 30N, <Z> for all wires (3+n)N, N = 2**n."""
         n, N = self.n_qubits, 1 << self.n_qubits
-        per = {OP_RX: 6, OP_RY: 6, OP_RZ: 6, OP_H: 4, OP_CNOT: 0, OP_CRX: 3, OP_CRZ: 3, OP_U4: 30, OP_EMBED: 6}
+        per = {OP_RX: 6, OP_RY: 6, OP_RZ: 6, OP_H: 4, OP_CNOT: 0, OP_CRX: 3, OP_CRZ: 3, OP_U4: 30, OP_EMBED: 6,
+               OP_EMBED_S: 6}
         return (6 * n + sum(per[g.op] for g in self.gates) + 3 + n) * N
 
 
-def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool, reupload: bool = False) -> GateProgram:
+def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool, reupload: bool = False,
+                  reupload_scale: Optional[str] = None) -> GateProgram:
     """Lower ``q_ansatz`` on ``n_qubits`` wires x ``n_layers`` into a gate program.
 
     ``use_haar`` mirrors the reference's gating (``nn/DVQuantumLayer.py:88-94,203-209``):
@@ -213,12 +218,26 @@ def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool, r
     embeds in front of every entangling layer): an EMBED layer on wires 0..n-1 in front of every ansatz layer after the
     first; layer 0 keeps the implicit embedding.  Slots, ``n_params``, the fixed unitaries and the final Hadamard do not
     change, and with one layer the program is the plain one.
+
+    ``reupload_scale`` (needs ``reupload``): ``"wire"`` or ``"layer"`` turns every EMBED row into an EMBEDS row, a
+    trainable scaling of the re-uploaded angle.  The scalings sit behind the ansatz slots, which do not move:
+    ``"wire"`` uses slot ``L P + (l - 1) n + w`` (one per layer and wire), ``"layer"`` slot ``L P + (l - 1)`` for the n
+    gates of layer l; ``n_params`` grows by ``(L - 1) n`` or ``L - 1``.
     """
+    if reupload_scale not in REUPLOAD_SCALES:
+        raise ValueError(f"reupload_scale must be one of {REUPLOAD_SCALES}, got {reupload_scale!r}")
+    if reupload_scale is not None and not reupload:
+        raise ValueError("reupload_scale needs reupload=True: there is no re-uploaded angle to scale")
     P = params_per_layer(q_ansatz, n_qubits)
+    base = n_layers * P
     gates: List[Gate] = []
     for layer in range(n_layers):
         if reupload and layer > 0:
-            gates += [Gate(OP_EMBED, w, -1, -1) for w in range(n_qubits)]
+            if reupload_scale is None:
+                gates += [Gate(OP_EMBED, w, -1, -1) for w in range(n_qubits)]
+            else:
+                per = n_qubits if reupload_scale == "wire" else 1
+                gates += [Gate(OP_EMBED_S, w, -1, base + (layer - 1) * per + (w if per > 1 else 0)) for w in range(n_qubits)]
         e = _Emitter(n_qubits, layer * P, P)
         _BUILDERS[q_ansatz](e)
         gates += e.gates
@@ -229,7 +248,8 @@ def build_program(q_ansatz: str, n_qubits: int, n_layers: int, use_haar: bool, r
         gates.append(Gate(OP_U4, 2, 3, 1))
     if n_qubits > 0:
         gates.append(Gate(OP_H, n_qubits - 1, -1, -1))
-    return GateProgram(n_qubits, n_layers, q_ansatz, n_layers * P, use_haar, gates)
+    n_scale = 0 if reupload_scale is None else (n_layers - 1) * (n_qubits if reupload_scale == "wire" else 1)
+    return GateProgram(n_qubits, n_layers, q_ansatz, base + n_scale, use_haar, gates)
 
 
 ROT_RING = "rot_ring"      # GateProgram.q_ansatz of build_rot_ring_program (not a DVQuantumLayer ansatz)

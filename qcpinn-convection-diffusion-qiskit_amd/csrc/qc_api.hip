@@ -121,16 +121,22 @@ const char* qc_error_string(int code) {
 int qc_last_hip_error(void) { return g_last_hip; }
 
 // gate rows (opcode, wire_a, wire_b, slot) -> bit-indexed gates; returns false on an invalid row.  EMBED rows
-// (wire, -1, -1) are valid only for a caller that counts them (n_embed_out): the plan describers never see one
+// (wire, -1, -1) and EMBED_S rows (wire, -1, slot) are valid only for a caller that counts them (n_embed_out): the plan
+// describers never see one
 static bool parse_rows(const int32_t* rows, int n_gates, int n_qubits, int n_params, QcGate* h, int* n_u4_out,
-                       int* n_embed_out = nullptr) {
-  int n_u4 = 0, n_embed = 0;
+                       int* n_embed_out = nullptr, int* scaled_out = nullptr) {
+  int n_u4 = 0, n_embed = 0, scaled = 0;
   for (int g = 0; g < n_gates; ++g) {
     const int op = rows[4 * g], a = rows[4 * g + 1], b = rows[4 * g + 2], slot = rows[4 * g + 3];
-    bool ok = op >= QC_RX && op <= QC_EMBED && a >= 0 && a < n_qubits;
+    bool ok = op >= QC_RX && op <= QC_EMBED_S && a >= 0 && a < n_qubits;
     if (op == QC_EMBED) {
       ok = ok && n_embed_out != nullptr && b == -1 && slot == -1;
       ++n_embed;
+    }
+    if (op == QC_EMBED_S) {   // the scaling is a parameter: a slot is required
+      ok = ok && n_embed_out != nullptr && scaled_out != nullptr && b == -1 && slot >= 0 && slot < n_params;
+      ++n_embed;
+      scaled = 1;
     }
     const bool two = (op == QC_CNOT || op == QC_CRX || op == QC_CRZ || op == QC_U4);
     if (two) ok = ok && b >= 0 && b < n_qubits && b != a;
@@ -144,10 +150,11 @@ static bool parse_rows(const int32_t* rows, int n_gates, int n_qubits, int n_par
     h[g].op = op;
     h[g].ba = n_qubits - 1 - a;
     h[g].bb = two ? n_qubits - 1 - b : -1;
-    h[g].slot = (par || op == QC_U4) ? slot : -1;
+    h[g].slot = (par || op == QC_U4 || op == QC_EMBED_S) ? slot : -1;
   }
   *n_u4_out = n_u4;
   if (n_embed_out) *n_embed_out = n_embed;
+  if (scaled_out) *scaled_out = scaled;
   return true;
 }
 // RX(p_w) right after the embedding RX(a_w), wire by wire, distinct slots
@@ -181,7 +188,7 @@ int qc_program_create(const int32_t* rows, int n_gates, int n_qubits, int n_para
   }
   p->n_qubits = n_qubits; p->n_gates = n_gates; p->n_params = n_params;
   p->h_gates = h;
-  if (!parse_rows(rows, n_gates, n_qubits, n_params, h, &p->n_u4, &p->n_embed)) {
+  if (!parse_rows(rows, n_gates, n_qubits, n_params, h, &p->n_u4, &p->n_embed, &p->embed_scaled)) {
     qc_program_destroy(p);
     return QC_ERR_ARG;
   }

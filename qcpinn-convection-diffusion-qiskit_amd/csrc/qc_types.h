@@ -11,7 +11,7 @@
 #define QC_ERR_ALLOC (-4)
 
 // ---- gate opcodes: must match circuits.py
-enum QcOp : int { QC_RX = 0, QC_RY = 1, QC_RZ = 2, QC_H = 3, QC_CNOT = 4, QC_CRX = 5, QC_CRZ = 6, QC_U4 = 7, QC_EMBED = 8 };
+enum QcOp : int { QC_RX = 0, QC_RY = 1, QC_RZ = 2, QC_H = 3, QC_CNOT = 4, QC_CRX = 5, QC_CRZ = 6, QC_U4 = 7, QC_EMBED = 8, QC_EMBED_S = 9 };
 
 // One gate of the device-resident program.  `ba`/`bb` are BIT positions of the amplitude
 // index (bit = n-1-wire: wire 0 is the most significant bit), not wires.
@@ -54,5 +54,6 @@ struct qc_program {
   int ff_m;             // Fourier-feature input map of that pre network: frequencies (0: none) and the library's device
   float* d_ff_freq;     // copy of B, [3][ff_m] (qc_program_set_input_map)
   int n_embed;          // EMBED gates (data re-uploading: RX of the per-point angle inside the program); > 0: the
-                        // re-uploading family or none
+                        // re-uploading family or none.  Counts EMBED_S gates too
+  int embed_scaled;     // 1: at least one of them is an EMBED_S gate (RX(theta[slot] * a_w)): the SCALED kernels
 };

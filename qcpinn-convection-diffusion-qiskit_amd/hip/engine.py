@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from ..circuits import GateProgram
+from ..circuits import OP_EMBED_S, GateProgram
 
 NCH = 6  # derivative channels: value, d/dt, d/dx, d/dy, d2/dx2, d2/dy2
 
@@ -30,10 +30,12 @@ def _need(t: torch.Tensor, device, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def param_layout(H: int, n: int, n_theta: int, K: int = 1, n_in: int = 3) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
+def param_layout(H: int, n: int, n_theta: int, K: int = 1, n_in: int = 3, n_scale: int = 0) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
     """Offsets/shapes of the flat parameter vector = the reference's ``model.parameters()`` order
     (nn/DVPDESolver.py:28-57: preprocessor, postprocessor, quantum_layer); ``K`` outputs: K rows in the last layer;
-    ``n_in`` columns of the first layer: 3, or 2 m behind a Fourier-feature map of m frequencies (sines, then cosines)."""
+    ``n_in`` columns of the first layer: 3, or 2 m behind a Fourier-feature map of m frequencies (sines, then cosines).
+    ``quantum_layer.params`` spans the whole theta vector of the gate program; its last ``n_scale`` entries, the trainable
+    input scalings of a re-uploaded layer, are named once more as ``quantum_layer.embed_scale``."""
     out, off = {}, 0
     for name, shape in (("preprocessor.0.weight", (H, n_in)), ("preprocessor.0.bias", (H,)),
                         ("preprocessor.2.weight", (n, H)), ("preprocessor.2.bias", (n,)),
@@ -43,6 +45,8 @@ def param_layout(H: int, n: int, n_theta: int, K: int = 1, n_in: int = 3) -> Dic
         out[name] = (off, shape)
         off += int(np.prod(shape))
     out["__total__"] = (off, ())
+    if n_scale:
+        out["quantum_layer.embed_scale"] = (off - int(n_scale), (int(n_scale),))
     return out
 
 
@@ -73,6 +77,8 @@ class Circuit:
         self.device = device
         self.n = program.n_qubits
         self.n_params = program.n_params
+        # trainable input scalings of a re-uploaded program (EMBEDS gates): the tail of theta, behind the ansatz slots
+        self.n_scale = len({g.slot for g in program.gates if g.op == OP_EMBED_S})
         rows = np.ascontiguousarray(program.rows())
         self.handle = C.c_void_p()
         with torch.cuda.device(device):
@@ -241,7 +247,7 @@ class SolverEngine:
         # behind an input map the first layer is [H][2m]; the post stage addresses nothing in front of W3, so qc_post* take
         # the flat vector and the gradient rows from `post_shift` entries further on and see their own [H][3] offsets
         self.ff_m = circuit.ff_m
-        self.layout = param_layout(self.H, self.n, self.n_theta, n_in=circuit.n_in)
+        self.layout = param_layout(self.H, self.n, self.n_theta, n_in=circuit.n_in, n_scale=circuit.n_scale)
         self.post_shift = (circuit.n_in - 3) * self.H
         self.NP = self.layout["__total__"][0]
         self.theta_off = self.layout["quantum_layer.params"][0]
@@ -535,7 +541,7 @@ class _Step:
         dev, n = circuit.device, circuit.n
         self.device, self.n, self.H, self.n_theta = dev, n, int(hidden), circuit.n_params
         check_network_shape(self.H, n)
-        self.layout = param_layout(self.H, n, self.n_theta, K, n_in=circuit.n_in)     # the step reads the map from the program
+        self.layout = param_layout(self.H, n, self.n_theta, K, n_in=circuit.n_in, n_scale=circuit.n_scale)     # the step reads the map from the program
         self.NP = self.layout["__total__"][0]
         self.theta_off = self.layout["quantum_layer.params"][0]
         NP_total = self.NP + self.N_OWN

@@ -22,6 +22,12 @@ front of every ansatz layer after the first (``circuits.OP_EMBED``; the referenc
 Parameters, their count and their initial values are those of the plain layer; ``create_graph=True`` goes through the
 derivative-channel kernels, since such a layer is a degree-L trigonometric polynomial per wire.
 
+``args["reupload_scale"]`` (``"wire"``, ``"layer"``; ``True`` = ``"wire"``; needs ``reupload``): trainable input scalings of
+the re-uploaded angles, RX(s a_w) with one s per later layer and wire (or per later layer), the w.x of Perez-Salinas et al.
+A second Parameter ``embed_scale`` (L - 1, n) or (L - 1, 1), ones at initialisation, registered behind ``params``; the
+kernels' theta vector is ``cat(params.flatten(), embed_scale.flatten())``.  With one layer there is nothing to scale and
+``embed_scale`` is None.
+
 Out of scope, by design: IBM Runtime devices / shot-based execution
 (``use_ibm_hardware=True``) are refused with an explicit error.
 """
@@ -207,10 +213,24 @@ class DVQuantumLayer(nn.Module):
                 raise ValueError("reupload=True needs the angle encoding: amplitude encoding has no angle to re-upload")
             if not 2 <= self.num_qubits <= 5:
                 raise ValueError(f"reupload=True is built for 2 <= num_qubits <= 5, got num_qubits={self.num_qubits}")
+        # trainable input scalings of the re-uploaded angles: None | "wire" (True) | "layer"
+        scale = args.get("reupload_scale", None)
+        scale = None if scale is None or scale is False else ("wire" if scale is True else scale)
+        if scale not in circuits.REUPLOAD_SCALES:
+            raise ValueError(f"reupload_scale must be None, False, True, 'wire' or 'layer', got {scale!r}")
+        if scale is not None and not self.reupload:
+            raise ValueError("reupload_scale needs reupload=True: there is no re-uploaded angle to scale")
+        self.reupload_scale = scale
 
         per_layer = circuits.params_per_layer(self.q_ansatz, self.num_qubits)   # ValueError on unknown ansatz
         self.params = nn.Parameter(torch.empty(self.num_quantum_layers, per_layer, dtype=torch.float32))
         torch.nn.init.xavier_normal_(self.params)
+        # registered AFTER params: model.parameters() order = the kernels' theta layout (ansatz slots, then the scalings)
+        if self.reupload_scale is not None and self.num_quantum_layers > 1:
+            self.embed_scale = nn.Parameter(torch.ones(self.num_quantum_layers - 1,
+                                                       self.num_qubits if self.reupload_scale == "wire" else 1, dtype=torch.float32))
+        else:
+            self.embed_scale = None
 
         seed = args.get("seed", None) if self.num_qubits >= 4 else None
         self.haar_seed1 = seed
@@ -224,8 +244,9 @@ class DVQuantumLayer(nn.Module):
         self.dev = "hip.statevector"
         # lowered once; raises the same IndexError the reference hits for over-indexed ansaetze
         self.program = circuits.build_program(self.q_ansatz, self.num_qubits, self.num_quantum_layers,
-                                              self.haar_seed1 is not None, reupload=self.reupload)
-        self.has_embed_gates = any(g.op == circuits.OP_EMBED for g in self.program.gates)
+                                              self.haar_seed1 is not None, reupload=self.reupload,
+                                              reupload_scale=self.reupload_scale)
+        self.has_embed_gates = any(g.op in (circuits.OP_EMBED, circuits.OP_EMBED_S) for g in self.program.gates)
         self._haar = circuits.haar_unitaries(self.haar_seed1, self.haar_seed2)
         self._circuits = {}
 
@@ -243,7 +264,14 @@ class DVQuantumLayer(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 2 or x.shape[1] != self.num_qubits:
             raise ValueError(f"expected angles of shape (B, {self.num_qubits}), got {tuple(x.shape)}")
-        return _ExpvalFn.apply(x, self.params, self)
+        return _ExpvalFn.apply(x, self.theta(), self)
+
+    def theta(self) -> torch.Tensor:
+        """The kernels' parameter vector as ONE differentiable tensor: ``params`` itself, or with input scalings
+        ``cat(params.flatten(), embed_scale.flatten())`` (autograd splits the gradient)."""
+        if self.embed_scale is None:
+            return self.params
+        return torch.cat([self.params.reshape(-1), self.embed_scale.reshape(-1)])
 
     def trig_interpolant(self, x: torch.Tensor, params: torch.Tensor = None) -> torch.Tensor:
         """The same (n, B) expectation values as ``forward`` written as a trigonometric polynomial of the
@@ -252,7 +280,7 @@ class DVQuantumLayer(nn.Module):
         if self.has_embed_gates:
             raise ValueError("trig_interpolant: a re-uploaded layer is a degree-L trigonometric polynomial per wire, not "
                              "the degree-1 form interpolated here")
-        params = self.params if params is None else params
+        params = self.theta() if params is None else params
         C = _TrigCoeffFn.apply(params, self, x.device)                       # (n, 3^n)
         return C @ _trig_features(x.to(torch.float32)).t()
 

@@ -38,7 +38,8 @@ class SystemTrainer(DatasetTrainer):
             raise ValueError("SystemTrainer needs classic_network = [3, H, K]: a two-input model keeps a zero-padded t column "
                              "in W1 that the step would train")
         if getattr(getattr(model, "quantum_layer", None), "reupload", False):
-            raise ValueError("SystemTrainer does not take a re-uploaded circuit (args['reupload']): train it with FusedTrainer")
+            raise ValueError("SystemTrainer does not take a re-uploaded circuit (args['reupload'], with or without "
+                             "args['reupload_scale']): train it with FusedTrainer")
         self.K = int(getattr(model, "n_out", 1))
         if self.K != dataset.K:
             raise ValueError(f"the model has {self.K} outputs but the dataset prescribes {dataset.K}")
