@@ -823,6 +823,77 @@ int qc_gradnorm_fold(float* part_dev, int64_t rows, int64_t rows_res, int64_t ro
 int qc_fused_pinn_gradnorm_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef* coef,
                                 const qc_step_gradnorm* gn, int phases, void* stream);
 
+/* ---- a seventh derivative channel, d2/dt2: equations that are second order in time over TWO space dimensions.  The
+ * reference's wave_operator and klein_gordon_operator (nn/pde.py:28-52) differentiate a two-input model twice in each of its
+ * inputs, so with the six channels above they are 1-D in space ((t, x) on the x / y slots); a three-input model needs u_tt
+ * beside u_xx and u_yy.  Every entry point below is its six-channel counterpart on jets [7][n][B]: channels 0..5 as at the
+ * head of this file, channel 6 = d2/dt2.  Operator rows have 8 columns, the seven of QC_COEF_COLS and d_tt:
+ *   res_p = c_u u + c_3 u^3 + c_t u_t + c_x u_x + c_y u_y - (d_xx u_xx + d_yy u_yy + d_tt u_tt)
+ * (wave equation u_tt - c^2 (u_xx + u_yy) = 0: d_tt = -1, d_xx = d_yy = c^2; telegraph: c_t = a as well; 2-D Klein-Gordon
+ * u_tt + alpha (u_xx + u_yy) + beta u + gamma u^3: d_tt = -1, d_xx = d_yy = -alpha, c_u = beta, c_3 = gamma).  A condition on
+ * u_t (the second initial condition of a wave problem) is a residual row (0, 1, 0, 0, 0, 0, 0, 0) with the prescribed
+ * velocity as its target.  Flat parameter vector, partial rows and loss columns are unchanged.
+ * Served: programs of the register family (2 <= n <= 5) without EMBED / EMBEDS gates, angle encoding, no input map
+ * (qc_program_set_input_map), angle map QC_ANGLE_MAP_NONE; the circuit stages run the gate program as run-time data and
+ * recompute the forward sweep in the adjoint kernel (nothing is kept between them, no workspace).  Anything else:
+ * QC_ERR_UNSUPPORTED before any launch, nothing written; the pre / post stages alone return it for n outside 2..5. */
+#define QC_NCH_TT 7
+#define QC_COEF_TT_COLS 8   /* c_u, c_t, c_x, c_y, d_xx, d_yy, c_3, d_tt */
+
+/* qc_pre_forward / qc_pre_backward with nch fixed at 7: ajets_dev / abar_dev are [7][n][B];
+ * a_tt[i] = sum_j W2[i][j] tanh''(s_j) W1[j][0]^2.  The reverse stage writes the W1, b1, W2, b2 columns of the tile rows. */
+int qc_pre_forward_tt(const float* X_dev /*[B][3]*/, const float* params_dev, int H, int n, int n_theta, float* ajets_dev,
+                      int64_t B, void* stream);
+int qc_pre_backward_tt(const float* X_dev, const float* params_dev, int H, int n, int n_theta, const float* abar_dev,
+                       float* part_dev, int64_t part_stride, int64_t row0, int64_t B, void* stream);
+
+/* qc_forward_jets / qc_backward_jets on [7][n][B]: q_tt[w] = 2 Re<chi_0|Z_w|chi_tt> + 2 <chi_t|Z_w|chi_t> with chi_tt built
+ * from (a_t, a_tt).  The reverse stage writes d_theta as partial rows at columns [0, n_params) of part_dev.  Two calls on
+ * equal inputs give the same bits. */
+int qc_forward_jets_tt(const qc_program* prog, const void* trig_dev, const float* umat_dev, const float* ajets_dev,
+                       float* qjets_dev, int64_t B, void* stream);
+int qc_backward_jets_tt(const qc_program* prog, const void* trig_dev, const float* umat_dev, const float* ajets_dev,
+                        const float* qbar_dev, float* abar_dev, float* part_dev, int64_t part_stride, int64_t row0, int64_t B,
+                        void* stream);
+
+/* qc_post_coef with coef_dev[8][B], cot_dev[7][B] and qjets / qbar [7][n][B] (pde->problem = QC_PROBLEM_TABULATED; w_res and
+ * inv_n_res are read).  cot_dev receives the per-point cotangents of the seven channels of u: with g = w_res (res - target),
+ *   (c_u + 3 c_3 u^2) g,  g c_t,  g c_x,  g c_y,  -d_xx g,  -d_yy g,  -d_tt g.
+ * The tile rows receive the W3, b3, W4, b4 columns (b4: the sum of the first cotangent) and the three loss columns. */
+int qc_post_coef_tt(const float* params_dev, int H, int n, int n_theta, const qc_pde* pde, const float* qjets_dev,
+                    const float* target_dev, const float* coef_dev, float* cot_dev, float* qbar_dev, float* part_dev,
+                    int64_t part_stride, int64_t row0, int64_t B, void* stream);
+/* qc_post modes 4 and 3 with seven channels (what a model's jets_tt and its backward ask for): mode 4: qjets -> the seven
+ * channels of u, io_dev = [7][B] (written); mode 3: io_dev = [7][B] cotangents of those channels (read) -> qbar jets and the
+ * W3, b3, W4, b4 columns of the tile rows.  Any other mode: QC_ERR_ARG. */
+int qc_post_jets_tt(int mode, const float* params_dev, int H, int n, int n_theta, const float* qjets_dev, float* io_dev,
+                    float* qbar_dev, float* part_dev, int64_t part_stride, int64_t row0, int64_t B, void* stream);
+
+typedef struct qc_step_coef_tt {
+  float* coef_res_dev;      /* [8][B_res] batch-minor: the rows of the CURRENT residual batch */
+  const float* ds_coef;     /* [ds_n_res][8] row-major, beside data->ds_X_res / ds_r: gathered with them under SAMPLE */
+} qc_step_coef_tt;
+
+/* qc_sample_dataset_coef for 8-column rows: coef_res_dev[k * n_res + i] = coef->ds_coef[idx * 8 + k], idx the row index
+ * qc_sample_dataset draws on the same seed, step and offsets (same Philox counters), so points and targets are bit-identical
+ * to its.  The rows travel through the dataset gather kernel in a second launch on the same counters.  coef_res_dev and
+ * coef->ds_coef may be NULL only with n_res = 0. */
+int qc_sample_dataset_coef_tt(float* X_res_dev, float* target_res_dev, int64_t n_res, int64_t off_res, float* X_val_dev,
+                              float* target_val_dev, int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc,
+                              float* coef_res_dev, const qc_step_data* data, const qc_step_coef_tt* coef, uint64_t seed,
+                              uint64_t step, void* stream);
+
+/* qc_fused_pinn_coef_step with the seven-channel residual pipeline: the four residual buffers of desc hold 7 n B_res floats
+ * each (the [7][B_res] cotangent scratch is the head of abar_res_dev), coef->coef_res_dev is [8][B_res]; desc->pde.c_t .. d_yy
+ * and data->c_u are not read.  The value batch goes through the one-channel kernels of every other step.  Always the
+ * two-stream form; row fold, optimiser launch, phases and desc->comm as in the data step.  No circuit workspace is needed:
+ * circ_ws_dev / circ_ws_bytes may be NULL / 0 and are not read.
+ * QC_ERR_UNSUPPORTED before any launch: what the head of this section lists.  QC_ERR_ARG before any launch: desc, data or
+ * coef NULL; a problem id other than QC_PROBLEM_TABULATED; coef_res_dev NULL with B_res > 0; QC_PHASE_SAMPLE with ds_coef NULL
+ * and B_res > 0; a NULL residual buffer with B_res > 0; whatever qc_fused_pinn_coef_step refuses. */
+int qc_fused_pinn_coef_tt_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef_tt* coef, int phases,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1332,4 +1332,184 @@ int qc_dataset_scores(const qc_step_desc* d, const qc_step_data* t, const qc_ste
   return QC_OK;
 }
 
+// ---- seven derivative channels (channel 6 = d2/dt2): stages and the coefficient step for equations second order in time
+static_assert(QC_NCH_TT_N == QC_NCH_TT && QC_COEF_TT_N == QC_COEF_TT_COLS && QC_COEF_TT_N == QC_COEF_N + 1, "seven-channel counts");
+// THE rule of what the seven-channel stages serve: the register family's qubit counts (whatever QC_FORCE_WAVE says: they
+// have their own kernels), no EMBED gates, angle encoding, plain inputs, no angle map
+static bool tt_prog_ok(const qc_program* p) {
+  return p->n_qubits >= 2 && p->n_qubits <= 5 && p->n_embed == 0 && !p->amplitude && p->ff_m == 0 &&
+         p->angle_map == QC_ANGLE_MAP_NONE;
+}
+static int check_mlp_tt(int H, int n, int n_theta, int64_t B) {
+  const int rc = check_mlp(H, n, n_theta, B, 6);
+  if (rc) return rc;
+  return (n >= 2 && n <= 5) ? QC_OK : QC_ERR_UNSUPPORTED;
+}
+
+int qc_pre_forward_tt(const float* X, const float* prm, int H, int n, int n_theta, float* ajets, int64_t B, void* stream) {
+  if (!X || !prm || !ajets) return QC_ERR_ARG;
+  int rc = check_mlp_tt(H, n, n_theta, B);
+  if (rc) return rc;
+  rc = qc_tt_pre_fwd(X, prm, make_layout(H, n, n_theta), ajets, B, (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+int qc_pre_backward_tt(const float* X, const float* prm, int H, int n, int n_theta, const float* abar, float* part,
+                       int64_t part_stride, int64_t row0, int64_t B, void* stream) {
+  if (!X || !prm || !abar || !part || row0 < 0) return QC_ERR_ARG;
+  int rc = check_mlp_tt(H, n, n_theta, B);
+  if (rc) return rc;
+  const QcLayout L = make_layout(H, n, n_theta);
+  if (part_stride < L.NP) return QC_ERR_ARG;
+  rc = qc_tt_pre_bwd(X, prm, L, abar, part, part_stride, row0, B, (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+int qc_forward_jets_tt(const qc_program* p, const void* trig, const float* umat, const float* ajets, float* qjets, int64_t B,
+                       void* stream) {
+  if (!p || !trig || B <= 0 || !ajets || !qjets || (p->n_u4 > 0 && !umat)) return QC_ERR_ARG;
+  if (!tt_prog_ok(p)) return QC_ERR_UNSUPPORTED;
+  const int rc = qc_tt_circ_fwd(p, (const QcTrig*)trig, umat, ajets, qjets, B, (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+int qc_backward_jets_tt(const qc_program* p, const void* trig, const float* umat, const float* ajets, const float* qbar,
+                        float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, void* stream) {
+  if (!p || !trig || B <= 0 || !ajets || !qbar || !abar || !part || (p->n_u4 > 0 && !umat)) return QC_ERR_ARG;
+  if (part_stride < p->n_params || row0 < 0) return QC_ERR_ARG;
+  if (!tt_prog_ok(p)) return QC_ERR_UNSUPPORTED;
+  const int rc = qc_tt_circ_bwd(p, (const QcTrig*)trig, umat, ajets, qbar, abar, part, part_stride, row0, B, (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+int qc_post_coef_tt(const float* prm, int H, int n, int n_theta, const qc_pde* pde, const float* qjets, const float* target,
+                    const float* coef, float* cot, float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B,
+                    void* stream) {
+  if (!prm || !pde || !qjets || !target || !coef || !cot || !qbar || !part || row0 < 0) return QC_ERR_ARG;
+  if (pde->problem != QC_PROBLEM_TABULATED) return QC_ERR_ARG;
+  int rc = check_mlp_tt(H, n, n_theta, B);
+  if (rc) return rc;
+  const QcLayout L = make_layout(H, n, n_theta);
+  if (part_stride < L.NP + 3) return QC_ERR_ARG;
+  rc = qc_tt_post(2, prm, L, to_pde(pde), qjets, target, coef, cot, qbar, part, part_stride, row0, B, (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+int qc_post_jets_tt(int mode, const float* prm, int H, int n, int n_theta, const float* qjets, float* io, float* qbar,
+                    float* part, int64_t part_stride, int64_t row0, int64_t B, void* stream) {
+  if ((mode != 3 && mode != 4) || !prm || !qjets || !io) return QC_ERR_ARG;
+  int rc = check_mlp_tt(H, n, n_theta, B);
+  if (rc) return rc;
+  const QcLayout L = make_layout(H, n, n_theta);
+  if (mode == 3 && (!qbar || !part || row0 < 0 || part_stride < L.NP)) return QC_ERR_ARG;
+  QcPde pde;
+  memset(&pde, 0, sizeof(pde));   // not read by these modes
+  rc = qc_tt_post(mode, prm, L, pde, qjets, nullptr, nullptr, io, qbar, part, part_stride, row0, B, (hipStream_t)stream);
+  return rc ? rc : after_launch();
+}
+
+// the operator rows of the residual batch: the dataset gather once more, on the counters of the gather that filled the
+// points (same row index), with the 8-column table as the residual segment's target rows
+static int tt_gather_coef(const QcBatches& b, const qc_step_data* t, float* coef_res, const float* ds_coef, void* stream) {
+  if (b.n_res <= 0) return QC_OK;
+  if (!coef_res || !ds_coef) return QC_ERR_ARG;
+  QcSource s;
+  s.kind = QC_SOURCE_ROWS;
+  s.res = {t->ds_X_res, ds_coef, t->ds_n_res};
+  s.w_res = QC_COEF_TT_N;
+  return fill_batches({b.X_res, coef_res, b.n_res, b.off_res, nullptr, nullptr, 0, 0, 0, 0, b.seed, b.step}, s, stream);
+}
+
+int qc_sample_dataset_coef_tt(float* X_res, float* target_res, int64_t n_res, int64_t off_res, float* X_val, float* target_val,
+                              int64_t n_ic, int64_t off_ic, int64_t n_bc, int64_t off_bc, float* coef_res, const qc_step_data* t,
+                              const qc_step_coef_tt* cf, uint64_t seed, uint64_t step, void* stream) {
+  if (!t || !cf) return QC_ERR_ARG;
+  const QcBatches b = {X_res, target_res, n_res, off_res, X_val, target_val, n_ic, off_ic, n_bc, off_bc, seed, step};
+  const QcSource src = make_source(t, nullptr, nullptr, nullptr);
+  if (!src.ok(b) || (n_res > 0 && (!coef_res || !cf->ds_coef))) return QC_ERR_ARG;   // nothing is written on a refusal
+  const int rc = fill_batches(b, src, stream);
+  return rc ? rc : tt_gather_coef(b, t, coef_res, cf->ds_coef, stream);
+}
+
+// the residual pipeline of the seven-channel step, on one stream: pre -> circuit -> post (coefficient form) -> circuit
+// adjoint -> pre adjoint.  The [7][B_res] channel cotangents are the head of abar_res_dev (written by the adjoint sweep only)
+static int tt_run_pipeline(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef_tt* cf, const QcLayout& L,
+                           hipStream_t st) {
+  const qc_program* p = d->prog;
+  const QcTrig* trig = (const QcTrig*)d->trig_dev;
+  const int64_t B = d->B_res;
+  int rc;
+  if ((rc = qc_tt_pre_fwd(d->X_res_dev, d->params_dev, L, d->ajets_res_dev, B, st))) return rc;
+  if ((rc = qc_tt_circ_fwd(p, trig, d->umat_dev, d->ajets_res_dev, d->qjets_res_dev, B, st)) || (rc = after_launch())) return rc;
+  if ((rc = qc_tt_post(2, d->params_dev, L, to_pde(&d->pde), d->qjets_res_dev, t->target_res_dev, cf->coef_res_dev, d->abar_res_dev,
+                       d->qbar_res_dev, d->part_dev, d->part_stride, 0, B, st))) return rc;
+  if ((rc = qc_tt_circ_bwd(p, trig, d->umat_dev, d->ajets_res_dev, d->qbar_res_dev, d->abar_res_dev, d->part_dev + L.oTh,
+                           d->part_stride, 0, B, st)) || (rc = after_launch())) return rc;
+  if ((rc = qc_tt_pre_bwd(d->X_res_dev, d->params_dev, L, d->abar_res_dev, d->part_dev, d->part_stride, 0, B, st))) return rc;
+  return after_launch();
+}
+
+int qc_fused_pinn_coef_tt_step(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef_tt* cf, int phases, void* stream) {
+  if (!d || !t || !cf || !d->part_dev || !d->flat_dev) return QC_ERR_ARG;
+  if (d->pde.problem != QC_PROBLEM_TABULATED) return QC_ERR_ARG;
+  if (!d->prog || !d->trig_dev || !d->params_dev) return QC_ERR_ARG;
+  if (!tt_prog_ok(d->prog)) return QC_ERR_UNSUPPORTED;
+  const QcBatches b = step_batches(d, t);
+  const QcSource src = make_source(t, nullptr, nullptr, nullptr, d->sample_bc_face_points);
+  if (!src.holds(b)) return QC_ERR_ARG;
+  int rc = check_step_desc(d, true, nullptr);
+  if (rc) return rc;
+  if (d->B_res > 0 && (!cf->coef_res_dev || !d->X_res_dev || !d->ajets_res_dev || !d->qjets_res_dev || !d->qbar_res_dev ||
+                       !d->abar_res_dev))
+    return QC_ERR_ARG;
+  if ((phases & QC_PHASE_SAMPLE) && (!src.ok(b) || (d->B_res > 0 && !cf->ds_coef))) return QC_ERR_ARG;
+  const QcLayout L = make_layout(d->H, d->n, d->n_theta);
+  const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
+  const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
+  const int64_t rows = rows_res + rows_val;
+  if (rows <= 0 || rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
+  if ((phases & QC_PHASE_UPDATE) && (!d->m_dev || !d->v_dev || !d->opt_state_dev)) return QC_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+
+  if (phases & QC_PHASE_SAMPLE) {
+    if ((rc = fill_batches(b, src, st)) || (rc = tt_gather_coef(b, t, cf->coef_res_dev, cf->ds_coef, st))) return rc;
+  }
+  if (phases & QC_PHASE_GRADS) {
+    // the two pipelines are independent until the row reduction: the value pipeline goes to the side stream, as in fused_step
+    QcSide* side = (d->B_res > 0 && d->B_val > 0) ? side_stream() : nullptr;
+    hipStream_t sv = st;
+    if (side) {
+      if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
+        side = nullptr;
+      else
+        sv = side->s;
+    }
+    const QcPipe val = {d->X_val_dev, d->ajets_val_dev, d->qjets_val_dev, d->qbar_val_dev, d->abar_val_dev, nullptr, nullptr,
+                        d->B_val, rows_res, 1, {nullptr, 0, false}};
+    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u)))) return rc;
+    if (d->B_res > 0 && (rc = tt_run_pipeline(d, t, cf, L, st))) return rc;
+    if (side) {
+      hipError_t e = hipEventRecord(side->join, sv);
+      if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);
+      if (e != hipSuccess) return hip_fail(e);
+    }
+    // row fold and optimiser launch: those of fused_step's plain branch
+    const int RS = qc_opt_fold_rows(d->part_dev, rows, d->part_stride, L.NP + 3, st);
+    if ((phases & QC_PHASE_UPDATE) && !d->comm) {
+      QcOptHyper h;
+      memcpy(&h, &d->hyper, sizeof(h));
+      qc_opt_adam_fold(d->part_dev, d->part_stride, RS, d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev,
+                       (QcOptState*)d->opt_state_dev, h, d->hist_dev, d->hist_cap, d->prog, L.oTh, (QcTrig*)d->trig_dev, st, nullptr);
+      return after_launch();
+    }
+    if ((rc = qc_reduce_rows(d->part_dev, RS, d->part_stride, L.NP + 3, d->flat_dev, st))) return rc;
+    if (d->comm && (phases & QC_PHASE_UPDATE) && (rc = qc_comm_allreduce(d->flat_dev, L.NP + 3, d->comm, st))) return rc;
+  }
+  if (phases & QC_PHASE_UPDATE) {
+    if ((rc = adam_step_impl(d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev, d->opt_state_dev, &d->hyper, d->hist_dev,
+                             d->hist_cap, d->prog, L.oTh, d->trig_dev, st, nullptr))) return rc;
+  }
+  return QC_OK;
+}
+
 }  // extern "C"

@@ -403,3 +403,19 @@ int64_t qc_h2_tiles_that_fit(const qc_program* pg, void* h2, int nch, bool backw
 int qc_comm_allreduce(float* buf, int64_t count, void* comm, hipStream_t st);   // qc_comm.hip: RCCL sum, fp32, in place
 int qc_amp_fwd_launch(const float* a, float* u, int n, int64_t B, int nch, hipStream_t);
 int qc_amp_bwd_launch(const float* a, const float* ub, float* ab, int n, int64_t B, int nch, hipStream_t);
+// ---- seven derivative channels (channel 6 = d2/dt2), 2 <= n <= 5: jets [7][n][B], operator rows [QC_COEF_TT_N][B]
+constexpr int QC_NCH_TT_N = 7;    // == QC_NCH_TT of the public header
+constexpr int QC_COEF_TT_N = 8;   // == QC_COEF_TT_COLS: the QC_COEF_N columns, then d_tt
+// qc_tt.hip: the pre network (plain inputs, no angle map) and the post network; QC_ERR_UNSUPPORTED outside 2 <= L.n <= 5.
+// qc_tt_post mode 2: the coefficient form (io = the [7][B] channel cotangents, written); 3: the reverse pass from given
+// cotangents io[7][B]; 4: forward only, io = the seven channels of u
+int qc_tt_pre_fwd(const float* X, const float* prm, QcLayout L, float* ajets, int64_t B, hipStream_t);
+int qc_tt_pre_bwd(const float* X, const float* prm, QcLayout L, const float* abar, float* part, int64_t part_stride,
+                  int64_t row0, int64_t B, hipStream_t);
+int qc_tt_post(int mode, const float* prm, QcLayout L, QcPde pde, const float* qjets, const float* target, const float* coef,
+               float* io, float* qbar, float* part, int64_t part_stride, int64_t row0, int64_t B, hipStream_t);
+// qc_circuit_tt.hip: the register family's interpreter kernels with seven waves (angle encoding, no EMBED gates)
+int qc_tt_circ_fwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, float* qjets, int64_t B,
+                   hipStream_t);
+int qc_tt_circ_bwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, const float* qbar,
+                   float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, hipStream_t);

@@ -28,6 +28,7 @@ from ..hip.lib import QC_ADAPT_FLOOR_MAX, QC_CAUSAL_MAX_SLABS, QC_EQMAX, QC_KMAX
 
 MAX_ROWS = 2 ** 31 - 1      # the device gather forms (32-bit word * rows) >> 32
 COEF_COLUMNS = ("c_u", "c_t", "c_x", "c_y", "d_xx", "d_yy", "c_3")     # column order of a coefficient row
+COEF_TT_COLUMNS = COEF_COLUMNS + ("d_tt",)      # ... of a row of the seven-channel step (qc_fused_pinn_coef_tt_step)
 _SCALARS = {"c_t": 1.0, "c_x": 1.0, "c_y": 1.0, "d_xx": 0.01, "d_yy": 0.01, "c_u": 0.0}
 
 
@@ -62,6 +63,31 @@ def _coef_rows(coef, n_res):
     if coef.shape[0] != n_res:
         raise ValueError(f"coefficient table: {n_res} residual points but {coef.shape[0]} rows")
     return coef.contiguous()
+
+
+def _tt_column(d_tt, X_res):
+    """The (N_res,) float32 ``d_tt`` column on the device of the residual points: a scalar, an (N_res,) / (N_res, 1)
+    float32 tensor or a callable of ``X_res`` returning either."""
+    import math
+    N = int(X_res.shape[0])
+    v = d_tt(X_res) if callable(d_tt) else d_tt
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        if not math.isfinite(float(v)):
+            raise ValueError(f"coefficient column d_tt: {v} is not finite")
+        return torch.full((N,), float(v), dtype=torch.float32, device=X_res.device)
+    v = torch.as_tensor(v)
+    if v.dtype != torch.float32:
+        raise ValueError(f"coefficient column d_tt: must be a float32 tensor, got {v.dtype}")
+    if v.dim() == 0:
+        return v.reshape(1).expand(N).to(X_res.device).contiguous()
+    if v.dim() > 2 or (v.dim() == 2 and v.shape[1] != 1):
+        raise ValueError(f"coefficient column d_tt: must have shape (N,) or (N, 1), got {tuple(v.shape)}")
+    v = v.reshape(-1)
+    if v.shape[0] != N:
+        raise ValueError(f"coefficient column d_tt: {N} points but {v.shape[0]} values")
+    if v.device != X_res.device:
+        raise ValueError("coefficient column d_tt: must be on the device of the residual points")
+    return v.contiguous()
 
 
 def _segment(name, X, y):
@@ -249,10 +275,12 @@ class TabulatedProblem:
     """Residual points with forcing values ``r``, initial points with ``u_ic``, boundary points with ``u_bc``."""
 
     def __init__(self, X_res, r, X_ic, u_ic, X_bc, u_bc, *, c_t=None, c_x=None, c_y=None, d_xx=None, d_yy=None, c_u=None,
-                 coef_res=None):
+                 coef_res=None, d_tt=None):
         """Scalar coefficients (defaults c_t = c_x = c_y = 1, d_xx = d_yy = 0.01, c_u = 0): one operator for every residual
         point.  ``coef_res`` (N_res, 7) float32 instead: one row per residual point; giving it together with any scalar
-        coefficient is an error."""
+        coefficient is an error.  ``d_tt`` (beside either): the coefficient of u_tt, a scalar, an (N_res,) float32 tensor or
+        a callable of ``X_res``; the problem is then second order in time, ``coef_tt`` is its (N_res, 8) table in
+        ``COEF_TT_COLUMNS`` order and training goes through ``qc_fused_pinn_coef_tt_step``.  None: nothing changes."""
         self.X_res, self.r = _segment("residual segment", X_res, r)
         self.X_ic, self.u_ic = _segment("initial segment", X_ic, u_ic)
         self.X_bc, self.u_bc = _segment("boundary segment", X_bc, u_bc)
@@ -267,6 +295,21 @@ class TabulatedProblem:
         sc = {**_SCALARS, **given}
         self.coeffs = tuple(float(sc[k]) for k in ("c_t", "c_x", "c_y", "d_xx", "d_yy"))
         self.c_u = float(sc["c_u"])
+        self.d_tt = None if d_tt is None else _tt_column(d_tt, self.X_res)
+
+    @property
+    def coef_tt(self):
+        """The (N_res, 8) float32 operator table in ``COEF_TT_COLUMNS`` order of a problem with ``d_tt``: the rows of
+        ``coef_res``, or the scalar coefficients on every row (c_3 = 0), and the ``d_tt`` column; None without ``d_tt``."""
+        if self.d_tt is None:
+            return None
+        if self.coef_res is not None:
+            head = self.coef_res
+        else:
+            c_t, c_x, c_y, d_xx, d_yy = self.coeffs
+            head = torch.tensor([self.c_u, c_t, c_x, c_y, d_xx, d_yy, 0.0], dtype=torch.float32,
+                                device=self.X_res.device).repeat(self.X_res.shape[0], 1)
+        return torch.cat([head, self.d_tt.reshape(-1, 1)], dim=1).contiguous()
 
     @classmethod
     def from_functions(cls, u_ic, u_bc, r, n_res, n_ic, n_bc, generator=None, coef=None, **coeffs):
@@ -274,7 +317,7 @@ class TabulatedProblem:
         uniform points of the trainer's three boxes (trainer/diffusion_train.py:9-20: t = 0 face, x = 0 face, unit cube),
         drawn IC -> BC -> residual from ``generator`` (default: torch's CPU generator).  ``coef``: a callable
         X -> (N, 7) coefficient rows (e.g. ``lambda X: coef_table(X, c_t=1.0, c_x=vx, c_y=vy, ...)``), evaluated on
-        the residual points."""
+        the residual points.  ``d_tt`` (among ``coeffs``): as in the constructor; a callable sees the residual points."""
         segs = []
         for name, n, f in (("ics", n_ic, u_ic), ("bc1", n_bc, u_bc), ("dom", n_res, r)):
             b = box(name, "cpu")
@@ -301,6 +344,8 @@ class TabulatedProblem:
         c = dict(zip(("c_t", "c_x", "c_y", "d_xx", "d_yy"), self.coeffs), c_u=self.c_u)
         if self.coef_res is not None:
             c = dict(coef_res=self.coef_res.to(device))
+        if self.d_tt is not None:
+            c["d_tt"] = self.d_tt.to(device)
         (Xr, rr), (Xi, ui), (Xb, ub) = [(X.to(device), y.to(device)) for X, y in self.segments()]
         return TabulatedProblem(Xr, rr, Xi, ui, Xb, ub, **c)
 

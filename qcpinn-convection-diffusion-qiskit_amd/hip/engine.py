@@ -14,6 +14,7 @@ from . import lib as L
 from ..circuits import OP_EMBED_S, GateProgram
 
 NCH = 6  # derivative channels: value, d/dt, d/dx, d/dy, d2/dx2, d2/dy2
+NCH_TT = L.QC_NCH_TT  # the same and d2/dt2 as channel 6 (the *_tt entry points)
 
 
 def _stream(device) -> int:
@@ -195,6 +196,35 @@ class Circuit:
         g = _need(qbar, self.device, "cotangent jets")
         return self._adjoint_reduced(a, g, NCH)
 
+    def forward_jets_tt(self, ajets: torch.Tensor) -> torch.Tensor:
+        """``forward_jets`` on seven channels, (7, n, B) -> (7, n, B) (``qc_forward_jets_tt``: 2 <= n <= 5, angle encoding)."""
+        a = _need(ajets, self.device, "angle jets")
+        out = torch.empty_like(a)
+        L.check(self.lib.qc_forward_jets_tt(self.handle, self.trig.data_ptr(), _ptr(self.umat), a.data_ptr(), out.data_ptr(),
+                                            a.shape[2], _stream(self.device)), "qc_forward_jets_tt")
+        return out
+
+    def _adjoint_tt(self, a: torch.Tensor, cot: torch.Tensor, part_ptr: int, stride: int) -> torch.Tensor:
+        """``_adjoint`` on seven channels (``qc_backward_jets_tt``)."""
+        abar = torch.empty_like(a)
+        L.check(self.lib.qc_backward_jets_tt(self.handle, self.trig.data_ptr(), _ptr(self.umat), a.data_ptr(), cot.data_ptr(),
+                                             abar.data_ptr(), part_ptr, stride, 0, a.shape[-1], _stream(self.device)),
+                "qc_backward_jets_tt")
+        return abar
+
+    def backward_jets_tt(self, ajets: torch.Tensor, qbar: torch.Tensor):
+        """``backward_jets`` on seven channels: (d_ajets (7, n, B), d_theta)."""
+        a = _need(ajets, self.device, "angle jets")
+        g = _need(qbar, self.device, "cotangent jets")
+        rows = (a.shape[-1] + 63) // 64
+        P = max(self.n_params, 1)
+        part = torch.empty(rows, P, dtype=torch.float32, device=self.device)
+        abar = self._adjoint_tt(a, g, part.data_ptr(), P)
+        d_theta = torch.empty(P, dtype=torch.float32, device=self.device)
+        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, P, P, d_theta.data_ptr(), _stream(self.device)),
+                "qc_reduce_rows")
+        return abar, d_theta[: self.n_params]
+
     def _adjoint_reduced(self, a: torch.Tensor, cot: torch.Tensor, nch: int):
         B = a.shape[-1]
         rows = (B + 63) // 64
@@ -359,6 +389,47 @@ class SolverEngine:
         d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
         L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st),
                 "qc_reduce_rows")
+        return d_flat
+
+    # ------------------------------------------------------------------ seven channels (with d2/dt2)
+    def forward_tt(self, X: torch.Tensor, refresh: bool = True):
+        """The seven derivative channels of u, (ujets [7, B], ajets [7, n, B], qjets [7, n, B]): value, d/dt, d/dx, d/dy,
+        d2/dx2, d2/dy2, d2/dt2 through ``qc_pre_forward_tt``, ``qc_forward_jets_tt`` and ``qc_post_jets_tt`` (2 <= n <= 5,
+        angle encoding, no input or angle map: anything else raises ``QcError``)."""
+        X = self._X(X)
+        B = X.shape[0]
+        st = _stream(self.device)
+        if self.circuit.ff_m or self.angle_map != L.QC_ANGLE_MAP_NONE:
+            raise L.QcError("the seven-channel stages take plain inputs: no Fourier-feature map, no angle map")
+        if refresh:
+            self.refresh_gates()
+        ajets = torch.empty(NCH_TT, self.n, B, dtype=torch.float32, device=self.device)
+        L.check(self.lib.qc_pre_forward_tt(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, ajets.data_ptr(),
+                                           B, st), "qc_pre_forward_tt")
+        qjets = self.circuit.forward_jets_tt(ajets)
+        uj = torch.empty(NCH_TT, B, dtype=torch.float32, device=self.device)
+        L.check(self.lib.qc_post_jets_tt(4, self.flat.data_ptr(), self.H, self.n, self.n_theta, qjets.data_ptr(), uj.data_ptr(),
+                                         None, None, 0, 0, B, st), "qc_post_jets_tt(forward)")
+        return uj, ajets, qjets
+
+    def backward_tt(self, X, ajets, qjets, ubar) -> torch.Tensor:
+        """Vector-Jacobian product of the seven channels w.r.t. the flat parameters: ``ubar`` [7, B] -> d_flat (NP)."""
+        X = self._X(X)
+        B = X.shape[0]
+        st = _stream(self.device)
+        rows = (B + 63) // 64
+        ub = _need(ubar.reshape(-1), self.device, "ubar").clone()
+        if ub.numel() != NCH_TT * B:
+            raise L.QcError("the seven-channel cotangent must be a [7, B] tensor")
+        part = torch.empty(rows, self.NP, dtype=torch.float32, device=self.device)
+        qbar = torch.empty_like(qjets)
+        L.check(self.lib.qc_post_jets_tt(3, self.flat.data_ptr(), self.H, self.n, self.n_theta, qjets.data_ptr(), ub.data_ptr(),
+                                         qbar.data_ptr(), part.data_ptr(), self.NP, 0, B, st), "qc_post_jets_tt(backward)")
+        abar = self.circuit._adjoint_tt(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP)
+        L.check(self.lib.qc_pre_backward_tt(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, abar.data_ptr(),
+                                            part.data_ptr(), self.NP, 0, B, st), "qc_pre_backward_tt")
+        d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
+        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st), "qc_reduce_rows")
         return d_flat
 
     # ------------------------------------------------------------------ K outputs behind one shared network
@@ -534,6 +605,7 @@ class _Step:
     trained in place; ``what`` names that layout in the size errors (None: the caller has checked)."""
 
     N_OWN = 0       # trainable entries behind theta (the operator's seven, a balancer's three)
+    RES_NCH = NCH   # derivative channels of the residual pipeline's scratch
 
     def __init__(self, circuit: Circuit, hidden: int, flat: torch.Tensor, opt: OptimState, pde: "L.QcPde", B_res: int,
                  n_ic: int, n_bc: int, K: int = 1, what: Optional[str] = None):
@@ -555,7 +627,7 @@ class _Step:
         f = dict(dtype=torch.float32, device=dev)
         self.X_res = torch.zeros(max(B_res, 1), 3, **f)
         self.X_val = torch.zeros(max(B_val, 1), 3, **f)
-        self.ws_res = torch.empty(4, NCH, n, max(B_res, 1), **f)
+        self.ws_res = torch.empty(4, self.RES_NCH, n, max(B_res, 1), **f)
         self.ws_val = torch.empty(4, 1, n, max(B_val, 1), **f)
         rows = (B_res + 63) // 64 + (B_val + 63) // 64
         self.stride = NP_total + 3
@@ -778,6 +850,49 @@ class FusedStep(_Step):
             self._bind_entry("qc_fused_pinn_data_step", self.data)
         else:
             self._bind_entry("qc_fused_pinn_residual_step")
+
+
+class FusedStepTT(FusedStep):
+    """One ``qc_fused_pinn_coef_tt_step`` descriptor: the coefficient step with a seventh channel, d2/dt2, for equations
+    second order in time over two space dimensions.  The engine's problem must be ``QC_PROBLEM_TABULATED``; ``coef_res``
+    [8][B_res] holds the operator rows of the residual batch (c_u, c_t, c_x, c_y, d_xx, d_yy, c_3, d_tt per point), filled
+    by the caller or gathered from the dataset's (N_res, 8) table (``set_dataset(segments, coef_tt)``).  2 <= n <= 5, angle
+    encoding, no input map, no angle map, no EMBED gates: the library refuses anything else when the step runs."""
+
+    RES_NCH = NCH_TT
+
+    def __init__(self, eng: SolverEngine, B_res: int, n_ic: int, n_bc: int, opt: OptimState, counts=None):
+        if eng.problem != L.QC_PROBLEM_TABULATED:
+            raise L.QcError("the seven-channel step is a tabulated step (problem = QC_PROBLEM_TABULATED)")
+        mode, eng.coef_mode = eng.coef_mode, False      # the 7-column buffers of FusedStep are not this step's
+        try:
+            super().__init__(eng, B_res, n_ic, n_bc, opt, counts)
+        finally:
+            eng.coef_mode = mode
+        self.coef_res = torch.zeros(L.QC_COEF_TT_COLS, max(B_res, 1), dtype=torch.float32, device=self.device)
+        self.coef_tt = L.QcStepCoefTT()
+        self.coef_tt.coef_res_dev, self.coef_tt.ds_coef = (self.coef_res.data_ptr() if B_res else None), None
+        self._bind()
+
+    def set_dataset(self, segments, coef_tt=None) -> None:
+        """``_Step.set_dataset``, and ``coef_tt``: the (N_res, 8) float32 operator table beside the residual segment (a
+        non-empty residual segment needs it)."""
+        self._bind_dataset(self.data, segments)
+        n_res = int(self.data.ds_n_res)
+        self.coef_tt.ds_coef = None
+        if coef_tt is not None and n_res:
+            coef_tt = _need(coef_tt, self.device, "dataset coefficient table")
+            if coef_tt.dim() != 2 or tuple(coef_tt.shape) != (n_res, L.QC_COEF_TT_COLS):
+                raise L.QcError(f"dataset coefficient table must be ({n_res}, {L.QC_COEF_TT_COLS}), got {tuple(coef_tt.shape)}")
+            self._dataset.append(coef_tt)
+            self.coef_tt.ds_coef = coef_tt.data_ptr()
+
+    def set_adaptive(self, power: int = 1, floor: float = 1.0) -> None:
+        raise L.QcError("the seven-channel step does not support adaptive sampling")
+
+    def _bind(self) -> None:
+        if hasattr(self, "coef_tt"):        # (FusedStep's constructor binds before the record exists)
+            self._bind_entry("qc_fused_pinn_coef_tt_step", self.data, self.coef_tt)
 
 
 class SystemStep(_Step):

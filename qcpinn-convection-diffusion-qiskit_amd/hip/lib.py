@@ -38,12 +38,16 @@ EXPORTS = (
     "qc_causal_init", "qc_sample_dataset_slabs", "qc_causal_fold", "qc_fused_pinn_causal_step",
     "qc_gradnorm_init", "qc_gradnorm_fold", "qc_fused_pinn_gradnorm_step",
     "qc_program_set_input_map", "qc_pre_forward_ff", "qc_pre_backward_ff",
+    "qc_pre_forward_tt", "qc_pre_backward_tt", "qc_forward_jets_tt", "qc_backward_jets_tt", "qc_post_coef_tt",
+    "qc_post_jets_tt", "qc_sample_dataset_coef_tt", "qc_fused_pinn_coef_tt_step",
 )
 
 
 QC_PROBLEM_CONVECTION_DIFFUSION, QC_PROBLEM_PURE_DIFFUSION, QC_PROBLEM_GAUSSIAN_PULSE = 0, 1, 2      # qc_pde.problem
 QC_PROBLEM_TABULATED = 3        # targets as data: accepted by qc_post_data / qc_fused_pinn_data_step only
 QC_COEF_COLS = 7                # operator row of a residual point: c_u, c_t, c_x, c_y, d_xx, d_yy, c_3 (qc_step_coef)
+QC_NCH_TT = 7                   # derivative channels of the seven-channel entry points: the six, then d2/dt2
+QC_COEF_TT_COLS = 8             # their operator row: the QC_COEF_COLS columns, then d_tt (qc_step_coef_tt)
 QC_BAL_TERMS = 3                # loss terms of a balancer: residual, BC, IC (qc_step_balance)
 QC_CAUSAL_MAX_SLABS = 64        # most time slabs of a causal record (qc_step_causal)
 QC_CAUSAL_HEAD = 4              # words {eps, n_raised, n_steps, hist_base} ahead of W[M], L[M] in a causal record
@@ -121,6 +125,12 @@ class QcStepData(C.Structure):
 
 class QcStepCoef(C.Structure):
     """qc_step_coef: the [7][B_res] operator rows of the current residual batch and the dataset's [N_res][7] table."""
+    _fields_ = [("coef_res_dev", C.c_void_p), ("ds_coef", C.c_void_p)]
+
+
+class QcStepCoefTT(C.Structure):
+    """qc_step_coef_tt: the [8][B_res] operator rows (c_u, c_t, c_x, c_y, d_xx, d_yy, c_3, d_tt) of the current residual
+    batch and the dataset's [N_res][8] table."""
     _fields_ = [("coef_res_dev", C.c_void_p), ("ds_coef", C.c_void_p)]
 
 
@@ -293,6 +303,15 @@ def load() -> C.CDLL:
     lib.qc_gradnorm_fold.argtypes = [fp, i64, i64, i64, i64, i32, C.POINTER(QcStepGradnorm), fp, fp, vp]
     lib.qc_fused_pinn_gradnorm_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoef),
                                                 C.POINTER(QcStepGradnorm), i32, vp]
+    lib.qc_pre_forward_tt.argtypes = [fp, fp, i32, i32, i32, fp, i64, vp]
+    lib.qc_pre_backward_tt.argtypes = [fp, fp, i32, i32, i32, fp, fp, i64, i64, i64, vp]
+    lib.qc_forward_jets_tt.argtypes = [vp, vp, fp, fp, fp, i64, vp]
+    lib.qc_backward_jets_tt.argtypes = [vp, vp, fp, fp, fp, fp, fp, i64, i64, i64, vp]
+    lib.qc_post_coef_tt.argtypes = [fp, i32, i32, i32, C.POINTER(QcPde), fp, fp, fp, fp, fp, fp, i64, i64, i64, vp]
+    lib.qc_post_jets_tt.argtypes = [i32, fp, i32, i32, i32, fp, fp, fp, fp, i64, i64, i64, vp]
+    lib.qc_sample_dataset_coef_tt.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, fp, C.POINTER(QcStepData),
+                                              C.POINTER(QcStepCoefTT), C.c_uint64, C.c_uint64, vp]
+    lib.qc_fused_pinn_coef_tt_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoefTT), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]

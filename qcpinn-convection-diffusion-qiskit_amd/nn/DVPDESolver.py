@@ -99,6 +99,33 @@ class _JetsFn(torch.autograd.Function):
         return None, None, d_flat
 
 
+class _JetsTTFn(torch.autograd.Function):
+    """``_JetsFn`` with a seventh channel: X (B,3) and ONE flat single-output parameter vector -> (B,7) = (u, u_t, u_x, u_y,
+    u_xx, u_yy, u_tt), through the seven-channel kernels (``SolverEngine.forward_tt`` / ``backward_tt``); the reverse pass
+    takes a cotangent per channel."""
+
+    @staticmethod
+    def forward(ctx, X, solver, flat):
+        eng = solver._jet_engine(X.device)
+        Xc = X.detach().to(torch.float32).contiguous()
+        fl = flat.detach().to(torch.float32).contiguous()
+        eng.flat.copy_(fl)
+        uj, ajets, qjets = eng.forward_tt(Xc)
+        ctx.eng = eng
+        ctx.save_for_backward(Xc, ajets, qjets, fl)
+        return uj.t().contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        Xc, ajets, qjets, fl = ctx.saved_tensors
+        eng = ctx.eng
+        eng.flat.copy_(fl)
+        eng.refresh_gates()
+        d_flat = eng.backward_tt(Xc, ajets, qjets, g.to(torch.float32).t().contiguous())
+        return None, None, d_flat
+
+
 class _JetsAllFn(torch.autograd.Function):
     """X (B,3), the flat vector of the SHARED parameters (single-output kernel layout, W4 / b4 slots unused) and the
     last layer's rows w4k [K, H + 1] -> (B, K, 6): the six derivative channels of every output from ONE pass through pre
@@ -357,6 +384,20 @@ class DVPDESolver(nn.Module):
             raise ValueError(f"output index {out} outside [0, {self.n_out})")
         self._jet_engine(X.device)
         return _JetsFn.apply(X, self, self._flat_for_output(out))
+
+    def jets_tt(self, X: torch.Tensor, out: int = 0) -> torch.Tensor:
+        """(B, 7) = (u, u_t, u_x, u_y, u_xx, u_yy, u_tt) of output ``out`` at X (B, 3): ``jets`` with the second derivative in
+        time, for equations second order in time over two space dimensions (``nn.pde.wave_2d_operator``); differentiable
+        once w.r.t. the parameters.  Three-input models with 2 .. 5 qubits, angle encoding, no Fourier features and no
+        re-uploading: the library refuses anything else (``QcError``)."""
+        if self.input_dim != 3:
+            raise ValueError("jets_tt needs a three-input model (t, x, y): a two-input model has its second derivatives in jets()")
+        if X.dim() != 2 or X.shape[1] != 3:
+            raise ValueError(f"Expected points of shape (B, 3), got {tuple(X.shape)}")
+        if not 0 <= out < self.n_out:
+            raise ValueError(f"output index {out} outside [0, {self.n_out})")
+        self._jet_engine(X.device)
+        return _JetsTTFn.apply(X, self, self._flat_for_output(out))
 
     def _engine_for(self, device) -> "_engine.SolverEngine":
         if self.n_out != 1:

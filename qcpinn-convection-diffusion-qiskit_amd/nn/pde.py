@@ -143,3 +143,34 @@ def helmholtz_operator(fluid_model, x1, x2):
     _, u_11 = _second(u, x1)
     _, u_22 = _second(u, x2)
     return [u, u_11 + u_22 + lam * u]
+
+
+def _jets_2d(model, X):
+    """(u, u_t, u_x, u_y, u_xx, u_yy, u_tt) as (B, 1) columns at X (B, 3) = (t, x, y) rows: the seven derivative channels of
+    the fused kernels for a ``DVPDESolver`` (``jets_tt``), the reference operators' double ``autograd.grad`` for any other
+    callable model."""
+    fused = getattr(model, "jets_tt", None)
+    if fused is not None and hasattr(model, "quantum_layer"):
+        J = fused(X)
+        return tuple(J[:, k:k + 1] for k in range(7))
+    t, x, y = (X[:, k:k + 1].clone() for k in range(3))
+    _track(t, x, y)
+    u = model(torch.cat((t, x, y), 1))
+    u_t, u_tt = _second(u, t)
+    u_x, u_xx = _second(u, x)
+    u_y, u_yy = _second(u, y)
+    return u, u_t, u_x, u_y, u_xx, u_yy, u_tt
+
+
+def wave_2d_operator(model, X, c=1.0, damping=0.0):
+    """The wave operator of the reference (nn/pde.py:42-52) over TWO space dimensions, with an optional damping term
+    (telegraph equation): X (B, 3) rows (t, x, y); returns (u, u_tt + damping u_t - c^2 (u_xx + u_yy)), both (B, 1)."""
+    u, u_t, _, _, u_xx, u_yy, u_tt = _jets_2d(model, X)
+    return u, u_tt + damping * u_t - c ** 2 * (u_xx + u_yy)
+
+
+def klein_gordon_2d_operator(model, X, alpha=-1.0, beta=0.0, gamma=1.0):
+    """The Klein-Gordon operator of the reference (nn/pde.py:28-41, its constants as defaults) over TWO space dimensions:
+    X (B, 3) rows (t, x, y); returns (u, u_tt + alpha (u_xx + u_yy) + beta u + gamma u^3), both (B, 1)."""
+    u, _, _, _, u_xx, u_yy, u_tt = _jets_2d(model, X)
+    return u, u_tt + alpha * (u_xx + u_yy) + beta * u + gamma * u ** 3

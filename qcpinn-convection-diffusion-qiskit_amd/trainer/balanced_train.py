@@ -16,7 +16,7 @@ from __future__ import annotations
 from ..data.tabulated import TabulatedProblem
 from ..hip import engine as _engine
 from ..nn.loss_balance import TERMS, AdaptiveMultiLoss
-from .diffusion_train import _dist_info, check_fused_single, load_with_targets, run_fused_loop
+from .diffusion_train import _dist_info, check_fused_single, check_tt, load_with_targets, run_fused_loop
 from .inverse_train import InverseTrainer
 
 
@@ -28,6 +28,7 @@ def check_balance(model, dataset, balancer, adaptive=None, lbfgs=None):
         raise ValueError(f"the balancer's names must be exactly the three loss terms {TERMS}, got {tuple(balancer.names)}")
     if not isinstance(dataset, TabulatedProblem):
         raise ValueError("balance= needs dataset= a TabulatedProblem: the analytic problems can be tabulated first")
+    check_tt(None, dataset, **{"balance=": balancer})
     if dataset.coef_res is not None:
         raise ValueError("balance= does not take a per-point coefficient table (dataset.coef_res)")
     if adaptive is not None:

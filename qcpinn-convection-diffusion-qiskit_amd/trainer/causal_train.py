@@ -15,7 +15,7 @@ from __future__ import annotations
 
 from ..data.tabulated import CausalWeighting, TabulatedProblem
 from ..hip import engine as _engine
-from .diffusion_train import FusedTrainer, _dist_info, check_fused_single, load_with_targets, run_fused_loop
+from .diffusion_train import FusedTrainer, _dist_info, check_fused_single, check_tt, load_with_targets, run_fused_loop
 
 
 def check_causal(model, dataset, causal, batch_size, adaptive=None, lbfgs=None, balance=None, operator=None):
@@ -26,6 +26,7 @@ def check_causal(model, dataset, causal, batch_size, adaptive=None, lbfgs=None, 
         raise ValueError("causal= does not take a system of equations (a TabulatedSystem)")
     if not isinstance(dataset, TabulatedProblem):
         raise ValueError("causal= needs dataset= a TabulatedProblem: the analytic problems can be tabulated first")
+    check_tt(None, dataset, **{"causal=": causal})
     if dataset.coef_res is not None:
         raise ValueError("causal= does not take a per-point coefficient table (dataset.coef_res)")
     if adaptive is not None:

@@ -42,6 +42,11 @@ by how well the earlier slabs are fitted, on the device (``qc_fused_pinn_causal_
 ``gradnorm=`` (keyword-only, an ``nn.loss_balance.GradNormWeighting``, with ``dataset=`` or on the analytic problem) weighs
 the BC and the IC term from the ratio of this step's per-class gradient statistics, on the device
 (``qc_fused_pinn_gradnorm_step``, ``trainer.gradnorm_train``): ``DVPDESolver`` models only, alone.
+
+A dataset with ``d_tt`` (``TabulatedProblem(..., d_tt=)``: the coefficient of u_tt, an equation second order in time over two
+space dimensions) takes ``qc_fused_pinn_coef_tt_step``: seven derivative channels, rows of eight coefficients.  ``DVPDESolver``
+models with 2 .. 5 qubits, angle encoding, without ``fourier_features`` and ``reupload``; single process; not together with
+``adaptive=``, ``lbfgs=``, ``balance=``, ``causal=`` or ``gradnorm=`` (``check_tt`` raises ``ValueError`` with the reason).
 """
 from __future__ import annotations
 
@@ -204,6 +209,10 @@ class StepTrainer:
         """The tensors behind the flat vector, in its order."""
         return list(self.model.parameters())
 
+    def _coef_table(self):
+        """The dataset's operator table whose rows travel with the residual batch, or None."""
+        return getattr(self.dataset, "coef_res", None)
+
     # -- optimiser state: continue from the torch optimiser / scheduler objects
     def _make_opt_state(self, capacity):
         return opt_state_from_torch(self._params(), self.optimizer, self.scheduler, self.device, capacity, self.max_norm,
@@ -239,8 +248,7 @@ class StepTrainer:
         if self.sampler == "device":
             return
         self._explicit = True
-        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), self.batch_minor,
-                    getattr(self.dataset, "coef_res", None))
+        gather_rows(self.fs, self.dataset.segments(), (self.B_res, self.n_ic, self.n_bc), self.batch_minor, self._coef_table())
 
     def step(self):
         draw = 0 if self._explicit else _lib.QC_PHASE_SAMPLE
@@ -310,6 +318,8 @@ class FusedTrainer(StepTrainer):
     ``torch.manual_seed`` still controls the run); ``sampler="torch"`` uses three ``torch.rand`` calls
     like the reference (IC -> BC -> residual)."""
 
+    tt, coef_cols = False, _lib.QC_COEF_COLS    # a dataset with d_tt: the seven-channel step, operator rows of eight columns
+
     def __init__(self, model, batch_size: int, capacity: int, sampler: str = "device", *, n_bc: int = None,
                  bc_faces=1, pde: dict = None, n_ic: int = None, loss_weights=(2.0, 4.0, 2.0), max_norm=1.0,
                  optimizer=None, scheduler=None, dataset=None, adaptive=None):
@@ -337,6 +347,8 @@ class FusedTrainer(StepTrainer):
                              "convection-diffusion step takes (t, x, y) points and one output"
                              % (getattr(model, "input_dim", None), getattr(model, "n_out", None)))
         _check_adaptive(adaptive, dataset, batch_size, sampler)
+        self.tt = is_tt(dataset)
+        check_tt(model, dataset, _dist_info()[0], **{"adaptive=": adaptive})
         dev = model._resolve_device(model.device)
         if dev is None or dev.type != "cuda":
             raise _lib.QcError("training a DVPDESolver needs a GPU (HIP kernels, no CPU fallback)")
@@ -361,7 +373,8 @@ class FusedTrainer(StepTrainer):
             self.eng.problem = _lib.QC_PROBLEM_TABULATED
             self.eng.coeffs, self.eng.c_u = self.dataset.coeffs, self.dataset.c_u
             self.eng.coef_mode = self.dataset.coef_res is not None
-        self.coef_mode = self.eng.coef_mode
+        self.coef_mode = self.eng.coef_mode or self.tt
+        self.coef_cols = _lib.QC_COEF_TT_COLS if self.tt else _lib.QC_COEF_COLS
         self.tabulated = self.eng.problem == _lib.QC_PROBLEM_TABULATED
         self.optimizer = model.optimizer if optimizer is None else optimizer
         self.scheduler = model.scheduler if scheduler is None else scheduler
@@ -387,7 +400,7 @@ class FusedTrainer(StepTrainer):
             for what, n_batch, n_rows in zip(("residual", "initial", "boundary"), self.global_counts, self.dataset.sizes()):
                 if n_batch > 0 and n_rows == 0:
                     raise ValueError(f"the dataset's {what} segment is empty but the step takes {n_batch} {what} points")
-            self.fs.set_dataset(self.dataset.segments(), self.dataset.coef_res)
+            self.fs.set_dataset(self.dataset.segments(), self._coef_table())
         self.adaptive = adaptive
         if adaptive is not None:
             self.fs.set_adaptive(adaptive.power, adaptive.floor)
@@ -406,7 +419,12 @@ class FusedTrainer(StepTrainer):
 
     def _make_step(self):
         """The step descriptor over this trainer's batch sizes (the engine holds what the constructor configured)."""
+        if self.tt:
+            return _engine.FusedStepTT(self.eng, self.B_res, self.n_ic, self.n_bc, self.opt, self.global_counts)
         return self.eng.fused(self.B_res, self.n_ic, self.n_bc, self.opt, self.global_counts)
+
+    def _coef_table(self):
+        return self.dataset.coef_tt if self.tt else self.dataset.coef_res
 
     def _make_comm(self):
         """One library-owned RCCL communicator over the ranks of the default process group (the 128-byte id travels
@@ -477,7 +495,7 @@ class FusedTrainer(StepTrainer):
         if coef is not None and not self.coef_mode:
             raise ValueError("coef needs a coefficient step: a dataset with coef_res, or pde={'problem': 3, 'coef': True, ...}")
         if coef is None and self.coef_mode:
-            raise ValueError("a coefficient step needs coef=(B_res, 7) operator rows with its batches")
+            raise ValueError(f"a coefficient step needs coef=(B_res, {self.coef_cols}) operator rows with its batches")
         if targets is not None and not self.tabulated:
             raise ValueError("targets need a tabulated step: construct the trainer with dataset= or pde={'problem': 3, ...}")
         if targets is None and self.tabulated:
@@ -485,8 +503,8 @@ class FusedTrainer(StepTrainer):
         if targets is not None and tuple(torch.as_tensor(t).numel() for t in targets) != (X_ic.shape[0], X_bc.shape[0],
                                                                                           X_res.shape[0]):
             raise ValueError("targets=(u_ic, u_bc, r_res) must hold one value per point of (X_ic, X_bc, X_res)")
-        if coef is not None and tuple(torch.as_tensor(coef).shape) != (X_res.shape[0], _lib.QC_COEF_COLS):
-            raise ValueError(f"coef must be ({X_res.shape[0]}, {_lib.QC_COEF_COLS}): one operator row per point of X_res")
+        if coef is not None and tuple(torch.as_tensor(coef).shape) != (X_res.shape[0], self.coef_cols):
+            raise ValueError(f"coef must be ({X_res.shape[0]}, {self.coef_cols}): one operator row per point of X_res")
         self._explicit = True
         fill_batches(self.fs, (self.B_res, self.n_ic, self.n_bc), (X_ic, X_bc, X_res), targets, coef=coef,
                      shard=(self.world, self.rank))
@@ -503,6 +521,39 @@ class FusedTrainer(StepTrainer):
         if self.adaptive is None:
             raise ValueError("adaptive_state() needs adaptive= sampling")
         return self.fs.adaptive_state()
+
+
+def is_tt(dataset) -> bool:
+    """The dataset carries a ``d_tt`` column: its problem is second order in time (the seven-channel step)."""
+    return getattr(dataset, "d_tt", None) is not None
+
+
+def check_tt(model, dataset, world=1, **options):
+    """The argument errors of a problem with ``d_tt``, one ``ValueError`` per fault, none of which needs a GPU: ``options``
+    names the step variants asked for beside it (``adaptive=...``, ``balance=...``: any that is not None is refused), and
+    the model must be one the seven-channel kernels serve."""
+    if not is_tt(dataset):
+        return
+    for name, v in options.items():
+        if v is not None:
+            raise ValueError(f"{name} is not supported for a problem with d_tt: the seven-channel step "
+                             "(qc_fused_pinn_coef_tt_step) has no such form")
+    if world > 1:
+        raise ValueError("a problem with d_tt trains in a single process: world_size > 1 is not supported")
+    if model is None:
+        return
+    if not (hasattr(model, "_engine_for") and hasattr(model, "quantum_layer")):
+        raise ValueError("a problem with d_tt runs in the fused step: it is only supported for DVPDESolver models")
+    args = getattr(model, "args", None) or {}
+    if args.get("fourier_features"):
+        raise ValueError("a problem with d_tt does not take args['fourier_features']: the seven-channel pre stage reads plain inputs")
+    if args.get("reupload") or getattr(model.quantum_layer, "reupload", False):
+        raise ValueError("a problem with d_tt does not take args['reupload']: the seven-channel circuit stages have no EMBED gates")
+    n = int(getattr(model, "num_qubits", 0))
+    if not 2 <= n <= 5:
+        raise ValueError(f"a problem with d_tt needs 2 .. 5 qubits (the register family of circuit kernels), got {n}")
+    if str(getattr(model, "encoding", "angle")).lower().startswith("amp"):
+        raise ValueError("a problem with d_tt needs angle encoding")
 
 
 def _check_adaptive(adaptive, dataset, batch_size, sampler="device"):
@@ -737,7 +788,8 @@ def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *
     models only, not with ``adaptive``, ``lbfgs``, ``balance`` or ``causal``; ``batch_size // 3`` must be a multiple of 64);
     ``model.gradnorm_history`` receives the rows (lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated) of the
     steps.  ``update_lam`` stays unused: the reference carries the flag of this algorithm without reading it, and it
-    switches nothing on here either."""
+    switches nothing on here either.  A ``dataset`` with ``d_tt`` (second order in time): module docstring."""
+    check_tt(None, dataset, **{"adaptive=": adaptive, "lbfgs=": lbfgs, "balance=": balance, "causal=": causal, "gradnorm=": gradnorm})
     if gradnorm is not None:
         from .gradnorm_train import check_gradnorm, train_gradnorm
         check_gradnorm(model, dataset, gradnorm, batch_size, adaptive, lbfgs, balance, causal)
@@ -762,4 +814,5 @@ def train(model, nIter=10000, batch_size=128, log_NTK=False, update_lam=False, *
             raise ValueError("lbfgs= runs on the device: it is only supported for DVPDESolver models")
         if batches is not None:
             raise ValueError("explicit batches are only supported for DVPDESolver models")
+        check_tt(model, dataset)
         _train_generic(model, batch_size, dataset, adaptive)

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 from ..hip import engine as _engine
 from ..nn.loss_balance import GradNormWeighting
-from .diffusion_train import FusedTrainer, _dist_info, check_fused_single, load_with_targets, run_fused_loop
+from .diffusion_train import FusedTrainer, _dist_info, check_fused_single, check_tt, load_with_targets, run_fused_loop
 
 
 def check_gradnorm(model, dataset, gradnorm, batch_size, adaptive=None, lbfgs=None, balance=None, causal=None, operator=None,
@@ -28,6 +28,7 @@ def check_gradnorm(model, dataset, gradnorm, batch_size, adaptive=None, lbfgs=No
         raise ValueError("gradnorm= must be an nn.loss_balance.GradNormWeighting")
     if dataset is not None and hasattr(dataset, "terms"):
         raise ValueError("gradnorm= does not take a system of equations (a TabulatedSystem)")
+    check_tt(None, dataset, **{"gradnorm=": gradnorm})
     if adaptive is not None:
         raise ValueError("gradnorm= cannot be combined with adaptive= sampling")
     if lbfgs is not None:

@@ -17,7 +17,7 @@ import torch
 
 from ..data.tabulated import LearnedOperator, TabulatedProblem, _SCALARS
 from ..hip import engine as _engine
-from .diffusion_train import DatasetTrainer, _dist_info, fill_batches
+from .diffusion_train import DatasetTrainer, _dist_info, check_tt, fill_batches
 
 
 def pack_with_tail(model, tail, attr, dev):
@@ -72,6 +72,7 @@ class InverseTrainer(DatasetTrainer):
             raise ValueError("InverseTrainer needs dataset= a TabulatedProblem (residual and observation segments)")
         if not isinstance(operator, LearnedOperator):
             raise ValueError("InverseTrainer needs operator= a LearnedOperator")
+        check_tt(None, dataset, **{"InverseTrainer": operator})
         if dataset.coef_res is not None:
             raise ValueError("the dataset carries a per-point coefficient table (coef_res): an inverse problem takes its "
                              "coefficients from operator= (LearnedOperator(fixed=..., learn=...)), one global value each")

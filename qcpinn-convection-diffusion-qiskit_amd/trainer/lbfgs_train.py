@@ -60,6 +60,9 @@ class LbfgsTrainer:
         if getattr(fused_trainer, "world", 1) > 1:
             raise ValueError("LbfgsTrainer runs on one rank: data-parallel L-BFGS is not supported (the library call itself "
                              "works on an all-reduced flat vector)")
+        if getattr(fused_trainer, "tt", False):
+            raise ValueError("LbfgsTrainer is not supported for a problem with d_tt: the seven-channel step "
+                             "(qc_fused_pinn_coef_tt_step) has no L-BFGS form")
         if getattr(fused_trainer, "adaptive", None) is not None:
             raise ValueError("LbfgsTrainer needs a fixed objective: the trainer must not use adaptive= sampling")
         if int(capacity) != capacity or capacity < 0:

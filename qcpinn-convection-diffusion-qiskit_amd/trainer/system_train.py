@@ -15,7 +15,7 @@ import torch
 from ..data.tabulated import TabulatedSystem
 from ..hip import engine as _engine
 from ..hip import lib as _lib
-from .diffusion_train import DatasetTrainer, _dist_info, fill_batches
+from .diffusion_train import DatasetTrainer, _dist_info, check_tt, fill_batches
 
 
 class SystemTrainer(DatasetTrainer):
@@ -32,6 +32,7 @@ class SystemTrainer(DatasetTrainer):
         ``batch_size`` residual, ``n_ic`` / ``n_bc`` (default ``batch_size // 3``) initial / boundary points per step;
         ``loss_weights`` = (residual, BC, IC); ``max_norm`` None: no clipping; ``capacity``: length of the loss history;
         ``sampler`` = "device" (the library's gather) or "torch" (``torch.randint`` rows and a copy)."""
+        check_tt(None, dataset, SystemTrainer=True)
         if not isinstance(dataset, TabulatedSystem):
             raise ValueError("SystemTrainer needs dataset= a TabulatedSystem (operator terms, weights and segments)")
         if getattr(model, "input_dim", 3) != 3:
