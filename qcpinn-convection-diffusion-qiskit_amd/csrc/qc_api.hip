@@ -91,6 +91,20 @@ static QcSide* side_stream() {
   }
   return q.ok ? &q : nullptr;
 }
+// fork: the stream the value pipeline runs on, the side stream behind an event of `st`; without one (`side` is then
+// null) `st` itself.  join: `st` waits for what the side stream was given since.
+static hipStream_t side_fork(QcSide*& side, hipStream_t st) {
+  if (side && hipEventRecord(side->fork, st) == hipSuccess && hipStreamWaitEvent(side->s, side->fork, 0) == hipSuccess)
+    return side->s;
+  side = nullptr;
+  return st;
+}
+static int side_join(QcSide* side, hipStream_t st) {
+  if (!side) return QC_OK;
+  hipError_t e = hipEventRecord(side->join, side->s);
+  if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);
+  return e == hipSuccess ? QC_OK : hip_fail(e);
+}
 
 bool qc_static_match(const qc_program* pg, int n_qubits, int n_gates, const int* rows) {
   static const bool off = [] { const char* e = getenv("QC_NO_STATIC"); return e && e[0] == '1'; }();
@@ -1022,83 +1036,50 @@ static int run_pipeline(const qc_step_desc* d, const QcPipe& q, hipStream_t st, 
                            q.nch, st);
 }
 
-// The step behind the four step entry points, which differ in `tg`, where the post stage takes its targets and its
-// operator from, and in `src`, where QC_PHASE_SAMPLE takes the batches `b` from.  The dataset kinds gather rows and targets
-// (and operator rows) AHEAD of the stages, in the merged form too (the merged pre stage then runs with its own draw off,
-// so its instantiations are the analytic step's); nothing else in the step depends on the source.
-// `sys` (qc_fused_pinn_system_step, validated by its entry): K last-layer rows in the layout, the system post stage in
-// both pipelines, always the two-stream form; `tg` is then not read.
-// `cz` (qc_fused_pinn_causal_step, validated by its entry): the causal fold in place of the plain row fold.
-// `gn` (qc_fused_pinn_gradnorm_step, validated by its entry, never with a communicator): the class fold and the
-// combination in place of both reduction levels; the optimiser launch then takes flat_dev.
-static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches& b, const QcSource& src, int phases,
-                      void* stream, const qc_step_system* sys = nullptr, const QcCausal* cz = nullptr,
-                      const QcGradnorm* gn = nullptr) {
-  if (!d->part_dev || !d->flat_dev || !src.holds(b)) return QC_ERR_ARG;
-  if (!sys && ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem))) return QC_ERR_ARG;
-  int rc = check_step_desc(d, false, nullptr);
-  if (rc) return rc;
-  // no kernel family: n > 20 (refused above by the network's shape) or EMBED gates outside 2 <= n <= 5 (qc_program_create)
-  if (!d->prog->fam) return QC_ERR_UNSUPPORTED;
-  const int n = d->n, H = d->H;
-  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1, sys ? 0 : tg.n_op(), prog_n_in(d->prog));
-  const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
-  const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
-  const int64_t rows = rows_res + rows_val;
-  if (rows <= 0 || rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const QcStepLayout ws = step_layout(d->prog, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
+// Everything the step entry points differ in, built by the entry that validated its records.  `tg`: where the post stage
+// takes its targets and its operator from (a balancer comes with it); `src`: where QC_PHASE_SAMPLE takes the batches `b`
+// from.  The dataset kinds gather rows and targets (and operator rows) AHEAD of the stages, in the merged form too (the
+// merged pre stage then runs with its own draw off, so its instantiations are the analytic step's); nothing else in the
+// step depends on the source.
+// `sys` (the system step): K last-layer rows in the layout, the system post stage in both pipelines, always the two-stream
+// form; `tg` is then not read.  `cz` (the causal step): the causal fold in place of the plain row fold.  `gn` (the
+// gradient-norm step, never with a communicator): the class fold and the combination in place of both reduction levels; the
+// optimiser launch then takes flat_dev.  `tt_data` and `tt_coef` (the seven-channel step, both or neither): the operator
+// rows gathered behind the batches, tt_run_pipeline as the residual pipeline, the value pipeline without a store, always
+// the two-stream form, nothing asked of the step workspace.
+struct QcStepPlan {
+  QcTarget tg;
+  QcBatches b;
+  QcSource src;
+  const qc_step_system* sys = nullptr;
+  const QcCausal* cz = nullptr;
+  const QcGradnorm* gn = nullptr;
+  const qc_step_data* tt_data = nullptr;
+  const qc_step_coef_tt* tt_coef = nullptr;
+};
+// the seven-channel pieces of a step (behind their stages, below)
+static int tt_gather_coef(const QcBatches& b, const qc_step_data* t, float* coef_res, const float* ds_coef, void* stream);
+static int tt_run_pipeline(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef_tt* cf, const QcLayout& L, hipStream_t st);
 
-  // (in the merged form below the first stage draws the points itself)
-  const bool draw_in_stage = src.kind == QC_SOURCE_DRAW && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);   // (never a system's)
-  if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage && (rc = fill_batches(b, src, st))) return rc;
-  // register family, angle encoding, both pipelines present, final-state store available: every stage is ONE launch
-  // over the value tiles and the residual tiles together (no side stream, 9 launches per step); QC_NO_MERGE=1 keeps
-  // the two-stream form below
-  const bool merged = !sys && (phases & QC_PHASE_GRADS) && merged_ok(d);
-  if (merged) {
-    for (int stage = 0; stage < QC_STAGE_COUNT; ++stage)
-      if ((rc = merged_stage(d, stage, st, draw_in_stage && stage == QC_STAGE_PRE_FWD, tg))) return rc;
-    if ((rc = after_launch())) return rc;
-  }
-  if ((phases & QC_PHASE_GRADS) && !merged) {
-    if (!ws.fits) return QC_ERR_ARG;
-    // the two pipelines are independent until the row reduction: fork the value pipeline onto a side
-    // stream (not for the HBM family, where both may share the statevector workspace)
-    QcSide* side = (d->B_res > 0 && d->B_val > 0 && d->prog->fam != &qc_family_hbm) ? side_stream() : nullptr;
-    hipStream_t sv = st;
-    if (side) {
-      if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
-        side = nullptr;
-      else
-        sv = side->s;
-    }
-    const QcPipe val = {d->X_val_dev, d->ajets_val_dev, d->qjets_val_dev, d->qbar_val_dev, d->abar_val_dev, ws.u_val,
-                        ws.ub_val, d->B_val, rows_res, 1, ws.val};
-    const QcPipe res = {d->X_res_dev, d->ajets_res_dev, d->qjets_res_dev, d->qbar_res_dev, d->abar_res_dev, ws.u_res,
-                        ws.ub_res, d->B_res, 0, 6, ws.res};
-    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, tg.value_side(), sys))) return rc;
-    if (d->B_res > 0 && (rc = run_pipeline(d, res, st, tg, sys))) return rc;
-    if (side) {
-      hipError_t e = hipEventRecord(side->join, sv);
-      if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);
-      if (e != hipSuccess) return hip_fail(e);
-    }
-  }
+// The tail of every step: the partial rows of the stages -> flat_dev [gradient | 3 loss sums] -> the optimiser
+static int step_tail(const qc_step_desc* d, const QcStepPlan& plan, const QcLayout& L, int64_t rows_res, int64_t rows_val,
+                     int phases, hipStream_t st) {
+  int rc;
   // the balanced step: the optimiser launch forms the balancer's three gradient entries from the reduced loss columns
-  const QcBal* bal = !sys && tg.kind == QC_TARGET_BAL ? &tg.bal : nullptr;
-  if ((phases & QC_PHASE_GRADS) && gn) {
+  const QcBal* bal = !plan.sys && plan.tg.kind == QC_TARGET_BAL ? &plan.tg.bal : nullptr;
+  if ((phases & QC_PHASE_GRADS) && plan.gn) {
     // value tile k wrote row rows_res + k in every stage and the IC points come first: the IC class ends on a tile boundary
-    const int64_t rows_ic = b.n_bc > 0 ? b.n_ic / 64 : rows_val;
-    qc_opt_gradnorm_fold(d->part_dev, rows_res, rows_ic, rows_val - rows_ic, d->part_stride, L.NP + 3, *gn, d->flat_dev, nullptr, st);
+    const int64_t rows_ic = plan.b.n_bc > 0 ? plan.b.n_ic / 64 : rows_val;
+    qc_opt_gradnorm_fold(d->part_dev, rows_res, rows_ic, rows_val - rows_ic, d->part_stride, L.NP + 3, *plan.gn, d->flat_dev,
+                         nullptr, st);
     if ((rc = after_launch())) return rc;
   } else if (phases & QC_PHASE_GRADS) {
     // the step owns its partial-row matrix, so the reduction folds it in place (two levels, fixed order);
     // with the update phase in the same call the second level rides in the optimiser launch
-    const int RS = cz ? qc_opt_causal_fold(d->part_dev, rows, rows_res, d->part_stride, L.NP + 3, *cz, st)
-                      : qc_opt_fold_rows(d->part_dev, rows, d->part_stride, L.NP + 3, st);
+    const int64_t rows = rows_res + rows_val;
+    const int RS = plan.cz ? qc_opt_causal_fold(d->part_dev, rows, rows_res, d->part_stride, L.NP + 3, *plan.cz, st)
+                           : qc_opt_fold_rows(d->part_dev, rows, d->part_stride, L.NP + 3, st);
     if ((phases & QC_PHASE_UPDATE) && !d->comm) {
-      if (!d->m_dev || !d->v_dev || !d->opt_state_dev) return QC_ERR_ARG;
       QcOptHyper h;
       memcpy(&h, &d->hyper, sizeof(h));
       qc_opt_adam_fold(d->part_dev, d->part_stride, RS, d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev,
@@ -1110,63 +1091,114 @@ static int fused_step(const qc_step_desc* d, const QcTarget& tg, const QcBatches
     // data parallelism inside the library: sum the flat [gradient | 3 loss sums] vector over the ranks (RCCL, same stream)
     if (d->comm && (phases & QC_PHASE_UPDATE) && (rc = qc_comm_allreduce(d->flat_dev, L.NP + 3, d->comm, st))) return rc;
   }
-  if (phases & QC_PHASE_UPDATE) {
-    if (!d->m_dev || !d->v_dev || !d->opt_state_dev) return QC_ERR_ARG;
-    if ((rc = adam_step_impl(d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev, d->opt_state_dev, &d->hyper,
-                             d->hist_dev, d->hist_cap, d->prog, L.oTh, d->trig_dev, st, bal))) return rc;
-  }
-  return QC_OK;
+  if (!(phases & QC_PHASE_UPDATE)) return QC_OK;
+  return adam_step_impl(d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev, d->opt_state_dev, &d->hyper, d->hist_dev,
+                        d->hist_cap, d->prog, L.oTh, d->trig_dev, st, bal);
 }
 
-// the six entry points: targets, batches and source from the records each was given (the kind of step is decided here)
-// `lr` (the inverse step, validated by its entry, never with `cf`): the trainable operator, with or without residual points
-// `bl` (the balanced step, validated by its entry, alone): the tabulated step under balanced loss weights
-// `gn` (the gradient-norm step, validated by its entry, never with `ad`, `lr` or `bl`): gradient-norm loss weights
-static int step_from(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_adapt* ad, int phases,
-                     void* stream, const qc_step_learn* lr = nullptr, const qc_step_balance* bl = nullptr,
-                     const QcGradnorm* gn = nullptr) {
-  if (!d) return QC_ERR_ARG;
-  const bool table = cf && d->B_res > 0;   // no residual points: the plain tabulated step
+// The step behind every step entry point: the plan's records are validated by its entry, the descriptor here.
+static int fused_step(const qc_step_desc* d, const QcStepPlan& plan, int phases, void* stream) {
+  const QcTarget& tg = plan.tg;
+  const qc_step_system* sys = plan.sys;
+  const bool tt = plan.tt_data != nullptr;
+  if (!d->part_dev || !d->flat_dev || !plan.src.holds(plan.b)) return QC_ERR_ARG;
+  if (!sys && ((tg.kind == QC_TARGET_ANALYTIC && !problem_ok(d->pde.problem)) || !tg.ok(2, 6, d->pde.problem))) return QC_ERR_ARG;
+  int rc = check_step_desc(d, false, nullptr);
+  if (rc) return rc;
+  // no kernel family: n > 20 (refused above by the network's shape) or EMBED gates outside 2 <= n <= 5 (qc_program_create)
+  if (!d->prog->fam) return QC_ERR_UNSUPPORTED;
+  const int n = d->n, H = d->H;
+  const QcLayout L = qc_layout(H, n, d->n_theta, sys ? sys->K : 1, sys ? 0 : tg.n_op(), prog_n_in(d->prog));
+  const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
+  const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
+  const int64_t rows = rows_res + rows_val;
+  if (rows <= 0 || rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
+  if ((phases & QC_PHASE_UPDATE) && (!d->m_dev || !d->v_dev || !d->opt_state_dev)) return QC_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  // seven channels: no kept final states, no amplitude encoding, nothing asked of the workspace
+  const QcStepLayout ws = tt ? QcStepLayout{0, true} : step_layout(d->prog, d->B_res, d->B_val, d->circ_ws_dev, d->circ_ws_bytes);
+
+  // (in the merged form below the first stage draws the points itself)
+  const bool draw_in_stage = plan.src.kind == QC_SOURCE_DRAW && (phases & QC_PHASE_SAMPLE) && (phases & QC_PHASE_GRADS) && merged_ok(d);   // (never a system's)
+  if ((phases & QC_PHASE_SAMPLE) && !draw_in_stage && (rc = fill_batches(plan.b, plan.src, st))) return rc;
+  if ((phases & QC_PHASE_SAMPLE) && tt && (rc = tt_gather_coef(plan.b, plan.tt_data, plan.tt_coef->coef_res_dev, plan.tt_coef->ds_coef, st)))
+    return rc;
+  // register family, angle encoding, both pipelines present, final-state store available: every stage is ONE launch
+  // over the value tiles and the residual tiles together (no side stream, 9 launches per step); QC_NO_MERGE=1 keeps
+  // the two-stream form below
+  const bool merged = !sys && !tt && (phases & QC_PHASE_GRADS) && merged_ok(d);
+  if (merged) {
+    for (int stage = 0; stage < QC_STAGE_COUNT; ++stage)
+      if ((rc = merged_stage(d, stage, st, draw_in_stage && stage == QC_STAGE_PRE_FWD, tg))) return rc;
+    if ((rc = after_launch())) return rc;
+  }
+  if ((phases & QC_PHASE_GRADS) && !merged) {
+    if (!ws.fits) return QC_ERR_ARG;
+    // the two pipelines are independent until the row reduction: fork the value pipeline onto a side
+    // stream (not for the HBM family, where both may share the statevector workspace)
+    QcSide* side = (d->B_res > 0 && d->B_val > 0 && d->prog->fam != &qc_family_hbm) ? side_stream() : nullptr;
+    const hipStream_t sv = side_fork(side, st);
+    const QcPipe val = {d->X_val_dev, d->ajets_val_dev, d->qjets_val_dev, d->qbar_val_dev, d->abar_val_dev, ws.u_val,
+                        ws.ub_val, d->B_val, rows_res, 1, ws.val};
+    const QcPipe res = {d->X_res_dev, d->ajets_res_dev, d->qjets_res_dev, d->qbar_res_dev, d->abar_res_dev, ws.u_res,
+                        ws.ub_res, d->B_res, 0, 6, ws.res};
+    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, tg.value_side(), sys))) return rc;
+    if (d->B_res > 0 && (rc = tt ? tt_run_pipeline(d, plan.tt_data, plan.tt_coef, L, st) : run_pipeline(d, res, st, tg, sys)))
+      return rc;
+    if ((rc = side_join(side, st))) return rc;
+  }
+  return step_tail(d, plan, L, rows_res, rows_val, phases, st);
+}
+
+// the plan of the entry points that take the optional records of the public header: no data: analytic targets and the
+// coordinate draw; data: tabulated targets and its dataset's rows; `cf`: with one operator row per residual point (no
+// residual points: the plain tabulated step); `ad`: the residual rows from its CDF
+static QcStepPlan plan_from(const qc_step_desc* d, const qc_step_data* t, const qc_step_coef* cf, const qc_step_adapt* ad) {
+  const bool table = cf && d->B_res > 0;
   const QcTarget tg = !t      ? QcTarget{}
-                      : lr    ? QcTarget::learned(t->target_res_dev, t->target_val_dev, to_learn(lr, d->opt_state_dev))
-                      : bl    ? QcTarget::balanced(t->target_res_dev, t->target_val_dev, t->c_u, to_bal(bl))
                       : table ? QcTarget::with_coef(t->target_res_dev, t->target_val_dev, cf->coef_res_dev)
                               : QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u);
-  return fused_step(d, tg, step_batches(d, t), make_source(t, cf, cf ? cf->coef_res_dev : nullptr, ad, d->sample_bc_face_points),
-                    phases, stream, nullptr, nullptr, gn);
+  return {tg, step_batches(d, t), make_source(t, cf, cf ? cf->coef_res_dev : nullptr, ad, d->sample_bc_face_points)};
 }
 
 int qc_fused_pinn_residual_step(const qc_step_desc* d, int phases, void* stream) {
-  return step_from(d, nullptr, nullptr, nullptr, phases, stream);
+  if (!d) return QC_ERR_ARG;
+  return fused_step(d, plan_from(d, nullptr, nullptr, nullptr), phases, stream);
 }
 
 int qc_fused_pinn_data_step(const qc_step_desc* d, const qc_step_data* data, int phases, void* stream) {
-  if (!data) return QC_ERR_ARG;
-  return step_from(d, data, nullptr, nullptr, phases, stream);
+  if (!data || !d) return QC_ERR_ARG;
+  return fused_step(d, plan_from(d, data, nullptr, nullptr), phases, stream);
 }
 
 int qc_fused_pinn_coef_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef, int phases,
                             void* stream) {
-  if (!data || !coef) return QC_ERR_ARG;
-  return step_from(d, data, coef, nullptr, phases, stream);
+  if (!data || !coef || !d) return QC_ERR_ARG;
+  return fused_step(d, plan_from(d, data, coef, nullptr), phases, stream);
 }
 
+// the trainable operator, with or without residual points
 int qc_fused_pinn_inverse_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_learn* learn, int phases,
                                void* stream) {
-  if (!data || !learn_ok(learn)) return QC_ERR_ARG;
-  return step_from(d, data, nullptr, nullptr, phases, stream, learn);
+  if (!data || !learn_ok(learn) || !d) return QC_ERR_ARG;
+  QcStepPlan plan = plan_from(d, data, nullptr, nullptr);
+  plan.tg = QcTarget::learned(data->target_res_dev, data->target_val_dev, to_learn(learn, d->opt_state_dev));
+  return fused_step(d, plan, phases, stream);
 }
 
+// the tabulated step under balanced loss weights
 int qc_fused_pinn_balanced_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_balance* bal, int phases,
                                 void* stream) {
-  if (!data || !bal_ok(bal)) return QC_ERR_ARG;
-  return step_from(d, data, nullptr, nullptr, phases, stream, nullptr, bal);
+  if (!data || !bal_ok(bal) || !d) return QC_ERR_ARG;
+  QcStepPlan plan = plan_from(d, data, nullptr, nullptr);
+  plan.tg = QcTarget::balanced(data->target_res_dev, data->target_val_dev, data->c_u, to_bal(bal));
+  return fused_step(d, plan, phases, stream);
 }
 
 int qc_fused_pinn_adaptive_step(const qc_step_desc* d, const qc_step_data* data, const qc_step_coef* coef,
                                 const qc_step_adapt* adapt, int phases, void* stream) {
   if (!d || !data || !adapt || d->B_res <= 0) return QC_ERR_ARG;
-  return step_from(d, data, coef, adapt, phases, stream);
+  return fused_step(d, plan_from(d, data, coef, adapt), phases, stream);
 }
 
 int qc_fused_pinn_system_step(const qc_step_desc* d, const qc_step_system* sys, int phases, void* stream) {
@@ -1179,7 +1211,9 @@ int qc_fused_pinn_system_step(const qc_step_desc* d, const qc_step_system* sys, 
   if ((phases & QC_PHASE_SAMPLE) && !src.ok(b)) return QC_ERR_ARG;   // ahead of everything the descriptor is asked
   if (d->H >= 1 && d->n >= 1 && d->n_theta >= 0 && d->part_stride < qc_layout(d->H, d->n, d->n_theta, sys->K).NP + 3)
     return QC_ERR_ARG;
-  return fused_step(d, QcTarget{}, b, src, phases, stream, sys);
+  QcStepPlan plan = {QcTarget{}, b, src};
+  plan.sys = sys;
+  return fused_step(d, plan, phases, stream);
 }
 
 // ---- causal weighting of the residual slabs
@@ -1245,8 +1279,9 @@ int qc_fused_pinn_causal_step(const qc_step_desc* d, const qc_step_data* t, cons
   s.slab_lo = causal->slab_lo_dev;
   s.n_slabs = causal->n_slabs;
   const QcCausal cz = to_causal(causal, d->sample_off_res / 64);
-  return fused_step(d, QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u), step_batches(d, t), s, phases, stream,
-                    nullptr, &cz);
+  QcStepPlan plan = {QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u), step_batches(d, t), s};
+  plan.cz = &cz;
+  return fused_step(d, plan, phases, stream);
 }
 
 // ---- gradient-norm loss weights
@@ -1296,7 +1331,9 @@ int qc_fused_pinn_gradnorm_step(const qc_step_desc* d, const qc_step_data* t, co
   if (d->n_ic > 0 && d->B_val > d->n_ic && d->n_ic % 64 != 0) return QC_ERR_ARG;   // a value tile would mix IC and BC points
   if (d->part_rows_cap >= ((int64_t)1 << 31)) return QC_ERR_ARG;
   const QcGradnorm q = to_gradnorm(gn, d->hyper.w_res, d->hyper.w_bc, d->hyper.w_ic);
-  return step_from(d, t, cf, nullptr, phases, stream, nullptr, nullptr, &q);
+  QcStepPlan plan = plan_from(d, t, cf, nullptr);
+  plan.gn = &q;
+  return fused_step(d, plan, phases, stream);
 }
 
 // Scores of the dataset's residual rows [row0, row0 + rows): the forward half of the residual pipeline (pipe_forward, then
@@ -1454,62 +1491,18 @@ int qc_fused_pinn_coef_tt_step(const qc_step_desc* d, const qc_step_data* t, con
   if (d->pde.problem != QC_PROBLEM_TABULATED) return QC_ERR_ARG;
   if (!d->prog || !d->trig_dev || !d->params_dev) return QC_ERR_ARG;
   if (!tt_prog_ok(d->prog)) return QC_ERR_UNSUPPORTED;
-  const QcBatches b = step_batches(d, t);
-  const QcSource src = make_source(t, nullptr, nullptr, nullptr, d->sample_bc_face_points);
-  if (!src.holds(b)) return QC_ERR_ARG;
-  int rc = check_step_desc(d, true, nullptr);
+  QcStepPlan plan = plan_from(d, t, nullptr, nullptr);   // tabulated targets, the dataset's rows
+  if (!plan.src.holds(plan.b)) return QC_ERR_ARG;
+  // umat and the residual buffers are asked for whatever the phases, and the sampler's inputs ahead of rows and stride
+  const int rc = check_step_desc(d, true, nullptr);
   if (rc) return rc;
   if (d->B_res > 0 && (!cf->coef_res_dev || !d->X_res_dev || !d->ajets_res_dev || !d->qjets_res_dev || !d->qbar_res_dev ||
                        !d->abar_res_dev))
     return QC_ERR_ARG;
-  if ((phases & QC_PHASE_SAMPLE) && (!src.ok(b) || (d->B_res > 0 && !cf->ds_coef))) return QC_ERR_ARG;
-  const QcLayout L = make_layout(d->H, d->n, d->n_theta);
-  const int64_t rows_res = d->B_res > 0 ? qc_ceil_div(d->B_res, 64) : 0;
-  const int64_t rows_val = d->B_val > 0 ? qc_ceil_div(d->B_val, 64) : 0;
-  const int64_t rows = rows_res + rows_val;
-  if (rows <= 0 || rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
-  if ((phases & QC_PHASE_UPDATE) && (!d->m_dev || !d->v_dev || !d->opt_state_dev)) return QC_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-
-  if (phases & QC_PHASE_SAMPLE) {
-    if ((rc = fill_batches(b, src, st)) || (rc = tt_gather_coef(b, t, cf->coef_res_dev, cf->ds_coef, st))) return rc;
-  }
-  if (phases & QC_PHASE_GRADS) {
-    // the two pipelines are independent until the row reduction: the value pipeline goes to the side stream, as in fused_step
-    QcSide* side = (d->B_res > 0 && d->B_val > 0) ? side_stream() : nullptr;
-    hipStream_t sv = st;
-    if (side) {
-      if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
-        side = nullptr;
-      else
-        sv = side->s;
-    }
-    const QcPipe val = {d->X_val_dev, d->ajets_val_dev, d->qjets_val_dev, d->qbar_val_dev, d->abar_val_dev, nullptr, nullptr,
-                        d->B_val, rows_res, 1, {nullptr, 0, false}};
-    if (d->B_val > 0 && (rc = run_pipeline(d, val, sv, QcTarget::tabulated(t->target_res_dev, t->target_val_dev, t->c_u)))) return rc;
-    if (d->B_res > 0 && (rc = tt_run_pipeline(d, t, cf, L, st))) return rc;
-    if (side) {
-      hipError_t e = hipEventRecord(side->join, sv);
-      if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join, 0);
-      if (e != hipSuccess) return hip_fail(e);
-    }
-    // row fold and optimiser launch: those of fused_step's plain branch
-    const int RS = qc_opt_fold_rows(d->part_dev, rows, d->part_stride, L.NP + 3, st);
-    if ((phases & QC_PHASE_UPDATE) && !d->comm) {
-      QcOptHyper h;
-      memcpy(&h, &d->hyper, sizeof(h));
-      qc_opt_adam_fold(d->part_dev, d->part_stride, RS, d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev,
-                       (QcOptState*)d->opt_state_dev, h, d->hist_dev, d->hist_cap, d->prog, L.oTh, (QcTrig*)d->trig_dev, st, nullptr);
-      return after_launch();
-    }
-    if ((rc = qc_reduce_rows(d->part_dev, RS, d->part_stride, L.NP + 3, d->flat_dev, st))) return rc;
-    if (d->comm && (phases & QC_PHASE_UPDATE) && (rc = qc_comm_allreduce(d->flat_dev, L.NP + 3, d->comm, st))) return rc;
-  }
-  if (phases & QC_PHASE_UPDATE) {
-    if ((rc = adam_step_impl(d->flat_dev, L.NP, d->params_dev, d->m_dev, d->v_dev, d->opt_state_dev, &d->hyper, d->hist_dev,
-                             d->hist_cap, d->prog, L.oTh, d->trig_dev, st, nullptr))) return rc;
-  }
-  return QC_OK;
+  if ((phases & QC_PHASE_SAMPLE) && (!plan.src.ok(plan.b) || (d->B_res > 0 && !cf->ds_coef))) return QC_ERR_ARG;
+  plan.tt_data = t;
+  plan.tt_coef = cf;
+  return fused_step(d, plan, phases, stream);
 }
 
 }  // extern "C"

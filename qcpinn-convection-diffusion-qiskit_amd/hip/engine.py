@@ -178,7 +178,7 @@ class Circuit:
     def backward_expval(self, angles_nB: torch.Tensor, cot_nB: torch.Tensor):
         a = _need(angles_nB, self.device, "angles")
         g = _need(cot_nB, self.device, "cotangent")
-        return self._adjoint_reduced(a, g, 1)
+        return self._adjoint_reduced(a, g, lambda *args: self._adjoint(*args, 1))
 
     def forward_jets(self, ajets: torch.Tensor) -> torch.Tensor:
         a = _need(ajets, self.device, "angle jets")            # (6, n, B)
@@ -194,7 +194,7 @@ class Circuit:
     def backward_jets(self, ajets: torch.Tensor, qbar: torch.Tensor):
         a = _need(ajets, self.device, "angle jets")
         g = _need(qbar, self.device, "cotangent jets")
-        return self._adjoint_reduced(a, g, NCH)
+        return self._adjoint_reduced(a, g, lambda *args: self._adjoint(*args, NCH))
 
     def forward_jets_tt(self, ajets: torch.Tensor) -> torch.Tensor:
         """``forward_jets`` on seven channels, (7, n, B) -> (7, n, B) (``qc_forward_jets_tt``: 2 <= n <= 5, angle encoding)."""
@@ -216,21 +216,16 @@ class Circuit:
         """``backward_jets`` on seven channels: (d_ajets (7, n, B), d_theta)."""
         a = _need(ajets, self.device, "angle jets")
         g = _need(qbar, self.device, "cotangent jets")
-        rows = (a.shape[-1] + 63) // 64
-        P = max(self.n_params, 1)
-        part = torch.empty(rows, P, dtype=torch.float32, device=self.device)
-        abar = self._adjoint_tt(a, g, part.data_ptr(), P)
-        d_theta = torch.empty(P, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, P, P, d_theta.data_ptr(), _stream(self.device)),
-                "qc_reduce_rows")
-        return abar, d_theta[: self.n_params]
+        return self._adjoint_reduced(a, g, self._adjoint_tt)
 
-    def _adjoint_reduced(self, a: torch.Tensor, cot: torch.Tensor, nch: int):
+    def _adjoint_reduced(self, a: torch.Tensor, cot: torch.Tensor, adjoint):
+        """``adjoint(a, cot, part_ptr, stride)`` (``_adjoint`` at a channel count, or ``_adjoint_tt``) on a row matrix of
+        its own, and the rows summed: (cotangent of ``a``, d_theta)."""
         B = a.shape[-1]
         rows = (B + 63) // 64
         P = max(self.n_params, 1)
         part = torch.empty(rows, P, dtype=torch.float32, device=self.device)
-        abar = self._adjoint(a, cot, part.data_ptr(), P, nch)
+        abar = adjoint(a, cot, part.data_ptr(), P)
         d_theta = torch.empty(P, dtype=torch.float32, device=self.device)
         L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, P, P, d_theta.data_ptr(), _stream(self.device)),
                 "qc_reduce_rows")
@@ -372,24 +367,37 @@ class SolverEngine:
         ``ubar`` is the [6, B] cotangent of u's six derivative channels (qc_post mode 3), ``rbar`` unused."""
         X = self._X(X)
         B = X.shape[0]
-        st = _stream(self.device)
-        rows = (B + 63) // 64
-        part = torch.empty(rows, self.NP, dtype=torch.float32, device=self.device)
-        qbar = torch.empty_like(qjets)
         pde = self._pde()
         ub = None if ubar is None else _need(ubar.reshape(-1), self.device, "ubar")
         rb = None if (rbar is None or ujets) else _need(rbar.reshape(-1), self.device, "rbar")
         if ujets and (ub is None or ub.numel() != NCH * B or nch != NCH):
             raise L.QcError("the six-channel cotangent must be a [6, B] tensor")
-        L.check(self.lib.qc_post(3 if ujets else 1, X.data_ptr(), self._post_flat(), self.H, self.n, self.n_theta,
-                                 C.byref(pde), qjets.data_ptr(), None, None, _ptr(ub), _ptr(rb), qbar.data_ptr(),
-                                 part.data_ptr() + 4 * self.post_shift, self.NP, 0, B, nch, st), "qc_post(backward)")
-        abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, nch)
-        self._pre_backward(X, ajets, abar, part, B, nch, st)
-        d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st),
-                "qc_reduce_rows")
-        return d_flat
+        return self._reverse(
+            B, ajets, qjets,
+            lambda qbar, part, st: L.check(
+                self.lib.qc_post(3 if ujets else 1, X.data_ptr(), self._post_flat(), self.H, self.n, self.n_theta, C.byref(pde),
+                                 qjets.data_ptr(), None, None, _ptr(ub), _ptr(rb), qbar.data_ptr(),
+                                 part.data_ptr() + 4 * self.post_shift, self.NP, 0, B, nch, st), "qc_post(backward)"),
+            lambda *args: self.circuit._adjoint(*args, nch),
+            lambda abar, part, st: self._pre_backward(X, ajets, abar, part, B, nch, st))
+
+    def _reduce_rows(self, part: torch.Tensor, st) -> torch.Tensor:
+        rows, cols = part.shape
+        out = torch.empty(cols, dtype=torch.float32, device=self.device)
+        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, cols, cols, out.data_ptr(), st), "qc_reduce_rows")
+        return out
+
+    def _reverse(self, B, ajets, qjets, post, adjoint, pre_adjoint) -> torch.Tensor:
+        """THE reverse pass, over one row of NP entries per 64-point tile: ``post(qbar, part, st)`` fills the cotangent of
+        ``qjets`` and the post network's columns, ``adjoint(ajets, qbar, theta columns, stride)`` returns the cotangent of
+        ``ajets``, ``pre_adjoint(abar, part, st)`` fills the pre network's columns; returns the rows summed, d_flat (NP)."""
+        st = _stream(self.device)
+        part = torch.empty((B + 63) // 64, self.NP, dtype=torch.float32, device=self.device)
+        qbar = torch.empty_like(qjets)
+        post(qbar, part, st)
+        abar = adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP)
+        pre_adjoint(abar, part, st)
+        return self._reduce_rows(part, st)
 
     # ------------------------------------------------------------------ seven channels (with d2/dt2)
     def forward_tt(self, X: torch.Tensor, refresh: bool = True):
@@ -416,21 +424,18 @@ class SolverEngine:
         """Vector-Jacobian product of the seven channels w.r.t. the flat parameters: ``ubar`` [7, B] -> d_flat (NP)."""
         X = self._X(X)
         B = X.shape[0]
-        st = _stream(self.device)
-        rows = (B + 63) // 64
         ub = _need(ubar.reshape(-1), self.device, "ubar").clone()
         if ub.numel() != NCH_TT * B:
             raise L.QcError("the seven-channel cotangent must be a [7, B] tensor")
-        part = torch.empty(rows, self.NP, dtype=torch.float32, device=self.device)
-        qbar = torch.empty_like(qjets)
-        L.check(self.lib.qc_post_jets_tt(3, self.flat.data_ptr(), self.H, self.n, self.n_theta, qjets.data_ptr(), ub.data_ptr(),
-                                         qbar.data_ptr(), part.data_ptr(), self.NP, 0, B, st), "qc_post_jets_tt(backward)")
-        abar = self.circuit._adjoint_tt(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP)
-        L.check(self.lib.qc_pre_backward_tt(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, abar.data_ptr(),
-                                            part.data_ptr(), self.NP, 0, B, st), "qc_pre_backward_tt")
-        d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st), "qc_reduce_rows")
-        return d_flat
+        return self._reverse(
+            B, ajets, qjets,
+            lambda qbar, part, st: L.check(
+                self.lib.qc_post_jets_tt(3, self.flat.data_ptr(), self.H, self.n, self.n_theta, qjets.data_ptr(), ub.data_ptr(),
+                                         qbar.data_ptr(), part.data_ptr(), self.NP, 0, B, st), "qc_post_jets_tt(backward)"),
+            self.circuit._adjoint_tt,
+            lambda abar, part, st: L.check(
+                self.lib.qc_pre_backward_tt(X.data_ptr(), self.flat.data_ptr(), self.H, self.n, self.n_theta, abar.data_ptr(),
+                                            part.data_ptr(), self.NP, 0, B, st), "qc_pre_backward_tt"))
 
     # ------------------------------------------------------------------ K outputs behind one shared network
     def forward_multi(self, X: torch.Tensor, w4k: torch.Tensor):
@@ -456,27 +461,21 @@ class SolverEngine:
         one circuit adjoint sweep and one pre-network reverse pass for all K outputs."""
         X = self._X(X)
         B, K = X.shape[0], int(w4k.shape[0])
-        st = _stream(self.device)
-        rows = (B + 63) // 64
         KW = K * (self.H + 1)
-        part = torch.empty(rows, self.NP, dtype=torch.float32, device=self.device)
-        partk = torch.empty(rows, KW, dtype=torch.float32, device=self.device)
-        qbar = torch.empty_like(qjets)
+        partk = torch.empty((B + 63) // 64, KW, dtype=torch.float32, device=self.device)
         ub = _need(ubar.reshape(-1), self.device, "ubar")
         if ub.numel() != K * NCH * B:
             raise L.QcError("the cotangent must be a [K, 6, B] tensor")
         w4k = _need(w4k, self.device, "last-layer rows")
-        L.check(self.lib.qc_post_multi(3, self._post_flat(), self.H, self.n, self.n_theta, K, w4k.data_ptr(),
-                                       qjets.data_ptr(), None, ub.data_ptr(), qbar.data_ptr(),
-                                       part.data_ptr() + 4 * self.post_shift, self.NP,
-                                       partk.data_ptr(), KW, 0, B, st), "qc_post_multi(backward)")
-        abar = self.circuit._adjoint(ajets, qbar, part.data_ptr() + 4 * self.theta_off, self.NP, NCH)
-        self._pre_backward(X, ajets, abar, part, B, NCH, st)
-        d_flat = torch.empty(self.NP, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(part.data_ptr(), rows, self.NP, self.NP, d_flat.data_ptr(), st), "qc_reduce_rows")
-        d_w4k = torch.empty(KW, dtype=torch.float32, device=self.device)
-        L.check(self.lib.qc_reduce_rows(partk.data_ptr(), rows, KW, KW, d_w4k.data_ptr(), st), "qc_reduce_rows")
-        return d_flat, d_w4k.view(K, self.H + 1)
+        d_flat = self._reverse(
+            B, ajets, qjets,
+            lambda qbar, part, st: L.check(
+                self.lib.qc_post_multi(3, self._post_flat(), self.H, self.n, self.n_theta, K, w4k.data_ptr(), qjets.data_ptr(),
+                                       None, ub.data_ptr(), qbar.data_ptr(), part.data_ptr() + 4 * self.post_shift, self.NP,
+                                       partk.data_ptr(), KW, 0, B, st), "qc_post_multi(backward)"),
+            lambda *args: self.circuit._adjoint(*args, NCH),
+            lambda abar, part, st: self._pre_backward(X, ajets, abar, part, B, NCH, st))
+        return d_flat, self._reduce_rows(partk, _stream(self.device)).view(K, self.H + 1)
 
     # ------------------------------------------------------------------ fused training step
     def fused(self, B_res: int, n_ic: int, n_bc: int, opt: "OptimState", counts=None) -> "FusedStep":

@@ -1,19 +1,21 @@
 """The seven-channel step on the GPU: qc_fused_pinn_coef_tt_step (QC_PHASE_GRADS) against the float64 reference of
 tests/tt_reference.py, its agreement with the coefficient step on a zero d_tt column, the bits of its gather, three training
-steps on the standing-wave problem against a float64 replay, and the autograd path (DVPDESolver.jets_tt, wave_2d_operator).
+steps on the standing-wave problem against a float64 replay, the bits of three steps against a recording of the step as it
+was before it shared the other entry points' host code, and the autograd path (DVPDESolver.jets_tt, wave_2d_operator).
 
 Tolerances are the project's (tests/test_gpu_tabulated.py): the gradient block by block at TOL_G x max(1, max |ref block|),
 the loss parts at TOL_L, 1e-4 on a loss history and 2e-3 on the weights behind it.  The negative controls (d_tt zeroed, d_tt
 and d_xx swapped, the table rolled by one row) must fail the same tolerance; tests/test_tt_cpu.py shows that each moves the
 reference by far more."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 import torch
 
 import tt_reference as TR
-from conftest import pkg
+from conftest import GOLDEN, pkg
 from step_reference import haar_for
 from test_gpu_coef import _coef_step, _load_coef
 from test_gpu_fullsize import Log, base_args
@@ -178,7 +180,55 @@ def test_training_on_the_standing_wave_matches_the_fp64_replay(gpu_device, tmp_p
     assert len(m2.loss_history) == STEPS and np.isfinite(m2.loss_history).all()
 
 
-# ---- 5. the autograd path
+# ---- 5. the bits of the step, recorded before it was routed through the step plan of the other entry points
+# (B_res, n_ic, n_bc): both streams (two residual tiles, a full and a partial value tile); no side stream; no residual pipeline
+BITS_SHAPES = ((128, 64, 5), (128, 0, 0), (0, 64, 5))
+BITS_STEPS = 3
+
+
+def step_bits(gpu_device, B_res, n_ic, n_bc, split_first=False):
+    """{"flat", "m", "v" (BITS_STEPS, NP), "loss" (BITS_STEPS, 3)} after each of BITS_STEPS steps SAMPLE | GRADS | UPDATE of
+    the cascade model n = 2, H = 3 from the seeded weights of TR.case_inputs, sampler seed 2024, on a resident dataset of
+    11 / 4 / 6 rows; ``split_first``: the first step as three calls, one phase each."""
+    L, engine = pkg("hip.lib"), pkg("hip.engine")
+    _, _, _, flat, X_ic, X_bc, X_res, u_ic, u_bc, r_res, coef = TR.case_inputs("cascade", 2, 1, 3, 11, 4, 6)
+    model, eng = _model(gpu_device, "cascade", 2, 1, "angle", flat, hidden=3)
+    eng.problem, eng.coeffs, eng.c_u = L.QC_PROBLEM_TABULATED, (NAN,) * 5, NAN
+    eng.refresh_gates()
+    opt = engine.OptimState(eng.NP, 0.005, eng.device)
+    fs = engine.FusedStepTT(eng, B_res, n_ic, n_bc, opt, (max(B_res, 1), max(n_ic, 1), max(n_bc, 1)))
+    to = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32).to(gpu_device)
+    fs.set_dataset(((to(X_res), to(r_res)), (to(X_ic), to(u_ic)), (to(X_bc), to(u_bc))), to(coef))
+    fs.set_sampler(2024)
+    phases = (L.QC_PHASE_SAMPLE, L.QC_PHASE_GRADS, L.QC_PHASE_UPDATE)
+    out = {"flat": [], "m": [], "v": [], "loss": []}
+    for s in range(BITS_STEPS):
+        for ph in (phases if split_first and s == 0 else (sum(phases),)):
+            fs.run(ph)
+        torch.cuda.synchronize()
+        for k, t in (("flat", eng.flat), ("m", opt.m), ("v", opt.v), ("loss", opt.state[6:9])):
+            out[k].append(t.detach().cpu().numpy().copy())
+    return {k: np.stack(v) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("shape", BITS_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_step_bits_are_those_of_the_recorded_step(shape, gpu_device):
+    """Flat parameters, m, v and the three logged loss sums after each of three steps, bit for bit against
+    tests/golden/tt_step_bits.npz (tests/golden/make_tt_step_bits.py: recorded on the GPU from the step as it was before the
+    entry point was routed through the step plan; two recorded runs agreed in every bit, the step's reductions being
+    fixed-order).  A step issued as three calls, one phase each, gives the bits of the combined call."""
+    want = np.load(os.path.join(GOLDEN, "tt_step_bits.npz"))
+    key = "x".join(map(str, shape))
+    got, split = step_bits(gpu_device, *shape), step_bits(gpu_device, *shape, split_first=True)
+    for k in ("flat", "m", "v", "loss"):
+        w = want[f"{key}__{k}"]
+        assert got[k].shape == w.shape and got[k].dtype == w.dtype == np.float32
+        assert np.isfinite(w).all() and not np.array_equal(w[0], w[-1])      # the recorded steps moved
+        assert np.array_equal(got[k].view(np.uint32), w.view(np.uint32)), (k, np.abs(got[k] - w).max())
+        assert np.array_equal(split[k].view(np.uint32), w.view(np.uint32)), (k, "one call per phase", np.abs(split[k] - w).max())
+
+
+# ---- 6. the autograd path
 def test_jets_tt_and_the_wave_operator(gpu_device):
     pde = pkg("nn.pde")
     ans, n, Lq, H, B = "cascade", 4, 1, 50, 70
