@@ -894,6 +894,53 @@ int qc_sample_dataset_coef_tt(float* X_res_dev, float* target_res_dev, int64_t n
 int qc_fused_pinn_coef_tt_step(const qc_step_desc* desc, const qc_step_data* data, const qc_step_coef_tt* coef, int phases,
                                void* stream);
 
+/* ---- ensembles: M independent models of ONE architecture and ONE gate program per launch sequence.  A seed / learning-rate /
+ * loss-weight / operator-constant sweep or a deep ensemble of the reference's small model (trainer/diffusion_train.py with
+ * batch_size 64: one residual tile and one value tile per stage) is M times a step that leaves the chip idle; the ensemble
+ * step has the single-model step's launches, each over the tiles of all M members (grid = tiles of one member x M).
+ *
+ * The contract: member m computes what qc_fused_pinn_residual_step computes on a descriptor whose buffers are member m's
+ * slices, whose sampler key is desc->sample_seed + m, and whose pde and hyper are member m's.
+ *
+ * desc describes member 0.  Every per-model buffer of it is the first of M consecutive slices; member m's slice starts m
+ * strides behind it:
+ *   params_dev, m_dev, v_dev          params_stride floats, >= NP
+ *   flat_dev                          flat_stride floats, >= NP + 3
+ *   opt_state_dev                     64-byte records, back to back
+ *   hist_dev                          hist_stride floats, >= hist_cap (not read when hist_dev is NULL)
+ *   trig_dev                          trig_stride BYTES, >= qc_trig_bytes(prog) and a multiple of 256
+ *   X_res_dev / X_val_dev             x_res_stride / x_val_stride floats, >= 3 B_res / 3 B_val
+ *   the four residual jet buffers     jets_res_stride floats, >= 6 n B_res
+ *   the four value jet buffers        jets_val_stride floats, >= n B_val
+ *   part_dev                          part_rows_cap * part_stride floats: [M][part_rows_cap][part_stride]
+ *   circ_ws_dev                       ws_stride BYTES, >= qc_step_workspace_bytes(prog, B_res, B_val) and a multiple of 256;
+ *                                     desc->circ_ws_bytes is the size of ONE slice
+ * prog and umat_dev are shared.  pde_dev / hyper_dev: device tables of M qc_pde / qc_opt_hyper records (8-byte aligned), or
+ * NULL: every member takes desc->pde / desc->hyper.  A table entry's problem id and n_seg_a must be desc->pde's (they are
+ * not checked: the tables live on the device).  The learning rate is per member already: it lives in the state record.
+ * qc_ensemble_strides fills the smallest strides for desc and M and leaves both tables NULL.
+ *
+ * Phases as in the single-model step; QC_PHASE_GRADS alone leaves member m's [gradient | L_r, L_bc, L_ic] in its flat slice.
+ * Scope: what the merged form of the single-model step covers with analytic targets: register family (2 <= n <= 5, no EMBED
+ * gates), angle encoding, no Fourier-feature map, B_res > 0 and B_val > 0, every buffer and the final-state store present,
+ * problems 0 .. 2, points drawn on the device or given, H <= 128 (the fused post kernel); compile-time programs where the
+ * single-model step uses them.  QC_ERR_UNSUPPORTED before any launch: another family, amplitude encoding, a Fourier-feature
+ * map, EMBED gates, H > 128.  QC_ERR_ARG before any launch: desc or ens NULL; desc->comm set; M < 1 or M > 65535; a stride
+ * below its bound or a trig / workspace stride that is no multiple of 256; a NULL buffer, an empty batch or a workspace
+ * slice smaller than the final-state store; a misaligned table; a problem id outside 0 .. 2 (tabulated targets have no
+ * ensemble form); and whatever qc_fused_pinn_residual_step refuses. */
+typedef struct qc_step_ensemble {
+  int M;
+  int64_t params_stride, flat_stride, hist_stride;
+  int64_t trig_stride;                      /* bytes */
+  int64_t x_res_stride, x_val_stride, jets_res_stride, jets_val_stride;
+  int64_t ws_stride;                        /* bytes */
+  const qc_pde* pde_dev;
+  const qc_opt_hyper* hyper_dev;
+} qc_step_ensemble;
+int qc_ensemble_strides(const qc_step_desc* desc, int M, qc_step_ensemble* ens_out);
+int qc_fused_pinn_ensemble_step(const qc_step_desc* desc, const qc_step_ensemble* ens, int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1505,4 +1505,101 @@ int qc_fused_pinn_coef_tt_step(const qc_step_desc* d, const qc_step_data* t, con
   return fused_step(d, plan, phases, stream);
 }
 
+// ---- ensembles: M members per launch sequence (the merged form of the analytic step, every stage over all members' tiles)
+static bool ens_supported(const qc_step_desc* d) {
+  const qc_program* p = d->prog;
+  return p->fam == &qc_family_reg && !p->amplitude && p->ff_m == 0 && p->n_embed == 0 &&
+         (d->H < 1 || qc_mlp_ens_ok(qc_layout(d->H, d->n, d->n_theta)));
+}
+
+int qc_ensemble_strides(const qc_step_desc* d, int M, qc_step_ensemble* out) {
+  if (!d || !out || !d->prog || M < 1 || d->B_res < 0 || d->B_val < 0 || d->H < 1 || d->n < 1 || d->n_theta < 0 || d->hist_cap < 0)
+    return QC_ERR_ARG;
+  const QcLayout L = qc_layout(d->H, d->n, d->n_theta, 1, 0, prog_n_in(d->prog));
+  out->M = M;
+  out->params_stride = L.NP;
+  out->flat_stride = L.NP + 3;
+  out->hist_stride = d->hist_cap;
+  out->trig_stride = (int64_t)round256(qc_trig_bytes(d->prog));
+  out->x_res_stride = 3 * d->B_res;
+  out->x_val_stride = 3 * d->B_val;
+  out->jets_res_stride = 6 * (int64_t)d->n * d->B_res;
+  out->jets_val_stride = (int64_t)d->n * d->B_val;
+  out->ws_stride = (int64_t)round256(qc_step_workspace_bytes(d->prog, d->B_res, d->B_val));
+  out->pde_dev = nullptr;
+  out->hyper_dev = nullptr;
+  return QC_OK;
+}
+
+int qc_fused_pinn_ensemble_step(const qc_step_desc* d, const qc_step_ensemble* ens, int phases, void* stream) {
+  if (!d || !ens || d->comm) return QC_ERR_ARG;
+  if (ens->M < 1 || ens->M > 65535) return QC_ERR_ARG;
+  if (!d->part_dev || !d->flat_dev) return QC_ERR_ARG;
+  if (!problem_ok(d->pde.problem) || d->sample_bc_face_points < QC_BC_RANDOM_FACE) return QC_ERR_ARG;
+  int rc = check_step_desc(d, false, ens_supported);
+  if (rc) return rc;
+  const qc_program* pg = d->prog;
+  if (pg->n_u4 > 0 && !d->umat_dev) return QC_ERR_ARG;
+  const QcLayout L = qc_layout(d->H, d->n, d->n_theta);
+  const size_t store = qc_family_reg.store_bytes(pg, 6, d->B_res > 0 ? d->B_res : 0);
+  if (d->B_res <= 0 || d->B_val <= 0 || d->n_ic < 0 || d->n_ic > d->B_val || !d->X_res_dev || !d->X_val_dev || !d->ajets_res_dev ||
+      !d->qjets_res_dev || !d->qbar_res_dev || !d->abar_res_dev || !d->ajets_val_dev || !d->qjets_val_dev || !d->qbar_val_dev ||
+      !d->abar_val_dev || !d->circ_ws_dev || d->circ_ws_bytes < store)
+    return QC_ERR_ARG;
+  const int64_t rows_res = qc_ceil_div(d->B_res, 64), rows_val = qc_ceil_div(d->B_val, 64), rows = rows_res + rows_val;
+  if (rows > d->part_rows_cap || d->part_stride < L.NP + 3) return QC_ERR_ARG;
+  if ((phases & QC_PHASE_UPDATE) && (!d->m_dev || !d->v_dev || !d->opt_state_dev)) return QC_ERR_ARG;
+  if (ens->params_stride < L.NP || ens->flat_stride < L.NP + 3 || (d->hist_dev && ens->hist_stride < d->hist_cap) ||
+      ens->trig_stride < (int64_t)qc_trig_bytes(pg) || (ens->trig_stride & 255) || ens->x_res_stride < 3 * d->B_res ||
+      ens->x_val_stride < 3 * d->B_val || ens->jets_res_stride < 6 * (int64_t)d->n * d->B_res ||
+      ens->jets_val_stride < (int64_t)d->n * d->B_val || ens->ws_stride < (int64_t)store || (ens->ws_stride & 255) ||
+      ((uintptr_t)ens->pde_dev & 7) || ((uintptr_t)ens->hyper_dev & 7))
+    return QC_ERR_ARG;
+  const QcEns e = {ens->M, ens->params_stride, ens->flat_stride, ens->hist_stride, ens->trig_stride, ens->x_res_stride,
+                   ens->x_val_stride, ens->jets_res_stride, ens->jets_val_stride, d->part_rows_cap * d->part_stride,
+                   ens->ws_stride, (const QcPde*)ens->pde_dev, (const QcOptHyper*)ens->hyper_dev};
+  hipStream_t st = (hipStream_t)stream;
+  const QcTrig* trig = (const QcTrig*)d->trig_dev;
+  float* chi_store = (float*)d->circ_ws_dev;
+  const QcBatches b0 = step_batches(d, nullptr);
+  if ((phases & QC_PHASE_SAMPLE) && !(phases & QC_PHASE_GRADS)) {
+    // points alone: one draw per member, keyed seed + m (with the gradients the first stage draws them itself)
+    QcSource src;
+    src.face_pts = d->sample_bc_face_points;
+    for (int m = 0; m < e.M; ++m) {
+      QcBatches b = b0;
+      b.X_res += m * e.X_res;
+      b.X_val += m * e.X_val;
+      b.seed += (uint64_t)m;
+      if ((rc = fill_batches(b, src, st))) return rc;
+    }
+  }
+  if (phases & QC_PHASE_GRADS) {
+    QcPde pde;
+    memcpy(&pde, &d->pde, sizeof(pde));
+    if ((rc = qc_mlp_pre_fwd_ens(b0, (phases & QC_PHASE_SAMPLE) ? 1 : 0, d->sample_bc_face_points, d->params_dev, L,
+                                 d->ajets_res_dev, d->ajets_val_dev, st, pg->angle_map, e)) ||
+        (rc = qc_reg_circ_fwd_ens(pg, trig, d->umat_dev, d->ajets_res_dev, d->qjets_res_dev, d->B_res, chi_store,
+                                  d->ajets_val_dev, d->qjets_val_dev, d->B_val, st, e)) ||
+        (rc = qc_mlp_post_ens(d->params_dev, L, pde, d->X_res_dev, d->qjets_res_dev, d->abar_res_dev, d->abar_res_dev + d->B_res,
+                              d->qbar_res_dev, 0, d->B_res, d->X_val_dev, d->qjets_val_dev, d->abar_val_dev, d->qbar_val_dev,
+                              rows_res, d->B_val, d->part_dev, d->part_stride, st, e)) ||
+        (rc = qc_reg_circ_bwd_ens(pg, trig, d->umat_dev, d->ajets_res_dev, d->qbar_res_dev, d->abar_res_dev, 0, d->B_res,
+                                  chi_store, d->ajets_val_dev, d->qbar_val_dev, d->abar_val_dev, rows_res, d->B_val,
+                                  d->part_dev + L.oTh, d->part_stride, st, e)) ||
+        (rc = qc_mlp_pre_bwd_ens(d->X_res_dev, d->X_val_dev, d->params_dev, L, d->abar_res_dev, d->abar_val_dev, d->part_dev,
+                                 d->part_stride, 0, rows_res, d->B_res, d->B_val, st, pg->angle_map, d->ajets_res_dev,
+                                 d->ajets_val_dev, e)))
+      return rc;
+    if ((rc = after_launch())) return rc;
+  }
+  if (!(phases & (QC_PHASE_GRADS | QC_PHASE_UPDATE))) return QC_OK;
+  QcOptHyper h;
+  memcpy(&h, &d->hyper, sizeof(h));
+  qc_opt_ens_tail(d->part_dev, (phases & QC_PHASE_GRADS) ? rows : 0, d->part_stride, d->flat_dev, L.NP, d->params_dev, d->m_dev,
+                  d->v_dev, (QcOptState*)d->opt_state_dev, h, d->hist_dev, d->hist_cap, pg, L.oTh, (QcTrig*)d->trig_dev,
+                  (phases & QC_PHASE_UPDATE) ? 1 : 0, e, st);
+  return after_launch();
+}
+
 }  // extern "C"

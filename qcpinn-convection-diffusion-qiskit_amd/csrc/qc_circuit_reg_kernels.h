@@ -1060,6 +1060,64 @@ __global__ void __launch_bounds__(192, 4) k_circ_bwd_both2(const QcBwd2Args) {
   }
 }
 
+// ---- ensembles (qc_internal.h, QcEns): the two merged circuit stages over the tiles of M members, grid (tiles of one
+// member, M).  Member blockIdx.y reads its own trig buffer (per-gate entries and phase tables), jets, cotangents, final-state
+// store and partial rows; the program and umat are shared.  The tile runs the bodies of k_circ_fwd_both and of
+// k_circ_bwd_both2, whose argument record travels inside this one with the strides behind it (read, like it, through the
+// kernel-argument segment inside the branch that needs it).
+template <class PG>
+__global__ void __launch_bounds__(384) k_circ_fwd_ens(const QcGate* __restrict__ prog, const QcTrig* __restrict__ trig,
+                                                      const float* __restrict__ umat, int n_gates,
+                                                      const float* __restrict__ ajets, float* __restrict__ qjets, int64_t Br,
+                                                      float* __restrict__ chi_store, const float* __restrict__ angles,
+                                                      float* __restrict__ expval, int64_t Bv, int amp, int n_val, QcEns e) {
+  const int64_t m = blockIdx.y;
+  trig = (const QcTrig*)((const char*)trig + m * e.trig);
+  if ((int)blockIdx.x >= n_val)
+    k_jets_fwd_body<PG>(blockIdx.x - n_val, prog, trig, umat, n_gates, ajets + m * e.jets_res, qjets + m * e.jets_res, Br,
+                        (float*)((char*)chi_store + m * e.ws), amp);
+  else
+    k_value_fwd_body<PG, 6>(blockIdx.x, prog, trig, umat, n_gates, angles + m * e.jets_val, expval + m * e.jets_val, Bv, amp);
+}
+
+struct QcBwd2EnsArgs {
+  QcBwd2Args a;
+  QcEns e;
+};
+template <class PG, bool ABSORB>
+__global__ void __launch_bounds__(192, 4) k_circ_bwd_ens2(const QcBwd2EnsArgs) {
+  using Args = const __attribute__((address_space(4))) QcBwd2EnsArgs*;
+  const Args a0 = (Args)__builtin_amdgcn_kernarg_segment_ptr();
+  auto args = [&]() {
+    Args a = a0;
+    asm volatile("" : "+s"(a));
+    return a;
+  };
+  const int n_val = a0->a.n_val;
+  const int64_t m = blockIdx.y;
+  if ((int)blockIdx.x >= n_val) {
+    const Args t = args();
+    const int64_t jr = m * t->e.jets_res;
+    k_jets_bwd2_body<PG, ABSORB>(
+        blockIdx.x - n_val, t->a.prog, (const QcTrig*)((const char*)t->a.trig + m * t->e.trig), t->a.umat, t->a.n_gates,
+        t->a.n_params, t->a.res.ajets + jr, t->a.res.qbar + jr, t->a.res.abar + jr,
+        [&]() {
+          const Args u = args();
+          return QcPartRow{u->a.part + (int64_t)blockIdx.y * u->e.part +
+                               (u->a.res.row0 + ((int)blockIdx.x - u->a.n_val)) * u->a.part_stride,
+                           u->a.n_params};
+        },
+        t->a.res.B, (const float*)((const char*)t->a.res.chi_store + m * t->e.ws));
+  } else {
+    const Args t = args();
+    const int64_t jv = m * t->e.jets_val;
+    k_value_bwd_body<PG, 3, ABSORB ? 1 : 0>(blockIdx.x, t->a.prog, (const QcTrig*)((const char*)t->a.trig + m * t->e.trig),
+                                            t->a.umat, t->a.n_gates, t->a.n_params, t->a.val.angles + jv, t->a.val.cot + jv,
+                                            t->a.val.d_angles + jv, t->a.part + m * t->e.part, t->a.part_stride, t->a.val.row0,
+                                            t->a.val.B, 0);
+  }
+}
+
 }  // namespace
 
 // bit 0: amplitude encoding; bit 1: leading RX layer folded into the embedding (QC_NO_ABSORB=1 disables)
@@ -1082,6 +1140,12 @@ struct QcRegLaunchers {
                        float*, int64_t, hipStream_t);
   int (*circ_bwd_both)(const qc_program*, const QcTrig*, const float*, const float*, const float*, float*, int64_t, int64_t,
                        const float*, const float*, const float*, float*, int64_t, int64_t, float*, int64_t, hipStream_t);
+  // the same two stages over the tiles of an ensemble's members (angle encoding only)
+  int (*circ_fwd_ens)(const qc_program*, const QcTrig*, const float*, const float*, float*, int64_t, float*, const float*,
+                      float*, int64_t, hipStream_t, const QcEns&);
+  int (*circ_bwd_ens)(const qc_program*, const QcTrig*, const float*, const float*, const float*, float*, int64_t, int64_t,
+                      const float*, const float*, const float*, float*, int64_t, int64_t, float*, int64_t, hipStream_t,
+                      const QcEns&);
 };
 
 template <class PG>
@@ -1164,7 +1228,37 @@ struct RegLaunch {
                        part_stride, qc_embed_flags(pg), nv);
     return QC_OK;
   }
+  static int circ_fwd_ens(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, float* qjets,
+                          int64_t Br, float* chi_store, const float* angles, float* expval, int64_t Bv, hipStream_t st,
+                          const QcEns& e) {
+    if (pg->amplitude) return QC_ERR_UNSUPPORTED;
+    const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 384);
+    hipLaunchKernelGGL(k_circ_fwd_ens<PG>, dim3(nr + nv, e.M), dim3(384), 0, st, pg->d_gates, trig, umat, pg->n_gates, ajets,
+                       qjets, Br, chi_store, angles, expval, Bv, qc_embed_flags(pg), nv, e);
+    return QC_OK;
+  }
+  static int circ_bwd_ens(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets,
+                          const float* qbar, float* abar, int64_t row0_r, int64_t Br, const float* chi_store,
+                          const float* angles, const float* cot, float* d_angles, int64_t row0_v, int64_t Bv, float* part,
+                          int64_t part_stride, hipStream_t st, const QcEns& e) {
+    if (pg->amplitude) return QC_ERR_UNSUPPORTED;
+    const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 192);
+    const size_t sh = ((size_t)3 * (2u << PG::N) * 64 + (size_t)4 * PG::N * 64 + (size_t)3 * pg->n_params) * sizeof(float);
+    const QcBwd2EnsArgs args = {{pg->d_gates, trig, umat, pg->n_gates, pg->n_params, part, part_stride, nv,
+                                 {ajets, qbar, abar, chi_store, row0_r, Br}, {angles, cot, d_angles, row0_v, Bv}}, e};
+    const bool absorb = (qc_embed_flags(pg) & 2) != 0;
+    if constexpr (PG::lead_rx) {
+      if (absorb) {
+        hipLaunchKernelGGL((k_circ_bwd_ens2<PG, true>), dim3(nr + nv, e.M), dim3(192), sh, st, args);
+        return QC_OK;
+      }
+    } else if (absorb) {
+      return QC_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL((k_circ_bwd_ens2<PG, false>), dim3(nr + nv, e.M), dim3(192), sh, st, args);
+    return QC_OK;
+  }
   static constexpr QcRegLaunchers table() {
-    return {&value_fwd, &value_bwd, &jets_fwd, &jets_bwd, &circ_fwd_both, &circ_bwd_both};
+    return {&value_fwd, &value_bwd, &jets_fwd, &jets_bwd, &circ_fwd_both, &circ_bwd_both, &circ_fwd_ens, &circ_bwd_ens};
   }
 };

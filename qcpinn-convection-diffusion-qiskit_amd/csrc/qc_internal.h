@@ -419,3 +419,52 @@ int qc_tt_circ_fwd(const qc_program* pg, const QcTrig* trig, const float* umat, 
                    hipStream_t);
 int qc_tt_circ_bwd(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, const float* qbar,
                    float* abar, float* part, int64_t part_stride, int64_t row0, int64_t B, hipStream_t);
+
+// ---- ensembles: M independent models per launch (qc_fused_pinn_ensemble_step).  Every per-model buffer of the step is M
+// consecutive slices; these are the distances between them, in floats except trig and ws (bytes).  A stage's ensemble
+// kernel has the grid (tiles of one member, M): it offsets its pointers by blockIdx.y slices with scalar arithmetic and
+// calls the single-model body.  pde / hyper: device tables of M records, or null (every member takes the launch's own).
+struct QcEns {
+  int M;
+  int64_t prm, flat, hist, trig, X_res, X_val, jets_res, jets_val, part, ws;
+  const QcPde* pde;
+  const QcOptHyper* hyper;
+};
+// record m of a device table, through the constant address space: m is wave-uniform (a block index), so the record arrives
+// by scalar loads
+template <class T>
+__device__ __forceinline__ T qc_ens_record(const T* table, const int m) {
+  static_assert(sizeof(T) % 4 == 0 && alignof(T) >= 4, "whole words");
+  T r;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto* w = (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(table + m);
+#else
+  const uint32_t* w = (const uint32_t*)(table + m);
+#endif
+  uint32_t* o = (uint32_t*)&r;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) o[i] = w[i];
+  return r;
+}
+// the stage launchers: the arguments of the merged single-model launchers (member 0's slices) and the strides
+int qc_mlp_pre_fwd_ens(const QcBatches& b, int draw, int64_t face_pts, const float* prm, QcLayout L, float* ajr, float* ajv,
+                       hipStream_t st, int map, const QcEns& e);
+int qc_mlp_post_ens(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr, float* qbr,
+                    int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv, int64_t row0_v,
+                    int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcEns& e);
+int qc_mlp_pre_bwd_ens(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
+                       float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv, hipStream_t st,
+                       int map, const float* ajr, const float* ajv, const QcEns& e);
+bool qc_mlp_ens_ok(const QcLayout& L);   // the fused post kernel serves this hidden width
+int qc_reg_circ_fwd_ens(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, float* qjets,
+                        int64_t Br, float* chi_store, const float* angles, float* expval, int64_t Bv, hipStream_t st,
+                        const QcEns& e);
+int qc_reg_circ_bwd_ens(const qc_program* pg, const QcTrig* trig, const float* umat, const float* ajets, const float* qbar,
+                        float* abar, int64_t row0_r, int64_t Br, const float* chi_store, const float* angles, const float* cot,
+                        float* d_angles, int64_t row0_v, int64_t Bv, float* part, int64_t part_stride, hipStream_t st,
+                        const QcEns& e);
+// the tail, one block per member: rows of the member's partial-row matrix -> flat [gradient | 3 loss sums]; with `update`
+// then adam_block on the member's slices and state record (hp: every member's without a table); rows = 0: flat is given
+int qc_opt_ens_tail(float* part, int64_t rows, int64_t stride, float* flat, int NP, float* prm, float* m, float* v,
+                    QcOptState* state, QcOptHyper hp, float* hist, int hist_cap, const qc_program* pg, int theta_off,
+                    QcTrig* trig, int update, const QcEns& e, hipStream_t);

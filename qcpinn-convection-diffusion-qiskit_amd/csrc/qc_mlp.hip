@@ -3344,3 +3344,119 @@ int qc_mlp_pre_ff_bwd_both(const float* Xr, const float* Xv, const float* prm, Q
     if (map) launch(qc_int<1>{}); else launch(qc_int<0>{});
   });
 }
+
+// ================================================================== ensembles: M members per launch
+// One wrapper per merged stage of the fused step, grid (blocks of one member, M): member blockIdx.y's slices lie
+// blockIdx.y strides behind member 0's (scalar arithmetic on kernel arguments), its sampler key is seed + blockIdx.y, its
+// operator record comes from the table when there is one (scalar loads), and the tile runs the body of the single-model
+// kernel: k_pre_fwd_both, k_post_fused_both (analytic targets) and k_pre_bwd_both.  Register family only (n = 2 .. 5).
+namespace {
+
+template <int N, int MAP, bool RF>
+__global__ void __launch_bounds__(256) k_pre_fwd_ens(float* __restrict__ Xr, float* __restrict__ Xv,
+                                                     const float* __restrict__ prm, QcLayout L, float* __restrict__ ajr,
+                                                     float* __restrict__ ajv, int64_t Br, int64_t Bv, int n_val, QcDraw draw,
+                                                     QcEns e) {
+  // (the points and the angle jets are addressed per lane: their bases ride in vector registers, which this kernel has
+  // to spare, where scalar registers are short)
+  auto lanes = [](float* p) {
+    asm volatile("" : "+v"(p));
+    return p;
+  };
+  const int64_t m = blockIdx.y;
+  draw.seed += (uint64_t)m;
+  prm += m * e.prm;
+  if ((int)blockIdx.x >= n_val) {
+    float* X = lanes(Xr + m * e.X_res);
+    k_pre_fwd_body<N, 6, MAP>(blockIdx.x - n_val, X, prm, L, lanes(ajr + m * e.jets_res), Br, &draw, X);
+  } else {
+    float* X = lanes(Xv + m * e.X_val);
+    k_pre_fwd_value4<N, MAP, RF>(blockIdx.x, X, prm, L, lanes(ajv + m * e.jets_val), Bv, &draw, X);
+  }
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) k_post_fused_ens(const float* __restrict__ prm, QcLayout L, QcPde pde, QcPostSeg r,
+                                                        QcPostSeg v, float* __restrict__ part, int64_t part_stride, int n_res,
+                                                        QcEns e) {
+  extern __shared__ float s_dyn[];
+  const int64_t m = blockIdx.y;
+  if (e.pde != nullptr) pde = qc_ens_record(e.pde, (int)blockIdx.y);
+  prm += m * e.prm;
+  part += m * e.part;
+  if ((int)blockIdx.x < n_res)
+    k_post_fused6_body<N>(blockIdx.x, r.X + m * e.X_res, prm, L, pde, r.qjets + m * e.jets_res, r.ub + m * e.jets_res,
+                          r.rb + m * e.jets_res, r.qbar + m * e.jets_res, part, part_stride, r.row0, r.B, s_dyn);
+  else
+    k_post_fused_value_body<N, QC_POST_VALUE_TPB>(blockIdx.x - n_res, v.X + m * e.X_val, prm, L, pde, v.qjets + m * e.jets_val,
+                                                  v.ub + m * e.jets_val, v.qbar + m * e.jets_val, part, part_stride, v.row0, v.B,
+                                                  s_dyn);
+}
+
+template <int N, int MAP>
+__global__ void k_pre_bwd_ens(const float* __restrict__ Xr, const float* __restrict__ Xv, const float* __restrict__ prm,
+                              QcLayout L, const float* __restrict__ abr, const float* __restrict__ abv,
+                              float* __restrict__ part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br,
+                              int64_t Bv, int HB, int PS, int n_val, const float* __restrict__ ajr,
+                              const float* __restrict__ ajv, QcEns e) {
+  const int64_t m = blockIdx.y;
+  prm += m * e.prm;
+  part += m * e.part;
+  if ((int)blockIdx.x >= n_val)
+    k_pre_bwd_body<N, 6, MAP>(blockIdx.x - n_val, Xr + m * e.X_res, prm, L, abr + m * e.jets_res, part, part_stride, row0_r, Br,
+                              HB, PS, ajr + m * e.jets_res);
+  else
+    k_pre_bwd_body<N, 1, MAP>(blockIdx.x, Xv + m * e.X_val, prm, L, abv + m * e.jets_val, part, part_stride, row0_v, Bv, HB, PS,
+                              ajv + m * e.jets_val);
+}
+
+}  // namespace
+
+bool qc_mlp_ens_ok(const QcLayout& L) { return L.H <= QC_POST_FUSED_MAXH; }
+
+int qc_mlp_pre_fwd_ens(const QcBatches& b, int draw, int64_t face_pts, const float* prm, QcLayout L, float* ajr, float* ajv,
+                       hipStream_t st, int map, const QcEns& e) {
+  float *Xr = b.X_res, *Xv = b.X_val;
+  const int64_t Br = b.n_res, Bv = b.n_ic + b.n_bc;
+  const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(qc_ceil_div(Bv, 64), 4);
+  const QcDraw dr = {draw, b.n_ic, b.off_res, b.off_ic, b.off_bc, face_pts, b.seed, b.step};
+  const bool rf = draw && face_pts < 0;
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    auto launch = [&](auto m, auto r) {
+      hipLaunchKernelGGL((k_pre_fwd_ens<n(), m(), r()>), dim3(nr + nv, e.M), dim3(256), 0, st, Xr, Xv, prm, L, ajr, ajv, Br, Bv,
+                         nv, dr, e);
+    };
+    if (map) { if (rf) launch(qc_int<1>{}, std::true_type{}); else launch(qc_int<1>{}, std::false_type{}); }
+    else if (rf) launch(qc_int<0>{}, std::true_type{});
+    else launch(qc_int<0>{}, std::false_type{});
+  });
+}
+
+int qc_mlp_post_ens(const float* prm, QcLayout L, QcPde pde, const float* Xr, const float* qjr, float* ubr, float* rbr, float* qbr,
+                    int64_t row0_r, int64_t Br, const float* Xv, const float* qjv, float* ubv, float* qbv, int64_t row0_v,
+                    int64_t Bv, float* part, int64_t part_stride, hipStream_t st, const QcEns& e) {
+  if (!qc_mlp_ens_ok(L)) return QC_ERR_UNSUPPORTED;
+  const int nr = qc_ceil_div(Br, 64), nvf = qc_ceil_div(qc_ceil_div(Bv, 64), QC_POST_VALUE_TPB);
+  const QcPostSeg r = {Xr, qjr, ubr, rbr, qbr, row0_r, Br}, v = {Xv, qjv, ubv, nullptr, qbv, row0_v, Bv};
+  const size_t shr = qc_post_fused_lds_res(L), shv = qc_post_fused_lds_val(L), shf = shr > shv ? shr : shv;
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    hipLaunchKernelGGL((k_post_fused_ens<n()>), dim3(nr + nvf, e.M), dim3(256), shf, st, prm, L, pde, r, v, part, part_stride, nr,
+                       e);
+  });
+}
+
+int qc_mlp_pre_bwd_ens(const float* Xr, const float* Xv, const float* prm, QcLayout L, const float* abr, const float* abv,
+                       float* part, int64_t part_stride, int64_t row0_r, int64_t row0_v, int64_t Br, int64_t Bv, hipStream_t st,
+                       int map, const float* ajr, const float* ajv, const QcEns& e) {
+  const int nr = qc_ceil_div(Br, 64), nv = qc_ceil_div(Bv, 64);
+  int HB, PS, threads;
+  hidden_geometry(L.H, &HB, &PS, &threads);
+  const size_t sh = (size_t)PS * (4 + L.n) * HB * sizeof(float);
+  return qc_dispatch_n<2, 5>(L.n, [&](auto n) {
+    auto launch = [&](auto m) {
+      hipLaunchKernelGGL((k_pre_bwd_ens<n(), m()>), dim3(nr + nv, e.M), dim3(threads), sh, st, Xr, Xv, prm, L, abr, abv, part,
+                         part_stride, row0_r, row0_v, Br, Bv, HB, PS, nv, ajr, ajv, e);
+    };
+    if (map) launch(qc_int<1>{}); else launch(qc_int<0>{});
+  });
+}

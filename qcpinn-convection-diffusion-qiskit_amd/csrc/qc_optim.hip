@@ -836,3 +836,93 @@ int qc_opt_gradnorm_fold(float* part, int64_t n_res, int64_t n_ic, int64_t n_bc,
     hipLaunchKernelGGL((k_gradnorm_combine<false>), dim3(1), dim3(1024), 0, st, (const float*)part, stride, ncols, sv, gn, flat, class_out);
   return QC_OK;
 }
+
+// ------------------------------------------------------------------ ensembles: the tail, one block per member
+// Member blockIdx.y's partial rows -> its flat vector -> (UPDATE) adam_block on its slices, its state record and its own
+// trig buffer, with its own hyper-parameter record when there is a table.  The sums have the single-model step's order:
+// more than 32 rows are first folded in place as k_fold_rows folds them (k_fold_rows_ens, the member in blockIdx.z; up to
+// 32 rows that fold copies every row onto itself and is not launched), then the surviving rows are added left to right,
+// as k_adam_fast<true> adds them.
+namespace {
+
+__global__ void __launch_bounds__(64 * QC_RED_WAVES) k_fold_rows_ens(float* __restrict__ part, int64_t rows, int64_t stride,
+                                                                     int ncols, int64_t member_stride) {
+  __shared__ float s[QC_RED_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const int rs = blockIdx.y, RS = gridDim.y;
+  part += (int64_t)blockIdx.z * member_stride;
+  float a0 = 0.f, a1 = 0.f;
+  if (col < ncols) {
+    const int64_t r0 = rs + (int64_t)RS * wave;
+    const int64_t hop = (int64_t)RS * QC_RED_WAVES;
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t r = r0 + k * hop;
+      v[k] = r < rows ? part[r * stride + col] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+      a0 += v[k];
+      a1 += v[k + 1];
+    }
+    for (int64_t r = r0 + 8 * hop; r < rows; r += 2 * hop) {
+      a0 += part[r * stride + col];
+      if (r + hop < rows) a1 += part[(r + hop) * stride + col];
+    }
+  }
+  s[wave][lane] = a0 + a1;
+  __syncthreads();
+  if (wave == 0 && col < ncols) {
+    float t = s[0][lane];
+#pragma unroll
+    for (int w = 1; w < QC_RED_WAVES; ++w) t += s[w][lane];
+    part[(int64_t)rs * stride + col] = t;
+  }
+}
+
+template <bool UPDATE>
+__global__ void __launch_bounds__(1024) k_ens_tail(QcAdamArgs a, const float* __restrict__ part, int64_t stride, int RS, QcEns e) {
+  __shared__ float s_red[16];
+  const int64_t m = blockIdx.y;
+  part += m * e.part;
+  float* __restrict__ flat = a.flat + m * e.flat;
+  for (int i = threadIdx.x; RS > 0 && i < a.NP + 3; i += 1024) {   // (RS = 0: the flat vector is given)
+    float t = 0.f;
+    for (int j = 0; j < RS; ++j) t += part[(int64_t)j * stride + i];
+    flat[i] = t;
+  }
+  if constexpr (UPDATE) {
+    // the member's argument record, in LDS: adam_block indexes the run list in it (a private copy would live in scratch)
+    __shared__ QcAdamArgs s_a;
+    if (threadIdx.x == 0) {
+      s_a = a;
+      s_a.flat = flat;
+      s_a.prm = a.prm + m * e.prm;
+      s_a.m = a.m + m * e.prm;
+      s_a.v = a.v + m * e.prm;
+      s_a.st = a.st + m;
+      if (a.hist != nullptr) s_a.hist = a.hist + m * e.hist;
+      s_a.trig = (QcTrig*)((char*)a.trig + m * e.trig);
+      if (e.hyper != nullptr) s_a.hp = qc_ens_record(e.hyper, (int)blockIdx.y);
+    }
+    __syncthreads();   // the record, and the flat vector, written above by other threads than read below
+    adam_block(s_a, s_red);
+  }
+}
+
+}  // namespace
+
+int qc_opt_ens_tail(float* part, int64_t rows, int64_t stride, float* flat, int NP, float* prm, float* m, float* v,
+                    QcOptState* state, QcOptHyper hp, float* hist, int hist_cap, const qc_program* pg, int theta_off,
+                    QcTrig* trig, int update, const QcEns& e, hipStream_t st) {
+  const int RS = (int)(rows < 32 ? rows : 32);
+  if (rows > 32)
+    hipLaunchKernelGGL(k_fold_rows_ens, dim3(qc_ceil_div(NP + 3, 64), RS, e.M), dim3(64 * QC_RED_WAVES), 0, st, part, rows, stride,
+                       NP + 3, e.part);
+  const QcAdamArgs a = adam_args(flat, NP, prm, m, v, state, hp, hist, hist_cap, pg, theta_off, trig);
+  if (update) hipLaunchKernelGGL((k_ens_tail<true>), dim3(1, e.M), dim3(1024), 0, st, a, (const float*)part, stride, RS, e);
+  else hipLaunchKernelGGL((k_ens_tail<false>), dim3(1, e.M), dim3(1024), 0, st, a, (const float*)part, stride, RS, e);
+  return QC_OK;
+}

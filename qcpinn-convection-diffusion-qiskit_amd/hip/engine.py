@@ -1109,3 +1109,111 @@ class GradNormStep(_WeightedStep):
         """Rows (lam_bc, lam_ic, m_r, a_bc, a_ic, lambda-weighted loss, updated) of the first ``steps`` steps of the
         history buffer (default: all taken so far)."""
         return self._history(self.gradnorm_hist, steps, self.gradnorm_cap)
+
+
+def _record_table(records, device) -> torch.Tensor:
+    """ctypes records of one type, back to back on the device (a table of ``qc_step_ensemble``)."""
+    raw = b"".join(bytes(r) for r in records)
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+
+
+class EnsembleStep(_Step):
+    """One ``qc_fused_pinn_ensemble_step`` descriptor: M models of one architecture and one gate program trained by one
+    launch sequence per step, every launch over the tiles of all members.  Member m computes what a ``FusedStep`` computes
+    on its own slices, with the sampler key ``seed + m``.
+
+    ``flats`` / ``opts`` / ``pdes``: every member's flat parameter vector, ``OptimState`` and ``QcPde``.  The step owns
+    STACKED copies, one row per member: ``params`` [M, .], ``m`` / ``v``, ``state`` [M, 16], ``hist``, ``trig``, ``X_res``
+    [M, .], ``X_val``, the stage scratch, ``part`` [M, rows, stride], ``flat_grad`` [M, .] and the workspaces; a row holds
+    the member's slice at its head and ``pad`` more floats behind it (guard bands for tests; 0 otherwise; byte strides are
+    rounded up to 256).  Records that differ between members (operator constants and loss weights in ``pdes``, clip norm,
+    scheduler settings and loss weights in the ``hyper`` of ``opts``) travel as device tables.  ``member(m)`` is an
+    ``OptimState`` over member m's rows; ``read`` / ``write`` / ``loss_history`` go through it."""
+
+    def __init__(self, circuit: Circuit, hidden: int, flats, opts, pdes, B_res: int, n_ic: int, n_bc: int, pad: int = 0):
+        M = len(flats)
+        if M < 1 or len(opts) != M or len(pdes) != M:
+            raise L.QcError("an ensemble needs one flat vector, one optimiser state and one operator record per member")
+        super().__init__(circuit, hidden, flats[0], opts[0], pdes[0], B_res, n_ic, n_bc)
+        self.M, self.pad = M, int(pad)
+        d, dev, lib = self.desc, self.device, self.lib
+        ens = L.QcStepEnsemble()
+        L.check(lib.qc_ensemble_strides(C.byref(d), M, C.byref(ens)), "qc_ensemble_strides")
+        for name in ("params_stride", "flat_stride", "hist_stride", "x_res_stride", "x_val_stride", "jets_res_stride",
+                     "jets_val_stride"):
+            setattr(ens, name, getattr(ens, name) + self.pad)
+        ens.trig_stride = (ens.trig_stride + 4 * self.pad + 255) // 256 * 256
+        ens.ws_stride = max((ens.ws_stride + 4 * self.pad + 255) // 256 * 256, 256)
+        f = dict(dtype=torch.float32, device=dev)
+        NP, cap = self.NP, opts[0].hist_cap
+        if any(x.numel() != NP for x in flats) or any(o.m.numel() != NP or o.hist_cap != cap for o in opts):
+            raise L.QcError(f"every member needs {NP} parameters and moments and a loss history of {cap} steps")
+        self.params = torch.zeros(M, ens.params_stride, **f)
+        self.m, self.v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.state = torch.zeros(M, 16, **f)
+        self.hist = torch.zeros(M, max(ens.hist_stride, 1), **f)
+        for k, (x, o) in enumerate(zip(flats, opts)):
+            self.params[k, :NP], self.m[k, :NP], self.v[k, :NP] = _need(x, dev, "flat params"), o.m, o.v
+            self.state[k] = o.state
+            if cap > 0:
+                self.hist[k, :cap] = o.hist[:cap]
+        self.hypers = [o.hyper for o in opts]
+        self.trig = torch.zeros(M, ens.trig_stride // 4, **f)
+        self.X_res = torch.zeros(M, ens.x_res_stride, **f)
+        self.X_val = torch.zeros(M, ens.x_val_stride, **f)
+        self.ws_res = torch.zeros(4, M, ens.jets_res_stride, **f)
+        self.ws_val = torch.zeros(4, M, ens.jets_val_stride, **f)
+        self.part = torch.zeros(M, int(d.part_rows_cap), self.stride, **f)
+        self.flat_grad = torch.zeros(M, ens.flat_stride, **f)
+        self.step_ws = torch.zeros(M, ens.ws_stride, dtype=torch.uint8, device=dev)
+        d.trig_dev, d.params_dev, d.m_dev, d.v_dev = (t.data_ptr() for t in (self.trig, self.params, self.m, self.v))
+        d.opt_state_dev = self.state.data_ptr()
+        d.hist_dev = self.hist.data_ptr() if cap > 0 else None
+        d.X_res_dev, d.X_val_dev = self.X_res.data_ptr(), self.X_val.data_ptr()
+        (d.ajets_res_dev, d.qjets_res_dev, d.qbar_res_dev, d.abar_res_dev) = [self.ws_res[i].data_ptr() for i in range(4)]
+        (d.ajets_val_dev, d.qjets_val_dev, d.qbar_val_dev, d.abar_val_dev) = [self.ws_val[i].data_ptr() for i in range(4)]
+        d.part_dev, d.flat_dev = self.part.data_ptr(), self.flat_grad.data_ptr()
+        d.circ_ws_dev = self.step_ws.data_ptr()
+        # the tables, only where the members differ
+        self.pdes = list(pdes)
+        self.pde_table = self.hyper_table = None
+        if any(bytes(p) != bytes(pdes[0]) for p in pdes):
+            self.pde_table = _record_table(pdes, dev)
+        if any(bytes(h) != bytes(self.hypers[0]) for h in self.hypers):
+            self.hyper_table = _record_table(self.hypers, dev)
+        ens.pde_dev, ens.hyper_dev = _ptr(self.pde_table), _ptr(self.hyper_table)
+        self.ens = ens
+        self._bind_entry("qc_fused_pinn_ensemble_step", self.ens)
+
+    def points(self, m: int):
+        """(X_res [B_res, 3], X_val [n_ic + n_bc, 3]) of member ``m``: views of its rows."""
+        B_val = self.n_ic + self.n_bc
+        return self.X_res[m, :3 * self.B_res].view(self.B_res, 3), self.X_val[m, :3 * B_val].view(B_val, 3)
+
+    def member(self, m: int) -> OptimState:
+        """An ``OptimState`` over member ``m``'s rows of the stacked moments, state records and loss histories."""
+        o = object.__new__(OptimState)
+        o.device, o.hyper, o.hist_cap = self.device, self.hypers[m], self.opt.hist_cap
+        o.m, o.v, o.state = self.m[m, :self.NP], self.v[m, :self.NP], self.state[m]
+        o.hist = self.hist[m, :max(o.hist_cap, 1)]
+        return o
+
+    def read(self, m: int) -> dict:
+        return self.member(m).read()
+
+    def write(self, m: int, **fields) -> None:
+        self.member(m).write(**fields)
+
+    def loss_history(self, m: int, steps: Optional[int] = None):
+        return self.member(m).loss_history(steps)
+
+    def refresh_gates(self) -> None:
+        st = _stream(self.device)
+        for m in range(self.M):
+            theta = self.params[m, self.theta_off: self.theta_off + self.n_theta]
+            L.check(self.lib.qc_prepare_gates(self.circuit.handle, theta.data_ptr(), self.trig[m].data_ptr(), st),
+                    "qc_prepare_gates")
+
+    def set_comm(self, comm) -> None:
+        if comm is not None:
+            raise L.QcError("an ensemble step is single-process: it takes no communicator")

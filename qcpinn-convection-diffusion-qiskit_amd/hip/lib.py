@@ -40,6 +40,7 @@ EXPORTS = (
     "qc_program_set_input_map", "qc_pre_forward_ff", "qc_pre_backward_ff",
     "qc_pre_forward_tt", "qc_pre_backward_tt", "qc_forward_jets_tt", "qc_backward_jets_tt", "qc_post_coef_tt",
     "qc_post_jets_tt", "qc_sample_dataset_coef_tt", "qc_fused_pinn_coef_tt_step",
+    "qc_ensemble_strides", "qc_fused_pinn_ensemble_step",
 )
 
 
@@ -162,6 +163,15 @@ class QcStepGradnorm(C.Structure):
     of QC_GRADNORM_STATE_WORDS words and the optional [cap][QC_GRADNORM_HIST_COLS] history."""
     _fields_ = [("alpha", C.c_float), ("lam_max", C.c_float), ("every", C.c_int32), ("lam0_bc", C.c_float),
                 ("lam0_ic", C.c_float), ("state_dev", C.c_void_p), ("hist_dev", C.c_void_p), ("hist_cap", C.c_int32)]
+
+
+class QcStepEnsemble(C.Structure):
+    """qc_step_ensemble: members, the distance between two members' slices of every per-model buffer of the descriptor
+    (floats; trig_stride and ws_stride bytes) and the optional device tables of M qc_pde / qc_opt_hyper records."""
+    _fields_ = [("M", C.c_int), ("params_stride", C.c_int64), ("flat_stride", C.c_int64), ("hist_stride", C.c_int64),
+                ("trig_stride", C.c_int64), ("x_res_stride", C.c_int64), ("x_val_stride", C.c_int64),
+                ("jets_res_stride", C.c_int64), ("jets_val_stride", C.c_int64), ("ws_stride", C.c_int64),
+                ("pde_dev", C.c_void_p), ("hyper_dev", C.c_void_p)]
 
 
 class QcStepAdapt(C.Structure):
@@ -312,6 +322,8 @@ def load() -> C.CDLL:
     lib.qc_sample_dataset_coef_tt.argtypes = [fp, fp, i64, i64, fp, fp, i64, i64, i64, i64, fp, C.POINTER(QcStepData),
                                               C.POINTER(QcStepCoefTT), C.c_uint64, C.c_uint64, vp]
     lib.qc_fused_pinn_coef_tt_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepData), C.POINTER(QcStepCoefTT), i32, vp]
+    lib.qc_ensemble_strides.argtypes = [C.POINTER(QcStepDesc), i32, C.POINTER(QcStepEnsemble)]
+    lib.qc_fused_pinn_ensemble_step.argtypes = [C.POINTER(QcStepDesc), C.POINTER(QcStepEnsemble), i32, vp]
     lib.qc_comm_unique_id.argtypes = [vp]
     lib.qc_comm_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.qc_comm_destroy.argtypes = [vp]
